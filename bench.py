@@ -30,6 +30,13 @@ pass over one batch and all K finish inside the timed region.  --depth 1 uses on
 jdaDetectBatchDevice call per step instead; that figure is reported next to the headline in "config" and
 "regimes".
 
+A plain run times the headline and nothing else: set-up, W warm-up steps, the K timed steps, the line.  --full adds
+every other leg after the headline (the synchronous caller, the one-lane roofline leg, all-pass, host frames, the
+FDDB-shaped job, dialect CPP, configs[2], configs[4], the CPU baseline and the check of the timed outputs against the
+reference); the legs and the keys named above that belong to them are in the line only then.  --dump-outputs DIR
+writes the detections of the last timed step as DIR/detections.npy; with the same arguments every run detects on the
+same frames with the same model.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -59,6 +66,17 @@ def algorithmic_bytes(dims, carts, stage_done, windows, accepted):
     per_cart = (D - 1) * 34 + 16
     per_stage = K * 2 * L * 4
     return carts * per_cart + sum(stage_done) * per_stage + windows * 2 * L * 4 + accepted * (16 + 8 * L)
+
+
+def make_frames(n, width, height, seed=0, first=0, chunk=16):
+    """synth.make_frames in chunks on up to 16 host threads.  Frame i depends only on (seed, first + i), so these are the
+    frames one call would make."""
+    from concurrent.futures import ThreadPoolExecutor
+    from jda_amd import synth
+    with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as ex:
+        parts = list(ex.map(lambda a: synth.make_frames(min(chunk, n - a), width, height, seed=seed, first=first + a),
+                            range(0, n, chunk)))
+    return np.concatenate(parts) if parts else synth.make_frames(0, width, height, seed=seed, first=first)
 
 
 def model_path(dims, regime, seed, calib_frames):
@@ -157,6 +175,23 @@ def rows_equal_d(rows, index, want):
     return bool(np.array_equal(np.ascontiguousarray(got).view(np.uint64), np.ascontiguousarray(exp).view(np.uint64)))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each array as out_dir/<name>.npy in float32 / float64.  When they hold more than `limit` bytes in all, every
+    array keeps the same fraction of its rows, chosen with a fixed seed and kept in order."""
+    arrays = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64) else v.astype(np.float64))
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > limit and len(a):
+            keep = max(1, int(len(a) * limit // total))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def free_port():
     import socket
     with socket.socket() as s:
@@ -208,7 +243,14 @@ def main():
     ap.add_argument("--no-x", action="store_true", help="skip the configs[4] all-pass leg (roofline_hbm_regime)")
     ap.add_argument("--no-config2", action="store_true",
                     help="skip the BASELINE.json configs[2] leg (256 x 1080p, scale 1.5: config.config2_*)")
-    ap.add_argument("--config2", action="store_true", help="(accepted for older command lines: the leg runs by default)")
+    ap.add_argument("--config2", action="store_true", help="(accepted for older command lines: the leg runs under --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg too: one synchronous caller, the one-lane roofline leg, "
+                         "all-pass, host frames, the FDDB-shaped job, dialect CPP, configs[2], configs[4], the CPU baseline "
+                         "and the parity check against the reference (the --no-* options pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the detections of the last timed step (packed float32 rows [frame, x, y, size, score, "
+                         "landmarks]) to DIR/detections.npy (DIR/rank<r>/ per rank when N > 1)")
     args = ap.parse_args()
     rc = maybe_self_spawn(args, sys.argv[1:])
     if rc is not None:
@@ -248,7 +290,7 @@ def main():
     R = max(1, args.rotate)
     # this rank's shard of the job: R distinct batches, so that a step does not re-read frames the previous step left
     # in the Infinity Cache
-    frames_all = [synth.make_frames(B, W, H, seed=0, first=(rank * R + j) * B) for j in range(R)]
+    frames_all = [make_frames(B, W, H, seed=0, first=(rank * R + j) * B) for j in range(R)]
     frames = frames_all[0]
     d_batches = [torch.from_numpy(f).to(dev) for f in frames_all]
     d_frames = d_batches[0]
@@ -490,12 +532,17 @@ def main():
     casc_info, casc_model = run_regime("cascade", args.steps, args.warmup, call["th"], depth=args.depth)
     headline_rows = private.get("last_rows")          # (rows of the last TIMED step, index of the batch it ran on)
     rank_ms = casc_info.get("rank_ms_per_step")
-    # one caller, one batch at a time (what a single jdaDetectBatchDevice loop sees)
-    single_info = casc_info if args.depth <= 1 else run_regime("cascade", max(1, min(20, args.steps)), 2, call["th"])[0]
-    # roofline leg: the same workload with the k_scan launches of a step back to back on one stream
-    roof_info, _ = run_regime("cascade", max(1, min(20, args.steps)), 2, call["th"], lanes=1)
-    allpass_info = None
-    if not args.no_allpass:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank),
+                     {"detections": headline_rows[0]})
+    # ---- everything from here to the line is --full only: a plain run measures the headline and nothing else ----
+    single_info = roof_info = allpass_info = None
+    if args.full:
+        # one caller, one batch at a time (what a single jdaDetectBatchDevice loop sees)
+        single_info = casc_info if args.depth <= 1 else run_regime("cascade", max(1, min(20, args.steps)), 2, call["th"])[0]
+        # roofline leg: the same workload with the k_scan launches of a step back to back on one stream
+        roof_info, _ = run_regime("cascade", max(1, min(20, args.steps)), 2, call["th"], lanes=1)
+    if args.full and not args.no_allpass:
         # every window walks all T*K carts; final th=+inf so NMS sees nothing
         allpass_info, _ = run_regime("allpass", max(1, min(2, args.steps)), 1, float("inf"))
 
@@ -528,7 +575,7 @@ def main():
     # (single-GPU legs from here on run on rank 0 only, at every N: the other ranks wait at the closing barrier, so that a
     # line printed by an N-rank job carries the same keys as the one-GPU line)
     host_info = None
-    if rank == 0:
+    if rank == 0 and args.full:
         hs = max(2, min(30, args.steps))
         host_info = {"pageable_windows_per_s": host_leg(False, hs), "pinned_windows_per_s": host_leg(True, hs), "steps": hs,
                      "entry": "jdaDetectBatchSubmitHost / jdaDetectBatchWait, three tickets (two batches submitted ahead)"}
@@ -640,12 +687,13 @@ def main():
         return info
 
     fddb_info = None
-    try:
-        fddb_info = fddb_leg(max(1, min(5, args.steps)))
-    except Exception as e:
-        if world > 1:
-            raise
-        fddb_info = {"error": repr(e)}
+    if args.full:
+        try:
+            fddb_info = fddb_leg(max(1, min(5, args.steps)))
+        except Exception as e:
+            if world > 1:
+                raise
+            fddb_info = {"error": repr(e)}
 
     # ---- dialect CPP, the dialect the reference's own `jda fddb` runs: joincascador.Detect with fddb.method = 1
     #      (src/test.cpp:142; model/config.json:41-45: minimum_size 20, step 5, scale 1.2, overlap 0.3, nms on).  Two legs,
@@ -722,21 +770,22 @@ def main():
         return info
 
     cpp_info = fddb_cpp_info = None
-    try:
-        cpp_info = cpp_leg(max(1, min(5, args.steps)))
-        fddb_cpp_info = fddb_cpp_leg(max(1, min(5, args.steps)))
-    except Exception as e:
-        if world > 1:
-            raise
-        cpp_info = cpp_info or {"error": repr(e)}
-        fddb_cpp_info = fddb_cpp_info or {"error": repr(e)}
+    if args.full:
+        try:
+            cpp_info = cpp_leg(max(1, min(5, args.steps)))
+            fddb_cpp_info = fddb_cpp_leg(max(1, min(5, args.steps)))
+        except Exception as e:
+            if world > 1:
+                raise
+            cpp_info = cpp_info or {"error": repr(e)}
+            fddb_cpp_info = fddb_cpp_info or {"error": repr(e)}
 
     # ---- BASELINE.json configs[2] at its stated size, live: 256 x 1920x1080 frames resident in HBM (531 MB), scale 1.5
     #      (8 window sizes), shipped model dimensions, cascade regime.  The frames are 32 synthesised ones (synth.make_frames,
     #      1.3 s of host time instead of 10 s for 256) and seven cyclic shifts of each, made on the device: 256 distinct
     #      frames of the same statistics at 256 distinct places in HBM ----
     config2_live = None
-    if rank == 0 and not args.no_config2:
+    if rank == 0 and args.full and not args.no_config2:
         try:
             n_base, n_var = 32, 8
             f2 = synth.make_frames(n_base, 1920, 1080, seed=0)
@@ -836,7 +885,7 @@ def main():
         return info
 
     x_info = x_big_info = None
-    if rank == 0 and not args.no_allpass and not args.no_x:
+    if rank == 0 and args.full and not args.no_allpass and not args.no_x:
         try:
             x_info = x_leg(7, 1920, 1080, "x_allpass_traffic.json")             # BASELINE configs[4]
         except Exception as e:
@@ -849,7 +898,7 @@ def main():
             x_big_info = {"error": repr(e)}
 
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         try:
             cpu = cpu_baseline(casc_model, dims, frames)
         except Exception as e:  # the checker is optional for the measurement itself
@@ -861,7 +910,7 @@ def main():
     #      for the dimensions, the oracle's restatement ("port"); the dialect-CPP legs with the oracle (unpinned).  The
     #      checker is test infrastructure: nothing inside a timed region touches it. ----
     parity = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         parity = {"kind": None, "ok": True, "legs": {}}
         try:
             kind, detect = make_checker(casc_model, dims)
@@ -902,7 +951,34 @@ def main():
     if world > 1:
         dist.barrier()          # (the other ranks have waited here while rank 0 ran its single-GPU legs and the checks)
 
+    line = None
     if rank == 0:
+        line = {
+            "metric": "candidate windows/sec, 640x480 batch (jdaDetect hot path); FDDB images/sec in config.fddb_images_per_s",
+            "value": casc_info["windows_per_s"], "unit": "windows/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": casc_info["ms_per_step"], "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "BASELINE.json configs[1]: batch=%d %dx%d frames per GPU, synthetic %dx%d-cart "
+                                   "%d-landmark depth-%d model, cascade regime, jdaDetect(1.25,0.1,40,-1,-0.5)"
+                                   % (B, W, H, T, K, L, D),
+                       "batch_per_gpu": B, "width": W, "height": H, "windows_per_frame": wpf, "levels": n_levels,
+                       "model_T": T, "model_K": K, "model_landmarks": L, "model_depth": D,
+                       "regime": "cascade", "sharding": "frames, %d rank(s)" % world,
+                       "gather": gather_kind[0],
+                       "distinct_resident_batches": R, "resident_frame_bytes": R * B * W * H,
+                       "batches_in_flight_per_gpu": casc_info["batches_in_flight"],
+                       "images_per_s": casc_info["images_per_s"],
+                       "average_cart_n": casc_info["average_cart_n"],
+                       "detections_after_nms": casc_info["detections_after_nms"]},
+            "regimes": {"cascade": casc_info},
+        }
+        if rank_ms is not None:
+            line["config"].update({"rank_ms_per_step_min": min(rank_ms), "rank_ms_per_step_max": max(rank_ms)})
+        if selftest is not None:
+            line["config"]["dist_selftest"] = selftest
+
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: the LDS-tiled k_scan launches of one step ----
         # Bound: the LDS pipe.  Every tree node costs three lane-reads from LDS (one 8-byte resolved node record, two
         # pixel bytes), every cart two more (leaf score, threshold): (D-1)*3 + 2 lane-reads per window-cart; a lane-read
@@ -951,7 +1027,6 @@ def main():
                 d = d[k]
             return d
         cfg_extra = {
-            "images_per_s": casc_info["images_per_s"],
             # BASELINE metric, second half: the FDDB-shaped job (configs[3]'s 2,845 images as one ragged job)
             "fddb_images_per_s": g(fddb_info, "images_per_s"), "fddb_ms_per_job": g(fddb_info, "ms_per_job"),
             "fddb_windows_per_s": g(fddb_info, "windows_per_s"), "fddb_images": g(fddb_info, "images"),
@@ -968,8 +1043,7 @@ def main():
             # all-pass regime of the headline batch (dense kernel) and configs[4] (one 1080p frame, all-pass)
             "allpass_windows_per_s": g(allpass_info, "windows_per_s"), "allpass_ms_per_step": g(allpass_info, "ms_per_step"),
             "config4_allpass_windows_per_s": g(x_info, "windows_per_s"), "config4_allpass_ms_per_frame": g(x_info, "ms_per_step"),
-            "one_lane_ms_per_step": roof_info["ms_per_step"], "average_cart_n": casc_info["average_cart_n"],
-            "detections_after_nms": casc_info["detections_after_nms"],
+            "one_lane_ms_per_step": roof_info["ms_per_step"],
             # dialect CPP -- the reference's own fddb() dialect (Detect, method 1), resident data, measured in this run
             "cpp_windows_per_s": g(cpp_info, "windows_per_s"), "cpp_ms_per_step": g(cpp_info, "ms_per_step"),
             "cpp_windows_per_frame": g(cpp_info, "windows_per_frame"),
@@ -982,10 +1056,6 @@ def main():
             "parity_checked": (parity["kind"] if parity and parity.get("ok") else (False if parity and parity.get("ok") is False else None)),
             "parity_legs": g(parity, "legs"),
         }
-        if rank_ms is not None:
-            cfg_extra.update({"rank_ms_per_step_min": min(rank_ms), "rank_ms_per_step_max": max(rank_ms)})
-        if selftest is not None:
-            cfg_extra["dist_selftest"] = selftest
         roof_extra = {
             # the regime in which memory traffic IS the bound (configs[4] all-pass), measured in this run
             "hbm_regime_bound": "hbm", "hbm_regime_frac": g(x_info, "frac"), "hbm_regime_achieved_GBps": g(x_info, "achieved"),
@@ -1002,27 +1072,14 @@ def main():
             "hbm_side_measured_frac_of_hbm_peak": hbm_frac,
             "hbm_side_algorithmic_GBps": scan_bytes_alg / lds_s / 1e9 if lds_s > 0 else None,
         }
-        line = {
-            "metric": "candidate windows/sec, 640x480 batch (jdaDetect hot path); FDDB images/sec in config.fddb_images_per_s",
-            "value": casc_info["windows_per_s"], "unit": "windows/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": casc_info["ms_per_step"], "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": dict({"workload": "BASELINE.json configs[1]: batch=%d %dx%d frames per GPU, synthetic %dx%d-cart "
-                                        "%d-landmark depth-%d model, cascade regime, jdaDetect(1.25,0.1,40,-1,-0.5)"
-                                        % (B, W, H, T, K, L, D),
-                            "batch_per_gpu": B, "width": W, "height": H, "windows_per_frame": wpf, "levels": n_levels,
-                            "model_T": T, "model_K": K, "model_landmarks": L, "model_depth": D,
-                            "regime": "cascade", "sharding": "frames, %d rank(s)" % world,
-                            "gather": gather_kind[0],
-                            "distinct_resident_batches": R, "resident_frame_bytes": R * B * W * H,
-                            "batches_in_flight_per_gpu": casc_info["batches_in_flight"],
-                            "single_caller_ms_per_step": single_info["ms_per_step"],
-                            "single_caller_windows_per_s": single_info["windows_per_s"],
-                            "host_frames_windows_per_s": host_info["pageable_windows_per_s"] if host_info else None,
-                            "host_frames_pinned_windows_per_s": host_info["pinned_windows_per_s"] if host_info else None,
-                            "host_frames_pinned_over_value": (host_info["pinned_windows_per_s"] / casc_info["windows_per_s"])
-                                                             if host_info else None}, **cfg_extra),
+        line["config"].update({
+            "single_caller_ms_per_step": single_info["ms_per_step"],
+            "single_caller_windows_per_s": single_info["windows_per_s"],
+            "host_frames_windows_per_s": host_info["pageable_windows_per_s"] if host_info else None,
+            "host_frames_pinned_windows_per_s": host_info["pinned_windows_per_s"] if host_info else None,
+            "host_frames_pinned_over_value": (host_info["pinned_windows_per_s"] / casc_info["windows_per_s"])
+                                             if host_info else None}, **cfg_extra)
+        line.update({
             "roofline": dict({"bound": "lds", "achieved": achieved, "peak": LDS_PEAK_GBPS,
                               "unit": "GB/s", "frac": achieved / LDS_PEAK_GBPS,
                               "traffic": traffic, "traffic_source": traffic_src,
@@ -1050,7 +1107,8 @@ def main():
             "roofline_allpass": allpass_roof,
             "regimes": {"cascade": casc_info, "cascade_single_caller": single_info, "cascade_one_lane": roof_info,
                         "allpass": allpass_info, "host_frames": host_info},
-        }
+        })
+    if rank == 0:
         print(json.dumps(line))
     close_gathers()
     if world > 1:

@@ -44,3 +44,30 @@ def test_free_port_is_bindable():
     p = bench.free_port()
     assert 1024 < p < 65536
     s = socket.socket(); s.bind(("127.0.0.1", p)); s.close()
+
+
+def test_full_and_dump_outputs_are_options():
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+def test_dump_outputs_writes_floats_within_the_limit(tmp_path):
+    import numpy as np
+    import bench
+    rows = np.arange(600 * 59, dtype=np.float32).reshape(600, 59)
+    ids = np.arange(600, dtype=np.int32)
+    bench.dump_outputs(str(tmp_path / "all"), {"detections": rows, "ids": ids})
+    assert np.array_equal(np.load(str(tmp_path / "all" / "detections.npy")), rows)
+    got = np.load(str(tmp_path / "all" / "ids.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got, ids)
+    # over the limit: the same fraction of every array's rows, in order, and the same rows from run to run
+    limit = (rows.nbytes + ids.nbytes * 2) // 4
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"detections": rows, "ids": ids}, limit=limit)
+    a, b = (np.load(str(tmp_path / d / "detections.npy")) for d in ("a", "b"))
+    ia = np.load(str(tmp_path / "a" / "ids.npy"))
+    assert 0 < len(a) < len(rows) and np.array_equal(a, b) and len(ia) == len(a)
+    assert a.nbytes + ia.nbytes <= limit
+    assert np.all(np.diff(a[:, 0]) > 0) and set(a[:, 0].tolist()) <= set(rows[:, 0].tolist())

@@ -146,7 +146,7 @@ def test_bench_two_ranks_with_the_c_gather_in_the_loop():
     env = dict(os.environ, LD_PRELOAD=stub, JDA_BENCH_BACKEND="gloo", JDA_BENCH_ONE_GPU="1", JDA_BENCH_C_GATHER_ON_GLOO="1", JDA_DENSE="1")
     env.pop("JDA_BENCH_GATHER", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "32",
-           "--no-allpass", "--no-config2"]
+           "--full", "--no-allpass", "--no-config2"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -924,7 +924,7 @@ def test_bench_control_flow_with_two_ranks_on_one_gpu(built, gpu):
     # no launcher: `python bench.py --gpus 2` starts its two ranks itself (bench.py:maybe_self_spawn), the way the
     # driver invokes it
     cmd = [sys.executable, os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "32", "--no-cpu", "--no-allpass"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "32", "--full", "--no-cpu", "--no-allpass"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -940,15 +940,15 @@ def test_bench_control_flow_with_two_ranks_on_one_gpu(built, gpu):
 
 
 def test_bench_plain_invocation_one_gpu(built, gpu):
-    """`python bench.py --gpus 1 --steps K --warmup W` exactly as the driver runs it (no launcher): one JSON line
-    with the contract's keys, the roofline and the FDDB-shaped images/s."""
+    """`python bench.py --gpus 1 --steps K --warmup W --full` (no launcher): one JSON line with the contract's keys,
+    the roofline and the FDDB-shaped images/s."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--batch", "32", "--no-cpu", "--no-allpass"]
+           "--batch", "32", "--full", "--no-cpu", "--no-allpass"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -967,6 +967,40 @@ def test_bench_plain_invocation_one_gpu(built, gpu):
     assert cfg["config2_submit_wait_windows_per_s"] > 1e9
     for k, v in list(cfg.items()) + list(roof.items()):
         assert v is None or isinstance(v, (int, float, str, bool)), (k, type(v))
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_detections(built, gpu, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` as the driver runs it: the headline leg alone, and with
+    --dump-outputs the rows of the last timed step, which are the oracle's detections of its frames."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from jda_amd import synth
+    from oracle.pyoracle import Oracle
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    B = 16
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--batch", str(B), "--rotate", "1", "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "windows/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32"
+    for k in ("roofline", "cpu_baseline", "fddb", "cpp", "config2", "parity"):
+        assert k not in d, k
+    rows = np.load(str(tmp_path / "out" / "detections.npy"))
+    assert rows.dtype == np.float32 and rows.shape == (d["config"]["detections_after_nms"], 5 + 2 * S_DIMS[2])
+    # --rotate 1: every step ran on batch 0, frames 0 .. B-1 of seed 0
+    frames = synth.make_frames(B, 640, 480, seed=0)
+    calib = synth.make_frames(8, 640, 480, seed=0, first=10_000_000)
+    orc = Oracle(bench.model_path(S_DIMS, "cascade", 1, calib))
+    for f in (0, B - 1):
+        assert bench.rows_equal(rows, f, orc.detect(frames[f], 1.25, 40, -1, -0.5)), f
 
 
 def test_pipelined_gather_device_path_over_rccl_group_of_one(built, gpu):

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."; mkdir -p gpurun_out; TAG=${TAG:-fddb_scaling}
 for v in "$@"; do
   echo "=== $v"
-  env $v timeout 300 python bench.py --no-cpu --no-allpass --no-x --steps 10 2>/dev/null | python -c "
+  env $v timeout 300 python bench.py --full --no-cpu --no-allpass --no-x --steps 10 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

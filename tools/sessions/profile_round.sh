@@ -8,9 +8,9 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp; export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu --no-allpass"
+B="python $R/bench.py --full --no-cpu --no-allpass"
 # kernel trace: one lane (k_scan launches back to back: durations comparable with roofline.kernel_ms_per_step)
 JDA_LANES=1 JDA_SIDE_STREAM=0 rocprofv3 --kernel-trace --stats -d $O/kt_lane1 -- $B --steps 10 --warmup 2 > $O/bench_kt_lane1.json 2> /dev/null
 # kernel trace: default (two lanes, kernels of the two sub-batches overlap)

@@ -7,7 +7,7 @@ bash tools/sessions/r06_x.sh > /dev/null 2>&1
 cp gpurun_out/r06_x/x_allpass_traffic.json gpurun_out/r06_x/x_allpass_T14_traffic.json profiles/
 O=$R/gpurun_out/r06_restamp
 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench.err
-python bench.py > $O/bench_default.json 2>> $O/bench.err
+python bench.py --full > $O/bench_default.json 2>> $O/bench.err
 python - <<'P'
 import json
 for f in ("bench_driver_args.json", "bench_default.json"):

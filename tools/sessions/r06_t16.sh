@@ -1,7 +1,7 @@
 #!/bin/bash
 # final bench lines with two batches in flight (bench.py's default since session r06_t15)
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/r06_t16; mkdir -p $O; cd $R
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 ( time python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_args.json 2>> $O/bench.err ) 2>&1 | grep real
 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-allpass --no-x --no-config2 > $O/bench_driver_args_2.json 2>> $O/bench.err
 python - <<'P'

@@ -13,5 +13,5 @@ python tools/rocpd_pmc.py $(db pmc_f) > $O/pmc_hbm.txt; python tools/rocpd_pmc.p
 python tools/pmc_traffic.py $(db cal_f) $(db cal_w) $(db pmc_f) $(db pmc_w) 13 "$TAG: JDA_LANES=1 JDA_SIDE_STREAM=0 rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python tools/variants.py ''" > $O/hbm_traffic.json
 cp $O/hbm_traffic.json $R/profiles/hbm_traffic.json      # (so that the bench line below checks its traffic figure against this device code)
 find $O -name "*.db" -delete; rm -rf $O/pmc_f $O/pmc_w $O/cal_f $O/cal_w
-timeout 300 python bench.py --no-cpu > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --no-cpu > $O/bench.json 2> $O/bench.err
 tail -1 $O/bench.json | cut -c1-260
