@@ -453,6 +453,95 @@ JDA_API int jdaTraceBatchCpp(void *cascador, const unsigned char *const *frames,
                              int width, int height, int minimum_size, int step, double factor,
                              int *carts_n, double *score, unsigned int *path_hash, double *shapes);
 
+/* ---- Dialect CPP: Validate on caller crops, hard-negative mining ------------------------------------------------------
+ * The trainer's second caller of JoinCascador::Validate (reference src/jda/cascador.cpp:166-211) is hard-negative mining:
+ * DataSet::MoreNegSamples (src/jda/data.cpp:479-530) -> NegGenerator::Generate -> ParallelMining -> Validate
+ * (data.cpp:885-1065).  These entries run that Validate on the device.  Every dialect-CPP rule holds: a trainer snapshot
+ * runs Validate's own loop bounds (stages [0, s), then carts [0, c] of stage s without its regression), and
+ * jdaSetSimilarityTransform(1) applies the similarity transform.  PARITY UNPINNED like every dialect-CPP entry: bit-exact
+ * against this project's restatements of Validate and cv::resize, not against the reference, which cannot be built here.
+ *
+ * Initial shape.  Validate starts from RandomShape(mean_shape) (data.cpp:225-236): mean_shape plus ONE global (x, y), each
+ * uniform in [-shift_size, shift_size).  shift_size == 0 gives mean_shape + 0., what every detect entry uses (test() and
+ * fddb() force it).  Otherwise crop / window `key` (the crop's index for jdaValidateCpp*, the window's ordinal for the
+ * mining entries) draws
+ *     x = g(2 key), y = g(2 key + 1),   g(c) = -shift_size + (shift_size - -shift_size) * u(c)
+ *     u(c) = (splitmix64(seed + (c + 1) * 0x9E3779B97F4A7C15) >> 11) * 2^-53      (arithmetic mod 2^64)
+ *     splitmix64(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31
+ * -- the a + (b - a) * u form of cv::RNG::uniform(double, double), reproducible and independent of how a job is cut into
+ * calls.  (The reference seeds with getTickCount(); its draws cannot be reproduced and are not a goal.)  The shift enters
+ * the initial shape only: STParameter::Calc keeps the stored mean_shape as its second argument.
+ *
+ * Patches.  origin_size / half_size / quarter_size are the config's image_size.* (48 / 36 / 24 shipped, common.cpp:129-131),
+ * each in [1, 128].  Every patch is cv::resize(INTER_LINEAR) as restated in this library (jdaResizeCv): the crop -> o, then
+ *   resize_mode 0, mining (data.cpp:987-990):           o -> h, o -> q
+ *   resize_mode 1, detectSingleScale (cascador.cpp:243-245): crop -> h, crop -> q
+ * A model without scale != 0 split nodes only reads o. */
+
+/* Validate on n_crops caller crops, each 5 ints (image, x, y, w, h); a crop must lie inside its image (-1 otherwise).
+ * images[i] is widths[i]*heights[i] bytes in HOST memory, rows back to back.  Per crop, into host arrays (any may be NULL):
+ *   is_face  1 if Validate returned true
+ *   score    the score where the walk stopped
+ *   carts_n  Validate's n (cascador.cpp:187): carts it ran -- s*K + c + 1 for a face of a snapshot, T*K for a face of a
+ *            complete model
+ *   shape    2L doubles, the window-normalised shape as Validate leaves it (rejected crops too)
+ * stats: patch_n, face_patch_n, nonface_patch_n, cart_gothrough_n (non-faces only), average_cart_n, call_ms.
+ * Returns 0, or -1 with jdaGetLastError(). */
+JDA_API int jdaValidateCpp(void *cascador, const unsigned char *const *images, const int *widths, const int *heights,
+                           int n_images, const int *crops, int n_crops, int origin_size, int half_size, int quarter_size,
+                           int resize_mode, double shift_size, uint64_t seed, unsigned char *is_face, double *score,
+                           int *carts_n, double *shape, jdaStats *stats);
+/* Same, images resident in device memory: image i at d_base + offsets[i] (jdaDetectBatchCppRaggedDevice's convention). */
+JDA_API int jdaValidateCppDevice(void *cascador, const unsigned char *d_base, const size_t *offsets, const int *widths,
+                                 const int *heights, int n_images, const int *crops, int n_crops, int origin_size,
+                                 int half_size, int quarter_size, int resize_mode, double shift_size, uint64_t seed,
+                                 unsigned char *is_face, double *score, int *carts_n, double *shape, jdaStats *stats);
+
+/* Work counters of one mining call; they cover exactly the windows [start, next_start). */
+typedef struct {
+  long long windows;        /* windows consumed: next_start - start                                   */
+  long long nega_n;         /* windows Validate rejected (ParallelMining's nega_n, data.cpp:1001-1004) */
+  long long carts_n;        /* their Validate n, summed (rejected windows only, like the reference)   */
+  long long next_start;     /* one past the size-th hit, or the end of the enumeration                */
+  long long total_windows;  /* windows of the whole enumeration                                       */
+  int hits;                 /* hard negatives returned                                                */
+  double call_ms;           /* wall clock of the call                                                 */
+} jdaMineStats;
+
+/* NegGenerator's background walk (NextImage, data.cpp:885-967), restated per image in list order:
+ *   - image i is first transformed by transforms[i] in 0..7 exactly as data.cpp:930-963 composes cv::flip and transpose
+ *     (1, 3, 5, 7 transpose, so W and H swap) -- on the device, by remapping coordinates;
+ *   - it is skipped unless W > origin_size && H > origin_size (data.cpp:921);
+ *   - win starts at origin_size; a level is the full grid, y from 0 in steps of steps[i] while y + win <= H, x the same
+ *     against W, row by row; the next level has win = (int)(win * factors[i]) (State::win_size is an int), and the
+ *     image ends when win >= W || win >= H (a factor that does not grow win is refused: the reference would never end).
+ * The reference draws step and factor from cv::RNG(getTickCount()) (data.cpp:910-911): here they are the caller's.
+ * One deliberate difference: the reference skips (0, 0) of the FIRST image of each thread (its `x += step` runs before the
+ * first crop) and interleaves threads nondeterministically; here every window is enumerated once, in order.
+ * Every window, ordinal by ordinal from `start`, goes through resize_mode 0 and Validate.  Returned: the FIRST `size` faces
+ * (hard negatives) at or after `start`, in enumeration order -- hits[4h..4h+3] = (image, x, y, win) in the transformed
+ * image, score[h], shape[2L h ..] and patches[h * (o^2 + h^2 + q^2) ..] (the o, h, q patch bytes MoreNegSamples stores,
+ * data.cpp:510-520); any output may be NULL, each must hold `size` entries.  Chaining calls through stats->next_start gives
+ * the results of one larger call.  The enumeration is processed in chunks in order, and the call stops after the chunk
+ * that holds the size-th hit (device workspace within the cascador's "workspace_mb").  Returns the number of hits, or -1. */
+JDA_API int jdaMineNegativesCpp(void *cascador, const unsigned char *const *images, const int *widths, const int *heights,
+                                int n_images, const int *steps, const double *factors, const int *transforms,
+                                int origin_size, int half_size, int quarter_size, long long start, int size,
+                                double shift_size, uint64_t seed, int *hits, double *score, double *shape,
+                                unsigned char *patches, jdaMineStats *stats);
+/* Same, images resident in device memory (image i at d_base + offsets[i]): the throughput entry -- a trainer keeps its
+ * background set in HBM across every MoreNegSamples call. */
+JDA_API int jdaMineNegativesCppDevice(void *cascador, const unsigned char *d_base, const size_t *offsets, const int *widths,
+                                      const int *heights, int n_images, const int *steps, const double *factors,
+                                      const int *transforms, int origin_size, int half_size, int quarter_size,
+                                      long long start, int size, double shift_size, uint64_t seed, int *hits,
+                                      double *score, double *shape, unsigned char *patches, jdaMineStats *stats);
+
+/* Host-only (no GPU): the mining enumeration of ONE (already transformed) w x h image -- windows and levels; the listing
+ * writes up to cap (x, y, win) triples in enumeration order and returns the number of windows (-1 on bad arguments). */
+JDA_API int jdaMineWindows(int w, int h, int origin_size, int step, double factor, long long *n, int *levels);
+JDA_API long long jdaMineWindowList(int w, int h, int origin_size, int step, double factor, int *xyw, long long cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,14 @@ class jdaStats(C.Structure):
         return d
 
 
+class jdaMineStats(C.Structure):
+    _fields_ = [("windows", C.c_longlong), ("nega_n", C.c_longlong), ("carts_n", C.c_longlong), ("next_start", C.c_longlong),
+                ("total_windows", C.c_longlong), ("hits", C.c_int), ("call_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class jdaDetectOptions(C.Structure):
     _fields_ = [("dialect", C.c_int), ("nms", C.c_int), ("nms_overlap", C.c_float), ("cpp_step", C.c_int),
                 ("hip_stream", C.c_void_p), ("stats", C.POINTER(jdaStats))]
@@ -174,6 +182,21 @@ def _load():
         lib.jdaTraceBatchCpp.argtypes = [C.c_void_p, C.POINTER(u8p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double),
                                          C.POINTER(C.c_uint), C.POINTER(C.c_double)]
+    if hasattr(lib, "jdaValidateCpp"):
+        crop_tail = [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64,
+                     u8p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(jdaStats)]
+        lib.jdaValidateCpp.argtypes = [C.c_void_p, C.POINTER(u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int] + crop_tail
+        lib.jdaValidateCppDevice.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_int), C.c_int] + crop_tail
+        mine_tail = [C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_longlong,
+                     C.c_int, C.c_double, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), u8p,
+                     C.POINTER(jdaMineStats)]
+        lib.jdaMineNegativesCpp.argtypes = [C.c_void_p, C.POINTER(u8p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int] + mine_tail
+        lib.jdaMineNegativesCppDevice.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_int), C.c_int] + mine_tail
+        lib.jdaMineWindows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
+        lib.jdaMineWindowList.restype = C.c_longlong
+        lib.jdaMineWindowList.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), C.c_longlong]
     return lib
 
 
@@ -191,6 +214,49 @@ jdaResultRelease = lib.jdaResultRelease
 
 def last_error():
     return (lib.jdaGetLastError() or b"").decode()
+
+
+def mine_windows(width, height, origin_size, step, factor, listing=False):
+    """The mining enumeration of one (transformed) image, NextImage's walk (jdaMineWindows): (windows, levels), or with
+    listing=True an [n, 3] int32 array of (x, y, win) in enumeration order."""
+    if not listing:
+        n, nl = C.c_longlong(), C.c_int()
+        if lib.jdaMineWindows(width, height, origin_size, step, factor, C.byref(n), C.byref(nl)) != 0:
+            raise JdaError(last_error())
+        return n.value, nl.value
+    n = lib.jdaMineWindowList(width, height, origin_size, step, factor, None, 0)
+    if n < 0:
+        raise JdaError(last_error())
+    out = np.zeros((max(n, 1), 3), np.int32)
+    lib.jdaMineWindowList(width, height, origin_size, step, factor, out.ctypes.data_as(C.POINTER(C.c_int)), n)
+    return out[:n]
+
+
+def mine_params(n_images, quarter_size=24, seed=0):
+    """Per-image step in [2, quarter_size) and factor in [1.1, 1.5), drawn the way NegGenerator's Load / NextImage draw
+    them (reference data.cpp:910-911, 1093-1094: rng.uniform(2, img_q_size), rng.uniform(1.1, 1.5)) -- with numpy's seeded
+    generator instead of cv::RNG(getTickCount()).  Returns (steps int32, factors float64)."""
+    rng = np.random.default_rng(seed)
+    steps = rng.integers(2, quarter_size, size=n_images).astype(np.int32)
+    factors = rng.uniform(1.1, 1.5, size=n_images)
+    return steps, factors
+
+
+def _image_set(images):
+    """A list of 2-D uint8 arrays (host) or (torch uint8 CUDA buffer, offsets, widths, heights) (device) ->
+    (device?, base or pointer array, offsets or None, widths, heights, keep-alive)."""
+    if isinstance(images, tuple):
+        buf, offsets, widths, heights = images
+        assert buf.is_cuda and buf.dtype.itemsize == 1 and buf.is_contiguous()
+        ko, offs = _ivec(offsets, C.c_size_t, np.uint64)
+        kw, ws = _ivec(widths)
+        kh, hs = _ivec(heights)
+        return True, C.c_void_p(buf.data_ptr()), offs, ws, hs, len(offsets), (ko, kw, kh, buf)
+    imgs = [np.ascontiguousarray(a, np.uint8) for a in images]
+    ptrs = (C.c_void_p * max(len(imgs), 1))(*[a.ctypes.data for a in imgs])
+    kw, ws = _ivec([a.shape[1] for a in imgs])
+    kh, hs = _ivec([a.shape[0] for a in imgs])
+    return False, C.cast(ptrs, C.POINTER(C.POINTER(C.c_ubyte))), None, ws, hs, len(imgs), (imgs, ptrs, kw, kh)
 
 
 def count_windows(width, height, scale=1.25, min_size=40, max_size=-1):
@@ -712,6 +778,82 @@ class Cascador:
         out = np.zeros((out_height, out_width), np.uint8)
         if lib.jdaResizeCv(self.h, _u8(img), w, h, _u8(out), out_width, out_height) != 0:
             raise JdaError(last_error())
+        return out
+
+    def validate_cpp(self, images, crops, mode=0, origin_size=48, half_size=36, quarter_size=24, shift_size=0.0, seed=0,
+                     stats=False):
+        """Validate (reference cascador.cpp:166-211) on caller crops, rows of (image, x, y, w, h): jdaValidateCpp for a list
+        of host images, jdaValidateCppDevice for (torch uint8 CUDA buffer, offsets, widths, heights).  mode 0: the mining
+        patch chain, 1: detectSingleScale's.  -> dict of is_face, score, carts_n, shape (numpy)."""
+        dev, base, offs, ws, hs, n_img, keep = _image_set(images)
+        cr = np.ascontiguousarray(np.asarray(crops, np.int32).reshape(-1, 5))
+        n = cr.shape[0]
+        face = np.zeros(max(n, 1), np.uint8)
+        score = np.zeros(max(n, 1), np.float64)
+        carts = np.zeros(max(n, 1), np.int32)
+        shape = np.zeros((max(n, 1), self.dim), np.float64)
+        st = jdaStats()
+        args = (cr.ctypes.data_as(C.POINTER(C.c_int)), n, origin_size, half_size, quarter_size, mode, float(shift_size),
+                int(seed) & 0xffffffffffffffff, _u8(face), score.ctypes.data_as(C.POINTER(C.c_double)),
+                carts.ctypes.data_as(C.POINTER(C.c_int)), shape.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st))
+        if dev:
+            rc = lib.jdaValidateCppDevice(self.h, base, offs, ws, hs, n_img, *args)
+        else:
+            rc = lib.jdaValidateCpp(self.h, base, ws, hs, n_img, *args)
+        del keep
+        if rc != 0:
+            raise JdaError(last_error())
+        out = dict(is_face=face[:n], score=score[:n], carts_n=carts[:n], shape=shape[:n])
+        return (out, st.asdict()) if stats else out
+
+    def mine_negatives_cpp(self, images, steps, factors, transforms, size, start=0, device=False, origin_size=48, half_size=36,
+                           quarter_size=24, shift_size=0.0, seed=0, patches=True):
+        """Hard-negative mining (reference data.cpp:885-1065): the first `size` windows of NextImage's walk over the
+        background images (from window ordinal `start` on) that Validate calls faces.  images: a list of host images, or
+        (torch uint8 CUDA buffer, offsets, widths, heights) -- the device entry.  device=True with a host list stages the
+        images on the device first (torch) and calls the device entry.  -> dict of hits [n, 4] (image, x, y, win), score,
+        shape, o / h / q patch bytes and stats (windows, nega_n, carts_n, next_start, total_windows, hits)."""
+        if device and not isinstance(images, tuple):
+            import torch
+            imgs = [np.ascontiguousarray(a, np.uint8) for a in images]
+            offs = np.zeros(len(imgs), np.uint64)
+            tot = 0
+            for i, a in enumerate(imgs):
+                offs[i] = tot
+                tot += (a.size + 255) // 256 * 256
+            host = np.zeros(max(tot, 256), np.uint8)
+            for i, a in enumerate(imgs):
+                host[int(offs[i]):int(offs[i]) + a.size] = a.ravel()
+            buf = torch.from_numpy(host).cuda()
+            images = (buf, offs, [a.shape[1] for a in imgs], [a.shape[0] for a in imgs])
+        dev, base, offs, ws, hs, n_img, keep = _image_set(images)
+        ks, sp = _ivec(steps)
+        kf, fp = _ivec(factors, C.c_double, np.float64)
+        kt, tp = _ivec(transforms)
+        cap = max(int(size), 1)
+        hits = np.zeros((cap, 4), np.int32)
+        score = np.zeros(cap, np.float64)
+        shape = np.zeros((cap, self.dim), np.float64)
+        pt = origin_size * origin_size + half_size * half_size + quarter_size * quarter_size
+        pat = np.zeros((cap, pt), np.uint8) if patches else None
+        st = jdaMineStats()
+        args = (sp, fp, tp, origin_size, half_size, quarter_size, int(start), int(size), float(shift_size),
+                int(seed) & 0xffffffffffffffff, hits.ctypes.data_as(C.POINTER(C.c_int)),
+                score.ctypes.data_as(C.POINTER(C.c_double)), shape.ctypes.data_as(C.POINTER(C.c_double)),
+                _u8(pat) if patches else None, C.byref(st))
+        if dev:
+            rc = lib.jdaMineNegativesCppDevice(self.h, base, offs, ws, hs, n_img, *args)
+        else:
+            rc = lib.jdaMineNegativesCpp(self.h, base, ws, hs, n_img, *args)
+        del keep, ks, kf, kt
+        if rc < 0:
+            raise JdaError(last_error())
+        out = dict(hits=hits[:rc], score=score[:rc], shape=shape[:rc], stats=st.asdict())
+        if patches:
+            o2, h2 = origin_size * origin_size, half_size * half_size
+            out["o"] = pat[:rc, :o2].reshape(rc, origin_size, origin_size)
+            out["h"] = pat[:rc, o2:o2 + h2].reshape(rc, half_size, half_size)
+            out["q"] = pat[:rc, o2 + h2:].reshape(rc, quarter_size, quarter_size)
         return out
 
     def trace_cpp(self, frames, minimum_size=20, step=5, factor=1.2):

@@ -97,7 +97,7 @@ void jdaCascadorRelease(void* cascador) try {
     c->aux = c->h2d = nullptr;
     for (auto& kv : c->plans) { if (kv.second.dp) (void)hipFree(kv.second.dp); if (kv.second.table) (void)hipFree(kv.second.table); }
     for (auto& b : c->plan_pool) { if (b.dp) (void)hipFree(b.dp); if (b.table) (void)hipFree(b.table); }
-    c->mf.buf.release(); c->md.buf.release();
+    c->mf.buf.release(); c->md.buf.release(); c->mine_buf.release();
   }
   delete[] c->pending;
   delete c;
@@ -629,7 +629,7 @@ long long jdaModelStreamBytes(int T, int K, int landmark_n, int tree_depth, int 
 namespace jda {
 void jda_bc_read_k_scan(unsigned long long*); void jda_bc_read_k_scan_d(unsigned long long*); void jda_bc_read_k_scan_r(unsigned long long*);
 void jda_bc_read_k_scan_dr(unsigned long long*); void jda_bc_read_k_scan_p(unsigned long long*); void jda_bc_read_k_finish(unsigned long long*);
-void jda_bc_read_k_wide(unsigned long long*); void jda_bc_read_k_stage(unsigned long long*);
+void jda_bc_read_k_wide(unsigned long long*); void jda_bc_read_k_stage(unsigned long long*); void jda_bc_read_k_mine(unsigned long long*);
 }
 // bounds-check build only (libjda_bounds.so): per translation unit {first violation: site << 32 | source line, violations}
 // since the last call -- out[16]; returns the total number of violations (kernels_common.h: Bc)
@@ -639,6 +639,14 @@ __attribute__((visibility("default"))) long long jdaDebugBoundsReport(unsigned l
                                         jda_bc_read_k_scan_p, jda_bc_read_k_finish, jda_bc_read_k_wide, jda_bc_read_k_stage};
   long long total = 0;
   for (int i = 0; i < 8; i++) { unsigned long long v[2] = {0, 0}; rd[i](v); if (out) { out[2 * i] = v[0]; out[2 * i + 1] = v[1]; } total += (long long)v[1]; }
+  // k_mine's words ride in k_finish's slot (out keeps its 16 words): the line names the k_mine.hip source line
+  unsigned long long v[2] = {0, 0};
+  jda_bc_read_k_mine(v);
+  if (v[1]) {
+    std::fprintf(stderr, "libjda: bounds check: k_mine: %llu violation(s), first at site %llu line %llu\n", v[1], v[0] >> 32, v[0] & 0xffffffffull);
+    if (out) { if (!out[11]) out[10] = v[0]; out[11] += v[1]; }
+    total += (long long)v[1];
+  }
   return total;
 }
 #endif

@@ -102,6 +102,7 @@ inline long long env_ll(const char* name, long long dflt) {
   X(ws_min_entries, "JDA_WS_MIN_ENTRIES", 65536) /* ... and never fewer entries than this */ \
   X(ragged_chunk_windows, "JDA_RAGGED_CHUNK_WINDOWS", 4000000) /* windows per chunk of a ragged batch at most */ \
   X(ragged_chunk_windows_cpp, "JDA_RAGGED_CHUNK_WINDOWS_CPP", 8000000) /* ... of a dialect-CPP ragged batch */ \
+  X(mine_chunk_windows, "JDA_MINE_CHUNK_WINDOWS", 4194304) /* windows per chunk of a mining call at most (mine.cpp) */ \
   X(ragged_chunk_min_windows, "JDA_RAGGED_CHUNK_MIN_WINDOWS", 1500000) /* ... and at least, where a small job is cut into ragged_split chunks */ \
   X(ragged_split, "JDA_RAGGED_SPLIT", 3)    /* chunks a job smaller than that many full chunks is cut into */ \
   X(ragged_single_windows, "JDA_RAGGED_SINGLE_WINDOWS", 5000000) /* a ragged job of at most this many windows (a rank's shard of a sharded job) runs as ONE chunk, its global-pixel launch on the lane's side stream; 0: always cut into ragged_split chunks */ \
@@ -181,7 +182,7 @@ struct Knobs {
   // Values no code path can work with are refused (jdaSetOption returns -1): negative sizes and counts; the rest of
   // a knob's range is clamped where it is used.
   bool set(const char* key, long long v) {
-    static const char* const non_negative[] = {"workspace_mb", "handoff", "plan_cache", "lanes", "ragged_chunk_windows", "ragged_chunk_windows_cpp",
+    static const char* const non_negative[] = {"workspace_mb", "handoff", "plan_cache", "lanes", "ragged_chunk_windows", "ragged_chunk_windows_cpp", "mine_chunk_windows",
                                                "ragged_chunk_min_windows", "h2d_min_bytes", "merge_blocks", "wide_max", "lanes_min_windows", "ragged_single_windows",
                                                "scan_p_handoff", "scan_p_slots", "max_lanes", "lane_idle_calls", "scan_p_tile_kb", "scan_p_grid",
                                                "ws_min_entries", "ws_factor_pct"};
@@ -458,6 +459,9 @@ struct Cascador {
   std::condition_variable lane_cv;           // a lane was given back (callers beyond max_lanes wait here, with mu)
   ModelOnDevice<float> mf;
   ModelOnDevice<double> md;
+  MineModel mine_m{};          // Validate's own tables for the caller-crop and mining entries (mine.cpp)
+  DevBuf mine_buf;
+  bool mine_ready = false;
   std::map<PlanKey, PlanEntry> plans;
   struct PlanBuffers { DevPlan* dp; S0Node* table; size_t table_cap; };
   std::vector<PlanBuffers> plan_pool;     // device allocations of evicted plans (hipFree + hipMalloc per miss cost ~0.1 ms)

@@ -350,6 +350,50 @@ template <typename Real>
 hipError_t launch_trace_fill(const DevModelT<Real>& m, const WorkT<Real>& w, unsigned n_windows,
                              hipStream_t stream);
 
+// ---- dialect CPP's Validate on caller crops and the hard-negative mining walk (k_mine.hip, mine.cpp) -----------------
+
+// The model as Validate reads it (cascador.cpp:166-211): raw node offsets (the similarity parameter is applied per window),
+// unpadded tables, Validate's own loop bounds -- `full` complete stages, then carts [0, part) of stage `full` without its
+// regression (a trainer snapshot; part = 0 for a complete model).
+struct MineModel {
+  int T, K, L, D, node_n, leaf_n, dim;
+  int full, part;
+  const NodeD* nodes;        // [T*K*node_n], offsets as stored
+  const double* leaf;        // [T*K*leaf_n]
+  const double* cth; const double* cmean; const double* cstd;   // [T*K]
+  const double* w;           // [T][K*leaf_n][dim]
+  const double* mean;        // [dim] as stored
+};
+// One background image of a mining job: d_base + off, w x h as stored (rows back to back); transform 0..7 of
+// data.cpp:930-963 as bits (kMineSwap: transpose, kMineFlipX / kMineFlipY: mirror the stored x / y).
+struct MineImg { unsigned long long off; int w, h, tf, pad; };
+constexpr int kMineSwap = 1, kMineFlipX = 2, kMineFlipY = 4;
+// One (image, level) of the enumeration: its windows are ordinals [first, first + nx*ny), row by row.
+struct MineSeg { unsigned long long first; int image, win, step, nx; };
+// One crop Validate runs on: (x, y, w, h) in the transformed image, key of its initial-shape draw.
+struct MineItem { int image, x, y, w, h, pad; unsigned long long key; };
+struct MineSizes { int os, hs, qs, mode; double shift; unsigned long long seed; };
+
+// Stage-0 prefix of every window with ordinals [lo, hi): carts [0, carts0) with the pixels computed on demand from the
+// background image (chain 0).  status[o - lo] = Validate's n of a window rejected there; survivors are appended to
+// surv (their ordinals, unordered) through *n_surv, status 0.
+hipError_t launch_mine_scan(const MineModel& m, const MineSizes& z, const uint8_t* base, const MineImg* imgs,
+                            const MineSeg* segs, int n_segs, unsigned long long lo, unsigned long long hi, int carts0,
+                            int* status, unsigned long long* surv, unsigned* n_surv, hipStream_t stream);
+// Ordinals -> crops (image, x, y, win, win, key = ordinal).
+hipError_t launch_mine_items(const MineSeg* segs, int n_segs, const unsigned long long* ords, int n, MineItem* items,
+                             hipStream_t stream);
+// The o / h / q patches of n crops (chain z.mode) at patches + i * pbytes: os^2, then hs^2, then qs^2 bytes.
+hipError_t launch_mine_patches(const MineSizes& z, const uint8_t* base, const MineImg* imgs, const MineItem* items, int n,
+                               uint8_t* patches, int pbytes, hipStream_t stream);
+// Validate on the patches of n crops, a lane per crop: face[i], n[i], score[i], shape[i*dim ..] (also the walk's state);
+// lbf / t1 / t2: per-crop scratch of K ints and 2 x dim doubles.
+hipError_t launch_mine_walk(const MineModel& m, const MineSizes& z, const MineItem* items, int n, const uint8_t* patches,
+                            int pbytes, int similarity, uint8_t* face, int* carts_n, double* score, double* shape, int* lbf,
+                            double* t1, double* t2, hipStream_t stream);
+// Sum of status[0, n) over the rejected entries (status > 0): out[0] += count, out[1] += sum.
+hipError_t launch_mine_sum(const int* status, unsigned long long n, unsigned long long* out, hipStream_t stream);
+
 // Hardware-queue probe (k_misc.hip): a one-wave spin of `ticks` wall-clock ticks (100 MHz) that leaves its end time in
 // *out (mapped pinned host memory), and a kernel that leaves the time it ran.
 hipError_t launch_hwq_spin(long long ticks, unsigned long long* out, hipStream_t stream);
