@@ -35,6 +35,16 @@ void maybe_throw(const Cascador* c) {
   if (c->kn.test_throw == 1) throw std::bad_alloc();
   if (c->kn.test_throw == 2) throw std::runtime_error("injected by test_throw");
 }
+// rows of a job -> the caller: the buffer itself, not a copy
+template <class D>
+int rows_out(Cascador* c, int rc, RowsOut<typename D::Real>& v, typename D::Real** rows, int* n_rows) {
+  *rows = nullptr; *n_rows = 0;
+  if (rc != 0) return rc;
+  *n_rows = (int)(v.n / ((size_t)D::head + c->hm.dim()));
+  *rows = v.release();
+  if (!*rows) { *n_rows = 0; fail("out of memory for the detection rows"); return -1; }
+  return 0;
+}
 }  // namespace
 #define JDA_ABI_CATCH(ret) catch (...) { abi_exception(__func__, false); return ret; }
 #define JDA_ABI_CATCH_SYNC(ret) catch (...) { abi_exception(__func__, true); return ret; }
@@ -243,7 +253,7 @@ int jdaDetectBatchRagged(void* cascador, const unsigned char* const* images, con
   Cascador* c = (Cascador*)cascador;
   if (!c || !images || !widths || !heights || !out || n < 0) { fail("bad arguments"); return -1; }
   if (opt && opt->dialect != JDA_DIALECT_C) { fail("jdaDetectBatchRagged runs dialect C"); return -1; }
-  return detect_ragged(c, images, nullptr, nullptr, widths, heights, n, scale, min_size, max_size, th, opt, out);
+  return detect_ragged(c, images, nullptr, nullptr, widths, heights, n, scale, min_size, max_size, th, opt, Sink<DialectC>{out});
 } JDA_ABI_CATCH_SYNC(-1)
 
 int jdaDetectBatchRaggedDevice(void* cascador, const unsigned char* d_base, const size_t* offsets, const int* widths,
@@ -254,28 +264,9 @@ int jdaDetectBatchRaggedDevice(void* cascador, const unsigned char* d_base, cons
   Cascador* c = (Cascador*)cascador;
   if (!c || !d_base || !offsets || !widths || !heights || !out || n < 0) { fail("bad arguments"); return -1; }
   if (opt && opt->dialect != JDA_DIALECT_C) { fail("jdaDetectBatchRaggedDevice runs dialect C"); return -1; }
-  return detect_ragged(c, nullptr, d_base, offsets, widths, heights, n, scale, min_size, max_size, th, opt, out);
+  return detect_ragged(c, nullptr, d_base, offsets, widths, heights, n, scale, min_size, max_size, th, opt, Sink<DialectC>{out});
 } JDA_ABI_CATCH_SYNC(-1)
 
-namespace {
-// rows of a job -> the caller: the buffer itself, not a copy
-int ragged_rows_out_f(Cascador* c, int rc, RowsOut<float>& v, float** rows, int* n_rows) {
-  *rows = nullptr; *n_rows = 0;
-  if (rc != 0) return rc;
-  *n_rows = (int)(v.n / ((size_t)5 + c->hm.dim()));
-  *rows = v.release();
-  if (!*rows) { *n_rows = 0; fail("out of memory for the detection rows"); return -1; }
-  return 0;
-}
-int ragged_rows_out_d(Cascador* c, int rc, RowsOut<double>& v, double** rows, int* n_rows) {
-  *rows = nullptr; *n_rows = 0;
-  if (rc != 0) return rc;
-  *n_rows = (int)(v.n / ((size_t)6 + c->hm.dim()));
-  *rows = v.release();
-  if (!*rows) { *n_rows = 0; fail("out of memory for the detection rows"); return -1; }
-  return 0;
-}
-}  // namespace
 
 int jdaDetectBatchRaggedRows(void* cascador, const unsigned char* const* images, const int* widths, const int* heights, int n,
                              float scale, float step, int min_size, int max_size, float th, const jdaDetectOptions* opt,
@@ -286,8 +277,8 @@ int jdaDetectBatchRaggedRows(void* cascador, const unsigned char* const* images,
   if (!c || !images || !widths || !heights || !rows || !n_rows || n < 0) { fail("bad arguments"); return -1; }
   if (opt && opt->dialect != JDA_DIALECT_C) { fail("jdaDetectBatchRaggedRows runs dialect C"); return -1; }
   RowsOut<float> v;
-  const int rc = detect_ragged_rows(c, images, nullptr, nullptr, widths, heights, n, scale, min_size, max_size, th, opt, frame_offset, &v);
-  return ragged_rows_out_f(c, rc, v, rows, n_rows);
+  const int rc = detect_ragged(c, images, nullptr, nullptr, widths, heights, n, scale, min_size, max_size, th, opt, Sink<DialectC>{nullptr, &v, frame_offset});
+  return rows_out<DialectC>(c, rc, v, rows, n_rows);
 } JDA_ABI_CATCH_SYNC(-1)
 
 int jdaDetectBatchRaggedDeviceRows(void* cascador, const unsigned char* d_base, const size_t* offsets, const int* widths,
@@ -299,8 +290,8 @@ int jdaDetectBatchRaggedDeviceRows(void* cascador, const unsigned char* d_base, 
   if (!c || !d_base || !offsets || !widths || !heights || !rows || !n_rows || n < 0) { fail("bad arguments"); return -1; }
   if (opt && opt->dialect != JDA_DIALECT_C) { fail("jdaDetectBatchRaggedDeviceRows runs dialect C"); return -1; }
   RowsOut<float> v;
-  const int rc = detect_ragged_rows(c, nullptr, d_base, offsets, widths, heights, n, scale, min_size, max_size, th, opt, frame_offset, &v);
-  return ragged_rows_out_f(c, rc, v, rows, n_rows);
+  const int rc = detect_ragged(c, nullptr, d_base, offsets, widths, heights, n, scale, min_size, max_size, th, opt, Sink<DialectC>{nullptr, &v, frame_offset});
+  return rows_out<DialectC>(c, rc, v, rows, n_rows);
 } JDA_ABI_CATCH_SYNC(-1)
 
 void jdaRowsRelease(float* rows) { std::free(rows); }
@@ -309,27 +300,20 @@ jdaResult jdaDetect(void* cascador, unsigned char* data, int width, int height,
                     float scale, float step, int min_size, int max_size, float th) {
   Cascador* c = (Cascador*)cascador;
   jdaResult r;
-  r.n = 0; r.landmark_n = c ? c->hm.L : 0; r.bboxes = nullptr; r.shapes = nullptr; r.scores = nullptr;
+  blank<DialectC>(&r, c ? c->hm.L : 0);
   try {
-    if (!c || !data) { fail("jdaDetect: null cascador or image"); return empty_result(r.landmark_n); }
+    if (!c || !data) { fail("jdaDetect: null cascador or image"); return empty_result<DialectC>(r.landmark_n); }
     const unsigned char* frames[1] = {data};
-    if (jdaDetectBatch(cascador, frames, 1, width, height, scale, step, min_size, max_size, th, nullptr, &r) != 0) {
-      jdaResultRelease(r);
-      return empty_result(c->hm.L);
-    }
+    if (jdaDetectBatch(cascador, frames, 1, width, height, scale, step, min_size, max_size, th, nullptr, &r) != 0)
+      return empty_result<DialectC>(c->hm.L);        // (r is blank: a failed call leaves nothing allocated)
     return r;
-  } catch (...) {      // (jdaDetectBatch has its own barrier; what is left is the error string of the first branch)
+  } catch (...) {      // (jdaDetectBatch has its own barrier; what is left is the error string and empty_result; r is blank)
     abi_exception("jdaDetect", false);
-    r.n = 0; r.bboxes = nullptr; r.shapes = nullptr; r.scores = nullptr;
     return r;
   }
 }
 
-void jdaResultRelease(jdaResult result) {
-  std::free(result.bboxes);
-  std::free(result.shapes);
-  std::free(result.scores);
-}
+void jdaResultRelease(jdaResult result) { release<DialectC>(&result); }
 
 int jdaTraceBatch(void* cascador, const unsigned char* const* frames, int n, int width, int height,
                   float scale, int min_size, int max_size, int* carts_n, float* score,
@@ -436,7 +420,7 @@ static int detect_cpp_pyramid_impl(void* cascador, const unsigned char* const* f
   Cascador* c = (Cascador*)cascador;
   if (!c || !frames || !out || n < 0) { fail("bad arguments"); return -1; }
   const int L = c->hm.L, dim = c->hm.dim();
-  for (int i = 0; i < n; i++) { out[i].n = 0; out[i].landmark_n = L; out[i].rects = nullptr; out[i].shapes = nullptr; out[i].scores = nullptr; }
+  OutGuard<DialectCpp> guard(out, n, L);
   if (origin_size < 1 || step < 1 || !(factor > 1.0)) { fail("origin_size/step must be positive and factor > 1"); return -1; }
   const bool multi = c->hm.multi_scale();
   if (multi && (half_size < 1 || quarter_size < 1 || half_size > 4096 || quarter_size > 4096)) {
@@ -452,10 +436,9 @@ static int detect_cpp_pyramid_impl(void* cascador, const unsigned char* const* f
   size_t stride0 = 0;
   if (!stage_frames(ln, frames, n, (size_t)width * height, &stride0)) return -1;
 
-  // per level: rects (already scaled back), scores, normalised shapes, per frame, in scan order
-  struct Cand { int rect[4]; double score; size_t shape_at; };
-  std::vector<std::vector<Cand>> per_frame(n);
-  std::vector<double> shape_pool;
+  // per frame, level after level in scan order: rects (already scaled back), scores, normalised shapes
+  struct Cands { std::vector<int> rc; std::vector<double> sc, sh; };
+  std::vector<Cands> per_frame(n);
   RunStats rs_total;
   long long patch_total = 0;
   // level images ping-pong inside one buffer; level 0 is the staged input
@@ -479,21 +462,14 @@ static int detect_cpp_pyramid_impl(void* cascador, const unsigned char* const* f
       HostFrames hf;
       if (multi) { hf.patch_hs = half_size; hf.patch_qs = quarter_size; }
       if (!run_device<double>(c, lanes, pe, cur, cur_stride, n, false, 0.0, nullptr, &dets, nullptr, &rs, hf)) return false;
-      rs_total.carts += rs.carts; rs_total.out += rs.out; rs_total.gpu_ms += rs.gpu_ms; rs_total.scan_ms += rs.scan_ms;
-      rs_total.carts_scan += rs.carts_scan; rs_total.win_scan += rs.win_scan; rs_total.scan_launches += rs.scan_launches;
-      rs_total.tail += rs.tail;
-      for (int t = 0; t < c->hm.T; t++) rs_total.stage_done[t] += rs.stage_done[t];
+      rs_total += rs;
       patch_total += sp.windows * n;
       for (size_t i = 0; i < dets.gid.size(); i++) {
         const WinRef wr = locate(sp, dets.gid[i]);
-        Cand cd;
-        int rx = wr.x, ry = wr.y, rw = wr.win, rh = wr.win;
-        rx = (int)(rx * scale); ry = (int)(ry * scale); rw = (int)(rw * scale); rh = (int)(rh * scale);   // cascador.cpp:292-294
-        cd.rect[0] = rx; cd.rect[1] = ry; cd.rect[2] = rw; cd.rect[3] = rh;
-        cd.score = dets.score[i];
-        cd.shape_at = shape_pool.size();
-        shape_pool.insert(shape_pool.end(), dets.shape.begin() + i * dim, dets.shape.begin() + (i + 1) * dim);
-        per_frame[wr.frame].push_back(cd);
+        Cands& cf = per_frame[wr.frame];
+        for (int v : {wr.x, wr.y, wr.win, wr.win}) cf.rc.push_back((int)(v * scale));   // cascador.cpp:292-294
+        cf.sc.push_back(dets.score[i]);
+        cf.sh.insert(cf.sh.end(), dets.shape.begin() + i * dim, dets.shape.begin() + (i + 1) * dim);
       }
       scale *= factor;                                            // cascador.cpp:299
       const int nw = (int)(w / factor), nh = (int)(h / factor);   // cascador.cpp:300-301
@@ -516,31 +492,13 @@ static int detect_cpp_pyramid_impl(void* cascador, const unsigned char* const* f
 
   const double t0 = now_ms();
   size_t total = 0;
-  for (auto& v : per_frame) total += v.size();
+  for (auto& v : per_frame) total += v.sc.size();
   parallel_for(n, [&](int f) {
-    const std::vector<Cand>& cs = per_frame[f];
-    const size_t cnt = cs.size();
-    std::vector<int> rc(cnt * 4);
-    std::vector<double> sc(cnt);
-    for (size_t i = 0; i < cnt; i++) { std::memcpy(&rc[4 * i], cs[i].rect, 16); sc[i] = cs[i].score; }
-    std::vector<int> pick;
-    if (nms) pick = nms_dialect_cpp(rc.data(), sc.data(), (int)cnt, overlap);
-    else { pick.resize(cnt); std::iota(pick.begin(), pick.end(), 0); }
-    jdaResultD& r = out[f];
-    r.n = (int)pick.size(); r.landmark_n = L;
-    r.rects = (int*)std::malloc(std::max<size_t>(1, pick.size() * 4) * sizeof(int));
-    r.scores = (double*)std::malloc(std::max<size_t>(1, pick.size()) * sizeof(double));
-    r.shapes = (double*)std::malloc(std::max<size_t>(1, pick.size() * dim) * sizeof(double));
-    for (size_t i = 0; i < pick.size(); i++) {
-      const int k = pick[i];
-      std::memcpy(r.rects + 4 * i, &rc[4 * k], 4 * sizeof(int));
-      r.scores[i] = sc[k];
-      double* sh = r.shapes + i * dim;
-      std::memcpy(sh, &shape_pool[cs[k].shape_at], dim * sizeof(double));
-      relocate_dialect_cpp(sh, L, rc[4 * k], rc[4 * k + 1], rc[4 * k + 2], rc[4 * k + 3]);
-    }
+    const Cands& cf = per_frame[f];
+    emit<DialectCpp>(cf.rc.data(), cf.sc.data(), cf.sh.data(), (int)cf.sc.size(), L, nms != 0, overlap, &out[f]);
   }, total < 6000);
   fill_stats(stats, rs_total, patch_total, c->hm.T, c->hm.K, now_ms() - t0);
+  guard.keep = true;
   return 0;
 }
 
@@ -572,32 +530,11 @@ int jdaNmsCpp(const int* rects, const double* scores, int n, double overlap, int
 } JDA_ABI_CATCH(-1)
 
 int jdaResultsPack(const jdaResult* results, int n, int frame_offset, float* rows, int capacity_rows) try {
-  if (!results || n < 0) return -1;
-  long long total = 0;
-  for (int i = 0; i < n; i++) total += results[i].n;
-  if (!rows) return (int)total;
-  if (total > capacity_rows) return -1;
-  float* o = rows;
-  for (int i = 0; i < n; i++) {
-    const jdaResult& r = results[i];
-    const int dim = 2 * r.landmark_n;
-    for (int j = 0; j < r.n; j++) {
-      o[0] = (float)(frame_offset + i);
-      o[1] = (float)r.bboxes[3 * j]; o[2] = (float)r.bboxes[3 * j + 1]; o[3] = (float)r.bboxes[3 * j + 2];
-      o[4] = r.scores[j];
-      std::memcpy(o + 5, r.shapes + (size_t)j * dim, dim * sizeof(float));
-      o += 5 + dim;
-    }
-  }
-  return (int)total;
+  return results && n >= 0 ? (int)pack<DialectC>(results, n, frame_offset, rows, capacity_rows) : -1;
 } JDA_ABI_CATCH(-1)
 
 void jdaResultsRelease(jdaResult* results, int n) {
-  if (!results) return;
-  for (int i = 0; i < n; i++) {
-    std::free(results[i].bboxes); std::free(results[i].shapes); std::free(results[i].scores);
-    results[i].bboxes = nullptr; results[i].shapes = nullptr; results[i].scores = nullptr; results[i].n = 0;
-  }
+  for (int i = 0; results && i < n; i++) release<DialectC>(results + i);
 }
 
 // Tile plan of a dialect-C call without touching a device (tests, tools): per level 10 ints
@@ -662,11 +599,7 @@ __attribute__((visibility("default"))) int jdaDebugScanTiming(void* cascador, un
 }
 #endif
 
-void jdaResultDRelease(jdaResultD result) {
-  std::free(result.rects);
-  std::free(result.shapes);
-  std::free(result.scores);
-}
+void jdaResultDRelease(jdaResultD result) { release<DialectCpp>(&result); }
 
 int jdaDetectBatchCpp(void* cascador, const unsigned char* const* frames, int n, int width, int height,
                       int minimum_size, int step, double factor, double overlap, int nms,
@@ -694,7 +627,7 @@ int jdaDetectBatchCppRagged(void* cascador, const unsigned char* const* images, 
   g_err.clear();
   Cascador* c = (Cascador*)cascador;
   if (!c || !images || !widths || !heights || !out || n < 0) { fail("bad arguments"); return -1; }
-  return detect_ragged_cpp(c, images, nullptr, nullptr, widths, heights, n, CppCall{minimum_size, step, factor, overlap, nms}, stats, out);
+  return detect_ragged_cpp(c, images, nullptr, nullptr, widths, heights, n, CppCall{minimum_size, step, factor, overlap, nms}, stats, Sink<DialectCpp>{out});
 } JDA_ABI_CATCH_SYNC(-1)
 
 int jdaDetectBatchCppRaggedDevice(void* cascador, const unsigned char* d_base, const size_t* offsets, const int* widths,
@@ -703,7 +636,7 @@ int jdaDetectBatchCppRaggedDevice(void* cascador, const unsigned char* d_base, c
   g_err.clear();
   Cascador* c = (Cascador*)cascador;
   if (!c || !d_base || !offsets || !widths || !heights || !out || n < 0) { fail("bad arguments"); return -1; }
-  return detect_ragged_cpp(c, nullptr, d_base, offsets, widths, heights, n, CppCall{minimum_size, step, factor, overlap, nms}, stats, out);
+  return detect_ragged_cpp(c, nullptr, d_base, offsets, widths, heights, n, CppCall{minimum_size, step, factor, overlap, nms}, stats, Sink<DialectCpp>{out});
 } JDA_ABI_CATCH_SYNC(-1)
 
 int jdaDetectBatchCppRaggedRows(void* cascador, const unsigned char* const* images, const int* widths, const int* heights, int n,
@@ -713,8 +646,9 @@ int jdaDetectBatchCppRaggedRows(void* cascador, const unsigned char* const* imag
   Cascador* c = (Cascador*)cascador;
   if (!c || !images || !widths || !heights || !rows || !n_rows || n < 0) { fail("bad arguments"); return -1; }
   RowsOut<double> v;
-  const int rc = detect_ragged_cpp_rows(c, images, nullptr, nullptr, widths, heights, n, CppCall{minimum_size, step, factor, overlap, nms}, stats, frame_offset, &v);
-  return ragged_rows_out_d(c, rc, v, rows, n_rows);
+  const int rc = detect_ragged_cpp(c, images, nullptr, nullptr, widths, heights, n, CppCall{minimum_size, step, factor, overlap, nms}, stats,
+                                 Sink<DialectCpp>{nullptr, &v, frame_offset});
+  return rows_out<DialectCpp>(c, rc, v, rows, n_rows);
 } JDA_ABI_CATCH_SYNC(-1)
 
 int jdaDetectBatchCppRaggedDeviceRows(void* cascador, const unsigned char* d_base, const size_t* offsets, const int* widths,
@@ -724,39 +658,19 @@ int jdaDetectBatchCppRaggedDeviceRows(void* cascador, const unsigned char* d_bas
   Cascador* c = (Cascador*)cascador;
   if (!c || !d_base || !offsets || !widths || !heights || !rows || !n_rows || n < 0) { fail("bad arguments"); return -1; }
   RowsOut<double> v;
-  const int rc = detect_ragged_cpp_rows(c, nullptr, d_base, offsets, widths, heights, n, CppCall{minimum_size, step, factor, overlap, nms}, stats, frame_offset, &v);
-  return ragged_rows_out_d(c, rc, v, rows, n_rows);
+  const int rc = detect_ragged_cpp(c, nullptr, d_base, offsets, widths, heights, n, CppCall{minimum_size, step, factor, overlap, nms}, stats,
+                                 Sink<DialectCpp>{nullptr, &v, frame_offset});
+  return rows_out<DialectCpp>(c, rc, v, rows, n_rows);
 } JDA_ABI_CATCH_SYNC(-1)
 
 void jdaRowsDRelease(double* rows) { std::free(rows); }
 
 int jdaResultsDPack(const jdaResultD* results, int n, int frame_offset, double* rows, int capacity_rows) try {
-  if (!results || n < 0) return -1;
-  long long total = 0;
-  for (int i = 0; i < n; i++) total += results[i].n;
-  if (!rows) return (int)total;
-  if (total > capacity_rows) return -1;
-  double* o = rows;
-  for (int i = 0; i < n; i++) {
-    const jdaResultD& r = results[i];
-    const int dim = 2 * r.landmark_n;
-    for (int j = 0; j < r.n; j++) {
-      o[0] = (double)(frame_offset + i);
-      for (int k = 0; k < 4; k++) o[1 + k] = (double)r.rects[4 * j + k];
-      o[5] = r.scores[j];
-      std::memcpy(o + 6, r.shapes + (size_t)j * dim, dim * sizeof(double));
-      o += 6 + dim;
-    }
-  }
-  return (int)total;
+  return results && n >= 0 ? (int)pack<DialectCpp>(results, n, frame_offset, rows, capacity_rows) : -1;
 } JDA_ABI_CATCH(-1)
 
 void jdaResultsDRelease(jdaResultD* results, int n) {
-  if (!results) return;
-  for (int i = 0; i < n; i++) {
-    std::free(results[i].rects); std::free(results[i].shapes); std::free(results[i].scores);
-    results[i].rects = nullptr; results[i].shapes = nullptr; results[i].scores = nullptr; results[i].n = 0;
-  }
+  for (int i = 0; results && i < n; i++) release<DialectCpp>(results + i);
 }
 
 }  // extern "C"

@@ -67,8 +67,7 @@ int detect_c_device(Cascador* c, const uint8_t* d_frames, size_t stride, int n, 
                            jdaResult* out, const unsigned char* const* host_frames) {
   const double t_call = now_ms();
   if (!c || !out || n < 0) { fail("bad arguments"); return -1; }
-  const int L = c->hm.L;
-  for (int i = 0; i < n; i++) { out[i].n = 0; out[i].landmark_n = L; out[i].bboxes = nullptr; out[i].shapes = nullptr; out[i].scores = nullptr; }
+  OutGuard<DialectC> guard(out, n, c->hm.L);
   if (host_frames) stride = (size_t)width * height;
   ScanPlan sp;
   PlanEntry* pe = nullptr;
@@ -91,9 +90,11 @@ int detect_c_device(Cascador* c, const uint8_t* d_frames, size_t stride, int n, 
   rs.timed = opt && opt->stats;
   if (!run_device<float>(c, lanes, pe, d_frames, stride, n, true, th, opt ? (hipStream_t)opt->hip_stream : nullptr, &dets, nullptr, &rs, host))
     return -1;
-  const double post_ms = post_c(c, sp, dets, n, opt, out);
+  const double post_ms = post_frames<DialectC>(sp.levels, FrameSet{n, sp.windows, sp.width, sp.height}, dets, c->hm.L, host.nms, host.nms_overlap,
+                                               Sink<DialectC>{out});
   fill_stats(opt ? opt->stats : nullptr, rs, sp.windows * n, c->hm.T, c->hm.K, post_ms);
   if (opt && opt->stats) opt->stats->call_ms = now_ms() - t_call;
+  guard.keep = true;
   return 0;
 }
 

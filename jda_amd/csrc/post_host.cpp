@@ -1,25 +1,9 @@
-// libjda.so, host side: detections of a batch -> per-frame results (sort back into scan order is done by the pass;
-// here: window of a gid, the worker pool of the per-frame post-processing, NMS + relocation through post.cpp, the
-// jdaResult structs and the statistics block).  Reference: c/jda.c:237-316, 414-440.
+// libjda.so, host side: detections of a batch -> per-frame results or rows (sort back into scan order is done by the pass;
+// here: the worker pool of the per-frame post-processing, the driver over the frames of a batch -- the result format
+// itself is results.h -- and the statistics block).  Reference: c/jda.c:237-316, 414-440.
 #include "detect.h"
 
 namespace jda {
-
-// window of a gid
-WinRef locate(const ScanPlan& sp, uint32_t gid) {
-  WinRef r;
-  r.frame = (int)(gid / (uint32_t)sp.windows);
-  const long long wid = gid - (long long)r.frame * sp.windows;
-  size_t l = 0;
-  for (size_t i = 1; i < sp.levels.size(); i++)
-    if (wid >= sp.levels[i].base) l = i;
-  const Level& lv = sp.levels[l];
-  const long long rel = wid - lv.base;
-  r.y = (int)(rel / lv.nx) * lv.step;
-  r.x = (int)(rel % lv.nx) * lv.step;
-  r.win = lv.win;
-  return r;
-}
 
 // Host post-processing pool: a few persistent workers for the per-frame NMS + result assembly of
 // a batch (0.9 us per frame, 0.22 ms per 256-frame batch when done by the calling thread alone;
@@ -161,74 +145,114 @@ void fill_stats(jdaStats* st, const RunStats& rs, long long patch_n, int T, int 
   st->scan_lds_ms = rs.scan_lds_ms; st->scan_lds_cart_n = rs.carts_scan - rs.carts_scan_glb;
 }
 
-jdaResult empty_result(int landmark_n) {
-  jdaResult r;
-  r.n = 0; r.landmark_n = landmark_n;
-  r.bboxes = (int*)std::malloc(sizeof(int));
-  r.shapes = (float*)std::malloc(sizeof(float));
-  r.scores = (float*)std::malloc(sizeof(float));
-  return r;
+// The statistics block of a per-image call back into the sums fill_stats made it from (the ragged job's per-image fallback)
+RunStats run_stats_of(const jdaStats& st) {
+  RunStats rs;
+  rs.carts = st.cart_total_n; rs.out = st.face_patch_n;
+  for (int t = 0; t < 16 && t < kMaxStages; t++) rs.stage_done[t] = st.stage_done_n[t];
+  rs.gpu_ms = st.gpu_ms; rs.scan_ms = st.scan_ms;
+  rs.carts_scan = st.scan_cart_n; rs.win_scan = st.scan_patch_n; rs.scan_launches = st.scan_launches;
+  rs.tail = st.handoff_n;
+  rs.dense_passes = st.dense_passes;
+  rs.scan_fallbacks = st.scan_fallbacks;
+  rs.ws_regrows = st.ws_regrows;
+  rs.scan_lds_ms = st.scan_lds_ms; rs.carts_scan_glb = st.scan_cart_n - st.scan_lds_cart_n;
+  return rs;
 }
 
-// NMS, relocation and the jdaResult of every frame of a dialect-C batch from its raw detections
-// (sorted by gid = frame, then scan order).  Returns the time it took (ms).
-double post_c(Cascador* c, const ScanPlan& sp, const RawDets<float>& dets, int n, const jdaDetectOptions* opt,
-                     jdaResult* out) {
+RunStats& operator+=(RunStats& a, const RunStats& b) {
+  a.carts += b.carts; a.out += b.out; a.carts_scan += b.carts_scan; a.carts_scan_glb += b.carts_scan_glb;
+  a.win_scan += b.win_scan; a.tail += b.tail; a.gpu_ms += b.gpu_ms; a.scan_ms += b.scan_ms; a.scan_lds_ms += b.scan_lds_ms;
+  a.scan_launches += b.scan_launches; a.dense_passes += b.dense_passes; a.scan_fallbacks += b.scan_fallbacks; a.ws_regrows += b.ws_regrows;
+  for (int t = 0; t < kMaxStages; t++) a.stage_done[t] += b.stage_done[t];
+  return a;
+}
+
+template <class D>
+double post_frames(const std::vector<Level>& levels, const FrameSet& fs, const RawDets<typename D::Real>& dets, int L, bool nms,
+                   double overlap, const Sink<D>& sink) {
+  using Real = typename D::Real;
   const double t0 = now_ms();
-  const int L = c->hm.L, dim = c->hm.dim();
-  const bool do_nms = !opt || opt->nms;
-  const float overlap = opt ? opt->nms_overlap : 0.3f;
-  // split by frame (dets are sorted by gid)
-  std::vector<size_t> first(n + 1, dets.gid.size());
+  const int n = fs.n, dim = 2 * L;
+  const size_t nd = dets.gid.size();
+  std::vector<size_t> first((size_t)n + 1);          // frame f's candidates: [first[f], first[f + 1])
   {
     size_t i = 0;
     for (int f = 0; f < n; f++) {
       first[f] = i;
-      while (i < dets.gid.size() && dets.gid[i] / (uint32_t)sp.windows == (uint32_t)f) i++;
+      while (i < nd && (long long)dets.gid[i] < fs.gid0(f + 1)) i++;
     }
     first[n] = i;
   }
+  // frames whose pass was post-processed on the device (k_post, dialect C): kept detections, relocated, in scan order,
+  // rows [p_first[f], p_first[f] + p_n[f]) of p_bb (x, y, size) / p_sc / p_sh
   const bool some_posted = dets.p_n.size() == (size_t)n;
-  parallel_for(n, [&](int f) {
-    if (some_posted && dets.p_n[f] >= 0) {
-      // this frame's pass was post-processed on the device (k_post): kept detections, relocated, in scan order
-      const size_t k = (size_t)dets.p_n[f], r0 = (size_t)dets.p_first[f];
-      jdaResult& r = out[f];
-      r.n = (int)k; r.landmark_n = L;
-      r.bboxes = (int*)std::malloc(std::max<size_t>(1, k * 3) * sizeof(int));
-      r.scores = (float*)std::malloc(std::max<size_t>(1, k) * sizeof(float));
-      r.shapes = (float*)std::malloc(std::max<size_t>(1, k * dim) * sizeof(float));
-      if (k) {
-        std::memcpy(r.bboxes, &dets.p_bb[r0 * 3], k * 3 * sizeof(int));
-        std::memcpy(r.scores, &dets.p_sc[r0], k * sizeof(float));
-        std::memcpy(r.shapes, &dets.p_sh[r0 * dim], k * dim * sizeof(float));
+  auto posted = [&](int f) { return some_posted && dets.p_n[f] >= 0; };
+  // window boxes of frame f's candidates, in scan order
+  auto decode = [&](int f, int* b) {
+    GidWalk walk(levels, fs.w(f), fs.h(f), (uint32_t)fs.gid0(f));
+    for (size_t i = first[f]; i < first[f + 1]; i++, b += D::box) walk.box<D>(dets.gid[i], b);
+  };
+  if (!sink.rows) {
+    parallel_for(n, [&](int f) {
+      typename D::Result& r = sink.out[f];
+      if (posted(f)) {
+        const size_t k = (size_t)dets.p_n[f], r0 = (size_t)dets.p_first[f];
+        alloc<D>(&r, k, L);
+        if (k) {
+          std::memcpy(D::boxes(r), &dets.p_bb[r0 * D::box], k * D::box * sizeof(int));
+          std::memcpy(r.scores, &dets.p_sc[r0], k * sizeof(Real));
+          std::memcpy(r.shapes, &dets.p_sh[r0 * dim], k * dim * sizeof(Real));
+        }
+        return;
       }
+      const size_t a = first[f], cnt = first[f + 1] - a;
+      static thread_local std::vector<int> boxes;          // per-frame scratch, grown once per thread
+      boxes.resize(cnt * D::box);
+      decode(f, boxes.data());
+      emit<D>(boxes.data(), dets.score.data() + a, dets.shape.data() + a * dim, (int)cnt, L, nms, overlap, &r);
+    }, nd < 6000);
+    return now_ms() - t0;
+  }
+  // rows, no result structs in between (a 2,845-image dialect-CPP job keeps 15 MB of rows).  A frame's picks (NMS) go
+  // where its candidates are; pick_frame returns how many rows it has, write_frame writes them from o on.
+  std::vector<int> boxes(nd * D::box), picks(nd);
+  auto pick_frame = [&](int f) -> size_t {
+    if (posted(f)) return (size_t)dets.p_n[f];
+    const size_t a = first[f], cnt = first[f + 1] - a;
+    static thread_local std::vector<int> keep;
+    decode(f, boxes.data() + a * D::box);
+    pick<D>(boxes.data() + a * D::box, dets.score.data() + a, (int)cnt, nms, overlap, &keep);
+    std::copy(keep.begin(), keep.end(), picks.begin() + a);
+    return keep.size();
+  };
+  const size_t rw = (size_t)D::head + dim;
+  auto write_frame = [&](int f, Real* o, size_t k) {
+    const int frame = sink.frame_offset + f;
+    if (posted(f)) {
+      for (size_t j = (size_t)dets.p_first[f]; j < (size_t)dets.p_first[f] + k; j++)
+        o = write_row<D>(o, frame, &dets.p_bb[j * D::box], dets.p_sc[j], &dets.p_sh[j * dim], dim);
       return;
     }
-    const size_t a = first[f], cnt = first[f + 1] - a;
-    static thread_local std::vector<int> bb, keep;          // per-frame scratch, grown once per thread
-    bb.resize(cnt * 3);
-    for (size_t i = 0; i < cnt; i++) {
-      const WinRef wr = locate(sp, dets.gid[a + i]);
-      bb[3 * i] = wr.x; bb[3 * i + 1] = wr.y; bb[3 * i + 2] = wr.win;
+    const size_t a = first[f];
+    write_rows<D>(o, frame, boxes.data() + a * D::box, dets.score.data() + a, dets.shape.data() + a * dim, picks.data() + a, k, L);
+  };
+  if (!D::parallel_rows) {             // frame after frame on the calling thread, rows appended
+    for (int f = 0; f < n; f++) {
+      const size_t k = pick_frame(f);
+      write_frame(f, sink.rows->grow(k * rw), k);
     }
-    if (do_nms) nms_dialect_c_into(bb.data(), dets.score.data() + a, (int)cnt, overlap, &keep);
-    else { keep.resize(cnt); std::iota(keep.begin(), keep.end(), 0); }
-    jdaResult& r = out[f];
-    r.n = (int)keep.size(); r.landmark_n = L;
-    r.bboxes = (int*)std::malloc(std::max<size_t>(1, keep.size() * 3) * sizeof(int));
-    r.scores = (float*)std::malloc(std::max<size_t>(1, keep.size()) * sizeof(float));
-    r.shapes = (float*)std::malloc(std::max<size_t>(1, keep.size() * dim) * sizeof(float));
-    for (size_t i = 0; i < keep.size(); i++) {
-      const int k = keep[i];
-      std::memcpy(r.bboxes + 3 * i, &bb[3 * k], 3 * sizeof(int));
-      r.scores[i] = dets.score[a + k];
-      float* sh = r.shapes + i * dim;
-      std::memcpy(sh, &dets.shape[(a + k) * dim], dim * sizeof(float));
-      relocate_dialect_c(sh, L, bb[3 * k], bb[3 * k + 1], bb[3 * k + 2]);
-    }
-  }, dets.gid.size() < 6000);
+    return now_ms() - t0;
+  }
+  // NMS per frame in parallel, then every frame's rows written in place, in parallel
+  std::vector<size_t> row0((size_t)n + 1, 0);
+  parallel_for(n, [&](int f) { row0[(size_t)f + 1] = pick_frame(f); }, nd < 6000);
+  for (int f = 0; f < n; f++) row0[(size_t)f + 1] += row0[f];
+  Real* base = sink.rows->grow(row0[n] * rw);
+  parallel_for(n, [&](int f) { write_frame(f, base + row0[f] * rw, row0[(size_t)f + 1] - row0[f]); }, row0[n] < 2000);
   return now_ms() - t0;
 }
+template double post_frames<DialectC>(const std::vector<Level>&, const FrameSet&, const RawDets<float>&, int, bool, double, const Sink<DialectC>&);
+template double post_frames<DialectCpp>(const std::vector<Level>&, const FrameSet&, const RawDets<double>&, int, bool, double, const Sink<DialectCpp>&);
 
 }  // namespace jda

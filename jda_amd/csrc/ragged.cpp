@@ -436,252 +436,59 @@ static bool ragged_build_chunk(Cascador* c, const RaggedJob& job, int i0, int n,
   return true;
 }
 
-// NMS, relocation and the jdaResult of every image of a ragged chunk (dets sorted by gid = image, level, y, x).
-// rows != nullptr (jdaDetectBatchRagged[Device]Rows): no jdaResult per image -- three allocations each, 1,065 for a
-// 355-image job whose 1,170 detections are 270 KB -- but one row [frame_offset + image index, x, y, size, score, shape]
-// per detection appended to *rows, images in order (what jdaResultsPack makes of the jdaResults, what the multi-GPU
-// gather ships).
-static double post_ragged(Cascador* c, const RaggedJob& job, const RaggedChunk& ch, const RawDets<float>& dets,
-                          const jdaDetectOptions* opt, jdaResult* out, RowsOut<float>* rows = nullptr, int frame_offset = 0) {
-  const double t0 = now_ms();
-  const int L = c->hm.L, dim = c->hm.dim();
-  const bool do_nms = !opt || opt->nms;
-  const float overlap = opt ? opt->nms_overlap : 0.3f;
-  const DevPlan& hp = job.pe->hp;
-  std::vector<size_t> first(ch.n + 1, dets.gid.size());
-  {
-    size_t i = 0;
-    for (int f = 0; f < ch.n; f++) {
-      first[f] = i;
-      while (i < dets.gid.size() && dets.gid[i] < ch.gid_base[f + 1]) i++;
-    }
-    first[ch.n] = i;
-  }
-  const bool some_posted = dets.p_n.size() == (size_t)ch.n;
-  auto one = [&](int f, jdaResult& r) {
-    if (some_posted && dets.p_n[f] >= 0) {           // post-processed on the device (k_post)
-      const size_t k = (size_t)dets.p_n[f], r0 = (size_t)dets.p_first[f];
-      r.n = (int)k; r.landmark_n = L;
-      r.bboxes = (int*)std::malloc(std::max<size_t>(1, k * 3) * sizeof(int));
-      r.scores = (float*)std::malloc(std::max<size_t>(1, k) * sizeof(float));
-      r.shapes = (float*)std::malloc(std::max<size_t>(1, k * dim) * sizeof(float));
-      if (k) {
-        std::memcpy(r.bboxes, &dets.p_bb[r0 * 3], k * 3 * sizeof(int));
-        std::memcpy(r.scores, &dets.p_sc[r0], k * sizeof(float));
-        std::memcpy(r.shapes, &dets.p_sh[r0 * dim], k * dim * sizeof(float));
-      }
-      return;
-    }
-    const size_t a = first[f], cnt = first[f + 1] - a;
-    static thread_local std::vector<int> bb, keep;
-    bb.resize(cnt * 3);
-    const int W = ch.widths[f], H = ch.heights[f];
-    int l = 0;
-    uint32_t lbase = ch.gid_base[f];
-    int nx = 0, cntl = 0;
-    auto level_grid = [&](int lv) {
-      const DevLevel& d = hp.lv[lv];
-      nx = (W - d.win) / d.step + 1;
-      cntl = nx * ((H - d.win) / d.step + 1);
-    };
-    if (cnt) level_grid(0);
-    for (size_t i = 0; i < cnt; i++) {          // gids ascend: levels are walked once
-      const uint32_t g = dets.gid[a + i];
-      while (g >= lbase + (uint32_t)cntl) { lbase += (uint32_t)cntl; l++; level_grid(l); }
-      const uint32_t rel = g - lbase;
-      const DevLevel& d = hp.lv[l];
-      bb[3 * i] = (int)(rel % (uint32_t)nx) * d.step; bb[3 * i + 1] = (int)(rel / (uint32_t)nx) * d.step; bb[3 * i + 2] = d.win;
-    }
-    if (do_nms) nms_dialect_c_into(bb.data(), dets.score.data() + a, (int)cnt, overlap, &keep);
-    else { keep.resize(cnt); std::iota(keep.begin(), keep.end(), 0); }
-    r.n = (int)keep.size(); r.landmark_n = L;
-    r.bboxes = (int*)std::malloc(std::max<size_t>(1, keep.size() * 3) * sizeof(int));
-    r.scores = (float*)std::malloc(std::max<size_t>(1, keep.size()) * sizeof(float));
-    r.shapes = (float*)std::malloc(std::max<size_t>(1, keep.size() * dim) * sizeof(float));
-    for (size_t i = 0; i < keep.size(); i++) {
-      const int k = keep[i];
-      std::memcpy(r.bboxes + 3 * i, &bb[3 * k], 3 * sizeof(int));
-      r.scores[i] = dets.score[a + k];
-      float* sh = r.shapes + i * dim;
-      std::memcpy(sh, &dets.shape[(a + k) * dim], dim * sizeof(float));
-      relocate_dialect_c(sh, L, bb[3 * k], bb[3 * k + 1], bb[3 * k + 2]);
-    }
-  };
-  if (rows) {
-    const size_t rw = (size_t)5 + dim;
-    for (int f = 0; f < ch.n; f++) {
-      const float fr = (float)(frame_offset + ch.i0 + f);
-      if (some_posted && dets.p_n[f] >= 0) {         // straight from what k_post left in pinned memory
-        const size_t k = (size_t)dets.p_n[f], r0 = (size_t)dets.p_first[f];
-        float* o = rows->grow(k * rw);
-        for (size_t j = 0; j < k; j++, o += rw) {
-          o[0] = fr; o[1] = (float)dets.p_bb[(r0 + j) * 3]; o[2] = (float)dets.p_bb[(r0 + j) * 3 + 1]; o[3] = (float)dets.p_bb[(r0 + j) * 3 + 2];
-          o[4] = dets.p_sc[r0 + j];
-          std::memcpy(o + 5, &dets.p_sh[(r0 + j) * dim], dim * sizeof(float));
-        }
-        continue;
-      }
-      jdaResult r{};
-      one(f, r);
-      float* o = rows->grow((size_t)r.n * rw);
-      for (int j = 0; j < r.n; j++, o += rw) {
-        o[0] = fr; o[1] = (float)r.bboxes[3 * j]; o[2] = (float)r.bboxes[3 * j + 1]; o[3] = (float)r.bboxes[3 * j + 2];
-        o[4] = r.scores[j];
-        std::memcpy(o + 5, r.shapes + (size_t)j * dim, dim * sizeof(float));
-      }
-      std::free(r.bboxes); std::free(r.scores); std::free(r.shapes);
-    }
-    return now_ms() - t0;
-  }
-  parallel_for(ch.n, [&](int f) { one(f, out[f]); }, dets.gid.size() < 6000);
-  return now_ms() - t0;
-}
-
-// The same for dialect CPP: candidates of an image in scan order -> Rect(x, y, win, win) (cascador.cpp:339), NMS by score
-// (cascador.cpp:387-429), relocation (462-474), jdaResultD.
-static double post_ragged(Cascador* c, const RaggedJob& job, const RaggedChunk& ch, const RawDets<double>& dets,
-                          const CppCall& call, jdaResultD* out, RowsOut<double>* rows = nullptr, int frame_offset = 0) {
-  const double t0 = now_ms();
-  const int L = c->hm.L, dim = c->hm.dim();
-  const DevPlan& hp = job.pe->hp;
-  std::vector<size_t> first(ch.n + 1, dets.gid.size());
-  {
-    size_t i = 0;
-    for (int f = 0; f < ch.n; f++) {
-      first[f] = i;
-      while (i < dets.gid.size() && dets.gid[i] < ch.gid_base[f + 1]) i++;
-    }
-    first[ch.n] = i;
-  }
-  // candidates of image f in scan order -> Rect(x, y, win, win) (cascador.cpp:339)
-  auto rects_of = [&](int f, std::vector<int>& rc) {
-    const size_t a = first[f], cnt = first[f + 1] - a;
-    rc.resize(cnt * 4);
-    const int W = ch.widths[f], H = ch.heights[f];
-    int l = 0;
-    uint32_t lbase = ch.gid_base[f];
-    int nx = 0, cntl = 0;
-    auto level_grid = [&](int lv) {
-      const DevLevel& d = hp.lv[lv];
-      nx = (W - d.win) / d.step + 1;
-      cntl = nx * ((H - d.win) / d.step + 1);
-    };
-    if (cnt) level_grid(0);
-    for (size_t i = 0; i < cnt; i++) {          // gids ascend: levels are walked once
-      const uint32_t g = dets.gid[a + i];
-      while (g >= lbase + (uint32_t)cntl) { lbase += (uint32_t)cntl; l++; level_grid(l); }
-      const uint32_t rel = g - lbase;
-      const DevLevel& d = hp.lv[l];
-      rc[4 * i] = (int)(rel % (uint32_t)nx) * d.step; rc[4 * i + 1] = (int)(rel / (uint32_t)nx) * d.step;
-      rc[4 * i + 2] = d.win; rc[4 * i + 3] = d.win;
-    }
-  };
-  if (rows) {
-    // rows mode: NMS per image in parallel (the picks), then every image's rows written in place, in parallel
-    std::vector<std::vector<int>> rcs((size_t)ch.n), picks((size_t)ch.n);
-    parallel_for(ch.n, [&](int f) {
-      const size_t a = first[f], cnt = first[f + 1] - a;
-      rects_of(f, rcs[(size_t)f]);
-      if (call.nms != 0) picks[(size_t)f] = nms_dialect_cpp(rcs[(size_t)f].data(), dets.score.data() + a, (int)cnt, call.overlap);   // cascador.cpp:444-446
-      else { picks[(size_t)f].resize(cnt); std::iota(picks[(size_t)f].begin(), picks[(size_t)f].end(), 0); }                         // cascador.cpp:447-451
-    }, dets.gid.size() < 6000);
-    std::vector<size_t> row0((size_t)ch.n + 1, 0);
-    for (int f = 0; f < ch.n; f++) row0[(size_t)f + 1] = row0[(size_t)f] + picks[(size_t)f].size();
-    const size_t rw = (size_t)6 + dim;
-    double* base = rows->grow(row0[(size_t)ch.n] * rw);
-    parallel_for(ch.n, [&](int f) {
-      const size_t a = first[f];
-      const std::vector<int>& rc = rcs[(size_t)f];
-      double* o = base + row0[(size_t)f] * rw;
-      for (int k : picks[(size_t)f]) {
-        o[0] = (double)(frame_offset + ch.i0 + f);
-        for (int q = 0; q < 4; q++) o[1 + q] = (double)rc[4 * (size_t)k + q];
-        o[5] = dets.score[a + k];
-        std::memcpy(o + 6, dets.shape.data() + (a + k) * dim, dim * sizeof(double));
-        relocate_dialect_cpp(o + 6, L, rc[4 * (size_t)k], rc[4 * (size_t)k + 1], rc[4 * (size_t)k + 2], rc[4 * (size_t)k + 3]);   // cascador.cpp:462-474
-        o += rw;
-      }
-    }, row0[(size_t)ch.n] < 2000);
-    return now_ms() - t0;
-  }
-  parallel_for(ch.n, [&](int f) {
-    const size_t a = first[f], cnt = first[f + 1] - a;
-    static thread_local std::vector<int> rc;
-    rects_of(f, rc);
-    emit_cpp_result(rc.data(), dets.score.data() + a, dets.shape.data() + a * dim, (int)cnt, L, call.overlap, call.nms != 0, &out[f]);
-  }, dets.gid.size() < 6000);
-  return now_ms() - t0;
-}
-
-static void add_stats(RunStats* a, const RunStats& b) {
-  a->carts += b.carts; a->out += b.out; a->carts_scan += b.carts_scan; a->carts_scan_glb += b.carts_scan_glb;
-  a->win_scan += b.win_scan; a->tail += b.tail; a->gpu_ms += b.gpu_ms; a->scan_ms += b.scan_ms;
-  a->scan_launches += b.scan_launches; a->dense_passes += b.dense_passes; a->scan_fallbacks += b.scan_fallbacks; a->ws_regrows += b.ws_regrows;
-  for (int t = 0; t < kMaxStages; t++) a->stage_done[t] += b.stage_done[t];
-}
-
-// What the two dialects do differently around a ragged job: the call's parameters, the per-image fallback, the
-// post-processing and the result type.
+// What the two dialects do differently around a ragged job: the call's parameters, the per-image fallback, device
+// post-processing and the final threshold.
 struct RagSideC {
-  using Real = float; using Result = jdaResult;
-  float scale; int min_size, max_size; float th; const jdaDetectOptions* opt; jdaResult* out;
-  RowsOut<float>* rows = nullptr; int frame_offset = 0;      // rows mode (post_ragged): `out` is the caller's scratch, left blank
-  bool rows_mode() const { return rows != nullptr; }
+  using D = DialectC;
+  float scale; int min_size, max_size; float th; const jdaDetectOptions* opt;
   jdaStats* stats() const { return opt ? opt->stats : nullptr; }
   bool apply_th() const { return true; }
-  Real final_th() const { return th; }
-  void blank(int n, int L) const { for (int i = 0; i < n; i++) { out[i].n = 0; out[i].landmark_n = L; out[i].bboxes = nullptr; out[i].shapes = nullptr; out[i].scores = nullptr; } }
-  bool filled(int i) const { return out[i].bboxes != nullptr; }
-  void set_empty(int i, int L) const { out[i] = empty_result(L); }
+  float final_th() const { return th; }
   void describe(RaggedJob* job) const { job->cpp = false; job->scale = scale; job->min_size = min_size; job->max_size = max_size; }
   bool usable(Cascador*) const { return true; }
   // one image as a pass of its own (detect.cpp)
-  int one_image(Cascador* c, const unsigned char* host, const uint8_t* dev, int W, int H, jdaStats* st1, int i) const {
+  int one_image(Cascador* c, const unsigned char* host, const uint8_t* dev, int W, int H, jdaStats* st1, jdaResult* out) const {
     jdaDetectOptions o1;
     if (opt) o1 = *opt; else jdaDetectOptionsInit(&o1);
     o1.stats = st1; o1.hip_stream = nullptr;
     const unsigned char* one[1] = {host};
-    return host ? detect_c_device(c, nullptr, 0, 1, W, H, scale, min_size, max_size, th, &o1, out + i, one)
-                : detect_c_device(c, dev, (size_t)W * H, 1, W, H, scale, min_size, max_size, th, &o1, out + i);
+    return host ? detect_c_device(c, nullptr, 0, 1, W, H, scale, min_size, max_size, th, &o1, out, one)
+                : detect_c_device(c, dev, (size_t)W * H, 1, W, H, scale, min_size, max_size, th, &o1, out);
   }
-  double post(Cascador* c, const RaggedJob& job, const RaggedChunk& ch, const RawDets<float>& dets) const { return post_ragged(c, job, ch, dets, opt, out + ch.i0, rows, frame_offset); }
   bool device_post(Cascador* c, int n_imgs) const { return c->kn.device_post >= 1 && n_imgs >= c->kn.device_post_min_frames; }
-  bool post_nms() const { return !opt || opt->nms; }
-  float post_overlap() const { return opt ? opt->nms_overlap : 0.3f; }
+  bool nms() const { return !opt || opt->nms; }
+  double overlap() const { return opt ? opt->nms_overlap : 0.3f; }
 };
 struct RagSideCpp {
-  using Real = double; using Result = jdaResultD;
-  CppCall call; jdaStats* st; jdaResultD* out;
+  using D = DialectCpp;
+  CppCall call; jdaStats* st;
   jdaStats* stats() const { return st; }
   bool apply_th() const { return false; }                  // Validate has no final threshold (cascador.cpp:166-211)
-  Real final_th() const { return 0.0; }
-  void blank(int n, int L) const { for (int i = 0; i < n; i++) { out[i].n = 0; out[i].landmark_n = L; out[i].rects = nullptr; out[i].shapes = nullptr; out[i].scores = nullptr; } }
-  bool filled(int i) const { return out[i].rects != nullptr; }
-  void set_empty(int i, int L) const { out[i] = empty_result_d(L); }
+  double final_th() const { return 0.0; }
   void describe(RaggedJob* job) const { job->cpp = true; job->call = call; }
-  RowsOut<double>* rows = nullptr; int frame_offset = 0;     // rows mode (post_ragged): `out` is the caller's scratch, left blank
-  bool rows_mode() const { return rows != nullptr; }
   bool usable(Cascador* c) const { return cpp_model_complete(c); }
-  int one_image(Cascador* c, const unsigned char* host, const uint8_t* dev, int W, int H, jdaStats* st1, int i) const {
+  int one_image(Cascador* c, const unsigned char* host, const uint8_t* dev, int W, int H, jdaStats* st1, jdaResultD* out) const {
     const unsigned char* one[1] = {host};
-    return host ? detect_cpp_device(c, nullptr, 0, 1, W, H, call, st1, out + i, one)
-                : detect_cpp_device(c, dev, (size_t)W * H, 1, W, H, call, st1, out + i);
+    return host ? detect_cpp_device(c, nullptr, 0, 1, W, H, call, st1, out, one)
+                : detect_cpp_device(c, dev, (size_t)W * H, 1, W, H, call, st1, out);
   }
-  double post(Cascador* c, const RaggedJob& job, const RaggedChunk& ch, const RawDets<double>& dets) const { return post_ragged(c, job, ch, dets, call, out + ch.i0, rows, frame_offset); }
   bool device_post(Cascador*, int) const { return false; }  // (k_post is dialect C's NMS; the multimap NMS runs on the host)
-  bool post_nms() const { return call.nms != 0; }
-  float post_overlap() const { return (float)call.overlap; }
+  bool nms() const { return call.nms != 0; }
+  double overlap() const { return call.overlap; }
 };
 
 // A ragged job: images of different sizes, in host memory (host_imgs) or on the device (d_base + d_offsets).
+// Results go to sink.out[i] or, as rows, to sink.rows (no jdaResult per image: three allocations each, 1,065 for a
+// 355-image job whose 1,170 detections are 270 KB).
 template <typename Side>
 static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, const uint8_t* d_base, const size_t* d_offsets,
-                           const int* widths, const int* heights, int n, const Side& side) {
-  using Real = typename Side::Real;
+                           const int* widths, const int* heights, int n, const Side& side, const Sink<typename Side::D>& sink) {
+  using D = typename Side::D;
+  using Real = typename D::Real;
   const double t_call = now_ms();
-  if (!c || !side.out || n < 0 || !widths || !heights || (!host_imgs && !(d_base && d_offsets))) { fail("bad arguments"); return -1; }
+  if (!c || !(sink.out || sink.rows) || n < 0 || !widths || !heights || (!host_imgs && !(d_base && d_offsets))) { fail("bad arguments"); return -1; }
   const int L = c->hm.L;
-  side.blank(n, L);
+  OutGuard<D> guard(sink.out, sink.out ? n : 0, L);
   if (!side.usable(c)) return -1;
   if (n == 0) return 0;
   {
@@ -697,6 +504,7 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
   auto finish = [&]() {
     fill_stats(side.stats(), total, patch_n, c->hm.T, c->hm.K, post_ms);
     if (side.stats()) side.stats()->call_ms = now_ms() - t_call;
+    guard.keep = true;
     return 0;
   };
   // per-image passes: models the ragged scan does not cover (multi-scale split nodes, levels without a tile), and
@@ -706,12 +514,12 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
       const int W = widths[i], H = heights[i];
       if (W <= 0 || H <= 0) { fail("image " + std::to_string(i) + " has no pixels"); return -1; }
       if (host_imgs && !host_imgs[i]) { fail("null image pointer"); return -1; }
-      const int rc = side.one_image(c, host_imgs ? host_imgs[i] : nullptr, host_imgs ? nullptr : d_base + d_offsets[i], W, H, &st1, i);
-      if (rc != 0) return -1;
-      total.carts += st1.cart_total_n; total.out += st1.face_patch_n; total.carts_scan += st1.scan_cart_n;
-      total.win_scan += st1.scan_patch_n; total.tail += st1.handoff_n; total.gpu_ms += st1.gpu_ms; total.scan_ms += st1.scan_ms;
-      total.scan_launches += st1.scan_launches; total.dense_passes += st1.dense_passes; total.scan_fallbacks += st1.scan_fallbacks; total.ws_regrows += st1.ws_regrows;
-      for (int t = 0; t < 16 && t < kMaxStages; t++) total.stage_done[t] += st1.stage_done_n[t];
+      typename D::Result r1;
+      OutGuard<D> scratch(&r1, 1, L);                   // (rows: the image's result, packed and released)
+      typename D::Result* r = sink.out ? sink.out + i : &r1;
+      if (side.one_image(c, host_imgs ? host_imgs[i] : nullptr, host_imgs ? nullptr : d_base + d_offsets[i], W, H, &st1, r) != 0) return -1;
+      if (sink.rows) pack<D>(&r1, 1, sink.frame_offset + i, sink.rows->grow((size_t)r1.n * ((size_t)D::head + 2 * L)), r1.n);
+      total += run_stats_of(st1);
       patch_n += st1.patch_n; post_ms += st1.host_ms;
     }
     return finish();
@@ -720,6 +528,13 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
   RaggedJob job;
   job.n = n; job.widths = widths; job.heights = heights; job.host_imgs = host_imgs; job.d_base = d_base; job.d_offsets = d_offsets;
   side.describe(&job);
+  // NMS, relocation and the results of a chunk's images (dets sorted by gid = image, level, y, x)
+  auto post = [&](const RaggedChunk& ch, const RawDets<Real>& dets) {
+    FrameSet fs;
+    fs.n = ch.n; fs.gid_first = ch.gid_base.data(); fs.widths = ch.widths; fs.heights = ch.heights;
+    return post_frames<D>(job.levels.levels, fs, dets, L, side.nms(), side.overlap(),
+                          Sink<D>{sink.out ? sink.out + ch.i0 : nullptr, sink.rows, sink.frame_offset + ch.i0});
+  };
   const int prep = ragged_prepare(c, &job);
   PlanPin pin{c, job.pe};
   tm[1] = now_ms() - t_call;
@@ -727,14 +542,13 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
   if (prep < 0) return -1;
   if (prep > 0) return fallback();
   if (job.levels.levels.empty()) {                                // no image holds a window: n empty results
-    for (int i = 0; i < n && !side.rows_mode(); i++) side.set_empty(i, L);
+    for (int i = 0; i < n && sink.out; i++) sink.out[i] = empty_result<D>(L);
     return finish();
   }
 
   // ---- chunks: as many images as make ragged_chunk_windows windows (<= 65535 images, the queues pack the index
   //      in 16 bits), walked through up to three lanes as a software pipeline: while the GPU works on chunks i-1 and i-2
   //      the host builds and issues chunk i and post-processes chunk i-3 ----
-  const DevPlan& hp = job.pe->hp;
   // (dialect CPP scans ~3.4x the windows of dialect C on the same images -- 20-pixel windows, 5-pixel step -- in levels of
   // few workgroups each: larger chunks, measured 42.3 -> 38.1 ms for the FDDB-shaped job)
   const long long chunk_windows = job.cpp ? c->kn.ragged_chunk_windows_cpp : c->kn.ragged_chunk_windows;
@@ -893,8 +707,8 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
       (void)hipEventElapsedTime(&ms_all, p.ev[0], p.ev[3]);
     }
     sl.rs.scan_ms += ms_scan; sl.rs.gpu_ms += ms_all;
-    post_ms += side.post(c, job, sl.ch, sl.dets);
-    add_stats(&total, sl.rs);
+    post_ms += post(sl.ch, sl.dets);
+    total += sl.rs;
     patch_n += sl.ch.windows;
     return true;
   };
@@ -923,7 +737,7 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
     tm[2] = now_ms() - t_call;
     if (c->kn.debug_times == 1) fprintf(stderr, "[jda] ragged chunk %d: tables built %.3f..%.3f ms (%d blocks, %d segments)\n", ci, t_b - t_call, now_ms() - t_call, sl.ch.n_blk, sl.ch.n_segs);
     if (sl.ch.windows == 0) {                        // images too small for any window
-      post_ms += side.post(c, job, sl.ch, sl.dets);
+      post_ms += post(sl.ch, sl.dets);
       continue;
     }
     // workspace: every lane holds a whole chunk (its previous chunk has been collected above)
@@ -941,7 +755,7 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
     p.bind(ln, lane, nullptr);
     p.f0 = 0; p.nf = sl.ch.n; p.rag = &sl.ch;
     if (side.device_post(c, sl.ch.n)) {
-      p.want_post = true; p.post_nms = side.post_nms(); p.post_overlap = side.post_overlap();
+      p.want_post = true; p.post_nms = side.nms(); p.post_overlap = (float)side.overlap();
       sl.dets.p_n.assign((size_t)sl.ch.n, -1); sl.dets.p_first.assign((size_t)sl.ch.n, 0);
     }
     p.w.half = nullptr; p.w.quarter = nullptr; p.w.half_stride = p.w.quarter_stride = 0;
@@ -968,8 +782,6 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
     for (Lane* l : held.v) (void)hipStreamSynchronize(l->stream);
     return -1;
   }
-  for (int i = 0; i < n && !side.rows_mode(); i++)
-    if (!side.filled(i)) side.set_empty(i, L);     // (chunks fill every image; belt and braces)
   if (c->kn.debug_times == 1) fprintf(stderr, "[jda] ragged job: done at %.3f ms (post-processing %.3f ms of it)\n", now_ms() - t_call, post_ms);
   if (c->kn.debug_times >= 2) fprintf(stderr, "[jda] ragged job: ready %.3f prepared %.3f last tables %.3f issued %.3f done %.3f ms (post %.3f; prepare: levels %.3f grids %.3f plan %.3f)\n", tm[0], tm[1], tm[2], tm[3], now_ms() - t_call, post_ms,
                                        t_prep_marks[0] - t_call, t_prep_marks[1] - t_call, t_prep_marks[2] - t_call);
@@ -978,73 +790,13 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
 
 int detect_ragged(Cascador* c, const unsigned char* const* host_imgs, const uint8_t* d_base, const size_t* d_offsets,
                   const int* widths, const int* heights, int n, float scale, int min_size, int max_size, float th,
-                  const jdaDetectOptions* opt, jdaResult* out) {
-  return detect_ragged_t(c, host_imgs, d_base, d_offsets, widths, heights, n, RagSideC{scale, min_size, max_size, th, opt, out});
-}
-
-// The same job with the results as one matrix of rows (jdaDetectBatchRagged[Device]Rows).  Jobs that run image by image
-// inside (multi-scale models, dense cascades) fill the scratch results; they are packed here.
-int detect_ragged_rows(Cascador* c, const unsigned char* const* host_imgs, const uint8_t* d_base, const size_t* d_offsets,
-                       const int* widths, const int* heights, int n, float scale, int min_size, int max_size, float th,
-                       const jdaDetectOptions* opt, int frame_offset, RowsOut<float>* rows) {
-  std::vector<jdaResult> scratch((size_t)std::max(n, 1));
-  RagSideC side{scale, min_size, max_size, th, opt, scratch.data()};
-  side.rows = rows; side.frame_offset = frame_offset;
-  rows->n = 0;
-  const int rc = detect_ragged_t(c, host_imgs, d_base, d_offsets, widths, heights, n, side);
-  bool any = false;
-  for (int i = 0; i < n; i++) any = any || scratch[(size_t)i].bboxes != nullptr;
-  if (any && rc == 0) {                              // (the per-image fallback ran: nothing has been appended yet)
-    rows->n = 0;
-    const int dim = c->hm.dim();
-    for (int i = 0; i < n; i++) {
-      const jdaResult& r = scratch[(size_t)i];
-      for (int j = 0; j < r.n && r.bboxes; j++) {
-        float* o = rows->grow(5 + (size_t)dim);
-        o[0] = (float)(frame_offset + i); o[1] = (float)r.bboxes[3 * j]; o[2] = (float)r.bboxes[3 * j + 1]; o[3] = (float)r.bboxes[3 * j + 2];
-        o[4] = r.scores[j];
-        std::memcpy(o + 5, r.shapes + (size_t)j * dim, dim * sizeof(float));
-      }
-    }
-  }
-  for (int i = 0; i < n; i++) { std::free(scratch[(size_t)i].bboxes); std::free(scratch[(size_t)i].shapes); std::free(scratch[(size_t)i].scores); }
-  return rc;
-}
-
-// Dialect CPP (jdaDetectBatchCppRagged[Device]Rows): rows [frame, x, y, w, h, score, shape] of doubles -- a job of 2,845
-// FDDB-sized images keeps 32 k candidates, 15 MB of rows: through n jdaResultDs and jdaResultsDPack they were copied
-// three times and cost the binding 4.3 ms of a 38-ms job.
-int detect_ragged_cpp_rows(Cascador* c, const unsigned char* const* host_imgs, const uint8_t* d_base, const size_t* d_offsets,
-                           const int* widths, const int* heights, int n, const CppCall& call, jdaStats* stats, int frame_offset,
-                           RowsOut<double>* rows) {
-  std::vector<jdaResultD> scratch((size_t)std::max(n, 1));
-  RagSideCpp side{call, stats, scratch.data()};
-  side.rows = rows; side.frame_offset = frame_offset;
-  rows->n = 0;
-  const int rc = detect_ragged_t(c, host_imgs, d_base, d_offsets, widths, heights, n, side);
-  bool any = false;
-  for (int i = 0; i < n; i++) any = any || scratch[(size_t)i].rects != nullptr;
-  if (any && rc == 0) {                              // (the per-image fallback ran)
-    rows->n = 0;
-    const int dim = c->hm.dim();
-    for (int i = 0; i < n; i++) {
-      const jdaResultD& r = scratch[(size_t)i];
-      for (int j = 0; j < r.n && r.rects; j++) {
-        double* o = rows->grow(6 + (size_t)dim);
-        o[0] = (double)(frame_offset + i);
-        for (int k = 0; k < 4; k++) o[1 + k] = (double)r.rects[4 * j + k];
-        o[5] = r.scores[j];
-        std::memcpy(o + 6, r.shapes + (size_t)j * dim, dim * sizeof(double));
-      }
-    }
-  }
-  for (int i = 0; i < n; i++) { std::free(scratch[(size_t)i].rects); std::free(scratch[(size_t)i].shapes); std::free(scratch[(size_t)i].scores); }
-  return rc;
+                  const jdaDetectOptions* opt, const Sink<DialectC>& sink) {
+  return detect_ragged_t(c, host_imgs, d_base, d_offsets, widths, heights, n, RagSideC{scale, min_size, max_size, th, opt}, sink);
 }
 
 int detect_ragged_cpp(Cascador* c, const unsigned char* const* host_imgs, const uint8_t* d_base, const size_t* d_offsets,
-                      const int* widths, const int* heights, int n, const CppCall& call, jdaStats* stats, jdaResultD* out) {
-  return detect_ragged_t(c, host_imgs, d_base, d_offsets, widths, heights, n, RagSideCpp{call, stats, out});
+                      const int* widths, const int* heights, int n, const CppCall& call, jdaStats* stats, const Sink<DialectCpp>& sink) {
+  return detect_ragged_t(c, host_imgs, d_base, d_offsets, widths, heights, n, RagSideCpp{call, stats}, sink);
 }
 
 }  // namespace jda

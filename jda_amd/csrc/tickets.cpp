@@ -146,8 +146,8 @@ int wait_c_device(Cascador* c, int slot, jdaStats* stats, jdaResult* out) {
       pb->active = false; pb->waiting = false;
     }
   } closer{c, &pb};
-  const int L = c->hm.L, n = pb.n;
-  for (int i = 0; i < n; i++) { out[i].n = 0; out[i].landmark_n = L; out[i].bboxes = nullptr; out[i].shapes = nullptr; out[i].scores = nullptr; }
+  const int n = pb.n;
+  OutGuard<DialectC> guard(out, n, c->hm.L);
   Pass<float>& p = pb.pass;
   pb.join_issuer();
   bool ok = pb.issue_ok;
@@ -163,11 +163,14 @@ int wait_c_device(Cascador* c, int slot, jdaStats* stats, jdaResult* out) {
     }
     pb.rs.scan_ms += ms_scan; pb.rs.gpu_ms += ms_all;
     if (p.lds_span && p.timed) { float ms = 0; if (hipEventElapsedTime(&ms, p.ev[1], p.ev[4]) == hipSuccess) pb.rs.scan_lds_ms += ms; }
-    post_ms = post_c(c, pb.sp, pb.dets, n, pb.opt_set ? &pb.opt : nullptr, out);
+    const jdaDetectOptions* opt = pb.opt_set ? &pb.opt : nullptr;
+    post_ms = post_frames<DialectC>(pb.sp.levels, FrameSet{n, pb.sp.windows, pb.sp.width, pb.sp.height}, pb.dets, c->hm.L, !opt || opt->nms,
+                                    opt ? opt->nms_overlap : 0.3f, Sink<DialectC>{out});
     fill_stats(stats, pb.rs, pb.sp.windows * n, c->hm.T, c->hm.K, post_ms);
     if (stats) stats->call_ms = now_ms() - pb.t_submit;
     closer.done = true;
   }
+  guard.keep = ok;
   return ok ? 0 : -1;
 }
 

@@ -249,3 +249,37 @@ def test_ragged_rows_entries_equal_the_packed_results(built, gpu, model_file, mo
     cm = api.Cascador(pm)
     res = cm.detect_ragged_packed(buf, offs, ws, hs)
     assert same(cm.detect_ragged_packed(buf, offs, ws, hs, keep_results="packed", frame_offset=7), jd.pack_detections(res, cm.L, frame_offset=7))
+
+
+@pytest.mark.parametrize("dialect", ["c", "cpp"])
+def test_ragged_failure_leaves_every_result_blank(built, gpu, model_file, dialect):
+    """A ragged job that fails after earlier chunks were post-processed (a NULL image pointer in its last chunk, a host
+    argument error caught before anything of that chunk is queued) returns -1 with every out[i] blank: n = 0, no
+    arrays -- nothing the caller would have to free."""
+    import ctypes as C
+    from jda_amd import api
+    p, _ = model_file((3, 20, 5, 4), 8, seed=3, cart_th=-1.0, norm_every=5)
+    c = api.Cascador(p)
+    c.set_option("ragged_chunk_windows" if dialect == "c" else "ragged_chunk_windows_cpp", 1)    # one image per chunk
+    c.set_option("ragged_single_windows", 0)
+    imgs = _images([(120, 100)] * 12, seed=5)
+    n = len(imgs)
+    arr = (C.c_void_p * n)(*([im.ctypes.data for im in imgs[:-1]] + [None]))
+    ptrs = C.cast(arr, C.POINTER(C.POINTER(C.c_ubyte)))
+    ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
+    hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
+    if dialect == "c":
+        res = (api.jdaResult * n)()
+        o, _st = c._opts(True, False)
+        rc = api.lib.jdaDetectBatchRagged(c.h, ptrs, ws, hs, n, 1.25, 0.1, 40, -1, -0.5, C.byref(o), res)
+    else:
+        res = (api.jdaResultD * n)()
+        rc = api.lib.jdaDetectBatchCppRagged(c.h, ptrs, ws, hs, n, 20, 5, 1.2, 0.3, 1, None, res)
+    assert rc == -1 and "null image pointer" in api.last_error()
+    for i in range(n):
+        r = res[i]
+        boxes = r.bboxes if dialect == "c" else r.rects
+        assert r.n == 0 and not boxes and not r.shapes and not r.scores, i
+    # the cascador is still usable
+    got = c.detect_ragged(imgs[:-1]) if dialect == "c" else c.detect_ragged_cpp(imgs[:-1])
+    assert len(got) == n - 1
