@@ -174,7 +174,16 @@ typedef struct {
                               /* summed over the NON-face windows only, like  */
                               /* the reference (cascador.cpp:359-364)         */
   long long stage_done_n[16]; /* windows that completed stage t (shape update) */
-  double average_cart_n;      /* cart_gothrough_n / nonface_patch_n           */
+  double average_cart_n;      /* cart_gothrough_n / nonface_patch_n; 0.0 when */
+                              /* nonface_patch_n is 0 (every window a face),  */
+                              /* where the reference divides 0 by 0 (NaN,     */
+                              /* cascador.cpp:307,375)                        */
+  /* Dialect CPP on a trainer snapshot (header stage s < T, cart c; jdaDetectBatchCpp): patch_n, face_patch_n,
+   * nonface_patch_n and cart_gothrough_n are Validate's.  The pass-through padding makes a face walk all T*K carts and
+   * complete every stage, so with ran = s*K + min(K, c+1), the carts Validate runs for a face:
+   *   cart_total_n    = Validate's carts over all windows + face_patch_n * (T*K - ran)
+   *                   = cart_gothrough_n + face_patch_n * T*K   (snapshot or not)
+   *   stage_done_n[t] = Validate's count for t < s;  face_patch_n for s <= t < T (Validate updates no shape there). */
   double gpu_ms;              /* device time of the call (HIP events; the events -- five marker packets per */
                               /* pass -- are only recorded when statistics are asked for)                   */
   double scan_ms;             /* device time of the stage-0 scan launches (first start to last end; */

@@ -461,7 +461,11 @@ static int detect_cpp_pyramid_impl(void* cascador, const unsigned char* const* f
       RunStats rs;
       HostFrames hf;
       if (multi) { hf.patch_hs = half_size; hf.patch_qs = quarter_size; }
-      if (!run_device<double>(c, lanes, pe, cur, cur_stride, n, false, 0.0, nullptr, &dets, nullptr, &rs, hf)) return false;
+      // (levels after the first read `cur`, which the resize below wrote on ln->stream: handing that stream in as the
+      // caller's stream makes run_device order every lane it uses behind it -- also a lane it only takes now, when the
+      // pool had none to spare for an earlier level -- and lane 0 keeps running on ln->stream)
+      if (!run_device<double>(c, lanes, pe, cur, cur_stride, n, false, 0.0, li > 0 ? ln->stream : nullptr, &dets, nullptr, &rs, hf))
+        return false;
       rs_total += rs;
       patch_total += sp.windows * n;
       for (size_t i = 0; i < dets.gid.size(); i++) {
@@ -476,12 +480,6 @@ static int detect_cpp_pyramid_impl(void* cascador, const unsigned char* const* f
       if (nw < 1 || nh < 1) break;
       uint8_t* nxt = (uint8_t*)levels.p + (size_t)(li & 1) * lvl_stride * (size_t)n;
       JDA_HIP(launch_resize_cv(cur, cur_stride, n, w, h, nxt, lvl_stride, nw, nh, ln->stream));   // cascador.cpp:302
-      // (no host wait: the next level's pass is queued behind the resize on this lane's stream; a second lane the first
-      // level took -- the first level has the most windows, so no later level takes one more -- waits for it on the device)
-      if (lanes.v.size() > 1) {
-        JDA_HIP(hipEventRecord(ln->ev_user, ln->stream));
-        for (size_t l = 1; l < lanes.v.size(); l++) JDA_HIP(hipStreamWaitEvent(lanes.v[l]->stream, ln->ev_user, 0));
-      }
       cur = nxt; cur_stride = lvl_stride; w = nw; h = nh; li++;
     }
     return true;

@@ -167,9 +167,29 @@ def forward(m, c, patches, shape, stp):
 FNV_SEED, FNV_MUL = 2166136261, 16777619        # the trace's leaf-path hash (a convention of this repo's checkers, not the reference's)
 
 
-def validate(m, img, x0=None, y0=None, width=None, height=None, patches=None, similarity=False):
+def new_stats(T):
+    """DetectionStatisic (include/jda/cascador.hpp:14-25) counted the way detectSingleScale / detectMultiScale1 count it
+    around Validate (cascador.cpp:249-255, 357-364), plus cart_total_n (n over every window) and stage_done_n (windows whose
+    shape a stage's regression moved, cascador.cpp:194-196)."""
+    return dict(patch_n=0, face_patch_n=0, nonface_patch_n=0, cart_gothrough_n=0, cart_total_n=0, stage_done_n=[0] * T)
+
+
+def count(stats, res):
+    """One window's Validate result into the counters."""
+    ok, _, _, n, _ = res
+    stats["patch_n"] += 1
+    stats["cart_total_n"] += n
+    if ok:
+        stats["face_patch_n"] += 1
+    else:
+        stats["nonface_patch_n"] += 1
+        stats["cart_gothrough_n"] += n             # cascador.cpp:255,363: the reject length of a NON-face only
+
+
+def validate(m, img, x0=None, y0=None, width=None, height=None, patches=None, similarity=False, stats=None):
     """JoinCascador::Validate -> (is_face, score, shape, n, path_hash).  Either one ORIGIN patch (img, x0, y0, width, height)
-    or the three patches of a multi-scale call."""
+    or the three patches of a multi-scale call.  stats (new_stats): the stages whose regression ran are counted into
+    stage_done_n; the caller counts the window (count)."""
     if patches is None:
         patches = ((img, x0, y0, width, height),) * 3     # (a single-scale model only ever reads patches[0])
     shape = list(m.mean_shape)
@@ -204,6 +224,8 @@ def validate(m, img, x0=None, y0=None, width=None, height=None, patches=None, si
             delta[2 * i], delta[2 * i + 1] = st_apply(stp, delta[2 * i], delta[2 * i + 1])
         for j in range(2 * m.L):
             shape[j] = shape[j] + delta[j]
+        if stats is not None:
+            stats["stage_done_n"][t] += 1
     if m.stage_idx < m.T:
         for k in range(m.cart_idx + 1):         # cascador.cpp:198-209: no regression for the stage in training
             c = m.carts[m.stage_idx][k]
@@ -287,10 +309,12 @@ def patches_method1(img, img_h, img_q, x, y, win):
             (img_q, x // 2, y // 2, win // 2, win // 2))
 
 
-def detect(m, img, minimum_size=20, step=5, factor=1.2, overlap=0.3, do_nms=True, resize=None, trace=None, similarity=False):
+def detect(m, img, minimum_size=20, step=5, factor=1.2, overlap=0.3, do_nms=True, resize=None, trace=None, similarity=False,
+           stats=None):
     """JoinCascador::Detect with fddb.method = 1 -> rects (x, y, w, h), scores, relocated shapes.
     resize(img, dw, dh): needed for multi-scale models only (img_h, img_q: cascador.cpp:323-331).  trace: a list that
-    receives every window's (is_face, score, shape, n, path_hash) in scan order."""
+    receives every window's (is_face, score, shape, n, path_hash) in scan order.  stats (new_stats): the call's counters
+    are added to it."""
     h, w = len(img), len(img[0])
     img_h = img_q = img
     if resize is not None:
@@ -298,19 +322,23 @@ def detect(m, img, minimum_size=20, step=5, factor=1.2, overlap=0.3, do_nms=True
         img_q = resize(img, w // 2, h // 2)
     rects, scores, shapes = [], [], []
     for (x, y, win) in windows_method1(w, h, minimum_size, step, factor):
-        res = validate(m, None, patches=patches_method1(img, img_h, img_q, x, y, win), similarity=similarity)
+        res = validate(m, None, patches=patches_method1(img, img_h, img_q, x, y, win), similarity=similarity, stats=stats)
         if trace is not None:
             trace.append(res)
+        if stats is not None:
+            count(stats, res)
         ok, score, shape, _, _ = res
         if ok:
             rects.append((x, y, win, win)); scores.append(score); shapes.append(shape)
     return _finish(m, rects, scores, shapes, overlap, do_nms)
 
 
-def detect_pyramid(m, img, resize, origin_size=48, half_size=36, quarter_size=24, step=5, factor=1.2, overlap=0.3, do_nms=True):
+def detect_pyramid(m, img, resize, origin_size=48, half_size=36, quarter_size=24, step=5, factor=1.2, overlap=0.3, do_nms=True,
+                   stats=None):
     """JoinCascador::Detect with fddb.method = 0: detectMultiScale (cascador.cpp:271-308) over detectSingleScale
     (cascador.cpp:215-265).  Windows are origin_size on every level; each window's three patches are cv::resize's of its ROI
-    to image_size.{origin,half,quarter}_size (cascador.cpp:243-245) -- resize() stands in for cv::resize."""
+    to image_size.{origin,half,quarter}_size (cascador.cpp:243-245) -- resize() stands in for cv::resize.  stats (new_stats):
+    the counters of every level's windows are added to it (detectSingleScale's statisic, cascador.cpp:249-255)."""
     width, height = len(img[0]), len(img)
     win = origin_size
     scale = 1.
@@ -328,9 +356,12 @@ def detect_pyramid(m, img, resize, origin_size=48, half_size=36, quarter_size=24
                 # (the reference resizes all three for every window; a single-scale model never reads the other two)
                 p_h = resize(roi, half_size, half_size) if m.multi_scale else None
                 p_q = resize(roi, quarter_size, quarter_size) if m.multi_scale else None
-                ok, score, shape, _, _ = validate(m, None, patches=((p_o, 0, 0, origin_size, origin_size),
-                                                                     (p_h, 0, 0, half_size, half_size),
-                                                                     (p_q, 0, 0, quarter_size, quarter_size)))
+                res = validate(m, None, patches=((p_o, 0, 0, origin_size, origin_size),
+                                                 (p_h, 0, 0, half_size, half_size),
+                                                 (p_q, 0, 0, quarter_size, quarter_size)), stats=stats)
+                if stats is not None:
+                    count(stats, res)
+                ok, score, shape, _, _ = res
                 if ok:
                     lv_r.append((x, y, win, win)); lv_s.append(score); lv_sh.append(shape)
                 x += step

@@ -596,8 +596,32 @@ typedef struct {
   int pw;                              /* patch width == height             */
 } orc_patch;
 
+/* DetectionStatisic (include/jda/cascador.hpp:14-25) as detectSingleScale / detectMultiScale1 accumulate it around
+ * Validate (cascador.cpp:249-255, 357-364): face_patch_n, nonface_patch_n, and cart_gothrough_n = the reject length n
+ * (cascador.cpp:187) summed over the NON-face windows only.  Two more, for the product's jdaStats: cart_total_n, Validate's
+ * n over every window, and stage_done_n[t], the windows whose shape stage t's regression updated (cascador.cpp:194-196;
+ * a snapshot's stage in training has none).  Sums over every window a walk visits; average_cart_n is the caller's
+ * division (cascador.cpp:307,375). */
+typedef struct {
+  long long patch_n, face_patch_n, nonface_patch_n, cart_gothrough_n, cart_total_n;
+  long long stage_done_n[16];
+} orc_cpp_stats;
+
+static void orc_stats_window(orc_cpp_stats *st, int alive, int n) {
+  if (!st) return;
+  st->patch_n++;
+  st->cart_total_n += n;
+  if (alive) {
+    st->face_patch_n++;
+  } else {
+    st->nonface_patch_n++;
+    st->cart_gothrough_n += n;
+  }
+}
+
 static int orc_walk_cpp(const orc_model *m, const orc_patch *pt,
-                        double *shape, double *delta, int *lbf, double *score_out, unsigned *hash_out, int *alive) {
+                        double *shape, double *delta, int *lbf, double *score_out, unsigned *hash_out, int *alive,
+                        orc_cpp_stats *st) {
   const int dim = m->dim, node_n = m->node_n, leaf_n = m->leaf_n;
   double score = 0.;
   unsigned hash = FNV_SEED;
@@ -654,7 +678,7 @@ static int orc_walk_cpp(const orc_model *m, const orc_patch *pt,
       score += m->leaf[c * leaf_n + leaf];
       score = (score - m->cmean[c]) / m->cstd[c];
       n++;
-      if (score < m->cth[c]) { *alive = 0; *score_out = score; *hash_out = hash; free(tmp); return n; }
+      if (score < m->cth[c]) { *alive = 0; *score_out = score; *hash_out = hash; free(tmp); orc_stats_window(st, 0, n); return n; }
       lbf[k] = k * leaf_n + leaf;
     }
     if (in_training) break;                  /* no global regression for the stage in training */
@@ -669,10 +693,12 @@ static int orc_walk_cpp(const orc_model *m, const orc_patch *pt,
       orc_stp_apply(&stp, dx, dy, &delta[2 * j], &delta[2 * j + 1]);
     }
     for (int i = 0; i < dim; i++) shape[i] += delta[i];
+    if (st && t < 16) st->stage_done_n[t]++;
   }
   free(tmp);
   *score_out = score;
   *hash_out = hash;
+  orc_stats_window(st, 1, n);
   return n;
 }
 
@@ -728,7 +754,7 @@ long long orc_trace_cpp(const orc_model *m, const unsigned char *img, int w, int
         double s; unsigned hsh; int alive;
         orc_patch pt[3];
         orc_patches_cpp(img, w, &pyr, ix * lv[l].step, iy * lv[l].step, lv[l].win, pt);
-        const int n = orc_walk_cpp(m, pt, shape, delta, lbf, &s, &hsh, &alive);
+        const int n = orc_walk_cpp(m, pt, shape, delta, lbf, &s, &hsh, &alive, NULL);
         if (carts_n) carts_n[id] = n;
         if (score) score[id] = s;
         if (path_hash) path_hash[id] = hsh;
@@ -800,10 +826,11 @@ static int orc_finish_cpp(const orc_model *m, const int *r0, const double *s0, c
 }
 
 /* JoinCascador::Detect with method 1 (cascador.cpp:431-477). Outputs sized per
- * window count. rects are (x,y,w,h). Returns detections. */
-int orc_detect_cpp(const orc_model *m, const unsigned char *img, int w, int h,
-                   int minimum_size, int step, double factor, double overlap, int do_nms,
-                   int *rects, double *scores, double *shapes) {
+ * window count. rects are (x,y,w,h). Returns detections.  st (may be NULL): the
+ * counters of every window are added to it. */
+int orc_detect_cpp_stats(const orc_model *m, const unsigned char *img, int w, int h,
+                         int minimum_size, int step, double factor, double overlap, int do_nms,
+                         int *rects, double *scores, double *shapes, orc_cpp_stats *st) {
   orc_level lv[256];
   long long tot = 0;
   const int nl = orc_levels_cpp(w, h, minimum_size, step, factor, lv, 256, &tot);
@@ -824,7 +851,7 @@ int orc_detect_cpp(const orc_model *m, const unsigned char *img, int w, int h,
         const int x = ix * lv[l].step, y = iy * lv[l].step;
         orc_patch pt[3];
         orc_patches_cpp(img, w, &pyr, x, y, lv[l].win, pt);
-        (void)orc_walk_cpp(m, pt, shape, delta, lbf, &s, &hsh, &alive);
+        (void)orc_walk_cpp(m, pt, shape, delta, lbf, &s, &hsh, &alive, st);
         if (!alive) continue;
         r0[4 * n] = x; r0[4 * n + 1] = y; r0[4 * n + 2] = lv[l].win; r0[4 * n + 3] = lv[l].win;
         s0[n] = s;
@@ -861,10 +888,11 @@ long long orc_count_windows_pyramid(int w, int h, int origin_size, int step, dou
 /* Method 0 with the config's three patch sizes (image_size.origin_size / half_size / quarter_size, common.cpp:129-131):
  * detectSingleScale resizes EVERY window's ROI to each of them (cascador.cpp:243-245) -- the first is the identity
  * (the window is origin_size wide), the other two feed the split nodes of scale 1 and 2 (data.cpp:21-34).
- * half_size = quarter_size = 0: the call of a single-scale model (multi-scale models are refused). */
-int orc_detect_cpp_pyramid_ms(const orc_model *m, const unsigned char *img, int w, int h,
-                              int origin_size, int half_size, int quarter_size, int step, double factor, double overlap,
-                              int do_nms, int *rects, double *scores, double *shapes) {
+ * half_size = quarter_size = 0: the call of a single-scale model (multi-scale models are refused).
+ * st (may be NULL): the counters of every window of every level are added to it (cascador.cpp:249-255). */
+int orc_detect_cpp_pyramid_ms_stats(const orc_model *m, const unsigned char *img, int w, int h,
+                                    int origin_size, int half_size, int quarter_size, int step, double factor, double overlap,
+                                    int do_nms, int *rects, double *scores, double *shapes, orc_cpp_stats *st) {
   const int multi = orc_has_multiscale(m);
   if (multi && (half_size < 1 || quarter_size < 1)) return -1;
   int nl = 0;
@@ -898,7 +926,7 @@ int orc_detect_cpp_pyramid_ms(const orc_model *m, const unsigned char *img, int 
           pt[1].data = ph; pt[1].iw = half_size; pt[1].ox = 0; pt[1].oy = 0; pt[1].pw = half_size;
           pt[2].data = pq; pt[2].iw = quarter_size; pt[2].ox = 0; pt[2].oy = 0; pt[2].pw = quarter_size;
         }
-        (void)orc_walk_cpp(m, pt, shape, delta, lbf, &s, &hsh, &alive);
+        (void)orc_walk_cpp(m, pt, shape, delta, lbf, &s, &hsh, &alive, st);
         if (!alive) continue;
         int rx = x, ry = y, rw = origin_size, rh = origin_size;
         rx *= scale; ry *= scale; rw *= scale; rh *= scale;      /* cascador.cpp:292-294 */
@@ -923,5 +951,20 @@ int orc_detect_cpp_pyramid(const orc_model *m, const unsigned char *img, int w, 
                            int origin_size, int step, double factor, double overlap, int do_nms,
                            int *rects, double *scores, double *shapes) {
   if (orc_has_multiscale(m)) return -1;
-  return orc_detect_cpp_pyramid_ms(m, img, w, h, origin_size, 0, 0, step, factor, overlap, do_nms, rects, scores, shapes);
+  return orc_detect_cpp_pyramid_ms_stats(m, img, w, h, origin_size, 0, 0, step, factor, overlap, do_nms, rects, scores, shapes, NULL);
+}
+
+/* The two entries without counters keep their signatures: callers bound to them (ctypes declares every argument) go on
+ * working with this library. */
+int orc_detect_cpp(const orc_model *m, const unsigned char *img, int w, int h,
+                   int minimum_size, int step, double factor, double overlap, int do_nms,
+                   int *rects, double *scores, double *shapes) {
+  return orc_detect_cpp_stats(m, img, w, h, minimum_size, step, factor, overlap, do_nms, rects, scores, shapes, NULL);
+}
+
+int orc_detect_cpp_pyramid_ms(const orc_model *m, const unsigned char *img, int w, int h,
+                              int origin_size, int half_size, int quarter_size, int step, double factor, double overlap,
+                              int do_nms, int *rects, double *scores, double *shapes) {
+  return orc_detect_cpp_pyramid_ms_stats(m, img, w, h, origin_size, half_size, quarter_size, step, factor, overlap, do_nms,
+                                         rects, scores, shapes, NULL);
 }

@@ -21,6 +21,20 @@ def _ptr(a, ty):
     return None if a is None else a.ctypes.data_as(C.POINTER(ty))
 
 
+class CppStats(C.Structure):
+    """jda_oracle.c's orc_cpp_stats: the reference's DetectionStatisic (include/jda/cascador.hpp:14-25) summed over the
+    windows of a dialect-CPP walk, plus cart_total_n and stage_done_n."""
+    _fields_ = [("patch_n", C.c_longlong), ("face_patch_n", C.c_longlong), ("nonface_patch_n", C.c_longlong),
+                ("cart_gothrough_n", C.c_longlong), ("cart_total_n", C.c_longlong), ("stage_done_n", C.c_longlong * 16)]
+
+    def asdict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "stage_done_n"}
+        d["stage_done_n"] = list(self.stage_done_n)
+        # cascador.cpp:307,375: double / int -- 0 / 0 when every window is a face, which is NaN
+        d["average_cart_n"] = d["cart_gothrough_n"] / d["nonface_patch_n"] if d["nonface_patch_n"] else float("nan")
+        return d
+
+
 class Oracle:
     def __init__(self, model_path):
         self.lib = C.CDLL(_build.build_oracle())
@@ -42,9 +56,9 @@ class Oracle:
         L.orc_trace_cpp.restype = C.c_longlong
         L.orc_trace_cpp.argtypes = [C.c_void_p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                     C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_uint), C.POINTER(C.c_double)]
-        L.orc_detect_cpp.restype = C.c_int
-        L.orc_detect_cpp.argtypes = [C.c_void_p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
-                                     C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.orc_detect_cpp_stats.restype = C.c_int
+        L.orc_detect_cpp_stats.argtypes = [C.c_void_p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(CppStats)]
         L.orc_resize.argtypes = [u8p, C.c_int, C.c_int, u8p, C.c_int, C.c_int]
         L.orc_resize_cv.argtypes = [u8p, C.c_int, C.c_int, u8p, C.c_int, C.c_int]
         L.orc_count_windows_pyramid.restype = C.c_longlong
@@ -52,9 +66,10 @@ class Oracle:
         L.orc_detect_cpp_pyramid.restype = C.c_int
         L.orc_detect_cpp_pyramid.argtypes = [C.c_void_p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                              C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.orc_detect_cpp_pyramid_ms.restype = C.c_int
-        L.orc_detect_cpp_pyramid_ms.argtypes = [C.c_void_p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
-                                                C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.orc_detect_cpp_pyramid_ms_stats.restype = C.c_int
+        L.orc_detect_cpp_pyramid_ms_stats.argtypes = [C.c_void_p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                                      C.POINTER(C.c_double), C.POINTER(CppStats)]
         L.orc_pyramid_dims.argtypes = [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4
         self.h = L.orc_load(os.fsencode(model_path))
         if not self.h:
@@ -128,7 +143,8 @@ class Oracle:
             raise RuntimeError("oracle cpp trace failed (multi-scale model?)")
         return dict(carts_n=carts, score=score, path_hash=hsh, shapes=shapes)
 
-    def detect_cpp(self, img, minimum_size=20, step=5, factor=1.2, overlap=0.3, nms=True):
+    def detect_cpp(self, img, minimum_size=20, step=5, factor=1.2, overlap=0.3, nms=True, stats=False):
+        """stats=True: also "stats", the work counters of the call (CppStats.asdict)."""
         img = np.ascontiguousarray(img, np.uint8)
         h, w = img.shape
         nl = C.c_int()
@@ -138,11 +154,15 @@ class Oracle:
         rc = np.zeros((max(n, 1), 4), np.int32)
         sc = np.zeros(max(n, 1), np.float64)
         sh = np.zeros((max(n, 1), self.dim), np.float64)
-        k = self.lib.orc_detect_cpp(self.h, _ptr(img, C.c_ubyte), w, h, minimum_size, step, factor, overlap, int(nms),
-                                    _ptr(rc, C.c_int), _ptr(sc, C.c_double), _ptr(sh, C.c_double))
+        st = CppStats()
+        k = self.lib.orc_detect_cpp_stats(self.h, _ptr(img, C.c_ubyte), w, h, minimum_size, step, factor, overlap, int(nms),
+                                    _ptr(rc, C.c_int), _ptr(sc, C.c_double), _ptr(sh, C.c_double), C.byref(st))
         if k < 0:
             raise RuntimeError("oracle cpp detect failed")
-        return dict(rects=rc[:k].copy(), scores=sc[:k].copy(), shapes=sh[:k].copy())
+        out = dict(rects=rc[:k].copy(), scores=sc[:k].copy(), shapes=sh[:k].copy())
+        if stats:
+            out["stats"] = st.asdict()
+        return out
 
     def resize(self, img, dw, dh):
         img = np.ascontiguousarray(img, np.uint8)
@@ -163,8 +183,10 @@ class Oracle:
         self.lib.orc_resize_cv(_ptr(img, C.c_ubyte), w, h, _ptr(out, C.c_ubyte), dw, dh)
         return out
 
-    def detect_cpp_pyramid(self, img, origin_size=48, step=5, factor=1.2, overlap=0.3, nms=True, half_size=0, quarter_size=0):
-        """half_size / quarter_size > 0: the per-window patches of a multi-scale model (cascador.cpp:243-245)."""
+    def detect_cpp_pyramid(self, img, origin_size=48, step=5, factor=1.2, overlap=0.3, nms=True, half_size=0, quarter_size=0,
+                           stats=False):
+        """half_size / quarter_size > 0: the per-window patches of a multi-scale model (cascador.cpp:243-245).
+        stats=True: also "stats", the work counters of the call (CppStats.asdict)."""
         img = np.ascontiguousarray(img, np.uint8)
         h, w = img.shape
         nl = C.c_int()
@@ -174,11 +196,16 @@ class Oracle:
         rc = np.zeros((max(n, 1), 4), np.int32)
         sc = np.zeros(max(n, 1), np.float64)
         sh = np.zeros((max(n, 1), self.dim), np.float64)
-        k = self.lib.orc_detect_cpp_pyramid_ms(self.h, _ptr(img, C.c_ubyte), w, h, origin_size, half_size, quarter_size, step,
-                                               factor, overlap, int(nms), _ptr(rc, C.c_int), _ptr(sc, C.c_double), _ptr(sh, C.c_double))
+        st = CppStats()
+        k = self.lib.orc_detect_cpp_pyramid_ms_stats(self.h, _ptr(img, C.c_ubyte), w, h, origin_size, half_size, quarter_size, step,
+                                               factor, overlap, int(nms), _ptr(rc, C.c_int), _ptr(sc, C.c_double), _ptr(sh, C.c_double),
+                                               C.byref(st))
         if k < 0:
             raise RuntimeError("oracle pyramid detect failed (multi-scale model?)")
-        return dict(rects=rc[:k].copy(), scores=sc[:k].copy(), shapes=sh[:k].copy(), windows=n, levels=nl.value)
+        out = dict(rects=rc[:k].copy(), scores=sc[:k].copy(), shapes=sh[:k].copy(), windows=n, levels=nl.value)
+        if stats:
+            out["stats"] = st.asdict()
+        return out
 
     def pyramid_dims(self, w, h):
         v = [C.c_int() for _ in range(4)]

@@ -238,3 +238,74 @@ def test_randomised_cases_agree():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "fuzz_second_reading.py"), "11", "6"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "the two readings agree" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+
+
+# cart thresholds of the three regimes: every window rejected by its first cart, a mix, every window a face
+REGIMES = {"reject_all": 1e30, "mix": -1.0, "pass_all": -3.0e38}
+
+
+def _counter_model(tmp_path, kind, regime):
+    """(path, (stage_idx, cart_idx)) of a small model: single-scale, multi-scale or a trainer snapshot."""
+    from jda_amd import synth
+    dims = (3, 20, 5, 4) if kind != "multi" else (2, 8, 5, 3)
+    mdl = synth.make_model(*dims, seed=3, cart_th=REGIMES[regime], norm_every=5, multi_scale=kind == "multi")
+    p = str(tmp_path / ("%s_%s.model" % (kind, regime)))
+    hdr = {"snap_1_6": (1, 6), "snap_0_-1": (0, -1)}.get(kind)
+    if hdr:
+        mdl.save(p, 8, header_stage=hdr[0], header_cart=hdr[1])
+    else:
+        mdl.save(p, 8)
+    return p, hdr or (dims[0], -1)
+
+
+def _check_regime(st, regime, windows):
+    assert st["patch_n"] == windows > 0
+    assert st["face_patch_n"] + st["nonface_patch_n"] == st["patch_n"]
+    if regime == "reject_all":
+        assert st["face_patch_n"] == 0 and st["cart_gothrough_n"] == st["cart_total_n"] == windows
+        assert not any(st["stage_done_n"])
+    elif regime == "pass_all":
+        assert st["nonface_patch_n"] == 0 and st["cart_gothrough_n"] == 0
+    else:
+        assert 0 < st["face_patch_n"] < st["patch_n"]
+
+
+@pytest.mark.parametrize("regime", sorted(REGIMES))
+@pytest.mark.parametrize("kind", ["single", "multi", "snap_1_6", "snap_0_-1"])
+def test_both_readings_count_the_same_work(tmp_path, kind, regime):
+    """DetectionStatisic (include/jda/cascador.hpp:14-25) plus cart_total_n and stage_done_n, counted by jda_oracle.c's walks
+    (orc_detect_cpp, orc_detect_cpp_pyramid_ms) and by the second reading: equal on method 1 and method 0, single- and
+    multi-scale models and trainer snapshots, in all three threshold regimes.  These are the numbers the GPU tests hold the
+    product's jdaStats to (tests/test_cpp_stats.py)."""
+    p, (s_idx, c_idx) = _counter_model(tmp_path, kind, regime)
+    orc = Oracle(p)
+    m = r2.Model2(p)
+    T, K = m.T, m.K
+    multi = kind == "multi"
+    resize = _resize_with(orc) if multi else None
+    regime = "pass_all" if kind == "snap_0_-1" else regime      # (Validate runs no cart of (0, -1): every window is a face)
+    keys = ("patch_n", "face_patch_n", "nonface_patch_n", "cart_gothrough_n", "cart_total_n")
+    # method 1
+    img = _image(64, 52, seed=17)
+    want = orc.detect_cpp(img, 20, 5, 1.2, 0.3, True, stats=True)["stats"]
+    mine = r2.new_stats(T)
+    r2.detect(m, img.tolist(), 20, 5, 1.2, 0.3, True, resize=resize, stats=mine)
+    for k in keys:
+        assert mine[k] == want[k], ("method 1", k, mine[k], want[k])
+    assert mine["stage_done_n"] == want["stage_done_n"][:T] and not any(want["stage_done_n"][T:])
+    _check_regime(want, regime, len(r2.windows_method1(64, 52, 20, 5, 1.2)))
+    # the walk stops where Validate stops: a face ran every cart of the stages it runs, no regression in the stage in training
+    ran = (s_idx * K + c_idx + 1) if s_idx < T else T * K
+    assert want["cart_total_n"] == want["cart_gothrough_n"] + want["face_patch_n"] * ran
+    assert not any(want["stage_done_n"][min(s_idx, T):])
+    # method 0
+    img0 = _image(70, 62, seed=13)
+    want0 = orc.detect_cpp_pyramid(img0, 48, 5, 1.2, 0.3, True, half_size=36 if multi else 0, quarter_size=24 if multi else 0,
+                                   stats=True)
+    mine0 = r2.new_stats(T)
+    r2.detect_pyramid(m, img0.tolist(), _resize_with(orc) if multi else r2.resize_cv2, 48, 36, 24, 5, 1.2, 0.3, True, stats=mine0)
+    for k in keys:
+        assert mine0[k] == want0["stats"][k], ("method 0", k, mine0[k], want0["stats"][k])
+    assert mine0["stage_done_n"] == want0["stats"]["stage_done_n"][:T]
+    _check_regime(want0["stats"], regime, want0["windows"])
+    orc.close()
