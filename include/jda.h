@@ -551,6 +551,126 @@ JDA_API int jdaMineNegativesCppDevice(void *cascador, const unsigned char *d_bas
 JDA_API int jdaMineWindows(int w, int h, int origin_size, int step, double factor, long long *n, int *levels);
 JDA_API long long jdaMineWindowList(int w, int h, int origin_size, int step, double factor, int *xyw, long long cap);
 
+/* ---- Dialect CPP: training one CART -------------------------------------------------------------------------------------
+ * What the reference's trainer does with the samples mining returns: Cart::Train -> Cart::SplitNode (reference
+ * src/jda/cart.cpp:41-162) -- per internal node a pool of candidate features is evaluated on every sample that reached the
+ * node (DataSet::CalcFeatureValues, data.cpp:148-173), one (feature, threshold) is picked by weighted entropy
+ * (SplitNodeWithClassification, cart.cpp:176-252) or by the variance of one landmark's residual (SplitNodeWithRegression,
+ * cart.cpp:288-350), the samples are partitioned and the children split in turn; a leaf's score is
+ * 0.5 * (log(pos_w) - log(neg_w)) (cart.cpp:63-89).  PARITY UNPINNED like every dialect-CPP entry: src/jda needs OpenCV and
+ * cannot be built here; these entries are bit-exact against a sequential restatement written from the reference's source
+ * (tests/train_ref.py), not against the reference.  Out of scope: BoostCart::Train's loop (weights, thresholds by recall,
+ * restarts), the global regression, writing the cart into a model file, data loading.
+ *
+ * Samples.  One struct describes a set of n samples.  origin_size / half_size / quarter_size are call arguments, each in
+ * [1, 128]; the landmark count L and tree_depth come from the cascador (it also supplies the device, the "workspace_mb"
+ * limit of the per-call workspace -- the pool is processed in chunks of features that fit it -- and the error state).
+ *
+ * Feature values.  Feature::CalcFeatureValue (data.cpp:18-58) with the identity STParameter, evaluated exactly as the
+ * dialect-CPP split node is everywhere in this library: fp64 (shape + offset) * side of the patch of the feature's scale,
+ * round (halves away from zero), clamp into the patch, pixel difference in [-255, 255].  With jdaSetSimilarityTransform(1)
+ * every entry below refuses (-1): CalcFeatureValues indexes the per-sample transform by the FEATURE index (data.cpp:168,
+ * stp_mc[i]), which reads past the array whenever the pool is larger than the set -- there is no behaviour to reproduce.
+ *
+ * Randomness is the caller's.  The reference seeds from getTickCount() and per-thread cv::RNGs; none of it is reproducible
+ * and none of it is a goal.  The caller passes, per internal node, the pool, the mode (1 classification, 0 regression: the
+ * reference's rng.uniform(0., 1.) < probs[stage], cart.cpp:101) and for regression one u per pool feature (the reference's
+ * rng.uniform(0.1, 0.9), cart.cpp:320; accepted range [0, 1)).  jdaGenFeaturePoolCpp makes pools the way
+ * Cart::GenFeaturePool does (cart.cpp:352-390) on the counter-based generator of the mining block above: with
+ *     G = 0x9E3779B97F4A7C15, base(i) = splitmix64(splitmix64(seed + (key + 1) * G) + (i + 1) * G)      (mod 2^64)
+ *     draw d = 1, 2, ... of feature i:  r(d) = splitmix64(base(i) + d * G),  unit(d) = (r(d) >> 11) * 2^-53
+ * feature i consumes its draws in this order: per round of the rejection loop four draws x1, y1, x2, y2, each
+ * -1 + (1 - -1) * unit (the loop ends when x1*x1 + y1*y1 <= 1 and x2*x2 + y2*y2 <= 1); then scale = r % 3 (drawn always,
+ * then forced to 0 without multi_scale); landmark_id1 = r % L; landmark_id2 = r % L; offsets = point * radius; last
+ * u = 0.1 + (0.9 - 0.1) * unit.
+ *
+ * Classification split, literally cart.cpp:176-252: per feature two 511-bin weighted histograms and two count histograms
+ * over value + 255, the totals wp_r / wn_r, the sweep th = -255 .. 255 with the 0.1 / 0.9 count-ratio gates, calcEntropy
+ * (isZero's 1e-9, division by log(2.)) and strict <; across features the first strict minimum.  An empty side follows from
+ * the same IEEE expressions (0/0 ratios and NaN entropies never pass a gate or a <) and is part of the contract.
+ * SUMMATION ORDER IS THE REFERENCE'S: every bin and both totals add the weights in sample order.
+ *
+ * Regression split, cart.cpp:288-350: pos_n == 0 -> feature 0, threshold -256 (criterion 0 / thresholds -256 reported for
+ * every feature; the reference returns before it computes any).  Otherwise per feature threshold_ = the int(pos_n * u)-th
+ * smallest value over ALL positives of the node (an order statistic of integers: taken from a count histogram), left / right
+ * by value <= threshold_ over the positives with has_gt, (var(lx) + var(ly)) * n_left + (var(rx) + var(ry)) * n_right,
+ * var = m2 - m1 * m1, an empty side 0; first strict minimum.  calcVariance goes through cv::mean and Mat::mul, whose
+ * summation order and form of division only the real OpenCV decides.  DEFINED here: m1 = (sum of v in sample order) * (1. / n),
+ * m2 = (sum of v * v in sample order) * (1. / n) -- the multiply-by-reciprocal form is how cv::mean is remembered
+ * (`s * (1. / nz)`), FROM MEMORY AND UNCHECKED; a third OpenCV-decided detail next to cv::norm and Mat /= double.
+ *
+ * Whole cart, cart.cpp:57-162: from the root, split, partition stably (a child's samples stay in ascending sample order,
+ * which is what makes the children's summation order the reference's), level by level to the leaves (the reference's
+ * depth-first order does not change the result); leaf score 0.5 * (log(pos_w) - log(neg_w)), pos_w = esp + the weights in
+ * order, esp = 2.2e-16 (common.cpp:143).  Every log() is the HOST C library's: the device makes the histograms and ordered
+ * sums, the host runs the sweep.  A training sample's leaf is what Cart::Forward returns for it (same feature, threshold and
+ * value), so pos_leaf / neg_leaf ARE DataSet::UpdateScores (data.cpp:305-317): the caller adds out_scores[leaf].
+ *
+ * Reference quirks kept or avoided: stp_mc[i] indexed by feature (avoided: refused); threshold -256 sends every sample
+ * right (kept); the classification gates use counts while the criterion uses weights (kept); regression takes its order
+ * statistic over all positives but the variance over the has_gt ones (kept). */
+
+typedef struct {
+  const unsigned char *patches;  /* n * (o*o + h*h + q*q) bytes: o, h, q back to back per sample -- the layout
+                                    jdaMineNegativesCpp writes into `patches`                                    */
+  int patches_on_device;         /* 0: host pointer, 1: device pointer (a trainer keeps its samples in HBM)      */
+  const double *shapes;          /* n * 2L, current shapes (host)                                                */
+  const double *weights;         /* n (host)                                                                     */
+  const double *residual;        /* positives only, n * 2: CalcShapeResidual(idx, landmark_id) (data.cpp:190-208)
+                                    as the caller computed it; NULL for negatives                                */
+  const unsigned char *has_gt;   /* positives only, n: DataSet::HasGtShape; NULL = all 1                         */
+  int n;
+} jdaSamplesCpp;
+
+/* The fields of Feature (reference include/jda/common.hpp), offsets already multiplied by the radius. */
+typedef struct {
+  int scale, landmark_id1, landmark_id2;
+  double offset1_x, offset1_y, offset2_x, offset2_y;
+} jdaFeatureCpp;
+
+typedef struct {
+  int pos_n, neg_n;      /* samples that reached the node                                   */
+  int feature_idx;       /* chosen pool index                                               */
+  int threshold;
+  int mode, pad;
+  double criterion;      /* es_ / vs_ of the chosen feature                                 */
+} jdaTrainNodeCpp;
+
+typedef struct {
+  double call_ms;            /* wall clock of the call                                                    */
+  double setup_ms;           /* ... sample upload, shape transpose, workspace                             */
+  double device_ms;          /* ... feature values, histograms / ordered sums, their copies to the host   */
+  double sweep_ms;           /* ... the host's entropy sweeps / variance arithmetic                       */
+  double partition_ms;       /* ... chosen feature's values and the stable partition                      */
+  long long feature_evals;   /* feature evaluations on the device                                         */
+  int feature_chunks;        /* (node, feature chunk) passes                                              */
+  jdaTrainNodeCpp *nodes;    /* IN: NULL, or nodes_n/2 - 1 slots, slot i - 1 for node i = 1 .. nodes_n/2 - 1 */
+} jdaTrainStatsCpp;
+
+/* Host only (no GPU): F pool features (and, out_u != NULL, their regression draws) as specified above. */
+JDA_API int jdaGenFeaturePoolCpp(int F, int landmark_n, double radius, int multi_scale, uint64_t seed, uint64_t key,
+                                 jdaFeatureCpp *out_features, double *out_u);
+
+/* CalcFeatureValues over the whole set: out[f * n + j] = value of pool[f] on sample j (F * n ints, row = feature). */
+JDA_API int jdaCalcFeatureValuesCpp(void *cascador, const jdaSamplesCpp *samples, int origin_size, int half_size,
+                                    int quarter_size, const jdaFeatureCpp *pool, int F, int *out);
+
+/* One node over the full sets: mode 1 classification / 0 regression (u: F draws, regression only).  criterion (F doubles:
+ * es_ / vs_) and thresholds (F ints: ths_) may be NULL. */
+JDA_API int jdaSplitNodeCpp(void *cascador, const jdaSamplesCpp *pos, const jdaSamplesCpp *neg, int origin_size,
+                            int half_size, int quarter_size, const jdaFeatureCpp *pool, int F, int mode, const double *u,
+                            int *feature_idx, int *threshold, double *criterion, int *thresholds);
+
+/* One cart.  With nodes_n = 2^tree_depth: pools is (nodes_n/2 - 1) * F features, node i = 1 .. nodes_n/2 - 1 (the root is 1,
+ * the children of i are 2i and 2i + 1, like Cart::features) uses pools[(i - 1) * F ..], modes[i - 1] and
+ * us[(i - 1) * F ..] (us may be NULL when no node is a regression node).  Outputs (any may be NULL): out_features /
+ * out_thresholds [nodes_n/2 - 1], out_scores [nodes_n/2 leaves], pos_leaf [pos->n] / neg_leaf [neg->n] the leaf of every
+ * sample, stats. */
+JDA_API int jdaTrainCartCpp(void *cascador, const jdaSamplesCpp *pos, const jdaSamplesCpp *neg, int origin_size,
+                            int half_size, int quarter_size, const jdaFeatureCpp *pools, int F, const int *modes,
+                            const double *us, jdaFeatureCpp *out_features, int *out_thresholds, double *out_scores,
+                            int *pos_leaf, int *neg_leaf, jdaTrainStatsCpp *stats);
+
 #ifdef __cplusplus
 }
 #endif

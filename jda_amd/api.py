@@ -64,6 +64,37 @@ class jdaMineStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class jdaSamplesCpp(C.Structure):
+    _fields_ = [("patches", C.c_void_p), ("patches_on_device", C.c_int), ("shapes", C.POINTER(C.c_double)),
+                ("weights", C.POINTER(C.c_double)), ("residual", C.POINTER(C.c_double)), ("has_gt", C.POINTER(C.c_ubyte)),
+                ("n", C.c_int)]
+
+
+class jdaFeatureCpp(C.Structure):
+    _fields_ = [("scale", C.c_int), ("landmark_id1", C.c_int), ("landmark_id2", C.c_int), ("offset1_x", C.c_double),
+                ("offset1_y", C.c_double), ("offset2_x", C.c_double), ("offset2_y", C.c_double)]
+
+
+class jdaTrainNodeCpp(C.Structure):
+    _fields_ = [("pos_n", C.c_int), ("neg_n", C.c_int), ("feature_idx", C.c_int), ("threshold", C.c_int), ("mode", C.c_int),
+                ("pad", C.c_int), ("criterion", C.c_double)]
+
+
+class jdaTrainStatsCpp(C.Structure):
+    _fields_ = [("call_ms", C.c_double), ("setup_ms", C.c_double), ("device_ms", C.c_double), ("sweep_ms", C.c_double),
+                ("partition_ms", C.c_double), ("feature_evals", C.c_longlong), ("feature_chunks", C.c_int),
+                ("nodes", C.POINTER(jdaTrainNodeCpp))]
+
+
+# numpy view of jdaFeatureCpp arrays (same layout: three ints, four bytes of padding, four doubles)
+FEATURE_DTYPE = np.dtype([("scale", np.int32), ("landmark_id1", np.int32), ("landmark_id2", np.int32), ("pad", np.int32),
+                          ("offset1_x", np.float64), ("offset1_y", np.float64), ("offset2_x", np.float64),
+                          ("offset2_y", np.float64)])
+NODE_DTYPE = np.dtype([("pos_n", np.int32), ("neg_n", np.int32), ("feature_idx", np.int32), ("threshold", np.int32),
+                       ("mode", np.int32), ("pad", np.int32), ("criterion", np.float64)])
+assert FEATURE_DTYPE.itemsize == C.sizeof(jdaFeatureCpp) and NODE_DTYPE.itemsize == C.sizeof(jdaTrainNodeCpp)
+
+
 class jdaDetectOptions(C.Structure):
     _fields_ = [("dialect", C.c_int), ("nms", C.c_int), ("nms_overlap", C.c_float), ("cpp_step", C.c_int),
                 ("hip_stream", C.c_void_p), ("stats", C.POINTER(jdaStats))]
@@ -197,6 +228,13 @@ def _load():
         lib.jdaMineWindows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
         lib.jdaMineWindowList.restype = C.c_longlong
         lib.jdaMineWindowList.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), C.c_longlong]
+    if hasattr(lib, "jdaTrainCartCpp"):
+        sp, fp, dp, ip = C.POINTER(jdaSamplesCpp), C.POINTER(jdaFeatureCpp), C.POINTER(C.c_double), C.POINTER(C.c_int)
+        lib.jdaGenFeaturePoolCpp.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_uint64, fp, dp]
+        lib.jdaCalcFeatureValuesCpp.argtypes = [C.c_void_p, sp, C.c_int, C.c_int, C.c_int, fp, C.c_int, ip]
+        lib.jdaSplitNodeCpp.argtypes = [C.c_void_p, sp, sp, C.c_int, C.c_int, C.c_int, fp, C.c_int, C.c_int, dp, ip, ip, dp, ip]
+        lib.jdaTrainCartCpp.argtypes = [C.c_void_p, sp, sp, C.c_int, C.c_int, C.c_int, fp, C.c_int, ip, dp, fp, ip, dp, ip, ip,
+                                        C.POINTER(jdaTrainStatsCpp)]
     return lib
 
 
@@ -240,6 +278,57 @@ def mine_params(n_images, quarter_size=24, seed=0):
     steps = rng.integers(2, quarter_size, size=n_images).astype(np.int32)
     factors = rng.uniform(1.1, 1.5, size=n_images)
     return steps, factors
+
+
+def gen_feature_pool_cpp(F, landmark_n, radius, multi_scale=False, seed=0, key=0):
+    """Cart::GenFeaturePool (reference cart.cpp:352-390) on the counter-based generator of include/jda.h
+    (jdaGenFeaturePoolCpp, host only) -> (features [F] of FEATURE_DTYPE, u [F] the regression draws)."""
+    feats = np.zeros(max(int(F), 1), FEATURE_DTYPE)
+    u = np.zeros(max(int(F), 1), np.float64)
+    if lib.jdaGenFeaturePoolCpp(int(F), int(landmark_n), float(radius), 1 if multi_scale else 0, int(seed) & 0xffffffffffffffff,
+                                int(key) & 0xffffffffffffffff, feats.ctypes.data_as(C.POINTER(jdaFeatureCpp)),
+                                u.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise JdaError(last_error())
+    return feats[:F], u[:F]
+
+
+def _features(pool):
+    a = np.ascontiguousarray(pool, FEATURE_DTYPE).reshape(-1)
+    return a, a.ctypes.data_as(C.POINTER(jdaFeatureCpp))
+
+
+def _samples(samples, dim, pbytes):
+    """dict(patches=[n, pbytes] uint8 numpy array or torch CUDA tensor, shapes=[n, 2L], weights=[n], residual=[n, 2] or
+    None, has_gt=[n] or None) -> (jdaSamplesCpp, keep-alive)."""
+    pa = samples["patches"]
+    sh = np.ascontiguousarray(samples["shapes"], np.float64).reshape(-1, dim)
+    n = sh.shape[0]
+    s = jdaSamplesCpp()
+    keep = [sh]
+    if hasattr(pa, "is_cuda"):
+        assert pa.is_cuda and pa.dtype.itemsize == 1 and pa.is_contiguous() and pa.numel() == n * pbytes
+        s.patches, s.patches_on_device = pa.data_ptr() if n else None, 1
+    else:
+        pa = np.ascontiguousarray(pa, np.uint8)
+        assert pa.size == n * pbytes, "patches must hold n * (o*o + h*h + q*q) bytes"
+        s.patches, s.patches_on_device = pa.ctypes.data if n else None, 0
+    keep.append(pa)
+    dp = C.POINTER(C.c_double)
+    s.shapes = sh.ctypes.data_as(dp)
+    if samples.get("weights") is not None:
+        w = np.ascontiguousarray(samples["weights"], np.float64).reshape(-1)
+        assert w.size == n
+        s.weights = w.ctypes.data_as(dp); keep.append(w)
+    if samples.get("residual") is not None:
+        r = np.ascontiguousarray(samples["residual"], np.float64).reshape(-1)
+        assert r.size == 2 * n
+        s.residual = r.ctypes.data_as(dp); keep.append(r)
+    if samples.get("has_gt") is not None:
+        g = np.ascontiguousarray(samples["has_gt"], np.uint8).reshape(-1)
+        assert g.size == n
+        s.has_gt = g.ctypes.data_as(C.POINTER(C.c_ubyte)); keep.append(g)
+    s.n = n
+    return s, keep
 
 
 def _image_set(images):
@@ -851,10 +940,83 @@ class Cascador:
         out = dict(hits=hits[:rc], score=score[:rc], shape=shape[:rc], stats=st.asdict())
         if patches:
             o2, h2 = origin_size * origin_size, half_size * half_size
-            out["o"] = pat[:rc, :o2].reshape(rc, origin_size, origin_size)
+            out["patches"] = pat[:rc]       # o, h, q back to back per hit: jdaSamplesCpp's layout (train_cart_cpp)
+            out["o"] =pat[:rc, :o2].reshape(rc, origin_size, origin_size)
             out["h"] = pat[:rc, o2:o2 + h2].reshape(rc, half_size, half_size)
             out["q"] = pat[:rc, o2 + h2:].reshape(rc, quarter_size, quarter_size)
         return out
+
+    # -- training one CART (include/jda.h, "Dialect CPP: training one CART") ------------------------------------
+    def calc_feature_values_cpp(self, samples, pool, origin_size=48, half_size=36, quarter_size=24):
+        """DataSet::CalcFeatureValues (reference data.cpp:148-173): [F, n] int32, row = feature.  samples: dict of patches
+        ([n, o*o + h*h + q*q] uint8, numpy or a torch CUDA tensor -- the layout mine_negatives_cpp returns), shapes
+        [n, 2L]; pool: FEATURE_DTYPE array."""
+        pb = origin_size * origin_size + half_size * half_size + quarter_size * quarter_size
+        s, keep = _samples(samples, self.dim, pb)
+        fa, fp = _features(pool)
+        out = np.zeros((len(fa), s.n), np.int32)
+        if lib.jdaCalcFeatureValuesCpp(self.h, C.byref(s), origin_size, half_size, quarter_size, fp, len(fa),
+                                       out.ctypes.data_as(C.POINTER(C.c_int))) != 0:
+            raise JdaError(last_error())
+        del keep
+        return out
+
+    def split_node_cpp(self, pos, neg, pool, mode, u=None, origin_size=48, half_size=36, quarter_size=24):
+        """Cart::SplitNode's choice over the full sets (reference cart.cpp:176-350): mode 1 classification, 0 regression
+        (u: one draw per pool feature) -> dict(feature_idx, threshold, criterion [F] es_ / vs_, thresholds [F] ths_)."""
+        pb = origin_size * origin_size + half_size * half_size + quarter_size * quarter_size
+        sp, kp = _samples(pos, self.dim, pb)
+        sn, kn = _samples(neg, self.dim, pb)
+        fa, fp = _features(pool)
+        F = len(fa)
+        ua = None if u is None else np.ascontiguousarray(u, np.float64).reshape(-1)
+        assert ua is None or ua.size == F
+        crit = np.zeros(F, np.float64)
+        ths = np.zeros(F, np.int32)
+        fi, th = C.c_int(), C.c_int()
+        rc = lib.jdaSplitNodeCpp(self.h, C.byref(sp), C.byref(sn), origin_size, half_size, quarter_size, fp, F, int(mode),
+                                 None if ua is None else ua.ctypes.data_as(C.POINTER(C.c_double)), C.byref(fi), C.byref(th),
+                                 crit.ctypes.data_as(C.POINTER(C.c_double)), ths.ctypes.data_as(C.POINTER(C.c_int)))
+        del kp, kn
+        if rc != 0:
+            raise JdaError(last_error())
+        return dict(feature_idx=fi.value, threshold=th.value, criterion=crit, thresholds=ths)
+
+    def train_cart_cpp(self, pos, neg, pools, modes, us=None, origin_size=48, half_size=36, quarter_size=24):
+        """Cart::Train (reference cart.cpp:41-162) with the caller's pools [nodes_n/2 - 1, F], modes [nodes_n/2 - 1] and
+        regression draws us [nodes_n/2 - 1, F] -> dict(features, thresholds, scores [leaves], pos_leaf, neg_leaf, nodes
+        (NODE_DTYPE per internal node), stats)."""
+        pb = origin_size * origin_size + half_size * half_size + quarter_size * quarter_size
+        sp, kp = _samples(pos, self.dim, pb)
+        sn, kn = _samples(neg, self.dim, pb)
+        half = 1 << (self.D - 1)
+        inner = half - 1
+        fa, fp = _features(pools)
+        assert inner > 0 and len(fa) % inner == 0, "pools must hold (nodes_n/2 - 1) * F features"
+        F = len(fa) // inner
+        md = np.ascontiguousarray(modes, np.int32).reshape(-1)
+        assert md.size == inner
+        ua = None if us is None else np.ascontiguousarray(us, np.float64).reshape(-1)
+        assert ua is None or ua.size == inner * F
+        feats = np.zeros(inner, FEATURE_DTYPE)
+        ths = np.zeros(inner, np.int32)
+        scores = np.zeros(half, np.float64)
+        pleaf = np.zeros(max(sp.n, 1), np.int32)
+        nleaf = np.zeros(max(sn.n, 1), np.int32)
+        nodes = np.zeros(inner, NODE_DTYPE)
+        st = jdaTrainStatsCpp()
+        st.nodes = nodes.ctypes.data_as(C.POINTER(jdaTrainNodeCpp))
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        rc = lib.jdaTrainCartCpp(self.h, C.byref(sp), C.byref(sn), origin_size, half_size, quarter_size, fp, F,
+                                 md.ctypes.data_as(ip), None if ua is None else ua.ctypes.data_as(dp),
+                                 feats.ctypes.data_as(C.POINTER(jdaFeatureCpp)), ths.ctypes.data_as(ip), scores.ctypes.data_as(dp),
+                                 pleaf.ctypes.data_as(ip), nleaf.ctypes.data_as(ip), C.byref(st))
+        del kp, kn
+        if rc != 0:
+            raise JdaError(last_error())
+        stats = {k: getattr(st, k) for k, _ in st._fields_ if k != "nodes"}
+        return dict(features=feats, thresholds=ths, scores=scores, pos_leaf=pleaf[:sp.n], neg_leaf=nleaf[:sn.n], nodes=nodes,
+                    stats=stats)
 
     def trace_cpp(self, frames, minimum_size=20, step=5, factor=1.2):
         frames = np.ascontiguousarray(frames, np.uint8)

@@ -394,6 +394,31 @@ hipError_t launch_mine_walk(const MineModel& m, const MineSizes& z, const MineIt
 // Sum of status[0, n) over the rejected entries (status > 0): out[0] += count, out[1] += sum.
 hipError_t launch_mine_sum(const int* status, unsigned long long n, unsigned long long* out, hipStream_t stream);
 
+// ---- dialect CPP: training one CART (k_train.hip, train.cpp; reference src/jda/cart.cpp:41-350, data.cpp:148-173) ----
+
+// One pool feature: the fields of Feature (include/jda/common.hpp), jdaFeatureCpp's layout.
+struct TrainFeat { int scale, lm1, lm2, pad; double o1x, o1y, o2x, o2y; };
+// A sample set on the device: patches tight (o, h, q back to back per sample), shapes TRANSPOSED [2L][n] so that the
+// lanes of a wave (lane = sample, the landmark wave-uniform) read neighbouring doubles.
+struct TrainSet { const uint8_t* patches; const double* shapes_t; int n, os, hs, qs; };
+constexpr int kTrainBins = 511;          // value + 255, cart.cpp:197-198
+// Per-feature ordered sums of the regression split (cart.cpp:321-334): left / right x, x*x, y, y*y and the counts.
+struct TrainVar { double s[8]; int n_left, n_right, th, pad; };
+
+// shapes [n][dim] -> [dim][n]
+hipError_t launch_train_transpose(const double* in, int n, int dim, double* out, hipStream_t stream);
+// CalcFeatureValues: out[f * stride + j] = value of pool feature f on sample list[j] (list == nullptr: sample j), j < count.
+hipError_t launch_train_values(const TrainSet& set, const int* list, int count, const TrainFeat* pool, int F, short* out,
+                               size_t stride, hipStream_t stream);
+// Per feature the 511-bin histogram of values[f][0, count): counts, and (weights != nullptr) the weights added IN LIST
+// ORDER per bin.  out_w [F][511] doubles, out_c [F][511] ints.
+hipError_t launch_train_hist(const short* values, size_t stride, int F, const int* list, int count, const double* weights,
+                             double* out_w, int* out_c, hipStream_t stream);
+// Regression split per feature: threshold = the kidx[f]-th smallest value (from the counts), then the eight sums over the
+// list in order (samples with has_gt only).
+hipError_t launch_train_var(const short* values, size_t stride, int F, const int* list, int count, const double* residual,
+                            const uint8_t* has_gt, const int* counts, const int* kidx, TrainVar* out, hipStream_t stream);
+
 // Hardware-queue probe (k_misc.hip): a one-wave spin of `ticks` wall-clock ticks (100 MHz) that leaves its end time in
 // *out (mapped pinned host memory), and a kernel that leaves the time it ran.
 hipError_t launch_hwq_spin(long long ticks, unsigned long long* out, hipStream_t stream);
