@@ -292,6 +292,11 @@ def gen_feature_pool_cpp(F, landmark_n, radius, multi_scale=False, seed=0, key=0
     return feats[:F], u[:F]
 
 
+def _patch_bytes(origin_size, half_size, quarter_size):
+    """Bytes of one sample's o, h, q patches back to back (jdaSamplesCpp's layout)."""
+    return origin_size * origin_size + half_size * half_size + quarter_size * quarter_size
+
+
 def _features(pool):
     a = np.ascontiguousarray(pool, FEATURE_DTYPE).reshape(-1)
     return a, a.ctypes.data_as(C.POINTER(jdaFeatureCpp))
@@ -346,6 +351,21 @@ def _image_set(images):
     kw, ws = _ivec([a.shape[1] for a in imgs])
     kh, hs = _ivec([a.shape[0] for a in imgs])
     return False, C.cast(ptrs, C.POINTER(C.POINTER(C.c_ubyte))), None, ws, hs, len(imgs), (imgs, ptrs, kw, kh)
+
+
+def _pack_images_device(images):
+    """A list of host images -> _image_set's device form: one torch CUDA buffer, every image at a 256-byte aligned offset."""
+    import torch
+    imgs = [np.ascontiguousarray(a, np.uint8) for a in images]
+    offs = np.zeros(len(imgs), np.uint64)
+    tot = 0
+    for i, a in enumerate(imgs):
+        offs[i] = tot
+        tot += (a.size + 255) // 256 * 256
+    host = np.zeros(max(tot, 256), np.uint8)
+    for i, a in enumerate(imgs):
+        host[int(offs[i]):int(offs[i]) + a.size] = a.ravel()
+    return torch.from_numpy(host).cuda(), offs, [a.shape[1] for a in imgs], [a.shape[0] for a in imgs]
 
 
 def count_windows(width, height, scale=1.25, min_size=40, max_size=-1):
@@ -903,18 +923,7 @@ class Cascador:
         images on the device first (torch) and calls the device entry.  -> dict of hits [n, 4] (image, x, y, win), score,
         shape, o / h / q patch bytes and stats (windows, nega_n, carts_n, next_start, total_windows, hits)."""
         if device and not isinstance(images, tuple):
-            import torch
-            imgs = [np.ascontiguousarray(a, np.uint8) for a in images]
-            offs = np.zeros(len(imgs), np.uint64)
-            tot = 0
-            for i, a in enumerate(imgs):
-                offs[i] = tot
-                tot += (a.size + 255) // 256 * 256
-            host = np.zeros(max(tot, 256), np.uint8)
-            for i, a in enumerate(imgs):
-                host[int(offs[i]):int(offs[i]) + a.size] = a.ravel()
-            buf = torch.from_numpy(host).cuda()
-            images = (buf, offs, [a.shape[1] for a in imgs], [a.shape[0] for a in imgs])
+            images = _pack_images_device(images)
         dev, base, offs, ws, hs, n_img, keep = _image_set(images)
         ks, sp = _ivec(steps)
         kf, fp = _ivec(factors, C.c_double, np.float64)
@@ -923,7 +932,7 @@ class Cascador:
         hits = np.zeros((cap, 4), np.int32)
         score = np.zeros(cap, np.float64)
         shape = np.zeros((cap, self.dim), np.float64)
-        pt = origin_size * origin_size + half_size * half_size + quarter_size * quarter_size
+        pt = _patch_bytes(origin_size, half_size, quarter_size)
         pat = np.zeros((cap, pt), np.uint8) if patches else None
         st = jdaMineStats()
         args = (sp, fp, tp, origin_size, half_size, quarter_size, int(start), int(size), float(shift_size),
@@ -951,7 +960,7 @@ class Cascador:
         """DataSet::CalcFeatureValues (reference data.cpp:148-173): [F, n] int32, row = feature.  samples: dict of patches
         ([n, o*o + h*h + q*q] uint8, numpy or a torch CUDA tensor -- the layout mine_negatives_cpp returns), shapes
         [n, 2L]; pool: FEATURE_DTYPE array."""
-        pb = origin_size * origin_size + half_size * half_size + quarter_size * quarter_size
+        pb = _patch_bytes(origin_size, half_size, quarter_size)
         s, keep = _samples(samples, self.dim, pb)
         fa, fp = _features(pool)
         out = np.zeros((len(fa), s.n), np.int32)
@@ -964,7 +973,7 @@ class Cascador:
     def split_node_cpp(self, pos, neg, pool, mode, u=None, origin_size=48, half_size=36, quarter_size=24):
         """Cart::SplitNode's choice over the full sets (reference cart.cpp:176-350): mode 1 classification, 0 regression
         (u: one draw per pool feature) -> dict(feature_idx, threshold, criterion [F] es_ / vs_, thresholds [F] ths_)."""
-        pb = origin_size * origin_size + half_size * half_size + quarter_size * quarter_size
+        pb = _patch_bytes(origin_size, half_size, quarter_size)
         sp, kp = _samples(pos, self.dim, pb)
         sn, kn = _samples(neg, self.dim, pb)
         fa, fp = _features(pool)
@@ -986,7 +995,7 @@ class Cascador:
         """Cart::Train (reference cart.cpp:41-162) with the caller's pools [nodes_n/2 - 1, F], modes [nodes_n/2 - 1] and
         regression draws us [nodes_n/2 - 1, F] -> dict(features, thresholds, scores [leaves], pos_leaf, neg_leaf, nodes
         (NODE_DTYPE per internal node), stats)."""
-        pb = origin_size * origin_size + half_size * half_size + quarter_size * quarter_size
+        pb = _patch_bytes(origin_size, half_size, quarter_size)
         sp, kp = _samples(pos, self.dim, pb)
         sn, kn = _samples(neg, self.dim, pb)
         half = 1 << (self.D - 1)

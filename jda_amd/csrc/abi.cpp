@@ -8,28 +8,7 @@
 
 using namespace jda;
 
-// ---- exception barrier -------------------------------------------------------------------------------------------
-// No C++ exception may cross `extern "C"`: the host side allocates (std::vector growth in the post-processing, the
-// 512 MB of a big model's tables, std::string in the error channel, std::thread) and a std::bad_alloc that left
-// jdaDetect* would end the caller's process in std::terminate.  The reference answers an allocation failure with NULL
-// (c/jda.c:487-493); every entry below is a function-try-block whose handler reports through jdaGetLastError() and
-// returns the entry's error value (NULL / -1 / an empty jdaResult).  Stack unwinding has given back what the call held
-// (PlanPin; LaneSet, which waits for its lanes' streams BEFORE it returns them to the pool when it is destroyed by an
-// exception); the detect entries also wait for the device as a whole, because the caller is free to release its frames
-// as soon as the entry returns.  Helper threads (the ticket issuer, the ragged uploader, the post-processing workers)
-// catch inside their bodies and hand the failure to the thread that joins them.
 namespace {
-void abi_exception(const char* fn, bool sync_device) noexcept {
-  const char* what = "unknown C++ exception";
-  char buf[200];
-  try { throw; }
-  catch (const std::bad_alloc&) { what = "out of host memory (std::bad_alloc)"; }
-  catch (const std::exception& e) { std::snprintf(buf, sizeof buf, "%s", e.what()); what = buf; }
-  catch (...) {}
-  try { fail(std::string(fn) + ": " + what); }
-  catch (...) { std::fprintf(stderr, "libjda: %s: %s\n", fn, what); }       // (not even the message could be allocated)
-  if (sync_device) { (void)hipDeviceSynchronize(); (void)hipGetLastError(); }
-}
 // test hook (option test_throw; tests/test_abi.py): 1 = std::bad_alloc, 2 = std::runtime_error inside the entry
 void maybe_throw(const Cascador* c) {
   if (c->kn.test_throw == 1) throw std::bad_alloc();
@@ -46,9 +25,6 @@ int rows_out(Cascador* c, int rc, RowsOut<typename D::Real>& v, typename D::Real
   return 0;
 }
 }  // namespace
-#define JDA_ABI_CATCH(ret) catch (...) { abi_exception(__func__, false); return ret; }
-#define JDA_ABI_CATCH_SYNC(ret) catch (...) { abi_exception(__func__, true); return ret; }
-#define JDA_ABI_CATCH_VOID catch (...) { abi_exception(__func__, false); }
 
 extern "C" {
 
@@ -347,10 +323,9 @@ int jdaBuildPyramid(void* cascador, const unsigned char* data, int width, int he
   const int w1 = (int)((float)width * r), h1 = (int)((float)height * r), w2 = width / 2, h2 = height / 2;
   if (hw) *hw = w1; if (hh) *hh = h1; if (qw) *qw = w2; if (qh) *qh = h2;
   if (!half && !quarter) return 0;
-  if (!begin_device(c)) return -1;
-  LaneSet lanes(c);
-  if (!lanes.take(1)) return -1;
-  Lane* ln = lanes.v[0];
+  OneLane one_lane(c);
+  if (!one_lane.open()) return -1;
+  Lane* ln = one_lane.lane;
   const unsigned char* frames[1] = {data};
   size_t stride = 0;
   if (!stage_frames(ln, frames, 1, (size_t)width * height, &stride)) return -1;
@@ -395,10 +370,9 @@ int jdaResizeCv(void* cascador, const unsigned char* data, int width, int height
   g_err.clear();
   Cascador* c = (Cascador*)cascador;
   if (!c || !data || !out || width <= 0 || height <= 0 || ow <= 0 || oh <= 0) { fail("bad arguments"); return -1; }
-  if (!begin_device(c)) return -1;
-  LaneSet lanes(c);
-  if (!lanes.take(1)) return -1;
-  Lane* ln = lanes.v[0];
+  OneLane one_lane(c);
+  if (!one_lane.open()) return -1;
+  Lane* ln = one_lane.lane;
   const unsigned char* frames[1] = {data};
   size_t stride = 0;
   if (!stage_frames(ln, frames, 1, (size_t)width * height, &stride)) return -1;
@@ -429,10 +403,9 @@ static int detect_cpp_pyramid_impl(void* cascador, const unsigned char* const* f
     return -1;
   }
   if (!cpp_model_complete(c)) return -1;
-  if (!begin_device(c)) return -1;
-  LaneSet lanes(c);
-  if (!lanes.take(1)) return -1;
-  Lane* ln = lanes.v[0];
+  OneLane one_lane(c);
+  if (!one_lane.open()) return -1;
+  Lane* ln = one_lane.lane;
   size_t stride0 = 0;
   if (!stage_frames(ln, frames, n, (size_t)width * height, &stride0)) return -1;
 
@@ -442,7 +415,7 @@ static int detect_cpp_pyramid_impl(void* cascador, const unsigned char* const* f
   RunStats rs_total;
   long long patch_total = 0;
   // level images ping-pong inside one buffer; level 0 is the staged input
-  struct LevelBuf : DevBuf { ~LevelBuf() { release(); } } levels;      // (freed on every way out, also an exception's)
+  CallBuf levels;
   const size_t lvl_stride = ((size_t)width * height + 255) & ~(size_t)255;
   auto body = [&]() -> bool {
     if (!levels.reserve(2 * lvl_stride * (size_t)std::max(n, 1))) return false;
@@ -464,7 +437,7 @@ static int detect_cpp_pyramid_impl(void* cascador, const unsigned char* const* f
       // (levels after the first read `cur`, which the resize below wrote on ln->stream: handing that stream in as the
       // caller's stream makes run_device order every lane it uses behind it -- also a lane it only takes now, when the
       // pool had none to spare for an earlier level -- and lane 0 keeps running on ln->stream)
-      if (!run_device<double>(c, lanes, pe, cur, cur_stride, n, false, 0.0, li > 0 ? ln->stream : nullptr, &dets, nullptr, &rs, hf))
+      if (!run_device<double>(c, one_lane.set, pe, cur, cur_stride, n, false, 0.0, li > 0 ? ln->stream : nullptr, &dets, nullptr, &rs, hf))
         return false;
       rs_total += rs;
       patch_total += sp.windows * n;
@@ -564,7 +537,7 @@ long long jdaModelStreamBytes(int T, int K, int landmark_n, int tree_depth, int 
 namespace jda {
 void jda_bc_read_k_scan(unsigned long long*); void jda_bc_read_k_scan_d(unsigned long long*); void jda_bc_read_k_scan_r(unsigned long long*);
 void jda_bc_read_k_scan_dr(unsigned long long*); void jda_bc_read_k_scan_p(unsigned long long*); void jda_bc_read_k_finish(unsigned long long*);
-void jda_bc_read_k_wide(unsigned long long*); void jda_bc_read_k_stage(unsigned long long*); void jda_bc_read_k_mine(unsigned long long*);
+void jda_bc_read_k_wide(unsigned long long*); void jda_bc_read_k_stage(unsigned long long*); void jda_bc_read_k_mine(unsigned long long*); void jda_bc_read_k_train(unsigned long long*);
 }
 // bounds-check build only (libjda_bounds.so): per translation unit {first violation: site << 32 | source line, violations}
 // since the last call -- out[16]; returns the total number of violations (kernels_common.h: Bc)
@@ -574,11 +547,13 @@ __attribute__((visibility("default"))) long long jdaDebugBoundsReport(unsigned l
                                         jda_bc_read_k_scan_p, jda_bc_read_k_finish, jda_bc_read_k_wide, jda_bc_read_k_stage};
   long long total = 0;
   for (int i = 0; i < 8; i++) { unsigned long long v[2] = {0, 0}; rd[i](v); if (out) { out[2 * i] = v[0]; out[2 * i + 1] = v[1]; } total += (long long)v[1]; }
-  // k_mine's words ride in k_finish's slot (out keeps its 16 words): the line names the k_mine.hip source line
-  unsigned long long v[2] = {0, 0};
-  jda_bc_read_k_mine(v);
-  if (v[1]) {
-    std::fprintf(stderr, "libjda: bounds check: k_mine: %llu violation(s), first at site %llu line %llu\n", v[1], v[0] >> 32, v[0] & 0xffffffffull);
+  // k_mine's and k_train's words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file or in cpp_patch.h
+  const struct { void (*rd)(unsigned long long*); const char* tu; } more[2] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}};
+  for (const auto& t : more) {
+    unsigned long long v[2] = {0, 0};
+    t.rd(v);
+    if (!v[1]) continue;
+    std::fprintf(stderr, "libjda: bounds check: %s: %llu violation(s), first at site %llu line %llu (of the .hip file or cpp_patch.h)\n", t.tu, v[1], v[0] >> 32, v[0] & 0xffffffffull);
     if (out) { if (!out[11]) out[10] = v[0]; out[11] += v[1]; }
     total += (long long)v[1];
   }

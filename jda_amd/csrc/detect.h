@@ -20,11 +20,16 @@ double post_frames(const std::vector<Level>& levels, const FrameSet& fs, const R
 bool plan_c_call(Cascador* c, size_t stride, int width, int height, float scale, int min_size, int max_size,
                  ScanPlan* sp, PlanEntry** pe);
 bool cpp_model_complete(const Cascador* c);
-bool begin_device(Cascador* c);
 bool stage_frames(Lane* ln, const unsigned char* const* frames, int n, size_t fbytes, size_t* stride, bool defer = false);
 int detect_c_device(Cascador* c, const uint8_t* d_frames, size_t stride, int n, int width, int height,
                     float scale, int min_size, int max_size, float th, const jdaDetectOptions* opt,
                     jdaResult* out, const unsigned char* const* host_frames = nullptr);
+
+// the o / h / q patch sides of the trainer-side entries (k_mine_patches stages the o patch in LDS)
+inline bool check_patch_sizes(int os, int hs, int qs) {
+  if (os < 1 || hs < 1 || qs < 1 || os > 128 || hs > 128 || qs > 128) { fail("origin/half/quarter_size must be in [1, 128]"); return false; }
+  return true;
+}
 
 // detect_cpp.cpp: dialect CPP, method 1 (cascador.cpp:310-376,431-477) on a uniform batch; frames on the device
 // (d_frames) or, with host_frames set, in host memory

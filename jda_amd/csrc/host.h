@@ -60,6 +60,31 @@ inline double now_ms() {
   return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
+// ---- exception barrier -------------------------------------------------------------------------------------------
+// No C++ exception may cross `extern "C"`: the host side allocates (std::vector growth in the post-processing, the
+// 512 MB of a big model's tables, std::string in the error channel, std::thread) and a std::bad_alloc that left
+// jdaDetect* would end the caller's process in std::terminate.  The reference answers an allocation failure with NULL
+// (c/jda.c:487-493); every entry is a function-try-block whose handler reports through jdaGetLastError() and
+// returns the entry's error value (NULL / -1 / an empty jdaResult).  Stack unwinding has given back what the call held
+// (PlanPin; LaneSet, which waits for its lanes' streams BEFORE it returns them to the pool when it is destroyed by an
+// exception); the entries that use the device (_SYNC) also wait for the device as a whole, because the caller is free to
+// release its frames as soon as the entry returns.  Helper threads (the ticket issuer, the ragged uploader, the
+// post-processing workers) catch inside their bodies and hand the failure to the thread that joins them.
+inline void abi_exception(const char* fn, bool sync_device) noexcept {
+  const char* what = "unknown C++ exception";
+  char buf[200];
+  try { throw; }
+  catch (const std::bad_alloc&) { what = "out of host memory (std::bad_alloc)"; }
+  catch (const std::exception& e) { std::snprintf(buf, sizeof buf, "%s", e.what()); what = buf; }
+  catch (...) {}
+  try { fail(std::string(fn) + ": " + what); }
+  catch (...) { std::fprintf(stderr, "libjda: %s: %s\n", fn, what); }       // (not even the message could be allocated)
+  if (sync_device) { (void)hipDeviceSynchronize(); (void)hipGetLastError(); }
+}
+#define JDA_ABI_CATCH(ret) catch (...) { jda::abi_exception(__func__, false); return ret; }
+#define JDA_ABI_CATCH_SYNC(ret) catch (...) { jda::abi_exception(__func__, true); return ret; }
+#define JDA_ABI_CATCH_VOID catch (...) { jda::abi_exception(__func__, false); }
+
 // LDS of a gfx950 CU is handed out in granules of 1,280 bytes, 128 of them (160 KB): a workgroup of 54,272 bytes takes 43
 // granules and only TWO of them fit, although 3 x 54,272 < 163,840 and hipOccupancyMaxActiveBlocksPerMultiprocessor says
 // three (measured: tools/experiments/lds_occupancy.hip, profiles/r06_lds_granule.txt).
@@ -236,6 +261,9 @@ struct DevBuf {
   void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
 
+// ... of one call: freed on every way out, also an exception's
+struct CallBuf : DevBuf { ~CallBuf() { release(); } };
+
 // carve typed arrays out of one allocation
 struct Carver {
   unsigned char* base; size_t off = 0;
@@ -247,6 +275,18 @@ struct Carver {
     return r;
   }
 };
+
+// Two-pass carving: `carve(Carver&)` takes its arrays once from a null Carver, for the size, and once more from the
+// buffer reserved for them (+ 256: take() aligns every array).
+template <typename Fn>
+bool carve_into(DevBuf& buf, Fn&& carve) {
+  Carver need(nullptr);
+  carve(need);
+  if (!buf.reserve(need.off + 256)) return false;
+  Carver cv(buf.p);
+  carve(cv);
+  return true;
+}
 
 template <typename Real>
 struct ModelOnDevice {
@@ -534,6 +574,21 @@ struct LaneSet {
       for (Lane* l : v) { if (l->stream) (void)hipStreamSynchronize(l->stream); if (l->side) (void)hipStreamSynchronize(l->side); }
     { std::lock_guard<std::mutex> lk(c->mu); for (Lane* l : v) l->busy = false; }
     c->lane_cv.notify_all();
+  }
+};
+
+bool begin_device(Cascador* c);       // detect.cpp: ensure_device under c->mu
+
+// A call that runs on one lane: makes the device current, takes the lane; the lane goes back like LaneSet's.
+struct OneLane {
+  LaneSet set;
+  Lane* lane = nullptr;
+  hipStream_t stream = nullptr;
+  explicit OneLane(Cascador* c) : set(c) {}
+  bool open() {
+    if (!begin_device(set.c) || !set.take(1)) return false;
+    lane = set.v[0]; stream = lane->stream;
+    return true;
   }
 };
 

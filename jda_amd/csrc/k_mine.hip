@@ -7,48 +7,13 @@
 //   k_mine_walk     lane = crop: Validate, literally, on the patches (fp64, snapshot loop bounds, similarity transform,
 //                   initial shape shift)
 //   k_mine_sum      reject lengths of a range of windows (NegGenerator's carts_n / nega_n, data.cpp:1001-1004)
+#include "cpp_patch.h"
 #include "finish_common.h"
+#include "splitmix.h"
 
 namespace jda {
 
 namespace {
-
-// One output pixel of cv::resize(INTER_LINEAR, 8UC1) of an sw x sh source whose pixels `f(x, y)` returns: the same
-// operations as resize_cv_pixel (k_misc.hip), with the source behind a function so that it can itself be a resize.
-struct Rs { double sx, sy; int sw, sh, area, ident; };
-
-__device__ __forceinline__ Rs rs_make(int sw, int sh, int dw, int dh) {     // launch_resize_cv's parameters
-  Rs r;
-  r.sw = sw; r.sh = sh;
-  const double inv_sx = (double)dw / sw, inv_sy = (double)dh / sh;
-  r.sx = 1. / inv_sx; r.sy = 1. / inv_sy;
-  r.area = (fabs(r.sx - 2.) < 2.220446049250313e-16 && fabs(r.sy - 2.) < 2.220446049250313e-16) ? 1 : 0;
-  r.ident = (sw == dw && sh == dh) ? 1 : 0;     // (the bilinear formula then returns the source pixel itself)
-  return r;
-}
-
-template <typename F>
-__device__ __forceinline__ int cv_px(const F& f, const Rs& r, int dx, int dy) {
-  if (r.ident) return f(dx, dy);
-  if (r.area) return (f(2 * dx, 2 * dy) + f(2 * dx + 1, 2 * dy) + f(2 * dx, 2 * dy + 1) + f(2 * dx + 1, 2 * dy + 1) + 2) >> 2;
-  float fx = (float)(((double)dx + 0.5) * r.sx - 0.5);
-  int sx = (int)floorf(fx);
-  fx -= (float)sx;
-  if (sx < 0) { fx = 0.f; sx = 0; }
-  const bool edge = sx + 1 >= r.sw;
-  if (sx >= r.sw - 1) { fx = 0.f; sx = r.sw - 1; }
-  float fy = (float)(((double)dy + 0.5) * r.sy - 0.5);
-  const int sy = (int)floorf(fy);
-  fy -= (float)sy;
-  auto sat_short = [](float v) { int i = __float2int_rn(v); return i < -32768 ? -32768 : (i > 32767 ? 32767 : i); };
-  const int a0 = sat_short((1.f - fx) * 2048.f), a1 = sat_short(fx * 2048.f);
-  const int b0 = sat_short((1.f - fy) * 2048.f), b1 = sat_short(fy * 2048.f);
-  const int y0 = min(max(sy, 0), r.sh - 1), y1 = min(max(sy + 1, 0), r.sh - 1);
-  int r0, r1;
-  if (!edge) { r0 = f(sx, y0) * a0 + f(sx + 1, y0) * a1; r1 = f(sx, y1) * a0 + f(sx + 1, y1) * a1; }
-  else { r0 = f(sx, y0) * 2048; r1 = f(sx, y1) * 2048; }
-  return ((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2) & 0xff;
-}
 
 // Pixels of a crop of a transformed background image (data.cpp:930-963 by coordinate remapping: transpose first, then
 // mirror the stored image's x / y).
@@ -72,22 +37,13 @@ __device__ __forceinline__ Crop make_crop(const uint8_t* base, const MineImg& im
   return c;
 }
 
-// The initial shape's global shift (RandomShape, data.cpp:225-236) of the crop with key `key`: draw c of the
-// counter-based generator (include/jda.h: SplitMix64 of seed + (c + 1) * golden gamma, top 53 bits), c = 2 key for x
-// and 2 key + 1 for y, mapped like cv::RNG::uniform(a, b): a + (b - a) * u.
-__device__ __forceinline__ double mine_draw(unsigned long long seed, unsigned long long c, double a, double b) {
-  unsigned long long z = seed + (c + 1ull) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  const double u = (double)(z >> 11) * 0x1.0p-53;
-  return a + (b - a) * u;
-}
-
+// The initial shape's global shift (RandomShape, data.cpp:225-236) of the crop with key `key`: draws 2 key (x) and
+// 2 key + 1 (y) of the counter-based generator (include/jda.h, splitmix.h), mapped like cv::RNG::uniform(a, b): a + (b - a) * u.
 __device__ __forceinline__ void mine_shift(const MineSizes& z, unsigned long long key, double* dx, double* dy) {
   if (z.shift == 0.) { *dx = 0.; *dy = 0.; return; }
-  *dx = mine_draw(z.seed, 2ull * key, -z.shift, z.shift);
-  *dy = mine_draw(z.seed, 2ull * key + 1ull, -z.shift, z.shift);
+  const double a = -z.shift, b = z.shift;
+  *dx = a + (b - a) * splitmix_unit(splitmix_draw(z.seed, 2ull * key));
+  *dy = a + (b - a) * splitmix_unit(splitmix_draw(z.seed, 2ull * key + 1ull));
 }
 
 // segment of ordinal o: the last one whose first <= o
@@ -98,10 +54,6 @@ __device__ __forceinline__ int find_seg(const MineSeg* segs, int n, unsigned lon
     if (segs[mid].first <= o) lo = mid; else hi = mid - 1;
   }
   return lo;
-}
-
-__device__ __forceinline__ int coord_cpp(double s, double o, int pw) {   // data.cpp:40-51, common.hpp:227-232
-  return clamp_win(DialectCPP::coord(s, o, pw), pw);
 }
 
 }  // namespace
@@ -121,9 +73,9 @@ __global__ __launch_bounds__(256) void k_mine_scan(MineModel m, MineSizes z, con
   const int wi = (int)(o - sg.first);
   const int wy = wi / sg.nx, wx = wi - wy * sg.nx;
   const Crop crop = make_crop(base, imgs[sg.image], wx * sg.step, wy * sg.step);
-  const Rs ro = rs_make(sg.win, sg.win, z.os, z.os);
-  const Rs rh = rs_make(z.os, z.os, z.hs, z.hs), rq = rs_make(z.os, z.os, z.qs, z.qs);
-  auto opx = [&](int x, int y) { return cv_px(crop, ro, x, y); };
+  const CvResize ro = cv_resize_make(sg.win, sg.win, z.os, z.os);
+  const CvResize rh = cv_resize_make(z.os, z.os, z.hs, z.hs), rq = cv_resize_make(z.os, z.os, z.qs, z.qs);
+  const Resized<Crop> opx{crop, ro};
   double dx, dy;
   mine_shift(z, o, &dx, &dy);
   double score = 0.;
@@ -133,17 +85,12 @@ __global__ __launch_bounds__(256) void k_mine_scan(MineModel m, MineSizes z, con
     int node = 0;
     for (int d = 0; d < m.D - 1; d++) {
       const NodeD nd = cart[node];
-      const int pw = nd.scale == 0 ? z.os : (nd.scale == 1 ? z.hs : z.qs);
       // stage 0: every landmark of the shape is mean + (dx, dy)
-      const int x1 = coord_cpp(m.mean[nd.lm1x2] + dx, nd.o1x, pw), y1 = coord_cpp(m.mean[nd.lm1x2 + 1] + dy, nd.o1y, pw);
-      const int x2 = coord_cpp(m.mean[nd.lm2x2] + dx, nd.o2x, pw), y2 = coord_cpp(m.mean[nd.lm2x2 + 1] + dy, nd.o2y, pw);
-      int a, b;
-      if (nd.scale == 0) { a = opx(x1, y1); b = opx(x2, y2); }
-      else {
-        const Rs& r = nd.scale == 1 ? rh : rq;
-        a = cv_px(opx, r, x1, y1); b = cv_px(opx, r, x2, y2);
-      }
-      node = (a - b <= nd.th) ? 2 * node + 1 : 2 * node + 2;
+      const FeatXY c = feature_xy(nd.scale == 0 ? z.os : (nd.scale == 1 ? z.hs : z.qs), m.mean[nd.lm1x2] + dx, m.mean[nd.lm1x2 + 1] + dy,
+                                  nd.o1x, nd.o1y, m.mean[nd.lm2x2] + dx, m.mean[nd.lm2x2 + 1] + dy, nd.o2x, nd.o2y);
+      // ... and an h / q pixel is a resize of o pixels, themselves made on demand
+      const int v = nd.scale == 0 ? feature_diff(opx, c) : feature_diff(Resized<Resized<Crop>>{opx, nd.scale == 1 ? rh : rq}, c);
+      node = (v <= nd.th) ? 2 * node + 1 : 2 * node + 2;
     }
     const int idx = node - m.node_n;
     score += m.leaf[(size_t)k * m.leaf_n + idx];
@@ -206,10 +153,10 @@ __global__ __launch_bounds__(256) void k_mine_patches(MineSizes z, const uint8_t
   const MineItem it = items[blockIdx.x];
   const Crop crop = make_crop(base, imgs[it.image], it.x, it.y);
   uint8_t* out = patches + (size_t)blockIdx.x * pbytes;
-  const Rs ro = rs_make(it.w, it.h, z.os, z.os);
+  const CvResize ro = cv_resize_make(it.w, it.h, z.os, z.os);
   for (int e = threadIdx.x; e < z.os * z.os; e += blockDim.x) {
     const int y = e / z.os, x = e - y * z.os;
-    const uint8_t v = (uint8_t)cv_px(crop, ro, x, y);
+    const uint8_t v = (uint8_t)cv_resize_px(crop, ro, x, y);
     o_lds[e] = v;
     out[e] = v;
   }
@@ -222,10 +169,10 @@ __global__ __launch_bounds__(256) void k_mine_patches(MineSizes z, const uint8_t
     const int ds = s == 1 ? z.hs : z.qs;
     uint8_t* dst = out + z.os * z.os + (s == 2 ? z.hs * z.hs : 0);
     // chain 0 (mining, data.cpp:987-990): from the o patch; chain 1 (detectSingleScale, cascador.cpp:243-245): from the crop
-    const Rs r = z.mode == 0 ? rs_make(z.os, z.os, ds, ds) : rs_make(it.w, it.h, ds, ds);
+    const CvResize r = z.mode == 0 ? cv_resize_make(z.os, z.os, ds, ds) : cv_resize_make(it.w, it.h, ds, ds);
     for (int e = threadIdx.x; e < ds * ds; e += blockDim.x) {
       const int y = e / ds, x = e - y * ds;
-      dst[e] = (uint8_t)(z.mode == 0 ? cv_px(lds_px, r, x, y) : cv_px(crop, r, x, y));
+      dst[e] = (uint8_t)(z.mode == 0 ? cv_resize_px(lds_px, r, x, y) : cv_resize_px(crop, r, x, y));
     }
   }
 }
@@ -250,9 +197,7 @@ __global__ __launch_bounds__(64) void k_mine_walk(MineModel m, MineSizes z, cons
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int dim = m.dim, K = m.K;
-  const uint8_t* pat = patches + (size_t)i * pbytes;
-  const uint8_t* pimg[3] = {pat, pat + z.os * z.os, pat + z.os * z.os + z.hs * z.hs};
-  const int pside[3] = {z.os, z.hs, z.qs};
+  const PatchSet pat{patches + (size_t)i * pbytes, z.os, z.hs, z.qs};
   double* sh = shape_out + (size_t)i * dim;
   int* lbf = lbf_ws + (size_t)i * K;
   double* t1 = t1_ws + (size_t)i * dim;
@@ -277,13 +222,7 @@ __global__ __launch_bounds__(64) void k_mine_walk(MineModel m, MineSizes z, cons
         stp_apply<double>(stp, nd.o2x, nd.o2y, &bx, &by);
         nd.o1x = ax; nd.o1y = ay; nd.o2x = bx; nd.o2y = by;
       }
-      const int s = nd.scale == 1 ? 1 : (nd.scale == 2 ? 2 : 0);
-      const int pw = pside[s];
-      const int x1 = coord_cpp(sh[nd.lm1x2], nd.o1x, pw), y1 = coord_cpp(sh[nd.lm1x2 + 1], nd.o1y, pw);
-      const int x2 = coord_cpp(sh[nd.lm2x2], nd.o2x, pw), y2 = coord_cpp(sh[nd.lm2x2 + 1], nd.o2y, pw);
-      JDA_BC(Bc(0, (long long)pw * pw), y1 * pw + x1, 1, kBcFinishPix);
-      JDA_BC(Bc(0, (long long)pw * pw), y2 * pw + x2, 1, kBcFinishPix);
-      const int v = (int)pimg[s][y1 * pw + x1] - (int)pimg[s][y2 * pw + x2];
+      const int v = pat.feature(nd, sh[nd.lm1x2], sh[nd.lm1x2 + 1], sh[nd.lm2x2], sh[nd.lm2x2 + 1]);
       node = (v <= nd.th) ? 2 * node + 1 : 2 * node + 2;
     }
     *leaf = node - m.node_n;

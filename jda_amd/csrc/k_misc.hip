@@ -1,11 +1,11 @@
 // HIP kernels of the JDA detect path for gfx950 (MI355X, wave64): pyramid images, stage-0 offset tables,
 // queue fill, trace defaults.
 //   k_resize        bilinear pyramid image        reference c/jda.c:203-230
-//   k_resize_cv     cv::resize(INTER_LINEAR) restated (dialect CPP pyramids, cascador.cpp:302,330-331)
+//   k_resize_cv     cv::resize(INTER_LINEAR) of cpp_patch.h (dialect CPP pyramids, cascador.cpp:302,330-331)
 //   k_prep_stage0   stage-0 feature offsets per level (hoisted c/jda.c:370-389)
 //   k_enqueue       windows of levels k_scan does not cover -> hand-off queue at cart 0
 //   k_trace_fill    per-window trace defaults (parity instrumentation)
-#include "kernels_common.h"
+#include "cpp_patch.h"
 
 namespace jda {
 
@@ -48,39 +48,7 @@ hipError_t launch_resize(const uint8_t* src, size_t src_stride, int n, int sw, i
   return hipGetLastError();
 }
 
-// cv::resize(INTER_LINEAR) for 8-bit single-channel images as dialect CPP uses it for the
-// half/quarter images (cascador.cpp:329-331) and the method-0 pyramid (cascador.cpp:300-303):
-// 11-bit fixed-point bilinear of OpenCV's 2.4/3.x imgwarp.cpp, with its routing of an exact
-// 2x2 down-scale to the box average.  PARITY UNPINNED (no OpenCV here to compare with);
-// bit-exact against the oracle's restatement of the same algorithm.
-// One output pixel (dx, dy) of the resize of an sw x sh image whose rows are `pitch` bytes apart.
-__device__ __forceinline__ uint8_t resize_cv_pixel(const uint8_t* __restrict__ s, int pitch, int sw, int sh, int dx, int dy,
-                                                   double scale_x, double scale_y, int area_fast) {
-  if (area_fast) {
-    const uint8_t* p = s + (size_t)(2 * dy) * pitch + 2 * dx;
-    return (uint8_t)((p[0] + p[1] + p[pitch] + p[pitch + 1] + 2) >> 2);
-  }
-  float fx = (float)(((double)dx + 0.5) * scale_x - 0.5);
-  int sx = (int)floorf(fx);
-  fx -= (float)sx;
-  if (sx < 0) { fx = 0.f; sx = 0; }
-  const bool edge = sx + 1 >= sw;            // dx >= xmax in OpenCV's loop
-  if (sx >= sw - 1) { fx = 0.f; sx = sw - 1; }
-  float fy = (float)(((double)dy + 0.5) * scale_y - 0.5);
-  const int sy = (int)floorf(fy);
-  fy -= (float)sy;
-  auto sat_short = [](float v) { int i = __float2int_rn(v); return i < -32768 ? -32768 : (i > 32767 ? 32767 : i); };
-  const int a0 = sat_short((1.f - fx) * 2048.f), a1 = sat_short(fx * 2048.f);
-  const int b0 = sat_short((1.f - fy) * 2048.f), b1 = sat_short(fy * 2048.f);
-  const int y0 = min(max(sy, 0), sh - 1), y1 = min(max(sy + 1, 0), sh - 1);
-  const uint8_t* S0 = s + (size_t)y0 * pitch;
-  const uint8_t* S1 = s + (size_t)y1 * pitch;
-  int r0, r1;
-  if (!edge) { r0 = S0[sx] * a0 + S0[sx + 1] * a1; r1 = S1[sx] * a0 + S1[sx + 1] * a1; }
-  else { r0 = S0[sx] * 2048; r1 = S1[sx] * 2048; }
-  return (uint8_t)((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2);
-}
-
+// cv::resize(INTER_LINEAR) restated: cpp_patch.h.  (ident = 0: a same-size resize goes through the bilinear formula.)
 __global__ void k_resize_cv(const uint8_t* __restrict__ src, size_t src_stride, int sw, int sh,
                             uint8_t* __restrict__ dst, size_t dst_stride, int dw, int dh,
                             double scale_x, double scale_y, int area_fast) {
@@ -89,7 +57,7 @@ __global__ void k_resize_cv(const uint8_t* __restrict__ src, size_t src_stride, 
   const int f = blockIdx.z;
   if (dx >= dw || dy >= dh) return;
   dst[(size_t)f * dst_stride + (size_t)dy * dw + dx] =
-      resize_cv_pixel(src + (size_t)f * src_stride, sw, sw, sh, dx, dy, scale_x, scale_y, area_fast);
+      (uint8_t)cv_resize_px(Pitched{src + (size_t)f * src_stride, sw}, CvResize{scale_x, scale_y, sw, sh, area_fast, 0}, dx, dy);
 }
 
 // The same resize for the ROI of every window of a level (method 0 on a multi-scale model, cascador.cpp:243-245: the ROI
@@ -105,18 +73,16 @@ __global__ void k_resize_cv_patches(const uint8_t* __restrict__ src, size_t src_
   const int dy = e / ds, dx = e - dy * ds;
   const int wy = wi / nx, wx = wi - wy * nx;
   const uint8_t* roi = src + (size_t)f * src_stride + (size_t)(wy * step) * lw + wx * step;
-  dst[(size_t)f * dst_stride + (size_t)wi * ds * ds + e] = resize_cv_pixel(roi, lw, win, win, dx, dy, scale, scale, area_fast);
+  dst[(size_t)f * dst_stride + (size_t)wi * ds * ds + e] =
+      (uint8_t)cv_resize_px(Pitched{roi, lw}, CvResize{scale, scale, win, win, area_fast, 0}, dx, dy);
 }
 
 hipError_t launch_resize_cv(const uint8_t* src, size_t src_stride, int n, int sw, int sh,
                             uint8_t* dst, size_t dst_stride, int dw, int dh, hipStream_t stream) {
   if (dw <= 0 || dh <= 0 || n <= 0) return hipSuccess;
-  const double inv_sx = (double)dw / sw, inv_sy = (double)dh / sh;
-  const double scale_x = 1. / inv_sx, scale_y = 1. / inv_sy;
-  const int area = (fabs(scale_x - 2.) < 2.220446049250313e-16 && fabs(scale_y - 2.) < 2.220446049250313e-16) ? 1 : 0;
+  const CvResize r = cv_resize_make(sw, sh, dw, dh);
   dim3 block(256), grid((dw + 255) / 256, dh, n);
-  hipLaunchKernelGGL(k_resize_cv, grid, block, 0, stream, src, src_stride, sw, sh, dst, dst_stride, dw, dh,
-                     scale_x, scale_y, area);
+  hipLaunchKernelGGL(k_resize_cv, grid, block, 0, stream, src, src_stride, sw, sh, dst, dst_stride, dw, dh, r.sx, r.sy, r.area);
   return hipGetLastError();
 }
 
@@ -124,11 +90,9 @@ hipError_t launch_resize_cv_patches(const uint8_t* src, size_t src_stride, int n
                                     uint8_t* dst, size_t dst_stride, int ds, hipStream_t stream) {
   if (ds <= 0 || n <= 0 || nx <= 0 || ny <= 0) return hipSuccess;
   if (n > 65535 || (long long)nx * ny * ((ds * ds + 255) / 256) > 0x7fffffffLL) return hipErrorInvalidValue;
-  const double inv = (double)ds / win;
-  const double scale = 1. / inv;
-  const int area = fabs(scale - 2.) < 2.220446049250313e-16 ? 1 : 0;
+  const CvResize r = cv_resize_make(win, win, ds, ds);
   dim3 block(256), grid((unsigned)((long long)nx * ny * ((ds * ds + 255) / 256)), (unsigned)n);
-  hipLaunchKernelGGL(k_resize_cv_patches, grid, block, 0, stream, src, src_stride, lw, nx, step, win, dst, dst_stride, ds, scale, area);
+  hipLaunchKernelGGL(k_resize_cv_patches, grid, block, 0, stream, src, src_stride, lw, nx, step, win, dst, dst_stride, ds, r.sx, r.area);
   return hipGetLastError();
 }
 

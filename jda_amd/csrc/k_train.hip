@@ -8,17 +8,9 @@
 //   k_train_var        lane = feature: the order statistic from the counts (cart.cpp:314-320), then the eight sums of
 //                      the left / right residuals in list order (cart.cpp:321-334)
 // No log() here: the entropy sweep and the leaf scores are host work on these kernels' outputs (train.cpp).
-#include "kernels_common.h"
+#include "cpp_patch.h"
 
 namespace jda {
-
-namespace {
-
-__device__ __forceinline__ int coord_cpp(double s, double o, int pw) {   // data.cpp:44-54, common.hpp:227-232
-  return clamp_win(DialectCPP::coord(s, o, pw), pw);
-}
-
-}  // namespace
 
 // =============================================================================
 // k_train_transpose
@@ -52,18 +44,14 @@ __global__ __launch_bounds__(256) void k_train_values(TrainSet set, const int* _
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= count) return;
   const int s = list ? list[j] : j;
-  const int o2 = set.os * set.os, h2 = set.hs * set.hs;
-  const uint8_t* pat = set.patches + (size_t)s * (size_t)(o2 + h2 + set.qs * set.qs);
+  const PatchSet pat{set.patches + (size_t)s * (size_t)(set.os * set.os + set.hs * set.hs + set.qs * set.qs), set.os, set.hs, set.qs};
   const double* sh = set.shapes_t + s;
   const size_t n = (size_t)set.n;
   const int f0 = blockIdx.y * kTrainFeatTile, f1 = min(F, f0 + kTrainFeatTile);
   for (int f = f0; f < f1; f++) {
     const TrainFeat ft = pool[f];                       // wave-uniform: scalar loads
-    const int pw = ft.scale == 0 ? set.os : (ft.scale == 1 ? set.hs : set.qs);
-    const uint8_t* img = pat + (ft.scale == 0 ? 0 : (ft.scale == 1 ? o2 : o2 + h2));
-    const int x1 = coord_cpp(sh[(size_t)(2 * ft.lm1) * n], ft.o1x, pw), y1 = coord_cpp(sh[(size_t)(2 * ft.lm1 + 1) * n], ft.o1y, pw);
-    const int x2 = coord_cpp(sh[(size_t)(2 * ft.lm2) * n], ft.o2x, pw), y2 = coord_cpp(sh[(size_t)(2 * ft.lm2 + 1) * n], ft.o2y, pw);
-    out[(size_t)f * stride + j] = (short)((int)img[y1 * pw + x1] - (int)img[y2 * pw + x2]);
+    out[(size_t)f * stride + j] = (short)pat.feature(ft, sh[(size_t)(2 * ft.lm1) * n], sh[(size_t)(2 * ft.lm1 + 1) * n],
+                                                     sh[(size_t)(2 * ft.lm2) * n], sh[(size_t)(2 * ft.lm2 + 1) * n]);
   }
 }
 
@@ -198,5 +186,7 @@ hipError_t launch_train_var(const short* values, size_t stride, int F, const int
                      counts, kidx, out);
   return hipGetLastError();
 }
+
+JDA_BC_READER(k_train)
 
 }  // namespace jda

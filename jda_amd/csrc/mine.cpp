@@ -10,9 +10,6 @@ namespace jda {
 
 namespace {
 
-// RAII device buffer of one call
-struct CallBuf : DevBuf { ~CallBuf() { release(); } };
-
 // NextImage's levels of one (transformed) W x H image (data.cpp:915-925): none unless W, H > origin_size; win starts at
 // origin_size, a level is the full grid of windows `step` apart (x and y from 0 while x + win <= W, y + win <= H), the
 // next level's win is the int of win * factor (State::win_size is an int), and the walk stops at win >= W || win >= H.
@@ -52,18 +49,16 @@ bool mine_model(Cascador* c, MineModel* out) {
       d.scale = s.scale; d.lm1x2 = 2 * s.lm1; d.lm2x2 = 2 * s.lm2; d.th = s.th;
       d.o1x = s.off[0]; d.o1y = s.off[1]; d.o2x = s.off[2]; d.o2y = s.off[3];
     }
-    Carver sz(nullptr);
-    sz.take<NodeD>(nodes.size()); sz.take<double>(h.leaf_score.size()); sz.take<double>(carts); sz.take<double>(carts);
-    sz.take<double>(carts); sz.take<double>(h.w.size()); sz.take<double>(dim);
-    if (!c->mine_buf.reserve(sz.off + 256)) return false;
-    Carver cv(c->mine_buf.p);
+    NodeD* dn; double* dl; double* dth; double* dmu; double* dsd; double* dw; double* dms;
+    if (!carve_into(c->mine_buf, [&](Carver& cv) {
+          dn = cv.take<NodeD>(nodes.size());
+          dl = cv.take<double>(h.leaf_score.size());
+          dth = cv.take<double>(carts); dmu = cv.take<double>(carts); dsd = cv.take<double>(carts);
+          dw = cv.take<double>(h.w.size());
+          dms = cv.take<double>(dim);
+        })) return false;
     MineModel& m = c->mine_m;
     auto up = [&](const void* src, size_t bytes, void* dst) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess; };
-    NodeD* dn = cv.take<NodeD>(nodes.size());
-    double* dl = cv.take<double>(h.leaf_score.size());
-    double* dth = cv.take<double>(carts); double* dmu = cv.take<double>(carts); double* dsd = cv.take<double>(carts);
-    double* dw = cv.take<double>(h.w.size());
-    double* dms = cv.take<double>(dim);
     if (!up(nodes.data(), nodes.size() * sizeof(NodeD), dn) || !up(h.leaf_score.data(), h.leaf_score.size() * 8, dl) ||
         !up(h.cart_th.data(), carts * 8, dth) || !up(h.cart_mean.data(), carts * 8, dmu) || !up(h.cart_std.data(), carts * 8, dsd) ||
         !up(h.w.data(), h.w.size() * 8, dw) || !up(h.mean_shape.data(), dim * 8, dms)) {
@@ -83,7 +78,7 @@ bool mine_model(Cascador* c, MineModel* out) {
 }
 
 bool check_sizes(int os, int hs, int qs, int mode, double shift) {
-  if (os < 1 || hs < 1 || qs < 1 || os > 128 || hs > 128 || qs > 128) { fail("origin/half/quarter_size must be in [1, 128]"); return false; }
+  if (!check_patch_sizes(os, hs, qs)) return false;
   if (mode != 0 && mode != 1) { fail("resize_mode must be 0 (mining chain) or 1 (detectSingleScale chain)"); return false; }
   if (!(shift >= 0.) || !std::isfinite(shift)) { fail("shift_size must be finite and >= 0"); return false; }
   return true;
@@ -100,22 +95,13 @@ size_t item_bytes(const MineModel& m, const MineSizes& z) {
 struct WalkBufs {
   MineItem* items; uint8_t* patches; double* shape; double* t1; double* t2; int* lbf; double* score; int* carts; uint8_t* face;
   unsigned long long* ords;
+  void carve(Carver& cv, const MineModel& m, const MineSizes& z, size_t cap) {
+    items = cv.take<MineItem>(cap); patches = cv.take<uint8_t>(cap * pbytes_of(z));
+    shape = cv.take<double>(cap * m.dim); t1 = cv.take<double>(cap * m.dim); t2 = cv.take<double>(cap * m.dim);
+    lbf = cv.take<int>(cap * m.K); score = cv.take<double>(cap); carts = cv.take<int>(cap); face = cv.take<uint8_t>(cap);
+    ords = cv.take<unsigned long long>(cap);
+  }
 };
-WalkBufs carve_walk(void* p, const MineModel& m, const MineSizes& z, size_t cap, size_t* bytes = nullptr) {
-  Carver cv(p);
-  WalkBufs b;
-  b.items = cv.take<MineItem>(cap); b.patches = cv.take<uint8_t>(cap * pbytes_of(z));
-  b.shape = cv.take<double>(cap * m.dim); b.t1 = cv.take<double>(cap * m.dim); b.t2 = cv.take<double>(cap * m.dim);
-  b.lbf = cv.take<int>(cap * m.K); b.score = cv.take<double>(cap); b.carts = cv.take<int>(cap); b.face = cv.take<uint8_t>(cap);
-  b.ords = cv.take<unsigned long long>(cap);
-  if (bytes) *bytes = cv.off + 256;
-  return b;
-}
-size_t walk_bytes(const MineModel& m, const MineSizes& z, size_t cap) {
-  size_t n = 0;
-  (void)carve_walk(nullptr, m, z, cap, &n);
-  return n;
-}
 
 // crops that a batch of the walk takes at once, within the call's workspace budget
 size_t walk_cap(Cascador* c, const MineModel& m, const MineSizes& z, size_t want) {
@@ -147,26 +133,50 @@ bool stage_images(const unsigned char* const* images, const int* widths, const i
   return true;
 }
 
+// The caller's images on the device, and what the four device entries are called with.
+struct ImageSet { const uint8_t* d_base; const size_t* offsets; const int* widths; const int* heights; int n; };
+struct ValidateArgs {
+  ImageSet im; const int* crops; int n_crops; int os, hs, qs, mode; double shift; unsigned long long seed;
+  unsigned char* is_face; double* score; int* carts_n; double* shape; jdaStats* stats;
+};
+struct MineArgs {
+  ImageSet im; const int* steps; const double* factors; const int* transforms; int os, hs, qs; long long start; int size;
+  double shift; unsigned long long seed; int* hits; double* score; double* shape; unsigned char* patches; jdaMineStats* stats;
+};
+
+// The nb items in b.items through k_mine_patches and k_mine_walk; face, carts and (score_h given) score queued back to the
+// host.  The caller queues what else it wants back and waits for the stream.
+bool walk_batch(Cascador* c, const MineModel& m, const MineSizes& z, const uint8_t* d_base, const CallBuf& imgs, const WalkBufs& b,
+                int nb, uint8_t* face_h, int* carts_h, double* score_h, hipStream_t st) {
+  JDA_HIP(launch_mine_patches(z, d_base, (const MineImg*)imgs.p, b.items, nb, b.patches, pbytes_of(z), st));
+  JDA_HIP(launch_mine_walk(m, z, b.items, nb, b.patches, pbytes_of(z), c->similarity, b.face, b.carts, b.score, b.shape, b.lbf,
+                           b.t1, b.t2, st));
+  JDA_HIP(hipMemcpyAsync(face_h, b.face, nb, hipMemcpyDeviceToHost, st));
+  JDA_HIP(hipMemcpyAsync(carts_h, b.carts, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+  if (score_h) JDA_HIP(hipMemcpyAsync(score_h, b.score, nb * sizeof(double), hipMemcpyDeviceToHost, st));
+  return true;
+}
+
 // ---- Validate on caller crops -------------------------------------------------------------------------------------
 
-int validate_impl(Cascador* c, const uint8_t* d_base, const size_t* offsets, const int* widths, const int* heights, int n_images,
-                  const int* crops, int n_crops, int os, int hs, int qs, int mode, double shift, unsigned long long seed,
-                  unsigned char* is_face, double* score, int* carts_n, double* shape, jdaStats* stats) {
+int validate_device(Cascador* c, const ValidateArgs& a) {
   const double t0 = now_ms();
-  if (!c || n_images < 0 || n_crops < 0 || (n_crops > 0 && (!crops || !d_base || !offsets || !widths || !heights))) {
+  const ImageSet& im = a.im;
+  const int n_crops = a.n_crops;
+  if (!c || im.n < 0 || n_crops < 0 || (n_crops > 0 && (!a.crops || !im.d_base || !im.offsets || !im.widths || !im.heights))) {
     fail("bad arguments"); return -1;
   }
-  if (!check_sizes(os, hs, qs, mode, shift)) return -1;
-  std::vector<MineImg> imgs(n_images);
-  for (int i = 0; i < n_images; i++) {
-    if (widths[i] < 1 || heights[i] < 1) { fail("image " + std::to_string(i) + " has an empty size"); return -1; }
-    imgs[i] = MineImg{(unsigned long long)offsets[i], widths[i], heights[i], 0, 0};
+  if (!check_sizes(a.os, a.hs, a.qs, a.mode, a.shift)) return -1;
+  std::vector<MineImg> imgs(im.n);
+  for (int i = 0; i < im.n; i++) {
+    if (im.widths[i] < 1 || im.heights[i] < 1) { fail("image " + std::to_string(i) + " has an empty size"); return -1; }
+    imgs[i] = MineImg{(unsigned long long)im.offsets[i], im.widths[i], im.heights[i], 0, 0};
   }
   std::vector<MineItem> items(n_crops);
   for (int i = 0; i < n_crops; i++) {
-    const int* q = crops + 5 * i;
-    if (q[0] < 0 || q[0] >= n_images || q[3] < 1 || q[4] < 1 || q[1] < 0 || q[2] < 0 ||
-        (long long)q[1] + q[3] > widths[q[0]] || (long long)q[2] + q[4] > heights[q[0]]) {
+    const int* q = a.crops + 5 * i;
+    if (q[0] < 0 || q[0] >= im.n || q[3] < 1 || q[4] < 1 || q[1] < 0 || q[2] < 0 ||
+        (long long)q[1] + q[3] > im.widths[q[0]] || (long long)q[2] + q[4] > im.heights[q[0]]) {
       fail("crop " + std::to_string(i) + " (image, x, y, w, h) = (" + std::to_string(q[0]) + ", " + std::to_string(q[1]) + ", " +
            std::to_string(q[2]) + ", " + std::to_string(q[3]) + ", " + std::to_string(q[4]) + ") does not lie inside its image");
       return -1;
@@ -175,41 +185,36 @@ int validate_impl(Cascador* c, const uint8_t* d_base, const size_t* offsets, con
   }
   MineModel m;
   if (!mine_model(c, &m)) return -1;
-  const MineSizes z{os, hs, qs, mode, shift, seed};
-  LaneSet lanes(c);
-  if (!lanes.take(1)) return -1;
-  const hipStream_t st = lanes.v[0]->stream;
+  const MineSizes z{a.os, a.hs, a.qs, a.mode, a.shift, a.seed};
+  OneLane one(c);
+  if (!one.open()) return -1;
+  const hipStream_t st = one.stream;
   const int dim = m.dim;
   long long faces = 0, nf_carts = 0;
   CallBuf ib, wb;
   auto body = [&]() -> bool {
     if (!upload_imgs(imgs, &ib, st)) return false;
     const size_t cap = walk_cap(c, m, z, (size_t)std::max(1, n_crops));
-    if (!wb.reserve(walk_bytes(m, z, cap))) return false;
-    const WalkBufs b = carve_walk(wb.p, m, z, cap);
+    WalkBufs b;
+    if (!carve_into(wb, [&](Carver& cv) { b.carve(cv, m, z, cap); })) return false;
     std::vector<uint8_t> f(cap);
     std::vector<int> cn(cap);
     for (int at = 0; at < n_crops; at += (int)cap) {
       const int nb = (int)std::min<size_t>(cap, (size_t)(n_crops - at));
       JDA_HIP(hipMemcpyAsync(b.items, items.data() + at, nb * sizeof(MineItem), hipMemcpyHostToDevice, st));
-      JDA_HIP(launch_mine_patches(z, d_base, (const MineImg*)ib.p, b.items, nb, b.patches, pbytes_of(z), st));
-      JDA_HIP(launch_mine_walk(m, z, b.items, nb, b.patches, pbytes_of(z), c->similarity, b.face, b.carts, b.score, b.shape, b.lbf,
-                               b.t1, b.t2, st));
-      JDA_HIP(hipMemcpyAsync(f.data(), b.face, nb, hipMemcpyDeviceToHost, st));
-      JDA_HIP(hipMemcpyAsync(cn.data(), b.carts, nb * sizeof(int), hipMemcpyDeviceToHost, st));
-      if (score) JDA_HIP(hipMemcpyAsync(score + at, b.score, nb * sizeof(double), hipMemcpyDeviceToHost, st));
-      if (shape) JDA_HIP(hipMemcpyAsync(shape + (size_t)at * dim, b.shape, (size_t)nb * dim * sizeof(double), hipMemcpyDeviceToHost, st));
+      if (!walk_batch(c, m, z, im.d_base, ib, b, nb, f.data(), cn.data(), a.score ? a.score + at : nullptr, st)) return false;
+      if (a.shape) JDA_HIP(hipMemcpyAsync(a.shape + (size_t)at * dim, b.shape, (size_t)nb * dim * sizeof(double), hipMemcpyDeviceToHost, st));
       JDA_HIP(hipStreamSynchronize(st));
       for (int i = 0; i < nb; i++) {
-        if (is_face) is_face[at + i] = f[i];
-        if (carts_n) carts_n[at + i] = cn[i];
+        if (a.is_face) a.is_face[at + i] = f[i];
+        if (a.carts_n) a.carts_n[at + i] = cn[i];
         if (f[i]) faces++; else nf_carts += cn[i];
       }
     }
     return true;
   };
   if (!body()) return -1;
-  if (stats) {
+  if (jdaStats* stats = a.stats) {
     std::memset(stats, 0, sizeof *stats);
     stats->patch_n = n_crops; stats->face_patch_n = faces; stats->nonface_patch_n = n_crops - faces;
     stats->cart_gothrough_n = nf_carts;
@@ -221,45 +226,45 @@ int validate_impl(Cascador* c, const uint8_t* d_base, const size_t* offsets, con
 
 // ---- the mining walk ----------------------------------------------------------------------------------------------
 
-int mine_impl(Cascador* c, const uint8_t* d_base, const size_t* offsets, const int* widths, const int* heights, int n_images,
-              const int* steps, const double* factors, const int* transforms, int os, int hs, int qs, long long start, int size,
-              double shift, unsigned long long seed, int* hits, double* score, double* shape, unsigned char* patches,
-              jdaMineStats* stats) {
+int mine_device(Cascador* c, const MineArgs& a) {
   const double t0 = now_ms();
+  const ImageSet& im = a.im;
+  jdaMineStats* stats = a.stats;
+  const int size = a.size;
   if (stats) std::memset(stats, 0, sizeof *stats);
-  if (!c || n_images < 0 || size < 0 || start < 0 ||
-      (n_images > 0 && (!d_base || !offsets || !widths || !heights || !steps || !factors || !transforms))) {
+  if (!c || im.n < 0 || size < 0 || a.start < 0 ||
+      (im.n > 0 && (!im.d_base || !im.offsets || !im.widths || !im.heights || !a.steps || !a.factors || !a.transforms))) {
     fail("bad arguments"); return -1;
   }
-  if (!check_sizes(os, hs, qs, 0, shift)) return -1;
+  if (!check_sizes(a.os, a.hs, a.qs, 0, a.shift)) return -1;
   // the enumeration: (image, level) segments in NextImage's order
-  std::vector<MineImg> imgs(n_images);
+  std::vector<MineImg> imgs(im.n);
   std::vector<MineSeg> segs;
   unsigned long long total = 0;
   std::vector<MineLevel> lv;
-  for (int i = 0; i < n_images; i++) {
-    if (widths[i] < 1 || heights[i] < 1) { fail("image " + std::to_string(i) + " has an empty size"); return -1; }
-    if (transforms[i] < 0 || transforms[i] > 7) { fail("transform must be in 0..7"); return -1; }
-    const int tf = kTf[transforms[i]];
-    imgs[i] = MineImg{(unsigned long long)offsets[i], widths[i], heights[i], tf, 0};
-    const int W = (tf & kMineSwap) ? heights[i] : widths[i], H = (tf & kMineSwap) ? widths[i] : heights[i];
+  for (int i = 0; i < im.n; i++) {
+    if (im.widths[i] < 1 || im.heights[i] < 1) { fail("image " + std::to_string(i) + " has an empty size"); return -1; }
+    if (a.transforms[i] < 0 || a.transforms[i] > 7) { fail("transform must be in 0..7"); return -1; }
+    const int tf = kTf[a.transforms[i]];
+    imgs[i] = MineImg{(unsigned long long)im.offsets[i], im.widths[i], im.heights[i], tf, 0};
+    const int W = (tf & kMineSwap) ? im.heights[i] : im.widths[i], H = (tf & kMineSwap) ? im.widths[i] : im.heights[i];
     std::string err;
-    if (!mine_levels(W, H, os, steps[i], factors[i], &lv, &err)) { fail("image " + std::to_string(i) + ": " + err); return -1; }
+    if (!mine_levels(W, H, a.os, a.steps[i], a.factors[i], &lv, &err)) { fail("image " + std::to_string(i) + ": " + err); return -1; }
     for (const MineLevel& l : lv) {
-      segs.push_back(MineSeg{total, i, l.win, steps[i], l.nx});
+      segs.push_back(MineSeg{total, i, l.win, a.steps[i], l.nx});
       total += (unsigned long long)l.nx * l.ny;
     }
   }
-  const unsigned long long begin = std::min<unsigned long long>((unsigned long long)start, total);
+  const unsigned long long begin = std::min<unsigned long long>((unsigned long long)a.start, total);
   unsigned long long lo = begin;
   long long n_hits = 0, nega = 0, carts = 0;
   if (size > 0 && begin < total) {
     MineModel m;
     if (!mine_model(c, &m)) return -1;
-    const MineSizes z{os, hs, qs, 0, shift, seed};
-    LaneSet lanes(c);
-    if (!lanes.take(1)) return -1;
-    const hipStream_t st = lanes.v[0]->stream;
+    const MineSizes z{a.os, a.hs, a.qs, 0, a.shift, a.seed};
+    OneLane one(c);
+    if (!one.open()) return -1;
+    const hipStream_t st = one.stream;
     const int dim = m.dim, pb = pbytes_of(z), pt = ptight_of(z);
     // the scan's share of stage 0: Validate's first carts, pixels on demand.  With the similarity transform every window
     // goes to the walk (its stage-0 parameter depends on the window's own shifted shape).
@@ -271,21 +276,15 @@ int mine_impl(Cascador* c, const uint8_t* d_base, const size_t* offsets, const i
     CallBuf ib, sb, wb;
     auto body = [&]() -> bool {
       if (!upload_imgs(imgs, &ib, st)) return false;
-      const size_t seg_bytes = segs.size() * sizeof(MineSeg);
-      auto carve = [&](Carver& cv, MineSeg** sg, int** status, unsigned long long** surv, unsigned** nsurv, unsigned long long** sum) {
-        *sg = cv.take<MineSeg>(segs.size()); *status = cv.take<int>(chunk); *surv = cv.take<unsigned long long>(chunk);
-        *nsurv = cv.take<unsigned>(4); *sum = cv.take<unsigned long long>(2);
-      };
       MineSeg* d_segs; int* d_status; unsigned long long* d_surv; unsigned* d_nsurv; unsigned long long* d_sum;
-      Carver need(nullptr);
-      carve(need, &d_segs, &d_status, &d_surv, &d_nsurv, &d_sum);
-      if (!sb.reserve(need.off + 256)) return false;
-      Carver cv(sb.p);
-      carve(cv, &d_segs, &d_status, &d_surv, &d_nsurv, &d_sum);
-      JDA_HIP(hipMemcpyAsync(d_segs, segs.data(), seg_bytes, hipMemcpyHostToDevice, st));
+      if (!carve_into(sb, [&](Carver& cv) {
+            d_segs = cv.take<MineSeg>(segs.size()); d_status = cv.take<int>(chunk); d_surv = cv.take<unsigned long long>(chunk);
+            d_nsurv = cv.take<unsigned>(4); d_sum = cv.take<unsigned long long>(2);
+          })) return false;
+      JDA_HIP(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(MineSeg), hipMemcpyHostToDevice, st));
       const size_t cap = walk_cap(c, m, z, 65536);
-      if (!wb.reserve(walk_bytes(m, z, cap))) return false;
-      const WalkBufs b = carve_walk(wb.p, m, z, cap);
+      WalkBufs b;
+      if (!carve_into(wb, [&](Carver& cv) { b.carve(cv, m, z, cap); })) return false;
       std::vector<unsigned long long> surv;
       std::vector<uint8_t> f(cap);
       std::vector<int> cn(cap);
@@ -297,7 +296,7 @@ int mine_impl(Cascador* c, const uint8_t* d_base, const size_t* offsets, const i
         const unsigned long long hi = std::min(total, lo + chunk);
         JDA_HIP(hipMemsetAsync(d_nsurv, 0, 4 * sizeof(unsigned), st));
         JDA_HIP(hipMemsetAsync(d_sum, 0, 2 * sizeof(unsigned long long), st));
-        JDA_HIP(launch_mine_scan(m, z, d_base, (const MineImg*)ib.p, d_segs, (int)segs.size(), lo, hi, carts0, d_status, d_surv,
+        JDA_HIP(launch_mine_scan(m, z, im.d_base, (const MineImg*)ib.p, d_segs, (int)segs.size(), lo, hi, carts0, d_status, d_surv,
                                  d_nsurv, st));
         unsigned ns = 0;
         JDA_HIP(hipMemcpyAsync(&ns, d_nsurv, sizeof ns, hipMemcpyDeviceToHost, st));
@@ -314,12 +313,7 @@ int mine_impl(Cascador* c, const uint8_t* d_base, const size_t* offsets, const i
           const int nb = (int)std::min<size_t>(cap, surv.size() - at);
           JDA_HIP(hipMemcpyAsync(b.ords, surv.data() + at, nb * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
           JDA_HIP(launch_mine_items(d_segs, (int)segs.size(), b.ords, nb, b.items, st));
-          JDA_HIP(launch_mine_patches(z, d_base, (const MineImg*)ib.p, b.items, nb, b.patches, pb, st));
-          JDA_HIP(launch_mine_walk(m, z, b.items, nb, b.patches, pb, c->similarity, b.face, b.carts, b.score, b.shape, b.lbf,
-                                   b.t1, b.t2, st));
-          JDA_HIP(hipMemcpyAsync(f.data(), b.face, nb, hipMemcpyDeviceToHost, st));
-          JDA_HIP(hipMemcpyAsync(cn.data(), b.carts, nb * sizeof(int), hipMemcpyDeviceToHost, st));
-          JDA_HIP(hipMemcpyAsync(sc.data(), b.score, nb * sizeof(double), hipMemcpyDeviceToHost, st));
+          if (!walk_batch(c, m, z, im.d_base, ib, b, nb, f.data(), cn.data(), sc.data(), st)) return false;
           JDA_HIP(hipMemcpyAsync(it.data(), b.items, nb * sizeof(MineItem), hipMemcpyDeviceToHost, st));
           JDA_HIP(hipStreamSynchronize(st));
           // the batch's faces in order: their rows now, their shapes and patch bytes in one copy each below
@@ -331,15 +325,15 @@ int mine_impl(Cascador* c, const uint8_t* d_base, const size_t* offsets, const i
           }
           if (take.empty()) continue;
           const int last = take.back() + 1;             // faces lie in the batch's first `last` entries
-          if (shape) { sh_h.resize((size_t)last * dim); JDA_HIP(hipMemcpyAsync(sh_h.data(), b.shape, sh_h.size() * sizeof(double), hipMemcpyDeviceToHost, st)); }
-          if (patches) { pa_h.resize((size_t)last * pb); JDA_HIP(hipMemcpyAsync(pa_h.data(), b.patches, pa_h.size(), hipMemcpyDeviceToHost, st)); }
+          if (a.shape) { sh_h.resize((size_t)last * dim); JDA_HIP(hipMemcpyAsync(sh_h.data(), b.shape, sh_h.size() * sizeof(double), hipMemcpyDeviceToHost, st)); }
+          if (a.patches) { pa_h.resize((size_t)last * pb); JDA_HIP(hipMemcpyAsync(pa_h.data(), b.patches, pa_h.size(), hipMemcpyDeviceToHost, st)); }
           JDA_HIP(hipStreamSynchronize(st));
           for (int i : take) {
             const long long h = n_hits++;
-            if (hits) { int* r = hits + 4 * h; r[0] = it[i].image; r[1] = it[i].x; r[2] = it[i].y; r[3] = it[i].w; }
-            if (score) score[h] = sc[i];
-            if (shape) std::memcpy(shape + (size_t)h * dim, sh_h.data() + (size_t)i * dim, dim * sizeof(double));
-            if (patches) std::memcpy(patches + (size_t)h * pt, pa_h.data() + (size_t)i * pb, pt);
+            if (a.hits) { int* r = a.hits + 4 * h; r[0] = it[i].image; r[1] = it[i].x; r[2] = it[i].y; r[3] = it[i].w; }
+            if (a.score) a.score[h] = sc[i];
+            if (a.shape) std::memcpy(a.shape + (size_t)h * dim, sh_h.data() + (size_t)i * dim, dim * sizeof(double));
+            if (a.patches) std::memcpy(a.patches + (size_t)h * pt, pa_h.data() + (size_t)i * pb, pt);
           }
         }
         // reject lengths of the windows the scan rejected in [lo, cut), plus the walk's rejects (all below cut)
@@ -362,13 +356,13 @@ int mine_impl(Cascador* c, const uint8_t* d_base, const size_t* offsets, const i
   return (int)n_hits;
 }
 
-int catch_all(const char* fn) noexcept {
-  try { throw; }
-  catch (const std::bad_alloc&) { fail(std::string(fn) + ": out of host memory (std::bad_alloc)"); }
-  catch (const std::exception& e) { fail(std::string(fn) + ": " + e.what()); }
-  catch (...) { fail(std::string(fn) + ": unknown C++ exception"); }
-  (void)hipDeviceSynchronize(); (void)hipGetLastError();
-  return -1;
+// The host entries' first step: the images to the device (the device is made current here), base and offsets into `im`.
+struct Staged { CallBuf buf; std::vector<size_t> offs; };
+bool stage(Cascador* c, const unsigned char* const* images, ImageSet* im, Staged* st) {
+  if (!c || im->n < 0 || (im->n > 0 && (!images || !im->widths || !im->heights))) { fail("bad arguments"); return false; }
+  if (!begin_device(c) || !stage_images(images, im->widths, im->heights, im->n, &st->buf, &st->offs, nullptr)) return false;
+  im->d_base = (const uint8_t*)st->buf.p; im->offsets = st->offs.data();
+  return true;
 }
 
 }  // namespace
@@ -387,7 +381,7 @@ int jdaMineWindows(int w, int h, int origin_size, int step, double factor, long 
   if (n) *n = t;
   if (levels) *levels = (int)lv.size();
   return 0;
-} catch (...) { return catch_all(__func__); }
+} JDA_ABI_CATCH(-1)
 
 long long jdaMineWindowList(int w, int h, int origin_size, int step, double factor, int* xyw, long long cap) try {
   std::vector<MineLevel> lv;
@@ -399,51 +393,39 @@ long long jdaMineWindowList(int w, int h, int origin_size, int step, double fact
       for (int x = 0; x < l.nx; x++, t++)
         if (xyw && t < cap) { xyw[3 * t] = x * step; xyw[3 * t + 1] = y * step; xyw[3 * t + 2] = l.win; }
   return t;
-} catch (...) { return catch_all(__func__); }
+} JDA_ABI_CATCH(-1)
 
 int jdaValidateCpp(void* cascador, const unsigned char* const* images, const int* widths, const int* heights, int n_images,
                    const int* crops, int n_crops, int origin_size, int half_size, int quarter_size, int resize_mode,
                    double shift_size, uint64_t seed, unsigned char* is_face, double* score, int* carts_n, double* shape,
                    jdaStats* stats) try {
   g_err.clear();
-  Cascador* c = (Cascador*)cascador;
-  if (!c || n_images < 0 || (n_images > 0 && (!images || !widths || !heights))) { fail("bad arguments"); return -1; }
-  if (!begin_device(c)) return -1;
-  CallBuf buf;
-  std::vector<size_t> offs;
-  hipStream_t st = nullptr;
-  if (!stage_images(images, widths, heights, n_images, &buf, &offs, st)) return -1;
-  return validate_impl(c, (const uint8_t*)buf.p, offs.data(), widths, heights, n_images, crops, n_crops, origin_size, half_size,
-                       quarter_size, resize_mode, shift_size, seed, is_face, score, carts_n, shape, stats);
-} catch (...) { return catch_all(__func__); }
+  ValidateArgs a{{nullptr, nullptr, widths, heights, n_images}, crops, n_crops, origin_size, half_size, quarter_size, resize_mode,
+                 shift_size, seed, is_face, score, carts_n, shape, stats};
+  Staged st;
+  return stage((Cascador*)cascador, images, &a.im, &st) ? validate_device((Cascador*)cascador, a) : -1;
+} JDA_ABI_CATCH_SYNC(-1)
 
 int jdaValidateCppDevice(void* cascador, const unsigned char* d_base, const size_t* offsets, const int* widths, const int* heights,
                          int n_images, const int* crops, int n_crops, int origin_size, int half_size, int quarter_size,
                          int resize_mode, double shift_size, uint64_t seed, unsigned char* is_face, double* score, int* carts_n,
                          double* shape, jdaStats* stats) try {
   g_err.clear();
-  Cascador* c = (Cascador*)cascador;
-  if (!c) { fail("bad arguments"); return -1; }
-  if (!begin_device(c)) return -1;
-  return validate_impl(c, d_base, offsets, widths, heights, n_images, crops, n_crops, origin_size, half_size, quarter_size,
-                       resize_mode, shift_size, seed, is_face, score, carts_n, shape, stats);
-} catch (...) { return catch_all(__func__); }
+  return validate_device((Cascador*)cascador, ValidateArgs{{d_base, offsets, widths, heights, n_images}, crops, n_crops, origin_size,
+                                                           half_size, quarter_size, resize_mode, shift_size, seed, is_face, score,
+                                                           carts_n, shape, stats});
+} JDA_ABI_CATCH_SYNC(-1)
 
 int jdaMineNegativesCpp(void* cascador, const unsigned char* const* images, const int* widths, const int* heights, int n_images,
                         const int* steps, const double* factors, const int* transforms, int origin_size, int half_size,
                         int quarter_size, long long start, int size, double shift_size, uint64_t seed, int* hits, double* score,
                         double* shape, unsigned char* patches, jdaMineStats* stats) try {
   g_err.clear();
-  Cascador* c = (Cascador*)cascador;
-  if (!c || n_images < 0 || (n_images > 0 && (!images || !widths || !heights))) { fail("bad arguments"); return -1; }
-  if (!begin_device(c)) return -1;
-  CallBuf buf;
-  std::vector<size_t> offs;
-  hipStream_t st = nullptr;
-  if (!stage_images(images, widths, heights, n_images, &buf, &offs, st)) return -1;
-  return mine_impl(c, (const uint8_t*)buf.p, offs.data(), widths, heights, n_images, steps, factors, transforms, origin_size,
-                   half_size, quarter_size, start, size, shift_size, seed, hits, score, shape, patches, stats);
-} catch (...) { return catch_all(__func__); }
+  MineArgs a{{nullptr, nullptr, widths, heights, n_images}, steps, factors, transforms, origin_size, half_size, quarter_size, start, size,
+             shift_size, seed, hits, score, shape, patches, stats};
+  Staged st;
+  return stage((Cascador*)cascador, images, &a.im, &st) ? mine_device((Cascador*)cascador, a) : -1;
+} JDA_ABI_CATCH_SYNC(-1)
 
 int jdaMineNegativesCppDevice(void* cascador, const unsigned char* d_base, const size_t* offsets, const int* widths,
                               const int* heights, int n_images, const int* steps, const double* factors, const int* transforms,
@@ -451,11 +433,9 @@ int jdaMineNegativesCppDevice(void* cascador, const unsigned char* d_base, const
                               uint64_t seed, int* hits, double* score, double* shape, unsigned char* patches,
                               jdaMineStats* stats) try {
   g_err.clear();
-  Cascador* c = (Cascador*)cascador;
-  if (!c) { fail("bad arguments"); return -1; }
-  if (!begin_device(c)) return -1;
-  return mine_impl(c, d_base, offsets, widths, heights, n_images, steps, factors, transforms, origin_size, half_size, quarter_size,
-                   start, size, shift_size, seed, hits, score, shape, patches, stats);
-} catch (...) { return catch_all(__func__); }
+  return mine_device((Cascador*)cascador, MineArgs{{d_base, offsets, widths, heights, n_images}, steps, factors, transforms, origin_size,
+                                                   half_size, quarter_size, start, size, shift_size, seed, hits, score, shape,
+                                                   patches, stats});
+} JDA_ABI_CATCH_SYNC(-1)
 
 }  // extern "C"

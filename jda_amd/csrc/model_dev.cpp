@@ -142,11 +142,6 @@ bool upload_model(Cascador* c) {
         for (unsigned d = split; d < levels; d++)
           for (unsigned n = (1u << d) - 1u; n < (2u << d) - 1u; n++)
             lm_deep[(t * h.K) * deep_per_cart + lm_deep_index(k, d, n, levels, split)] = nodes[(t * h.K + k) * node_n + n];
-  Carver sz(nullptr);
-  sz.take<Node>(lm_deep.size());
-  sz.take<NodeOff<Real>>(nodes.size()); sz.take<uint2>(nodes.size());
-  sz.take<Node>(nodes.size()); sz.take<Real>(leaf.size()); sz.take<Real>(carts); sz.take<Real>(carts);
-  sz.take<Real>(carts); sz.take<uint8_t>(carts); sz.take<Real>(w.size()); sz.take<Real>(dim); sz.take<Real>(dim); sz.take<Real>(par0.size());
   // k_finish's copy of the weight rows: every row on its own 128-byte lines (the file layout, c/jda.c:146, is what
   // k_stage and k_finish_wide stage whole carts of; a wave-per-window gather of single rows pays per line touched)
   const size_t w_rows_n = w.size() / (size_t)dim;
@@ -154,26 +149,19 @@ bool upload_model(Cascador* c) {
   const int line_elems = (c->kn.w_pad == 2 ? 64 : 128) / (int)sizeof(Real);
   const int w_pitch = c->kn.w_pad ? ((dim + line_elems - 1) / line_elems) * line_elems : dim;
   const bool padded = w_pitch != dim && w_rows_n * (size_t)w_pitch < (1ull << 32);      // (k_finish keeps row offsets in 32 bits)
-  if (padded) sz.take<Real>(w_rows_n * (size_t)w_pitch);
-  if (!mo.buf.reserve(sz.off + 256)) return false;
-  Carver cv(mo.buf.p);
-  Node* d_lm_deep = cv.take<Node>(lm_deep.size());
+  Node* d_lm_deep; NodeOff<Real>* d_lm_off; uint2* d_lm_meta; Node* d_nodes; Real* d_leaf; Real* d_cth; Real* d_cmean; Real* d_cstd;
+  uint8_t* d_cnorm; Real* d_w; Real* d_ms; Real* d_ms_raw; Real* d_par0; Real* d_w_rows;
+  if (!carve_into(mo.buf, [&](Carver& cv) {
+        d_lm_deep = cv.take<Node>(lm_deep.size());
+        d_lm_off = cv.take<NodeOff<Real>>(nodes.size()); d_lm_meta = cv.take<uint2>(nodes.size());
+        d_nodes = cv.take<Node>(nodes.size()); d_leaf = cv.take<Real>(leaf.size());
+        d_cth = cv.take<Real>(carts); d_cmean = cv.take<Real>(carts); d_cstd = cv.take<Real>(carts); d_cnorm = cv.take<uint8_t>(carts);
+        d_w = cv.take<Real>(w.size()); d_ms = cv.take<Real>(dim); d_ms_raw = cv.take<Real>(dim); d_par0 = cv.take<Real>(par0.size());
+        d_w_rows = padded ? cv.take<Real>(w_rows_n * (size_t)w_pitch) : d_w;
+      })) return false;
   if (!lm_deep.empty()) JDA_HIP(hipMemcpy(d_lm_deep, lm_deep.data(), lm_deep.size() * sizeof(Node), hipMemcpyHostToDevice));
-  NodeOff<Real>* d_lm_off = cv.take<NodeOff<Real>>(nodes.size());
-  uint2* d_lm_meta = cv.take<uint2>(nodes.size());
   JDA_HIP(hipMemcpy(d_lm_off, lm_off.data(), nodes.size() * sizeof(NodeOff<Real>), hipMemcpyHostToDevice));
   JDA_HIP(hipMemcpy(d_lm_meta, lm_meta.data(), nodes.size() * sizeof(uint2), hipMemcpyHostToDevice));
-  Node* d_nodes = cv.take<Node>(nodes.size());
-  Real* d_leaf = cv.take<Real>(leaf.size());
-  Real* d_cth = cv.take<Real>(carts);
-  Real* d_cmean = cv.take<Real>(carts);
-  Real* d_cstd = cv.take<Real>(carts);
-  uint8_t* d_cnorm = cv.take<uint8_t>(carts);
-  Real* d_w = cv.take<Real>(w.size());
-  Real* d_ms = cv.take<Real>(dim);
-  Real* d_ms_raw = cv.take<Real>(dim);
-  Real* d_par0 = cv.take<Real>(par0.size());
-  Real* d_w_rows = padded ? cv.take<Real>(w_rows_n * (size_t)w_pitch) : d_w;
   JDA_HIP(hipMemcpy(d_nodes, nodes.data(), nodes.size() * sizeof(Node), hipMemcpyHostToDevice));
   JDA_HIP(hipMemcpy(d_leaf, leaf.data(), leaf.size() * sizeof(Real), hipMemcpyHostToDevice));
   JDA_HIP(hipMemcpy(d_cth, cth.data(), carts * sizeof(Real), hipMemcpyHostToDevice));

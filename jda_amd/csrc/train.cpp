@@ -9,14 +9,13 @@
 #include <limits>
 
 #include "detect.h"
+#include "splitmix.h"
 
 namespace jda {
 
 namespace {
 
 static_assert(sizeof(TrainFeat) == sizeof(jdaFeatureCpp), "TrainFeat is jdaFeatureCpp's layout");
-
-struct CallBuf : DevBuf { ~CallBuf() { release(); } };
 
 constexpr double kEsp = 2.2e-16;          // Config::esp, common.cpp:143
 
@@ -44,19 +43,14 @@ bool upload_set(const jdaSamplesCpp* s, int L, int os, int hs, int qs, DevSet* d
   const size_t n = (size_t)s->n, dim = 2 * (size_t)L, pt = (size_t)os * os + (size_t)hs * hs + (size_t)qs * qs;
   d->ts.n = s->n; d->ts.os = os; d->ts.hs = hs; d->ts.qs = qs;
   if (n == 0) return true;
-  auto carve = [&](Carver& cv, uint8_t** pa, double** raw, double** tr, double** w, double** res, uint8_t** gt) {
-    *pa = s->patches_on_device ? nullptr : cv.take<uint8_t>(n * pt);
-    *raw = cv.take<double>(n * dim); *tr = cv.take<double>(n * dim);
-    *w = s->weights ? cv.take<double>(n) : nullptr;
-    *res = s->residual ? cv.take<double>(2 * n) : nullptr;
-    *gt = s->has_gt ? cv.take<uint8_t>(n) : nullptr;
-  };
   uint8_t* pa; double* raw; double* tr; double* w; double* res; uint8_t* gt;
-  Carver need(nullptr);
-  carve(need, &pa, &raw, &tr, &w, &res, &gt);
-  if (!d->buf.reserve(need.off + 256)) return false;
-  Carver cv(d->buf.p);
-  carve(cv, &pa, &raw, &tr, &w, &res, &gt);
+  if (!carve_into(d->buf, [&](Carver& cv) {
+        pa = s->patches_on_device ? nullptr : cv.take<uint8_t>(n * pt);
+        raw = cv.take<double>(n * dim); tr = cv.take<double>(n * dim);
+        w = s->weights ? cv.take<double>(n) : nullptr;
+        res = s->residual ? cv.take<double>(2 * n) : nullptr;
+        gt = s->has_gt ? cv.take<uint8_t>(n) : nullptr;
+      })) return false;
   if (pa) JDA_HIP(hipMemcpyAsync(pa, s->patches, n * pt, hipMemcpyHostToDevice, st));
   JDA_HIP(hipMemcpyAsync(raw, s->shapes, n * dim * sizeof(double), hipMemcpyHostToDevice, st));
   if (w) JDA_HIP(hipMemcpyAsync(w, s->weights, n * sizeof(double), hipMemcpyHostToDevice, st));
@@ -128,7 +122,8 @@ inline double variance_of(double s1, double s2, int n) {
 // ---- one call's device state --------------------------------------------------------------------------------------------
 
 struct Ctx {
-  Cascador* c = nullptr;
+  Cascador* c;
+  OneLane one;
   hipStream_t st = nullptr;
   int L = 0;
   DevSet pos, neg;
@@ -146,6 +141,15 @@ struct Ctx {
   double device_ms = 0, sweep_ms = 0, partition_ms = 0;
   long long evals = 0;
   int chunks = 0;
+
+  explicit Ctx(Cascador* c_) : c(c_), one(c_) {}
+
+  // The call's lane, both sample sets on the device (neg may be empty) and the workspace for pools of F features.
+  bool open(const jdaSamplesCpp* p, const jdaSamplesCpp* n, int os, int hs, int qs, int F_) {
+    if (!one.open()) return false;
+    st = one.stream; L = c->hm.L;
+    return upload_set(p, L, os, hs, qs, &pos, st) && upload_set(n, L, os, hs, qs, &neg, st) && reserve(F_);
+  }
 
   void carve(Carver& cv) {
     const size_t np = (size_t)pos.ts.n, nn = (size_t)neg.ts.n;
@@ -166,11 +170,7 @@ struct Ctx {
     const size_t per = (stride_p + stride_n) * 2 + 2 * (size_t)kTrainBins * 12 + sizeof(TrainVar) + 1024;
     const size_t room = budget / 2 > fixed ? budget / 2 - fixed : 0;
     Fc = (int)std::max<size_t>(1, std::min<size_t>((size_t)F, room / per));
-    Carver need(nullptr);
-    carve(need);
-    if (!work.reserve(need.off + 256)) return false;
-    Carver cv(work.p);
-    carve(cv);
+    if (!carve_into(work, [&](Carver& cv) { carve(cv); })) return false;
     hw_p.resize((size_t)Fc * kTrainBins); hw_n.resize((size_t)Fc * kTrainBins);
     hc_p.resize((size_t)Fc * kTrainBins); hc_n.resize((size_t)Fc * kTrainBins);
     var.resize(Fc); kidx.resize(F); pool.resize(F);
@@ -276,7 +276,7 @@ bool feature_row(Ctx& x, const DevSet& set, const int* d_list, int count, int f,
 
 bool begin(Cascador* c, int os, int hs, int qs, const char* fn) {
   if (!c) { fail("bad arguments"); return false; }
-  if (os < 1 || hs < 1 || qs < 1 || os > 128 || hs > 128 || qs > 128) { fail("origin/half/quarter_size must be in [1, 128]"); return false; }
+  if (!check_patch_sizes(os, hs, qs)) return false;
   if (c->similarity) {
     fail(std::string(fn) + ": refused with jdaSetSimilarityTransform(1): the reference's CalcFeatureValues indexes the per-sample "
          "transform by the feature index (data.cpp:168), there is no behaviour to reproduce");
@@ -285,26 +285,12 @@ bool begin(Cascador* c, int os, int hs, int qs, const char* fn) {
   return true;
 }
 
-int catch_all(const char* fn) noexcept {
-  try { throw; }
-  catch (const std::bad_alloc&) { fail(std::string(fn) + ": out of host memory (std::bad_alloc)"); }
-  catch (const std::exception& e) { fail(std::string(fn) + ": " + e.what()); }
-  catch (...) { fail(std::string(fn) + ": unknown C++ exception"); }
-  (void)hipDeviceSynchronize(); (void)hipGetLastError();
-  return -1;
-}
-
-// counter-based draws of jdaGenFeaturePoolCpp (include/jda.h): draw d of feature i under (seed, key)
-inline uint64_t splitmix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// counter-based draws of jdaGenFeaturePoolCpp (include/jda.h): draw d = 1, 2, ... of feature i under (seed, key)
 struct PoolRng {
   uint64_t base, d = 0;
-  PoolRng(uint64_t seed, uint64_t key, uint64_t feature) : base(splitmix64(splitmix64(seed + (key + 1) * 0x9E3779B97F4A7C15ull) + (feature + 1) * 0x9E3779B97F4A7C15ull)) {}
-  uint64_t next() { return splitmix64(base + (++d) * 0x9E3779B97F4A7C15ull); }
-  double unit() { return (double)(next() >> 11) * 0x1.0p-53; }
+  PoolRng(uint64_t seed, uint64_t key, uint64_t feature) : base(splitmix_draw(splitmix_draw(seed, key), feature)) {}
+  uint64_t next() { return splitmix_draw(base, d++); }
+  double unit() { return splitmix_unit(next()); }
   double uniform(double a, double b) { return a + (b - a) * unit(); }
   int below(int n) { return (int)(next() % (uint64_t)n); }
 };
@@ -338,7 +324,7 @@ int jdaGenFeaturePoolCpp(int F, int landmark_n, double radius, int multi_scale, 
     if (out_u) out_u[i] = rng.uniform(0.1, 0.9);                              // cart.cpp:320
   }
   return 0;
-} catch (...) { return catch_all(__func__); }
+} JDA_ABI_CATCH(-1)
 
 int jdaCalcFeatureValuesCpp(void* cascador, const jdaSamplesCpp* samples, int origin_size, int half_size, int quarter_size,
                             const jdaFeatureCpp* pool, int F, int* out) try {
@@ -349,16 +335,10 @@ int jdaCalcFeatureValuesCpp(void* cascador, const jdaSamplesCpp* samples, int or
   if (!check_set(samples, "samples", false) || !check_pool(pool, (size_t)F, c->hm.L)) return -1;
   if (F == 0 || samples->n == 0) return 0;
   if (!out) { fail("bad arguments"); return -1; }
-  if (!begin_device(c)) return -1;
-  LaneSet lanes(c);
-  if (!lanes.take(1)) return -1;
-  Ctx x;
-  x.c = c; x.st = lanes.v[0]->stream; x.L = c->hm.L;
+  Ctx x(c);
   jdaSamplesCpp none{};
   auto body = [&]() -> bool {
-    if (!upload_set(samples, x.L, origin_size, half_size, quarter_size, &x.pos, x.st)) return false;
-    if (!upload_set(&none, x.L, origin_size, half_size, quarter_size, &x.neg, x.st)) return false;
-    if (!x.reserve(F) || !x.upload_pool(pool)) return false;
+    if (!x.open(samples, &none, origin_size, half_size, quarter_size, F) || !x.upload_pool(pool)) return false;
     const int n = samples->n;
     std::vector<short> h((size_t)x.Fc * x.stride_p);
     for (int f0 = 0; f0 < F; f0 += x.Fc) {
@@ -372,7 +352,7 @@ int jdaCalcFeatureValuesCpp(void* cascador, const jdaSamplesCpp* samples, int or
     return true;
   };
   return body() ? 0 : -1;
-} catch (...) { return catch_all(__func__); }
+} JDA_ABI_CATCH_SYNC(-1)
 
 int jdaSplitNodeCpp(void* cascador, const jdaSamplesCpp* pos, const jdaSamplesCpp* neg, int origin_size, int half_size,
                     int quarter_size, const jdaFeatureCpp* pool, int F, int mode, const double* u, int* feature_idx,
@@ -382,22 +362,16 @@ int jdaSplitNodeCpp(void* cascador, const jdaSamplesCpp* pos, const jdaSamplesCp
   if (!begin(c, origin_size, half_size, quarter_size, __func__)) return -1;
   if (F < 1 || !pool || (mode != 0 && mode != 1) || !feature_idx || !threshold) { fail("bad arguments"); return -1; }
   if (!check_set(pos, "pos", true) || !check_set(neg, "neg", true) || !check_pool(pool, (size_t)F, c->hm.L)) return -1;
-  if (!begin_device(c)) return -1;
-  LaneSet lanes(c);
-  if (!lanes.take(1)) return -1;
-  Ctx x;
-  x.c = c; x.st = lanes.v[0]->stream; x.L = c->hm.L;
+  Ctx x(c);
   auto body = [&]() -> bool {
-    if (!upload_set(pos, x.L, origin_size, half_size, quarter_size, &x.pos, x.st)) return false;
-    if (!upload_set(neg, x.L, origin_size, half_size, quarter_size, &x.neg, x.st)) return false;
-    if (!x.reserve(F)) return false;
+    if (!x.open(pos, neg, origin_size, half_size, quarter_size, F)) return false;
     std::vector<int> pl(pos->n), nl(neg->n);
     std::iota(pl.begin(), pl.end(), 0); std::iota(nl.begin(), nl.end(), 0);
     double best;
     return split_node(x, pl, nl, pool, mode, u, feature_idx, threshold, &best, criterion, thresholds);
   };
   return body() ? 0 : -1;
-} catch (...) { return catch_all(__func__); }
+} JDA_ABI_CATCH_SYNC(-1)
 
 int jdaTrainCartCpp(void* cascador, const jdaSamplesCpp* pos, const jdaSamplesCpp* neg, int origin_size, int half_size,
                     int quarter_size, const jdaFeatureCpp* pools, int F, const int* modes, const double* us,
@@ -419,17 +393,11 @@ int jdaTrainCartCpp(void* cascador, const jdaSamplesCpp* pos, const jdaSamplesCp
   }
   if (any_reg && !us) { fail("regression nodes need us"); return -1; }
   if (any_reg && pos->n > 0 && !pos->residual) { fail("regression nodes need pos->residual"); return -1; }
-  if (!begin_device(c)) return -1;
-  LaneSet lanes(c);
-  if (!lanes.take(1)) return -1;
-  Ctx x;
-  x.c = c; x.st = lanes.v[0]->stream; x.L = c->hm.L;
+  Ctx x(c);
   jdaTrainNodeCpp* ns = stats ? stats->nodes : nullptr;
   double setup_ms = 0;
   auto body = [&]() -> bool {
-    if (!upload_set(pos, x.L, origin_size, half_size, quarter_size, &x.pos, x.st)) return false;
-    if (!upload_set(neg, x.L, origin_size, half_size, quarter_size, &x.neg, x.st)) return false;
-    if (!x.reserve(F)) return false;
+    if (!x.open(pos, neg, origin_size, half_size, quarter_size, F)) return false;
     setup_ms = now_ms() - t0;
     // the lists of every node, level by level; a node's children keep ascending sample order (cart.cpp:120-150)
     std::vector<std::vector<int>> pl(2 * (size_t)half), nl(2 * (size_t)half);
@@ -478,6 +446,6 @@ int jdaTrainCartCpp(void* cascador, const jdaSamplesCpp* pos, const jdaSamplesCp
     stats->partition_ms = x.partition_ms; stats->feature_evals = x.evals; stats->feature_chunks = x.chunks;
   }
   return 0;
-} catch (...) { return catch_all(__func__); }
+} JDA_ABI_CATCH_SYNC(-1)
 
 }  // extern "C"

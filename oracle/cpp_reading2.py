@@ -186,19 +186,22 @@ def count(stats, res):
         stats["cart_gothrough_n"] += n             # cascador.cpp:255,363: the reject length of a NON-face only
 
 
-def validate(m, img, x0=None, y0=None, width=None, height=None, patches=None, similarity=False, stats=None):
+def validate(m, img, x0=None, y0=None, width=None, height=None, patches=None, similarity=False, stats=None, shift=None):
     """JoinCascador::Validate -> (is_face, score, shape, n, path_hash).  Either one ORIGIN patch (img, x0, y0, width, height)
     or the three patches of a multi-scale call.  stats (new_stats): the stages whose regression ran are counted into
-    stage_done_n; the caller counts the window (count)."""
+    stage_done_n; the caller counts the window (count).  shift (dx, dy): the trainer's initial shape, mean_shape moved as
+    a whole (RandomShape, data.cpp:225-236); Calc keeps the stored mean_shape."""
     if patches is None:
         patches = ((img, x0, y0, width, height),) * 3     # (a single-scale model only ever reads patches[0])
     shape = list(m.mean_shape)
+    if shift is not None:
+        shape = [v + shift[j & 1] for j, v in enumerate(shape)]
     score = 0.0
     n = 0
     h = FNV_SEED
     base = 1 << (m.D - 1)
     stp = IDENTITY
-    for t in range(m.stage_idx):
+    for t in range(min(m.stage_idx, m.T)):
         # STParameter::Calc(shape, mean_shape) (cascador.cpp:180); the identity with the transform off (data.cpp:68-70)
         stp = st_calc(shape, m.mean_shape, m.L) if similarity else IDENTITY
         lbf = [0] * m.K

@@ -5,8 +5,7 @@ data.cpp:225-236) and the mining walk (ParallelMining, data.cpp:969-1016) on exp
 import numpy as np
 
 from oracle import cpp_reading2 as r2
-
-M64 = (1 << 64) - 1
+from train_ref import G, M64, splitmix64
 
 
 def levels(W, H, origin_size, step, factor):
@@ -42,12 +41,8 @@ def transform(img, t):
 
 
 def draw(seed, c, shift):
-    """include/jda.h's counter-based draw c of the initial-shape shift."""
-    z = (seed + (c + 1) * 0x9E3779B97F4A7C15) & M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    z ^= z >> 31
-    u = float(z >> 11) * 2.0 ** -53
+    """include/jda.h's counter-based draw c of the initial-shape shift (the generator: train_ref.splitmix64)."""
+    u = float(splitmix64((seed + (c + 1) * G) & M64) >> 11) * 2.0 ** -53
     return -shift + (shift - -shift) * u
 
 
@@ -58,45 +53,10 @@ def shift_of(seed, key, shift):
 
 
 def validate(m, patches, dx=0.0, dy=0.0, similarity=False):
-    """cpp_reading2.validate with RandomShape's global shift: the initial shape is mean_shape + (dx, dy); Calc keeps the
-    stored mean_shape.  patches: (o, h, q) numpy arrays.  -> (is_face, score, shape, n)."""
+    """cpp_reading2.validate with RandomShape's global shift: the initial shape is mean_shape + (dx, dy).  patches: (o, h, q)
+    numpy arrays.  -> (is_face, score, shape, n)."""
     pt = tuple((p, 0, 0, p.shape[1], p.shape[0]) for p in patches)
-    shape = [v + (dy if j & 1 else dx) for j, v in enumerate(m.mean_shape)]
-    score, n = 0.0, 0
-    base = 1 << (m.D - 1)
-    stp = r2.IDENTITY
-    for t in range(m.stage_idx if m.stage_idx < m.T else m.T):
-        stp = r2.st_calc(shape, m.mean_shape, m.L) if similarity else r2.IDENTITY
-        lbf = [0] * m.K
-        for k in range(m.K):
-            c = m.carts[t][k]
-            idx = r2.forward(m, c, pt, shape, stp)
-            score += c.scores[idx]
-            score = (score - c.mean) / c.std
-            n += 1
-            if score < c.th:
-                return False, score, shape, n
-            lbf[k] = k * base + idx
-        delta = [0.0] * (2 * m.L)
-        for k in range(m.K):
-            row = m.w[t][lbf[k]]
-            for j in range(2 * m.L):
-                delta[j] += row[j]
-        if similarity:
-            for i in range(m.L):
-                delta[2 * i], delta[2 * i + 1] = r2.st_apply(stp, delta[2 * i], delta[2 * i + 1])
-        for j in range(2 * m.L):
-            shape[j] = shape[j] + delta[j]
-    if m.stage_idx < m.T:
-        for k in range(m.cart_idx + 1):
-            c = m.carts[m.stage_idx][k]
-            idx = r2.forward(m, c, pt, shape, stp)
-            score += c.scores[idx]
-            score = (score - c.mean) / c.std
-            n += 1
-            if score < c.th:
-                return False, score, shape, n
-    return True, score, shape, n
+    return r2.validate(m, None, patches=pt, similarity=similarity, shift=(dx, dy))[:4]
 
 
 def chain(resize, crop, mode, os_, hs, qs):
