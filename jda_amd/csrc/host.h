@@ -115,6 +115,7 @@ inline long long env_ll(const char* name, long long dflt) {
   X(h2d_min_bytes, "JDA_H2D_MIN_BYTES", 8 << 20) /* ... for uploads of at least this many bytes */ \
   X(kernel_d2h, "JDA_KERNEL_D2H", 1)        /* counters and detections -> pinned host memory by a kernel, not the copy engine */ \
   X(filter0, "JDA_FILTER0", 1)              /* large hand-off queues: k_filter0 + k_finish(survivors) instead of two k_finish passes */ \
+  X(fin_carry, "JDA_FIN_CARRY", 1)          /* ... with the survivors' stage-0 leaves carried from k_filter0 to k_finish where they fit 32 bits a lane (0: k_finish walks all of stage 0 again) */ \
   X(predict, "JDA_PREDICT", 1)              /* size the finishing launches from the previous pass (no host round trip) */ \
   X(debug_times, "JDA_DEBUG_TIMES", 0)                                                                 \
   X(test_wpf_scale, "JDA_TEST_WPF_SCALE", 1) /* test hook of the 32-bit window-id guard */             \

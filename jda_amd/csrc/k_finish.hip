@@ -2,6 +2,8 @@
 // (c/jda.c:366-400, cart.cpp:392-404), the score recurrence replayed in cart order (c/jda.c:395-399),
 // then lanes = shape coordinates for the regression gather in cart order (c/jda.c:404-411,
 // btcart.cpp:407-424), final cut (c/jda.c:414) and emit.
+// Survivors of k_filter0 bring their stage-0 leaves along (the carry: WorkT::m_leaf / m_k0, kernels.h: carry_pack), so
+// their stage 0 is the walk of the carts the scan scored, the unpacking of the rest, and the regression.
 #include "finish_common.h"
 
 #ifndef FIN_ROW_BATCH
@@ -46,7 +48,8 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
   if (lane < kMaxStages) stage_cnt[lane] = 0;
   // the input queue: the hand-off queue of k_scan (t_begin == 0), the mid queue of an earlier k_finish launch
   // (t_begin > 0), or -- survivors -- the mid queue as k_filter0 leaves it: windows that passed every cart of stage 0,
-  // still holding the mean shape (their stage-0 leaves are walked again here, no score is applied)
+  // still holding the mean shape (no score is applied here; their stage-0 leaves from cart m_k0 on come with them in
+  // m_leaf, only the carts k_scan scored -- at most the hand-off depth -- are walked again for theirs)
   const bool from_scan = t_begin == 0 && !survivors;
   const unsigned n = (unsigned)min(w.counters[from_scan ? kCntTail : kCntMid], (unsigned long long)(from_scan ? w.cap_q : w.cap_m));
   unsigned long long carts_acc = 0;
@@ -64,6 +67,9 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
     const uint32_t gid = from_scan ? w.q_gid[i] : w.m_gid[i];
     Real score = from_scan ? w.q_score[i] : w.m_score[i];
     const int kstart = from_scan ? (int)w.q_kstart[i] : (survivors ? K : 0);
+    // the carry: k_filter0 left this survivor's stage-0 leaves of the carts [kc, K) in m_leaf (kernels.h: carry_pack); kc == K:
+    // nothing carried (no carry in this pass, or an entry k_scan_p queued itself)
+    const int kc = survivors && w.m_leaf != nullptr ? min((int)w.m_k0[i], K) : K;
     unsigned hash = kFnvSeed;
     if (TRACE) hash = from_scan ? w.q_hash[i] : w.m_hash[i];
     int win;
@@ -109,7 +115,8 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
       const Real* cstd = m.cstd + (size_t)t * K;
       const uint8_t* cnorm = m.cnorm + (size_t)t * K;
       const int kbeg = t == 0 ? min(kstart, K) : 0;   // first cart whose score is still to be applied
-      const int k_first = kbeg & ~63;
+      const bool carried = t == 0 && kc < K;          // (survivors: no score is left to apply in stage 0, only leaves to find)
+      const int k_first = carried ? kc : kbeg & ~63;
       // similarity transform of this stage (cascador.cpp:180); identity unless enabled
       Stp<Real> stp;
       stp.scale = 1; stp.r00 = 1; stp.r01 = 0; stp.r10 = 0; stp.r11 = 1;
@@ -135,7 +142,7 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
       // ---- tree walks, kG groups of 64 carts per round (the shape is fixed during a
       //      stage, so the trees of a stage are independent of each other and of the
       //      score); then the score recurrence replayed in cart order ----
-      for (int k0 = k_first; k0 < K && alive; k0 += 64 * kG) {
+      for (int k0 = carried ? K : k_first; k0 < K && alive; k0 += 64 * kG) {
         int kk[kG], lf[kG], nrm[kG];
         Real ls[kG], thk[kG], mk[kG], sk[kG];
 #pragma unroll
@@ -169,6 +176,14 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
       }
       if (t != t_begin) JDA_FSTAMP();
       if (!alive) break;
+      if (carried) {
+        // the leaves of the carts [kc, K) as k_filter0 found them: lane l's word holds carts l, 64 + l, ..
+        const int bits = carry_bits(leaf_n);
+        const uint32_t word = w.m_leaf[(size_t)i * 64 + lane];
+        for (int k = kc + lane; k < K; k += 64)
+          lbf[k] = (uint32_t)(k * leaf_n + carry_unpack(word, bits, k >> 6)) * (uint32_t)w_pitch;
+        JDA_FSTAMP();                                  // (where the walk's one round of [512, K) is stamped without the carry)
+      }
       // leaves of the carts k_scan already scored (needed only now that the stage is passed)
       for (int k0 = 0; k0 < k_first; k0 += 128) {
         int kk[2], lf[2];
@@ -276,8 +291,15 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
 // independent waves per workgroup (no LDS, no barrier), stage-0 walks from the resolved tables with the pixels read
 // from the frame, the systolic replay; few registers, so a CU holds several times as many windows.  A window that is
 // rejected is final here (counters, trace); one that passes every cart of stage 0 goes to the mid queue with its
-// score, and k_finish(survivors) takes it through the regression of stage 0 (re-walking its trees for the leaves) and
-// the later stages.  Same walks, same replay: c/jda.c:366-400.
+// score AND the leaves found here -- one 32-bit word a lane, `bits` bits per round of 64 carts (kernels.h: carry_pack;
+// WorkT::m_leaf, m_k0), where the model's leaves fit -- and k_finish(survivors) takes it through the regression of
+// stage 0 and the later stages; of stage 0's trees it walks only the carts the scan had scored (the hand-off depth,
+// 128).  Before the carry it walked all K again for the leaves: 7.3 % of a survivor's 190-us chain, 29 us of the
+// 413-us launch and a fifth of its fabric reads (profiles/r07_finish_carry_traces.txt).  Same walks, same replay:
+// c/jda.c:366-400.
+// The queue is dealt round-robin (entry i0 to wave i0, its second window a grid away).  Dealing it in runs of
+// consecutive entries -- neighbouring windows of one tile, 90 % overlapped, on one CU -- was measured with the carry:
+// FETCH_SIZE unchanged (-0.4 %), the launch 11 us slower.
 namespace {
 // One depth-4 cart of stage 0 from the level-major table with ALL seven node records fetched up front: the root, the
 // pair of its children (16 contiguous bytes) and the four grandchildren (32 contiguous bytes) of cart k sit at
@@ -316,6 +338,8 @@ __global__ __launch_bounds__(256) void k_filter0(const DevPlan* __restrict__ pla
   constexpr int NW = 2;                    // windows a wave walks side by side: their memory round trips overlap
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int K = m.K, node_n = m.node_n, leaf_n = m.leaf_n;
+  const bool carry = w.m_leaf != nullptr;  // survivors take their leaves along (the host has checked carry_fits)
+  const int cbits = carry_bits(leaf_n);
   const unsigned n = (unsigned)min(w.counters[kCntTail], (unsigned long long)w.cap_q);
   const Real* leaf_tab = m.leaf;
   const int W = plan->width;
@@ -328,7 +352,7 @@ __global__ __launch_bounds__(256) void k_filter0(const DevPlan* __restrict__ pla
   const unsigned waves = gridDim.x * 4u;
   for (unsigned i0 = blockIdx.x * 4u + (unsigned)wv; i0 < n; i0 += NW * waves) {
     unsigned idx[NW]; bool has[NW];
-    uint32_t gid[NW], xy[NW], wf[NW];
+    uint32_t gid[NW], xy[NW], wf[NW], packed[NW];
     Real score[NW];
     int kbeg[NW], rej[NW];
     unsigned hash[NW];
@@ -336,7 +360,7 @@ __global__ __launch_bounds__(256) void k_filter0(const DevPlan* __restrict__ pla
     const S0Node* tbl[NW];
 #pragma unroll
     for (int u = 0; u < NW; u++) {
-      idx[u] = i0 + (unsigned)u * waves; has[u] = idx[u] < n;
+      idx[u] = i0 + (unsigned)u * waves; has[u] = idx[u] < n; packed[u] = 0u;
       const unsigned i = has[u] ? idx[u] : i0;
       gid[u] = w.q_gid[i]; score[u] = w.q_score[i]; kbeg[u] = min((int)w.q_kstart[i], K);
       hash[u] = TRACE ? w.q_hash[i] : kFnvSeed;
@@ -378,6 +402,7 @@ __global__ __launch_bounds__(256) void k_filter0(const DevPlan* __restrict__ pla
         if (m.D == 4) l1[0] = walk_cart_s0_d4(tbl[u], (unsigned)K, (unsigned)kk[0], wbase[u], W, bc_fr);
         else walk_carts_s0<1, false>(tbl[u], K, kk, m.D, node_n, wbase[u], W, l1, bc_fr);
         lf[u] = l1[0];
+        if (carry) packed[u] = carry_pack(packed[u], lf[u], cbits, k0[u] >> 6);   // (lanes past cart K - 1 repeat it: never read)
       }
 #pragma unroll
       for (int u = 0; u < NW; u++) {
@@ -410,6 +435,12 @@ __global__ __launch_bounds__(256) void k_filter0(const DevPlan* __restrict__ pla
         if (o < w.cap_m && lane == 0) {
           w.m_gid[o] = gid[u]; w.m_score[o] = score[u]; w.m_xy[o] = xy[u]; w.m_wf[o] = wf[u];
           if (TRACE) w.m_hash[o] = hash[u];
+        }
+        if (carry && o < w.cap_m) {
+          // every round from the one that holds cart kbeg on has been walked here (a window queued at cart K walked none)
+          const bool room = o < w.cap_l && kbeg[u] < K;
+          if (room) w.m_leaf[(size_t)o * 64 + lane] = packed[u];
+          if (lane == 0) w.m_k0[o] = room ? (uint32_t)(kbeg[u] & ~63) : (uint32_t)K;
         }
       }
     }

@@ -437,6 +437,7 @@ void k_scan_p(const DevPlan* __restrict__ plan, DevModelT<float> m, const S0Node
         const uint32_t wf = (uint32_t)lv.win | ((uint32_t)frame << 16);
         if (cfg.to_mid) {                  // stage 0 passed: k_finish(survivors) takes it from the mid queue, as k_filter0 leaves it
           w.m_gid[slot] = gid; w.m_score[slot] = score; w.m_xy[slot] = xy; w.m_wf[slot] = wf;
+          w.m_k0[slot] = (uint32_t)K;      // (no stage-0 leaves come with it: k_finish walks them all)
         } else {
           w.q_gid[slot] = gid; w.q_score[slot] = score; w.q_kstart[slot] = (uint32_t)K; w.q_xy[slot] = xy; w.q_wf[slot] = wf;
         }

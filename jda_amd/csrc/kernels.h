@@ -162,6 +162,11 @@ struct WorkT {
   unsigned long long* counters;                                // see Counter
   // mid queue: windows alive after stage 0, with their regressed shape (k_finish pass 1 -> pass 2)
   uint32_t* m_gid; Real* m_score; uint32_t* m_hash; Real* m_shape; uint32_t* m_xy; uint32_t* m_wf;
+  // ... and the stage-0 leaves k_filter0 found on the way (the carry, see carry_pack): entry o's 64 words at m_leaf + 64 * o --
+  // lane l's word holds the leaves of carts l, 64 + l, 128 + l, .. -- for the carts from m_k0[o] on (a multiple of 64; K:
+  // nothing carried, the entry comes from a producer that holds no leaves, or lies beyond cap_l).  m_leaf is null in a pass
+  // whose model or path does not carry (Pass::carry_ok): k_finish(survivors) then walks every cart of stage 0 itself.
+  uint32_t* m_leaf; uint32_t* m_k0; unsigned cap_l;            // cap_l: entries of m_leaf (the first cap_l of the mid queue, kCarryCapMax at most)
   // dense mode (k_stage): per-window state indexed by gid -- m_score / m_hash / m_shape are reused as
   // score / hash / shape, st_carts holds carts evaluated (-1 = still alive)
   int* st_carts;
@@ -184,6 +189,34 @@ struct WorkT {
   const uint8_t* bc_lo; const uint8_t* bc_hi;                  // bounds-check build: the device range [lo, hi) the pass's frames occupy
 #endif
 };
+
+// The carry of stage-0 leaves from k_filter0 to k_finish(survivors): the leaf of cart k lives in word k & 63 of the window's
+// 64 words, in the `bits` bits from bit bits * (k >> 6) on -- what lane k & 63 of the wave walked in round k >> 6.
+constexpr unsigned kCarryCapMax = 1u << 16;                    // mid-queue entries that get leaf words (16 MB per lane at most)
+__host__ __device__ constexpr int carry_bits(int leaf_n) { int b = 0; while ((1 << b) < leaf_n) b++; return b; }
+__host__ __device__ constexpr int carry_rounds(int K) { return (K + 63) >> 6; }
+__host__ __device__ constexpr bool carry_fits(int leaf_n, int K) { return carry_bits(leaf_n) * carry_rounds(K) <= 32; }
+__host__ __device__ constexpr uint32_t carry_pack(uint32_t word, int leaf, int bits, int round) { return word | ((uint32_t)leaf << (bits * round)); }
+__host__ __device__ constexpr int carry_unpack(uint32_t word, int bits, int round) { return (int)((word >> (bits * round)) & ((1u << bits) - 1u)); }
+namespace carry_check {
+// every leaf value in every round of a word comes back, whatever the other rounds hold
+__host__ __device__ constexpr bool round_trip(int leaf_n, int K) {
+  const int bits = carry_bits(leaf_n), rounds = carry_rounds(K);
+  if (!carry_fits(leaf_n, K)) return false;
+  for (int seed = 0; seed < leaf_n; seed++) {
+    uint32_t word = 0;
+    for (int r = 0; r < rounds; r++) word = carry_pack(word, (seed + r * 5) % leaf_n, bits, r);
+    for (int r = 0; r < rounds; r++) if (carry_unpack(word, bits, r) != (seed + r * 5) % leaf_n) return false;
+  }
+  return true;
+}
+static_assert(carry_bits(2) == 1 && carry_bits(4) == 2 && carry_bits(8) == 3 && carry_bits(1) == 0 && carry_bits(32) == 5, "bits = ceil(log2(leaf_n))");
+static_assert(carry_rounds(64) == 1 && carry_rounds(540) == 9 && carry_rounds(682) == 11, "rounds = ceil(K / 64)");
+static_assert(round_trip(2, 64) && round_trip(4, 64) && round_trip(8, 64), "K = 64");
+static_assert(round_trip(2, 540) && round_trip(4, 540) && round_trip(8, 540), "K = 540: 27 bits with depth-4 trees");
+static_assert(round_trip(2, 682) && round_trip(4, 682) && !carry_fits(8, 682), "K = 682: 11 rounds, depth 4 needs 33 bits -- no carry");
+static_assert(!carry_fits(32, 2000) && carry_fits(2, 2048) && !carry_fits(2, 2049), "depth 6 with K = 2000 walks as before; 32 rounds of one bit fit");
+}  // namespace carry_check
 
 // Work counters live in kCntShards copies, one 256-byte line apart, so that the
 // workgroups of a launch do not serialise on one L2 atomic unit; the host sums

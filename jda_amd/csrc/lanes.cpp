@@ -191,7 +191,7 @@ Lane* acquire_lane_locked(Cascador* c, size_t want_cap, bool* exhausted, Lane::B
 // its queues cannot be bounded: traces, dense mode, plans without a prediction under ws_bound = 0).
 template <typename Real>
 size_t bytes_per_window(int dim, bool trace) {
-  size_t b = (4 + sizeof(Real) + 4 + 8) + 2 * (4 + sizeof(Real) + (size_t)dim * sizeof(Real)) + 8 + 4;
+  size_t b = (4 + sizeof(Real) + 4 + 8) + 2 * (4 + sizeof(Real) + (size_t)dim * sizeof(Real)) + 8 + 4 + 4;
   if (trace) b += 4 + 4 + sizeof(Real) + 4 + (size_t)dim * sizeof(Real);
   return b;
 }
@@ -214,6 +214,9 @@ size_t carve_workspace(void* base, WorkT<Real>& w, size_t cap, size_t cap_q, siz
   w.m_shape = cv.take<Real>(cap_m * dim);
   w.m_xy = cv.take<uint32_t>(cap_m);
   w.m_wf = cv.take<uint32_t>(cap_m);
+  w.m_k0 = cv.take<uint32_t>(cap_m);
+  w.cap_l = (unsigned)std::min<size_t>(cap_m, kCarryCapMax);   // (the stage-0 leaves k_filter0 carries to k_finish: 256 bytes an entry)
+  w.m_leaf = cv.take<uint32_t>((size_t)w.cap_l * 64);
   w.st_carts = dense ? cv.take<int>(cap) : nullptr;          // (dense mode only: k_stage)
   w.out_gid = cv.take<uint32_t>(cap_m);
   w.out_score = cv.take<Real>(cap_m);

@@ -149,6 +149,8 @@ struct Pass {
   const Knobs& kn() const { return c->kn; }
   // k_filter0 + k_finish(survivors) can take this pass's hand-off queue (every level has a resolved stage-0 table)
   bool filter0_ok() const { return kn().filter0 && s0_tbl() != nullptr && pe->fast_scan && !pe->any_untiled && !multi; }
+  // ... and its survivors take their stage-0 leaves along to k_finish (WorkT::m_leaf; kernels.h: carry_pack)
+  bool carry_ok() const { return kn().fin_carry && filter0_ok() && carry_fits(hm().leaf_n(), hm().K); }
   long long windows() const { return rag ? rag->windows : (long long)nf * pe->sp.windows; }
 
   bool dense_ok(int* pix_cap, int* lds_max) const {
@@ -537,13 +539,15 @@ struct Pass {
     const int gm = kn().fin_gm > 0 ? (int)kn().fin_gm : stage_groups();
     const int g2 = kn().fin_g2 > 0 ? (int)kn().fin_g2 : stage_groups();
     n_grid = std::max<long long>(n_grid, 1);
+    WorkT<Real> wc = w;                    // the workspace as k_filter0 and k_finish(survivors) see it: no leaf words where the carry does not apply
+    if (!carry_ok()) wc.m_leaf = nullptr;
     if (mid_direct) {
       // the mid queue already holds stage-0 survivors (k_scan_p): the rest of the hand-off queue is filtered into it,
       // then everybody goes through k_finish(survivors)
       const long long nmid = pred_mid >= 0 ? (long long)(pred_mid * (double)windows() * 1.25) + 64 : 0;
       const long long wg2 = std::min<long long>((long long)cap_m, std::max<long long>(std::max<long long>(2048, n_grid / std::max<long long>(1, kn().fin_grid_div)), nmid));
-      JDA_HIP(launch_filter0<Real>(want_trace(), pe->dp, model(), w, n_grid, s0_tbl(), st));
-      JDA_HIP(launch_finish<Real>(want_trace(), 0, T, apply_th, th, pe->dp, model(), w, g2, wg2, s0_tbl(), (int)kn().fin_tile, st, true));
+      JDA_HIP(launch_filter0<Real>(want_trace(), pe->dp, model(), wc, n_grid, s0_tbl(), st));
+      JDA_HIP(launch_finish<Real>(want_trace(), 0, T, apply_th, th, pe->dp, model(), wc, g2, wg2, s0_tbl(), (int)kn().fin_tile, st, true));
       finished = true;
       return true;
     }
@@ -570,8 +574,8 @@ struct Pass {
     if (filter0_ok()) {
       // the dying majority is filtered by a lean kernel (four windows per workgroup, stage 0 only); the survivors --
       // a few per cent -- go through k_finish for the regression of stage 0 and every later stage
-      JDA_HIP(launch_filter0<Real>(want_trace(), pe->dp, model(), w, n_grid, s0_tbl(), st));
-      JDA_HIP(launch_finish<Real>(want_trace(), 0, T, apply_th, th, pe->dp, model(), w, g2, wg2, s0_tbl(), (int)kn().fin_tile, st, true));
+      JDA_HIP(launch_filter0<Real>(want_trace(), pe->dp, model(), wc, n_grid, s0_tbl(), st));
+      JDA_HIP(launch_finish<Real>(want_trace(), 0, T, apply_th, th, pe->dp, model(), wc, g2, wg2, s0_tbl(), (int)kn().fin_tile, st, true));
       finished = true;
       return true;
     }

@@ -20,7 +20,8 @@ sel = tag == 0x7777
 print("k_finish pass-2 workgroups with stamps:", int(sel.sum()))
 t0 = buf[sel, 1].astype(np.int64).min()
 win = buf[:, 16].astype(int)
-tot = (buf[np.arange(65536), np.maximum(n, 1)] - buf[:, 1]).astype(np.int64)
+n = np.where(sel, np.clip(n, 1, 15), 1)          # (rows no k_finish workgroup wrote hold whatever the scan's stamps left there)
+tot = (buf[np.arange(65536), n] - buf[:, 1]).astype(np.int64)
 xcd = np.arange(65536) % 8
 for wv in sorted(set(win[sel].tolist())):
     s3 = sel & (win == wv)
@@ -55,3 +56,9 @@ for k in sorted(set(n[sel].tolist())):
     print("stamps %2d: %5d workgroups; median ticks per segment %s; total median %d; start offset median %d max %d; end max %d" % (
         k, int(s2.sum()), np.median(dt, axis=0).astype(int).tolist(), int(np.median(stp[:, -1] - stp[:, 0])),
         int(np.median(stp[:, 0] - t0)), int((stp[:, 0] - t0).max()), int((stp[:, -1] - t0).max())))
+    if k >= 5:
+        # segments 2 and 3 of a k_finish(survivors) window: the walk round of stage 0's last carts (or the unpacking of the
+        # carried leaves) and the walks of the carts the scan had scored -- what stage 0 costs before its regression
+        s0 = dt[:, 1] + dt[:, 2]
+        print("           stage-0 leaves (segments 2 + 3): median %d ticks = %.1f %% of the window's chain (sum over windows: %.1f %%)" % (
+            int(np.median(s0)), 100.0 * np.median(s0 / np.maximum(1, stp[:, -1] - stp[:, 0])), 100.0 * s0.sum() / max(1, (stp[:, -1] - stp[:, 0]).sum())))
