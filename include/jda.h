@@ -560,7 +560,8 @@ JDA_API long long jdaMineWindowList(int w, int h, int origin_size, int step, dou
  * 0.5 * (log(pos_w) - log(neg_w)) (cart.cpp:63-89).  PARITY UNPINNED like every dialect-CPP entry: src/jda needs OpenCV and
  * cannot be built here; these entries are bit-exact against a sequential restatement written from the reference's source
  * (tests/train_ref.py), not against the reference.  Out of scope: BoostCart::Train's loop (weights, thresholds by recall,
- * restarts), the global regression, writing the cart into a model file, data loading.
+ * restarts), liblinear's fit of the global regression (what goes into it and what comes out of it: the block "closing a
+ * stage" below), writing the cart into a model file, data loading.
  *
  * Samples.  One struct describes a set of n samples.  origin_size / half_size / quarter_size are call arguments, each in
  * [1, 128]; the landmark count L and tree_depth come from the cascador (it also supplies the device, the "workspace_mb"
@@ -670,6 +671,84 @@ JDA_API int jdaTrainCartCpp(void *cascador, const jdaSamplesCpp *pos, const jdaS
                             int half_size, int quarter_size, const jdaFeatureCpp *pools, int F, const int *modes,
                             const double *us, jdaFeatureCpp *out_features, int *out_thresholds, double *out_scores,
                             int *pos_leaf, int *neg_leaf, jdaTrainStatsCpp *stats);
+
+/* ---- Dialect CPP: closing a stage ---------------------------------------------------------------------------------------
+ * What BoostCart::Train does after the K-th cart of a stage (reference src/jda/btcart.cpp:255-292): GenLBF (btcart.cpp:390-405)
+ * walks all K carts of the stage over every sample that is still alive, positives and negatives; the leaf indicators go to
+ * liblinear as X (GlobalRegression, btcart.cpp:328-388); GenDeltaShape (btcart.cpp:407-424) sums K rows of the fitted w per
+ * sample and the sum is added to the sample's current shape (btcart.cpp:285-292); calcMeanError (common.cpp:41-77) is the
+ * "Regression Mean Error" the stage reports.  These entries are the walk, the update and the error on a resident sample
+ * set, with the stage's carts and weights as caller arrays -- the form jdaTrainCartCpp hands carts out in.  Nothing is
+ * written into a model.  PARITY UNPINNED like every dialect-CPP entry: src/jda needs OpenCV and cannot be built here; these
+ * entries are bit-exact against a sequential restatement written from the reference's source (tests/stage_ref.py), not
+ * against the reference.  Out of scope: the fit itself (liblinear's L2R_L2LOSS_SVR_DUAL draws from rand(); INTEGRATION.md
+ * says what it consumes and returns), BoostCart::Train's loop, writing into a model file.
+ *
+ * Sizes.  nodes_n = 2^tree_depth and the landmark count L come from the cascador, as in the training block (it also
+ * supplies the device, the LDS budget "lbf_lds_kb" and the "workspace_mb" limit of the per-call workspace: the samples are
+ * processed in chunks that fit it; device-resident patches are read in place); leafNum = nodes_n/2; origin_size /
+ * half_size / quarter_size are call arguments, each in [1, 128].
+ *
+ * Patches.  GenLBF resizes the sample's image to the half and the quarter size itself (btcart.cpp:397-398): for a set built
+ * by the resize_mode-0 chain (data.cpp:987-990, o -> h, o -> q) those are the h / q bytes the set already stores, the layout
+ * of jdaSamplesCpp.patches.  The entries READ THE STORED PATCHES and resize nothing.
+ *
+ * Similarity transform.  With jdaSetSimilarityTransform(1) all three device entries refuse (-1): the training entries
+ * refuse too, so a sample set for them cannot exist with it on.  The split node is evaluated with the identity STParameter
+ * and GenDeltaShape's Apply is the identity.
+ *
+ * Refused with -1 and jdaGetLastError(), never a crash: NULL where data is needed, K <= 0, a scale outside 0..2, a landmark
+ * id outside [0, L), a patch size outside [1, 128], an lbf_in entry outside its cart's leaves.  n == 0 returns 0 without
+ * touching the device. */
+
+typedef struct {
+  const jdaFeatureCpp *features;   /* K * (nodes_n/2 - 1): node i = 1 .. nodes_n/2 - 1 of cart k at [k*(nodes_n/2-1) + i-1]
+                                      -- K times jdaTrainCartCpp's out_features                                        */
+  const int *thresholds;           /* same layout, K times out_thresholds                                              */
+  int K;
+} jdaStageCartsCpp;
+
+typedef struct {
+  double call_ms;            /* wall clock of the call                                                              */
+  double upload_ms;          /* ... carts, weights and the chunks' shapes (and host patches) to the device          */
+  double device_ms;          /* ... the k_lbf launches, HIP events, summed over the chunks                           */
+  double download_ms;        /* ... shapes and leaf indicators back to the host                                      */
+  int chunks;                /* chunks the samples were cut into ("workspace_mb")                                   */
+  int lds_path;              /* 1: a sample's patches, shape and indicators staged in LDS; 0: read from global memory */
+  int waves_per_group;       /* samples (waves) per workgroup                                                       */
+  int lds_bytes;             /* LDS of a workgroup                                                                  */
+} jdaStageStatsCpp;
+
+/* BoostCart::GenLBF over the set: lbf[i*K + k] = k*leafNum + Cart::Forward(cart k, sample i) (cart.cpp:392-404: from node 1,
+ * value <= threshold goes to 2*node, else 2*node + 1, depth - 1 times; the result is node - leafNum).  lbf is the ZERO-based
+ * liblinear index: X[i][k].index = lbf[i*K + k] + 1 (btcart.cpp:341).  samples->weights and residual are not read and may
+ * be NULL.  A cascador of tree_depth 1 has no split node: every entry is k, features / thresholds may be NULL. */
+JDA_API int jdaGenLbfCpp(void *cascador, const jdaSamplesCpp *samples, int origin_size, int half_size, int quarter_size,
+                         const jdaStageCartsCpp *carts, int *lbf);
+
+/* The shape update of btcart.cpp:285-292.  w is K*leafNum rows of 2L doubles on the host, row-major: BoostCart::w, as the
+ * model file stores a stage's weights.  Per sample, delta[j] starts at 0. and adds w[lbf[k]][j] for k = 0 .. K-1 IN CART
+ * ORDER (btcart.cpp:414-420; the order decides bits); then out_shapes[i*2L + j] = shapes[i*2L + j] + delta[j].
+ * lbf_in == NULL: the entry walks the carts itself, walk and sums in ONE device pass.  Otherwise it uses the given
+ * indices, each checked against 0 <= lbf_in[i*K + k] - k*leafNum < leafNum, and `carts` may be NULL (K is then the cascador's K) or
+ * carry NULL arrays (only its K is read).  out_lbf (n*K ints) may be
+ * NULL; so may stats.  out_shapes (n * 2L doubles) must not be NULL and MAY ALIAS NOTHING: not samples->shapes, not w. */
+JDA_API int jdaStageUpdateShapesCpp(void *cascador, const jdaSamplesCpp *samples, int origin_size, int half_size,
+                                    int quarter_size, const jdaStageCartsCpp *carts, const double *w, const int *lbf_in,
+                                    double *out_shapes, int *out_lbf, jdaStageStatsCpp *stats);
+
+/* Host only (no GPU, no cascador): calcMeanError (common.cpp:41-77) over n samples of L landmarks, IN ITS OWN ORDER:
+ *   per sample i, in order:  left_x, left_y = the gt coordinates of the n_left left-pupil landmarks summed from 0. in list
+ *     order, each then divided by (double)n_left; right_x, right_y the same over the right pupils;
+ *     pupil_dis = sqrt(dx*dx + dy*dy) with dx = left_x - right_x, dy = left_y - right_y;
+ *     e_ = 0., + sqrt(ex*ex + ey*ey) for landmark j = 0 .. L-1 in order, (ex, ey) = gt - current of landmark j;
+ *     e += e_ / pupil_dis  (e from 0.);
+ *   *out = e / (double)(L * n).
+ * The reference writes the squares as std::pow(v, 2): DEFINED here as v * v, what the C library returns for an exponent
+ * of exactly 2 and what compilers fold it into -- a detail only the reference's build decides, unchecked like cv::mean.
+ * n == 0 gives 0. / 0. = NaN, like the reference.  -1: NULL arguments, n < 0, L < 1, an empty pupil list, an id outside [0, L). */
+JDA_API int jdaMeanErrorCpp(const double *gt_shapes, const double *cur_shapes, int n, int L, const int *left_pupils,
+                            int n_left, const int *right_pupils, int n_right, double *out);
 
 #ifdef __cplusplus
 }

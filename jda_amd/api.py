@@ -86,6 +86,18 @@ class jdaTrainStatsCpp(C.Structure):
                 ("nodes", C.POINTER(jdaTrainNodeCpp))]
 
 
+class jdaStageCartsCpp(C.Structure):
+    _fields_ = [("features", C.POINTER(jdaFeatureCpp)), ("thresholds", C.POINTER(C.c_int)), ("K", C.c_int)]
+
+
+class jdaStageStatsCpp(C.Structure):
+    _fields_ = [("call_ms", C.c_double), ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double),
+                ("chunks", C.c_int), ("lds_path", C.c_int), ("waves_per_group", C.c_int), ("lds_bytes", C.c_int)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # numpy view of jdaFeatureCpp arrays (same layout: three ints, four bytes of padding, four doubles)
 FEATURE_DTYPE = np.dtype([("scale", np.int32), ("landmark_id1", np.int32), ("landmark_id2", np.int32), ("pad", np.int32),
                           ("offset1_x", np.float64), ("offset1_y", np.float64), ("offset2_x", np.float64),
@@ -235,6 +247,12 @@ def _load():
         lib.jdaSplitNodeCpp.argtypes = [C.c_void_p, sp, sp, C.c_int, C.c_int, C.c_int, fp, C.c_int, C.c_int, dp, ip, ip, dp, ip]
         lib.jdaTrainCartCpp.argtypes = [C.c_void_p, sp, sp, C.c_int, C.c_int, C.c_int, fp, C.c_int, ip, dp, fp, ip, dp, ip, ip,
                                         C.POINTER(jdaTrainStatsCpp)]
+    if hasattr(lib, "jdaStageUpdateShapesCpp"):
+        sp, dp, ip, cp = C.POINTER(jdaSamplesCpp), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(jdaStageCartsCpp)
+        lib.jdaGenLbfCpp.argtypes = [C.c_void_p, sp, C.c_int, C.c_int, C.c_int, cp, ip]
+        lib.jdaStageUpdateShapesCpp.argtypes = [C.c_void_p, sp, C.c_int, C.c_int, C.c_int, cp, dp, ip, dp, ip,
+                                                C.POINTER(jdaStageStatsCpp)]
+        lib.jdaMeanErrorCpp.argtypes = [dp, dp, C.c_int, C.c_int, ip, C.c_int, ip, C.c_int, dp]
     return lib
 
 
@@ -290,6 +308,42 @@ def gen_feature_pool_cpp(F, landmark_n, radius, multi_scale=False, seed=0, key=0
                                 u.ctypes.data_as(C.POINTER(C.c_double))) != 0:
         raise JdaError(last_error())
     return feats[:F], u[:F]
+
+
+def mean_error_cpp(gt_shapes, cur_shapes, left_pupils, right_pupils):
+    """calcMeanError (reference common.cpp:41-77), the "Regression Mean Error" a stage reports, in the reference's own
+    summation order (jdaMeanErrorCpp, host only).  gt_shapes / cur_shapes: [n, 2L]; the pupil lists are landmark ids."""
+    gt = np.ascontiguousarray(gt_shapes, np.float64)
+    cur = np.ascontiguousarray(cur_shapes, np.float64)
+    assert gt.ndim == 2 and gt.shape == cur.shape and gt.shape[1] % 2 == 0
+    kl, lp = _ivec(left_pupils)
+    kr, rp = _ivec(right_pupils)
+    out = C.c_double()
+    dp = C.POINTER(C.c_double)
+    if lib.jdaMeanErrorCpp(gt.ctypes.data_as(dp), cur.ctypes.data_as(dp), gt.shape[0], gt.shape[1] // 2, lp, int(np.asarray(left_pupils).size), rp,
+                           int(np.asarray(right_pupils).size),
+                           C.byref(out)) != 0:
+        raise JdaError(last_error())
+    return out.value
+
+
+def _stage_carts(features, thresholds, inner, K=None):
+    """A stage's carts -- features [K, nodes_n/2 - 1] of FEATURE_DTYPE and thresholds, the outputs of K train_cart_cpp
+    calls stacked -- as a jdaStageCartsCpp (and what keeps its arrays alive)."""
+    c = jdaStageCartsCpp()
+    if features is None:
+        c.K = int(K)
+        return c, []
+    fa, fp = _features(features)
+    th = np.ascontiguousarray(thresholds, np.int32).reshape(-1)
+    assert len(fa) == th.size, "one threshold per split node"
+    if inner > 0:
+        assert len(fa) % inner == 0, "carts must hold K * (nodes_n/2 - 1) split nodes"
+        c.K = len(fa) // inner
+        c.features, c.thresholds = fp, th.ctypes.data_as(C.POINTER(C.c_int))
+    else:
+        c.K = int(K)
+    return c, [fa, th]
 
 
 def _patch_bytes(origin_size, half_size, quarter_size):
@@ -1026,6 +1080,54 @@ class Cascador:
         stats = {k: getattr(st, k) for k, _ in st._fields_ if k != "nodes"}
         return dict(features=feats, thresholds=ths, scores=scores, pos_leaf=pleaf[:sp.n], neg_leaf=nleaf[:sn.n], nodes=nodes,
                     stats=stats)
+
+    # -- closing a stage (include/jda.h, "Dialect CPP: closing a stage") ------------------------------------------
+    def gen_lbf_cpp(self, samples, features, thresholds, origin_size=48, half_size=36, quarter_size=24, K=None):
+        """BoostCart::GenLBF (reference btcart.cpp:390-405) over a sample set: [n, K] int32, lbf[i, k] = k * leafNum + the
+        leaf of cart k on sample i (the zero-based liblinear index).  samples: the dict calc_feature_values_cpp takes
+        (patches numpy or a torch CUDA tensor; weights are not needed); features [K * (nodes_n/2 - 1)] of FEATURE_DTYPE and
+        thresholds: K times train_cart_cpp's.  K: only for a cascador of tree_depth 1, whose carts have no split node."""
+        pb = _patch_bytes(origin_size, half_size, quarter_size)
+        s, keep = _samples(samples, self.dim, pb)
+        carts, kc = _stage_carts(features, thresholds, (1 << (self.D - 1)) - 1, K)
+        out = np.zeros((s.n, max(carts.K, 0)), np.int32)
+        rc = lib.jdaGenLbfCpp(self.h, C.byref(s), origin_size, half_size, quarter_size, C.byref(carts),
+                              out.ctypes.data_as(C.POINTER(C.c_int)))
+        del keep, kc
+        if rc != 0:
+            raise JdaError(last_error())
+        return out
+
+    def stage_update_shapes_cpp(self, samples, features, thresholds, w, lbf=None, origin_size=48, half_size=36,
+                                quarter_size=24, want_lbf=False, stats=False, K=None):
+        """The shape update that closes a stage (reference btcart.cpp:285-292, 407-424): shapes + the K rows of w
+        [K * leafNum, 2L] the sample's leaf indicators select, added in cart order -> [n, 2L] float64.  lbf=None: the carts
+        (features / thresholds as in gen_lbf_cpp) are walked in the same device pass; otherwise lbf [n, K] is used and
+        features / thresholds may be None.  want_lbf: also return the indicators; stats: also the call's jdaStageStatsCpp.
+        -> shapes, or a tuple (shapes[, lbf][, stats])."""
+        pb = _patch_bytes(origin_size, half_size, quarter_size)
+        s, keep = _samples(samples, self.dim, pb)
+        leaf_n = 1 << (self.D - 1)
+        wa = np.ascontiguousarray(w, np.float64)
+        if lbf is not None:
+            la = np.ascontiguousarray(lbf, np.int32).reshape(s.n, -1) if s.n else np.zeros((0, wa.size // (leaf_n * self.dim)), np.int32)
+            if features is None and K is None:
+                K = la.shape[1]
+        carts, kc = _stage_carts(features, thresholds, leaf_n - 1, K)
+        assert wa.size == max(carts.K, 0) * leaf_n * self.dim, "w must hold K * leafNum rows of 2L doubles"
+        assert lbf is None or la.shape[1] == carts.K
+        out = np.zeros((s.n, self.dim), np.float64)
+        olbf = np.zeros((s.n, max(carts.K, 0)), np.int32) if want_lbf else None
+        st = jdaStageStatsCpp()
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        rc = lib.jdaStageUpdateShapesCpp(self.h, C.byref(s), origin_size, half_size, quarter_size, C.byref(carts),
+                                         wa.ctypes.data_as(dp), None if lbf is None else la.ctypes.data_as(ip),
+                                         out.ctypes.data_as(dp), None if olbf is None else olbf.ctypes.data_as(ip), C.byref(st))
+        del keep, kc
+        if rc != 0:
+            raise JdaError(last_error())
+        res = (out,) + ((olbf,) if want_lbf else ()) + ((st.asdict(),) if stats else ())
+        return res[0] if len(res) == 1 else res
 
     def trace_cpp(self, frames, minimum_size=20, step=5, factor=1.2):
         frames = np.ascontiguousarray(frames, np.uint8)

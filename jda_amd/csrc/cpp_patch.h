@@ -1,5 +1,5 @@
-// Patch numerics of dialect CPP, once, for k_misc.hip (pyramid and ROI resizes), k_mine.hip (Validate on crops, mining)
-// and k_train.hip (feature pool values): one pixel of cv::resize(INTER_LINEAR), the split-node feature on o / h / q patches.
+// Patch numerics of dialect CPP, once, for k_misc.hip (pyramid and ROI resizes), k_mine.hip (Validate on crops, mining),
+// k_train.hip (feature pool values) and k_lbf.hip (a stage's carts over the sample set): one pixel of cv::resize(INTER_LINEAR), the split-node feature on o / h / q patches.
 #pragma once
 #include "kernels_common.h"
 

@@ -31,6 +31,10 @@ inline bool check_patch_sizes(int os, int hs, int qs) {
   return true;
 }
 
+// train.cpp: a caller's sample set / pool features as the trainer-side entries accept them (fail() says what is wrong)
+bool check_set(const jdaSamplesCpp* s, const char* name, bool need_weights);
+bool check_pool(const jdaFeatureCpp* pool, size_t count, int L);
+
 // detect_cpp.cpp: dialect CPP, method 1 (cascador.cpp:310-376,431-477) on a uniform batch; frames on the device
 // (d_frames) or, with host_frames set, in host memory
 struct CppCall { int minimum_size, step; double factor, overlap; int nms; };

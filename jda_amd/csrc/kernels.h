@@ -452,6 +452,25 @@ hipError_t launch_train_hist(const short* values, size_t stride, int F, const in
 hipError_t launch_train_var(const short* values, size_t stride, int F, const int* list, int count, const double* residual,
                             const uint8_t* has_gt, const int* counts, const int* kidx, TrainVar* out, hipStream_t stream);
 
+// ---- dialect CPP: closing a stage (k_lbf.hip, stage.cpp; reference src/jda/btcart.cpp:255-292, 390-424) ----
+
+// One split node of a stage's carts as k_lbf reads it: jdaFeatureCpp's fields with the landmark ids doubled, and the threshold.
+struct LbfNode { int scale, lm1x2, lm2x2, th; double o1x, o1y, o2x, o2y; };
+// The table is level-major: node i (1-based, children 2i and 2i + 1) of cart k, on level d = floor(log2 i), sits at
+inline size_t lbf_node_at(int K, int k, int i, int d) { return (size_t)K * (((size_t)1 << d) - 1) + ((size_t)k << d) + ((size_t)i - ((size_t)1 << d)); }
+constexpr int kLbfWaves = 4;             // samples (waves) of a workgroup at most
+// One chunk of a resident sample set (device pointers).  walk = 1: the carts are walked and lbf [n][K] is written;
+// walk = 0: lbf is read.  w != nullptr: out_shapes [n][dim] = shapes + the K rows of w [K * 2^(D-1)][dim] in cart order.
+struct LbfArgs {
+  const uint8_t* patches; const double* shapes; const LbfNode* nodes; const double* w;
+  int* lbf; double* out_shapes;
+  int n, K, D, dim, os, hs, qs, walk;
+};
+struct LbfLaunch { int lds, waves, lds_bytes; };   // how it ran: staged in LDS (1) or from global memory (0), waves and LDS bytes per workgroup
+// lds_budget: the LDS bytes a workgroup may take (at most the CU's 160 KB); where one sample's slice does not fit, the
+// kernel reads everything from global memory.
+hipError_t launch_lbf(const LbfArgs& a, int lds_budget, LbfLaunch* how, hipStream_t stream);
+
 // Hardware-queue probe (k_misc.hip): a one-wave spin of `ticks` wall-clock ticks (100 MHz) that leaves its end time in
 // *out (mapped pinned host memory), and a kernel that leaves the time it ran.
 hipError_t launch_hwq_spin(long long ticks, unsigned long long* out, hipStream_t stream);

@@ -13,6 +13,27 @@
 
 namespace jda {
 
+// (declared in detect.h: stage.cpp checks its sample sets and carts the same way)
+bool check_set(const jdaSamplesCpp* s, const char* name, bool need_weights) {
+  if (!s) { fail(std::string(name) + ": null sample set"); return false; }
+  if (s->n < 0) { fail(std::string(name) + ": negative n"); return false; }
+  if (s->n > 0 && (!s->patches || !s->shapes || (need_weights && !s->weights))) {
+    fail(std::string(name) + ": patches, shapes and weights must be given for a non-empty set"); return false;
+  }
+  return true;
+}
+
+bool check_pool(const jdaFeatureCpp* pool, size_t count, int L) {
+  for (size_t i = 0; i < count; i++) {
+    const jdaFeatureCpp& f = pool[i];
+    if (f.scale < 0 || f.scale > 2) { fail("feature " + std::to_string(i) + ": scale must be 0, 1 or 2"); return false; }
+    if (f.landmark_id1 < 0 || f.landmark_id1 >= L || f.landmark_id2 < 0 || f.landmark_id2 >= L) {
+      fail("feature " + std::to_string(i) + ": landmark id outside [0, " + std::to_string(L) + ")"); return false;
+    }
+  }
+  return true;
+}
+
 namespace {
 
 static_assert(sizeof(TrainFeat) == sizeof(jdaFeatureCpp), "TrainFeat is jdaFeatureCpp's layout");
@@ -28,15 +49,6 @@ struct DevSet {
   const jdaSamplesCpp* host = nullptr;
   CallBuf buf;
 };
-
-bool check_set(const jdaSamplesCpp* s, const char* name, bool need_weights) {
-  if (!s) { fail(std::string(name) + ": null sample set"); return false; }
-  if (s->n < 0) { fail(std::string(name) + ": negative n"); return false; }
-  if (s->n > 0 && (!s->patches || !s->shapes || (need_weights && !s->weights))) {
-    fail(std::string(name) + ": patches, shapes and weights must be given for a non-empty set"); return false;
-  }
-  return true;
-}
 
 bool upload_set(const jdaSamplesCpp* s, int L, int os, int hs, int qs, DevSet* d, hipStream_t st) {
   d->host = s;
@@ -60,17 +72,6 @@ bool upload_set(const jdaSamplesCpp* s, int L, int os, int hs, int qs, DevSet* d
   JDA_HIP(hipStreamSynchronize(st));      // (the host arrays are the caller's: done with them before anything else)
   d->ts.patches = pa ? pa : s->patches;
   d->ts.shapes_t = tr; d->weights = w; d->residual = res; d->has_gt = gt;
-  return true;
-}
-
-bool check_pool(const jdaFeatureCpp* pool, size_t count, int L) {
-  for (size_t i = 0; i < count; i++) {
-    const jdaFeatureCpp& f = pool[i];
-    if (f.scale < 0 || f.scale > 2) { fail("feature " + std::to_string(i) + ": scale must be 0, 1 or 2"); return false; }
-    if (f.landmark_id1 < 0 || f.landmark_id1 >= L || f.landmark_id2 < 0 || f.landmark_id2 >= L) {
-      fail("feature " + std::to_string(i) + ": landmark id outside [0, " + std::to_string(L) + ")"); return false;
-    }
-  }
   return true;
 }
 
