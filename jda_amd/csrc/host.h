@@ -1,8 +1,9 @@
 // Host side of libjda.so, shared by its translation units: error channel, options, device buffers, the cascador with
 // its scan plans and lanes, and the types a pass over a batch works with.
 //   lanes.cpp      device / lane / workspace management            plans.cpp    tile chooser, scan plans
-//   model_dev.cpp  the model's device copies                       pass.h       one sub-batch through the device pipeline
-//   run.h          a call's sub-batches over its lanes              detect.cpp   dialect-C batch entry
+//   model_dev.cpp  the model's device copies                       pass.h       one sub-batch through the device pipeline (declarations)
+//   run.h          a call's sub-batches over its lanes (decl.)      pass.cpp     the bodies of pass.h and run.h, both dialects
+//   detect.cpp     dialect-C batch entry
 //   post_host.cpp  sort, NMS, relocation, jdaResult, statistics     tickets.cpp  submit / wait
 //   ragged.cpp     images of different sizes as one job             abi.cpp      the extern "C" entry points of include/jda.h
 #pragma once

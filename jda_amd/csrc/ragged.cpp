@@ -700,13 +700,8 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
   auto collect = [&](Slot& sl) -> bool {
     Pass<Real>& p = sl.pass;
     sl.busy = false;
-    if (!p.after_tail() || !p.issue_counters() || !p.after_counters() || !p.collect()) return false;
-    float ms_scan = 0, ms_all = 0;
-    if (p.timed) {
-      (void)hipEventElapsedTime(&ms_scan, p.ev[1], p.ev[2]);
-      (void)hipEventElapsedTime(&ms_all, p.ev[0], p.ev[3]);
-    }
-    sl.rs.scan_ms += ms_scan; sl.rs.gpu_ms += ms_all;
+    if (!p.complete()) return false;
+    p.tally_times(sl.rs);
     post_ms += post(sl.ch, sl.dets);
     total += sl.rs;
     patch_n += sl.ch.windows;
@@ -748,18 +743,16 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
       const QueueCaps qc = plan_queue_caps(c, job.pe, want, false, &want_dense);
       if (!ensure_workspace<Real>(ln, want, false, c->hm.dim(), qc.q, qc.m, false)) { ok = false; break; }      // (a ragged pass never runs dense)
     }
-    Pass<Real>& p = sl.pass;
-    p = Pass<Real>();
-    p.c = c; p.pe = job.pe; p.trace = nullptr; p.dets = &sl.dets; p.rs = &sl.rs; p.apply_th = side.apply_th(); p.th = side.final_th(); p.multi = false;
-    p.solo = lanes == 1;
-    p.bind(ln, lane, nullptr);
-    p.f0 = 0; p.nf = sl.ch.n; p.rag = &sl.ch;
+    PassSetup<Real> s;
+    s.c = c; s.pe = job.pe; s.dets = &sl.dets; s.rs = &sl.rs; s.apply_th = side.apply_th(); s.th = side.final_th();
+    s.ln = ln; s.lane = lane; s.solo = lanes == 1;
+    s.nf = sl.ch.n; s.rag = &sl.ch;
     if (side.device_post(c, sl.ch.n)) {
-      p.want_post = true; p.post_nms = side.nms(); p.post_overlap = (float)side.overlap();
+      s.want_post = true; s.post_nms = side.nms(); s.post_overlap = (float)side.overlap();
       sl.dets.p_n.assign((size_t)sl.ch.n, -1); sl.dets.p_first.assign((size_t)sl.ch.n, 0);
     }
-    p.w.half = nullptr; p.w.quarter = nullptr; p.w.half_stride = p.w.quarter_stride = 0;
-    p.w.hw = p.w.hh = p.w.qw = p.w.qh = 0;
+    Pass<Real>& p = sl.pass;
+    p.open(s);
     if (job.d_job_raw) {
       const double t_w = now_ms();
       std::unique_lock<std::mutex> lk(up.mu);
@@ -768,7 +761,7 @@ static int detect_ragged_t(Cascador* c, const unsigned char* const* host_imgs, c
       if (up.failed) { fail(up.err); ok = false; break; }
       sl.ch.d_uploaded = job.d_job_raw + job.raw_off[ci];
     }
-    if (!p.issue_scan(nullptr, 0, nullptr, 0, nullptr)) { ok = false; break; }
+    if (!p.issue_scan()) { ok = false; break; }
     sl.busy = true;
   }
   tm[3] = now_ms() - t_call;

@@ -56,26 +56,19 @@ int submit_c_device(Cascador* c, const uint8_t* d_frames, size_t stride, int n, 
   pb.rs.timed = opt && opt->stats;        // (a flag here: the statistics themselves are handed to Wait)
   pb.opt.stats = nullptr;
   pb.t_submit = now_ms();
-  Pass<float>& p = pb.pass;
-  p = Pass<float>();
-  p.c = c; p.pe = pb.pe; p.trace = nullptr; p.dets = &pb.dets; p.rs = &pb.rs; p.apply_th = true; p.th = th; p.multi = false;
-  p.solo = true;
+  PassSetup<float> s;
+  s.c = c; s.pe = pb.pe; s.dets = &pb.dets; s.rs = &pb.rs; s.th = th; s.ln = ln;
   if (c->kn.device_post >= 1 && n >= c->kn.device_post_min_frames) {      // (k_post: even with the host work hidden behind the other tickets' kernels, +1 %)
-    p.want_post = true; p.post_nms = !opt || opt->nms; p.post_overlap = opt ? opt->nms_overlap : 0.3f;
+    s.want_post = true; s.post_nms = !opt || opt->nms; s.post_overlap = opt ? opt->nms_overlap : 0.3f;
     pb.dets.p_n.assign((size_t)n, -1); pb.dets.p_first.assign((size_t)n, 0);
   }
-  p.bind(ln, 0, nullptr);
-  p.f0 = 0; p.nf = n;
-  p.w.frames = d_frames; p.w.frame_stride = stride; p.w.n_frames = n;
-#ifdef JDA_BOUNDS_CHECK
-  p.w.bc_lo = d_frames; p.w.bc_hi = d_frames + (size_t)(n - 1) * stride + (size_t)width * height;
-#endif
-  p.w.half = nullptr; p.w.quarter = nullptr; p.w.half_stride = p.w.quarter_stride = 0;
-  p.w.hw = p.w.hh = p.w.qw = p.w.qh = 0;
+  s.nf = s.n_call = n; s.frames = d_frames; s.stride = stride;
   if (host_frames) {
     pb.host_ptrs.assign(host_frames, host_frames + n);       // (the helper thread reads them after Submit has returned)
-    p.host_frames = pb.host_ptrs.data(); p.host_fbytes = (size_t)width * height;
+    s.host_frames = pb.host_ptrs.data(); s.host_fbytes = (size_t)width * height;
   }
+  Pass<float>& p = pb.pass;
+  p.open(s);
   auto give_up = [&]() { return -1; };      // (the Reservation guard releases the slot)
   // opt->hip_stream: the stream the caller produced the frames on -- the scan is ordered behind the work
   // already queued there (the batch itself still runs on the lane's own stream)
@@ -101,7 +94,7 @@ int submit_c_device(Cascador* c, const uint8_t* d_frames, size_t stride, int n, 
     auto issue = [pbp, dev]() {
       // (a thread body: nothing may be thrown out of it -- std::terminate -- so a failed allocation becomes issue_ok = false)
       try {
-        if (hipSetDevice(dev) != hipSuccess || !pbp->pass.issue_scan(nullptr, 0, nullptr, 0, nullptr)) {
+        if (hipSetDevice(dev) != hipSuccess || !pbp->pass.issue_scan()) {
           pbp->issue_ok = false;
           pbp->issue_err = g_err.empty() ? std::string("issuing the batch failed") : g_err;
         }
@@ -116,7 +109,7 @@ int submit_c_device(Cascador* c, const uint8_t* d_frames, size_t stride, int n, 
     catch (const std::system_error&) { issue(); }
     return slot;
   }
-  if (!p.issue_scan(nullptr, 0, nullptr, 0, nullptr)) { (void)hipStreamSynchronize(ln->stream); return give_up(); }
+  if (!p.issue_scan()) { (void)hipStreamSynchronize(ln->stream); return give_up(); }
   commit();
   return slot;
 }
@@ -152,17 +145,10 @@ int wait_c_device(Cascador* c, int slot, jdaStats* stats, jdaResult* out) {
   pb.join_issuer();
   bool ok = pb.issue_ok;
   if (!ok) fail(pb.issue_err);
-  p.dets = &pb.dets; p.rs = &pb.rs;
-  ok = ok && p.after_tail() && p.after_mid() && p.issue_counters() && p.after_counters() && p.collect();
+  ok = ok && p.complete();
   double post_ms = 0;
   if (ok) {
-    float ms_scan = 0, ms_all = 0;
-    if (p.timed) {
-      (void)hipEventElapsedTime(&ms_scan, p.ev[1], p.ev[2]);
-      (void)hipEventElapsedTime(&ms_all, p.ev[0], p.ev[3]);
-    }
-    pb.rs.scan_ms += ms_scan; pb.rs.gpu_ms += ms_all;
-    if (p.lds_span && p.timed) { float ms = 0; if (hipEventElapsedTime(&ms, p.ev[1], p.ev[4]) == hipSuccess) pb.rs.scan_lds_ms += ms; }
+    p.tally_times(pb.rs);
     const jdaDetectOptions* opt = pb.opt_set ? &pb.opt : nullptr;
     post_ms = post_frames<DialectC>(pb.sp.levels, FrameSet{n, pb.sp.windows, pb.sp.width, pb.sp.height}, pb.dets, c->hm.L, !opt || opt->nms,
                                     opt ? opt->nms_overlap : 0.3f, Sink<DialectC>{out});

@@ -318,6 +318,79 @@ def test_bounded_queues_overflow_is_noticed_and_the_pass_rerun(built, model_file
             assert same(a[k], b[k]), k
 
 
+# jdaStats.scan_launches of the second call below, derived from the plan: one lane (4800 windows), its five levels all
+# LDS-tiled (plan_tiles) and 80 tiles in all -- below merge_blocks, so they share ONE launch -- and no rerun
+RERUN_SCAN_LAUNCHES = 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cart_th,predicted", [(1.15, True), (-0.2, False)], ids=["cascade", "busy"])
+def test_reruns_in_a_row_on_one_cascador_overflow_then_sized_then_dense(built, model_file, cart_th, predicted):
+    """Three calls in a row on ONE cascador, each leaving the pass another way (csrc/pass.h: Attempt / restart()), first
+    synchronously, then as tickets: what a rerun keeps and what it forgets must hold from call to call.
+    16 frames of 96x72, the forced-overflow settings of the test above, dense mode left on auto.  Scanned with scale 1.15
+    from 36 pixels up the batch has 4800 windows; stage 0 is 20 carts, all of them in the scan.
+    Call 1 has no prediction: it reads the hand-off count (after_tail), finds more than the first pass's guess for the
+    hand-off queue (an eighth), is run again, and wants k_post.  Call 2 finds the queues sized by call 1: no rerun.
+    Call 3 hands off after ONE cart, which rejects nobody (its threshold is lowered): 4800 > 4096 windows alive, the pass
+    switches to dense mode from after_tail.  Every call: the oracle's rows, an empty error string.
+
+    "cascade": stage 0 keeps 700 windows (15 %).  Hand-off and mid queue together stay below the 40 % from which a pass
+    on auto waits for its hand-off count, so calls 2 and 3 are issued WITH the prediction call 1 left: finishing launches,
+    k_post, counters and results queued behind the scan, one host wait.  Call 3 shows it: a predicted pass does not look
+    at the hand-off count before after_counters, so its 4800 survivors overflow the queues the prediction sized
+    (ws_regrows >= 1, found in after_counters), and only the rerun -- prediction withdrawn -- reaches after_tail and goes
+    dense.  Issued without a prediction it would go dense at once, with no regrow: that is the "busy" case.
+    "busy": stage 0 keeps 63 %.  From 40 % on a pass on auto reads its hand-off count even when it has a prediction
+    (issue_rest), so here calls 2 and 3 wait in after_tail and call 3 goes dense from there directly.  One sequence cannot
+    have both a predicted second call and a third call whose FIRST attempt waits in after_tail: a new plan inherits the
+    cascador's prediction."""
+    import torch
+    from jda_amd import api, synth
+    from oracle.pyoracle import Oracle
+    kw = dict(scale=1.15, min_size=36)
+    p, m = model_file((3, 20, 5, 4), 8, seed=3, cart_th=cart_th, norm_every=5)
+    m.cth[0, 0] = -1.0e30
+    m.save(p, 8)
+    frames = synth.make_frames(16, 96, 72, seed=11)
+    d = torch.from_numpy(frames).cuda()
+    o = Oracle(p)
+    want = [o.detect(f, **kw) for f in frames]
+    trs = [o.trace(f, want_shapes=False, **kw)["carts_n"] for f in frames]
+    n, tail, alive1 = sum(len(t) for t in trs), sum(int((t > 20).sum()) for t in trs), sum(int((t > 1).sum()) for t in trs)
+    # preconditions (host.h: queue_caps without a prediction; pass.cpp: after_tail, issue_rest -- the mid queue takes
+    # survivors of the hand-off, so at most `tail` of them)
+    assert sum(len(w["scores"]) for w in want) > 0
+    assert n // 8 + 64 < tail <= 4096 < alive1 == n and 2 * alive1 >= n, (n, tail, alive1)
+    assert (2 * tail < 0.4 * n) if predicted else (tail >= 0.4 * n), (n, tail)
+
+    def check(got, st, what):
+        assert api.last_error() == "", what
+        for i, (a, b) in enumerate(zip(got, want)):
+            for k in ("bboxes", "scores", "shapes"):
+                assert same(a[k], b[k]), (what, i, k)
+        print(what, {k: st[k] for k in ("ws_regrows", "dense_passes", "scan_launches", "handoff_n", "scan_fallbacks")})
+
+    for mode, call in (("sync", lambda c: c.detect_batch_device(d, stats=True, **kw)),
+                       ("ticket", lambda c: c.wait_batch(c.submit_batch_device(d, stats=True, **kw), stats=True))):
+        c = api.Cascador(p)
+        c.set_option("ws_min_entries", 1); c.set_option("ws_factor_pct", 100); c.set_option("device_post_min_frames", 2)
+        assert c.get_option("predict") == 1 and c.get_option("dense") == 1
+        got, st = call(c)
+        check(got, st, mode + " 1")
+        assert st["ws_regrows"] >= 1 and st["dense_passes"] == 0 and st["handoff_n"] == tail, (mode, st)
+        got, st = call(c)
+        check(got, st, mode + " 2")
+        assert st["ws_regrows"] == 0 and st["dense_passes"] == 0 and st["handoff_n"] == tail, (mode, st)
+        assert st["scan_launches"] == RERUN_SCAN_LAUNCHES, (mode, st["scan_launches"])
+        c.set_option("handoff", 1)
+        got, st = call(c)
+        check(got, st, mode + " 3")
+        assert st["dense_passes"] >= 1, (mode, st)
+        assert (st["ws_regrows"] >= 1) == predicted, (mode, st)
+        c.close()
+
+
 def test_lanes_get_hardware_queues_of_their_own(built, gpu, model_file, monkeypatch):
     """The runtime deals a process's streams to four hardware queues -- which one depends on every stream the host program
     created before -- and the kernels of one queue run one after the other (tools/experiments/hwq_probe.hip).  The
