@@ -559,9 +559,10 @@ JDA_API long long jdaMineWindowList(int w, int h, int origin_size, int step, dou
  * cart.cpp:288-350), the samples are partitioned and the children split in turn; a leaf's score is
  * 0.5 * (log(pos_w) - log(neg_w)) (cart.cpp:63-89).  PARITY UNPINNED like every dialect-CPP entry: src/jda needs OpenCV and
  * cannot be built here; these entries are bit-exact against a sequential restatement written from the reference's source
- * (tests/train_ref.py), not against the reference.  Out of scope: BoostCart::Train's loop (weights, thresholds by recall,
- * restarts), liblinear's fit of the global regression (what goes into it and what comes out of it: the block "closing a
- * stage" below), writing the cart into a model file, data loading.
+ * (tests/train_ref.py), not against the reference.  Out of scope: BoostCart::Train's loop and its restart policy (one step
+ * of that loop -- scores, order, cut, weights and the move of the surviving samples -- is the block "from one cart to the
+ * next" at the end of this file), liblinear's fit of the global regression (what goes into it and what comes out of it:
+ * the block "closing a stage" below), writing the cart into a model file, data loading.
  *
  * Samples.  One struct describes a set of n samples.  origin_size / half_size / quarter_size are call arguments, each in
  * [1, 128]; the landmark count L and tree_depth come from the cascador (it also supplies the device, the "workspace_mb"
@@ -682,7 +683,8 @@ JDA_API int jdaTrainCartCpp(void *cascador, const jdaSamplesCpp *pos, const jdaS
  * written into a model.  PARITY UNPINNED like every dialect-CPP entry: src/jda needs OpenCV and cannot be built here; these
  * entries are bit-exact against a sequential restatement written from the reference's source (tests/stage_ref.py), not
  * against the reference.  Out of scope: the fit itself (liblinear's L2R_L2LOSS_SVR_DUAL draws from rand(); INTEGRATION.md
- * says what it consumes and returns), BoostCart::Train's loop, writing into a model file.
+ * says what it consumes and returns), BoostCart::Train's loop (one step of it: the last block of this file), writing into a
+ * model file.
  *
  * Sizes.  nodes_n = 2^tree_depth and the landmark count L come from the cascador, as in the training block (it also
  * supplies the device, the LDS budget "lbf_lds_kb" and the "workspace_mb" limit of the per-call workspace: the samples are
@@ -749,6 +751,113 @@ JDA_API int jdaStageUpdateShapesCpp(void *cascador, const jdaSamplesCpp *samples
  * n == 0 gives 0. / 0. = NaN, like the reference.  -1: NULL arguments, n < 0, L < 1, an empty pupil list, an id outside [0, L). */
 JDA_API int jdaMeanErrorCpp(const double *gt_shapes, const double *cur_shapes, int n, int L, const int *left_pupils,
                             int n_left, const int *right_pupils, int n_right, double *out);
+
+/* ---- Dialect CPP: from one cart to the next ---------------------------------------------------------------------------
+ * What BoostCart::Train does between two carts (reference src/jda/btcart.cpp:146-253 with src/jda/data.cpp:255-448): the new
+ * cart's leaf scores are added to every sample (DataSet::UpdateScores), optionally normalised (CalcMeanAndStd /
+ * ApplyMeanAndStd), both sets are sorted by score with the reference's own quicksort (_QSort_), the cart's threshold is the
+ * score of the drop_n-th positive from the end (CalcThresholdByNumber), both sets are cut at it (PreRemove / Remove), mined
+ * negatives are appended (MoreNegSamples) and the weights recomputed (UpdateWeights).  Every sum of the next cart runs in
+ * the sample order this leaves, and the quicksort is NOT stable: a caller who sorts with anything else trains other carts.
+ * The reference's Swap exchanges cv::Mat headers; here a set is a dense patch array in device memory that k_train_values
+ * and k_lbf read in place, so the surviving samples' bytes move, on the device, into the new order
+ * (jdaGatherSamplesCpp).  These entries are ONE STEP of the loop as arithmetic on caller arrays.  PARITY UNPINNED like
+ * every dialect-CPP entry: bit-exact against a sequential restatement written from the reference's source
+ * (tests/boost_ref.py), not against the reference.  Out of scope: the loop itself and the restart decision
+ * (btcart.cpp:189-232: the caller compares will_removed with its own policy and, to restart, copies `last` back --
+ * ResetScores), the call into mining (the caller invokes jdaMineNegativesCpp* and passes the result as a segment),
+ * CalcSTParameters (the training entries refuse the similarity transform), snapshots, writing carts or weights into a
+ * model, liblinear.
+ *
+ * All of it is fp64 in the reference's own order.  The host entries take no cascador, use no GPU and never crash: bad
+ * input returns -1 and sets jdaGetLastError().  exp() and sqrt() are the HOST C library's: the weights stay on the host for
+ * the reason log() does in the training block -- the device's exp is another function. */
+
+/* DataSet::UpdateScores (data.cpp:305-317) for both sets, then -- normalize != 0 -- CalcMeanAndStd and ApplyMeanAndStd
+ * (data.cpp:420-448), literally:
+ *   for every positive i in order, then every negative i in order:  last[i] = score[i];  score[i] += cart_scores[leaf[i]];
+ *   normalize == 0:  *mean = 0., *stddev = 1., the scores stay as they are.  Otherwise
+ *   m = 0., + every positive score in order, then + every negative score in order;  m /= (double)(pos_n + neg_n);
+ *   var = 0., + v * v with v = score - m, over the positives in order, then the negatives in order;
+ *   var /= (double)(pos_n + neg_n);  *stddev = sqrt(var);  *mean = m;  every score = (score - m) / *stddev.
+ * The reference writes the square as std::pow(v, 2): DEFINED as v * v, as jdaMeanErrorCpp defines it (what the C library
+ * returns for an exponent of exactly 2 and what compilers fold it into; unchecked).  THE SUMS RUN OVER THE ORDER THE ARRAYS
+ * HAVE AT THE CALL, that is before the sort.  leaf is jdaTrainCartCpp's pos_leaf / neg_leaf, cart_scores its out_scores of
+ * leaf_n = nodes_n/2 entries; every leaf index is checked against [0, leaf_n) before anything is written.  pos_scores /
+ * neg_scores are updated in place; pos_last / neg_last receive the scores from before the call.  *stddev == 0 (all scores
+ * equal) gives inf / NaN scores like the reference and the call succeeds; so does an empty pair of sets (0. / 0.).  mean /
+ * stddev may be NULL.  -1: NULL where n > 0, a negative count, leaf_n < 1, a leaf index outside [0, leaf_n). */
+JDA_API int jdaBoostScoresCpp(const double *cart_scores, int leaf_n, const int *pos_leaf, int pos_n, const int *neg_leaf,
+                              int neg_n, int normalize, double *pos_scores, double *neg_scores, double *pos_last,
+                              double *neg_last, double *mean, double *stddev);
+
+/* DataSet::_QSort_ (data.cpp:385-410) on one set's scores together with an index array, literally: for a range
+ * [left, right], i = left, j = right, t = scores[(left + right) / 2] (the pivot VALUE, read before any swap);
+ *   do { while (scores[i] > t) i++;  while (scores[j] < t) j--;  if (i <= j) { swap i and j;  i++;  j--; } } while (i <= j);
+ * then [left, j] if left < j and [i, right] if i < right.  The two halves are disjoint, so an explicit stack (no recursion,
+ * depth O(log n)) gives the reference's result.  order[i] = the original index of the sample now at position i (descending
+ * scores); sorted_scores (may be NULL) = scores[order[i]].  The sort is NOT stable: [3, 2, 2, 1] gives order 0 2 1 3, eight
+ * equal scores give 5 4 7 6 1 0 3 2; without ties the result equals a descending stable sort.  `scores` itself is not
+ * changed.  n == 0 returns 0 and reads nothing (the reference would read scores[0]).  -1: any NaN score (the reference's
+ * scans would run off the array), NULL, n < 0.  +-inf are ordinary values. */
+JDA_API int jdaSampleOrderCpp(const double *scores, int n, int *order, double *sorted_scores);
+
+/* DataSet::CalcThresholdByNumber (data.cpp:340-345) on scores ALREADY SORTED by jdaSampleOrderCpp: offset = n - 1 - drop_n,
+ * clamped to 0 from below; *th = sorted_scores[offset].  -1: n < 1, drop_n < 0, NULL. */
+JDA_API int jdaScoreThresholdCpp(const double *sorted_scores, int n, int drop_n, double *th);
+
+/* DataSet::PreRemove / Remove (data.cpp:347-378) on sorted scores: offset = n - 1; while (offset >= 0 &&
+ * sorted_scores[offset] < th) offset--;  *keep = offset + 1 (the leading samples that stay: ties at th stay),
+ * *will_removed = n - *keep (either may be NULL).  n == 0 gives 0 / 0.  The restart decision on will_removed is the
+ * caller's.  -1: a NaN th, n < 0, NULL scores where n > 0. */
+JDA_API int jdaScoreCutCpp(const double *sorted_scores, int n, double th, int *keep, int *will_removed);
+
+/* DataSet::UpdateWeights(pos, neg) (data.cpp:255-303): w = exp(-score) for every positive, exp(score) for every negative
+ * (the host C library's exp); sum_pos = 0. + the positive weights in order, sum_neg = 0. + the negative weights in order;
+ * r = 1. / (sum_pos + sum_neg); every weight *= r.  Two empty sets: nothing is written.  -1: NULL where n > 0, n < 0. */
+JDA_API int jdaUpdateWeightsCpp(const double *pos_scores, int pos_n, const double *neg_scores, int neg_n,
+                                double *pos_weights, double *neg_weights);
+
+/* Host only: the per-sample rows that travel with the patches (shapes, ground truth, masks, scores, last) by the same
+ * index list.  The source is the concatenation of n_segs (1 .. 8) host arrays, rows[s] holding rows_n[s] rows of
+ * row_bytes; dst row i = source row index[i] for i < keep: a memcpy per row.  Every index is checked against the total
+ * before anything is written; repeats are allowed.  dst must not overlap a source (refused).  keep == 0 returns 0. */
+JDA_API int jdaGatherRowsCpp(const void *const *rows, const int *rows_n, int n_segs, size_t row_bytes, const int *index,
+                             int keep, void *dst);
+
+typedef struct {
+  const unsigned char *patches;  /* n records of P = o*o + h*h + q*q bytes, jdaSamplesCpp.patches' layout; any alignment */
+  int on_device;                 /* 0: host pointer (staged in chunks within "workspace_mb"), 1: device pointer (read in place) */
+  int n;                         /* records; 0: an empty segment, patches is not read                                       */
+} jdaGatherSegCpp;
+
+typedef struct {
+  double call_ms;            /* wall clock of the call                                                          */
+  double upload_ms;          /* ... the index list and the chunks of host segments to the device                */
+  double device_ms;          /* ... the k_gather launches, HIP events, summed                                   */
+  double download_ms;        /* ... a host dst: the gathered records back                                       */
+  long long bytes;           /* keep * P: the bytes written to dst                                              */
+  int chunks;                /* chunks of host segments (or, for a host dst, of dst) that went through the workspace */
+  int launches;              /* k_gather launches                                                               */
+} jdaGatherStatsCpp;
+
+/* A new dense sample set from up to 8 segments: with the source set = the concatenation of segs[0 .. n_segs), dst record i
+ * = source record index[i] for i < keep, P = o*o + h*h + q*q bytes each (every size in [1, 128]: P = 3 .. 49,152).  One call
+ * is "sort and cut" (one segment, index = jdaSampleOrderCpp's order, keep = jdaScoreCutCpp's), "append mined negatives"
+ * (two segments, an identity index) or "append, then sort" (two segments, the order of the concatenated scores:
+ * MoreNegSamples followed by QSort).  Device segments are read in place, host segments staged in chunks within the
+ * cascador's "workspace_mb"; dst is the caller's buffer of keep * P bytes, on the device (dst_on_device = 1) or on the host
+ * (then device records come back in chunks and host records are copied by the host).  No byte outside
+ * [dst, dst + keep * P) is written, whatever the alignment of dst and of the segments (none is required).  dst MUST NOT
+ * OVERLAP A SOURCE: a device dst that overlaps a device segment (or a host dst a host segment) is refused; callers
+ * alternate between two buffers.  index is validated entry by entry against the total number of records before anything
+ * is launched; repeats are allowed.  keep == 0 returns 0 without touching the device.  The cascador supplies the device,
+ * the workspace limit and the error state only -- no model is read, so the entry works with jdaSetSimilarityTransform on or
+ * off.  -1: NULL where data is needed, n_segs outside [1, 8], a negative n, more than INT_MAX records in all, a size outside
+ * [1, 128], an index outside [0, total), an overlap. */
+JDA_API int jdaGatherSamplesCpp(void *cascador, const jdaGatherSegCpp *segs, int n_segs, int origin_size, int half_size,
+                                int quarter_size, const int *index, int keep, unsigned char *dst, int dst_on_device,
+                                jdaGatherStatsCpp *stats);
 
 #ifdef __cplusplus
 }

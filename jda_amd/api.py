@@ -98,6 +98,18 @@ class jdaStageStatsCpp(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class jdaGatherSegCpp(C.Structure):
+    _fields_ = [("patches", C.c_void_p), ("on_device", C.c_int), ("n", C.c_int)]
+
+
+class jdaGatherStatsCpp(C.Structure):
+    _fields_ = [("call_ms", C.c_double), ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double),
+                ("bytes", C.c_longlong), ("chunks", C.c_int), ("launches", C.c_int)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # numpy view of jdaFeatureCpp arrays (same layout: three ints, four bytes of padding, four doubles)
 FEATURE_DTYPE = np.dtype([("scale", np.int32), ("landmark_id1", np.int32), ("landmark_id2", np.int32), ("pad", np.int32),
                           ("offset1_x", np.float64), ("offset1_y", np.float64), ("offset2_x", np.float64),
@@ -253,6 +265,16 @@ def _load():
         lib.jdaStageUpdateShapesCpp.argtypes = [C.c_void_p, sp, C.c_int, C.c_int, C.c_int, cp, dp, ip, dp, ip,
                                                 C.POINTER(jdaStageStatsCpp)]
         lib.jdaMeanErrorCpp.argtypes = [dp, dp, C.c_int, C.c_int, ip, C.c_int, ip, C.c_int, dp]
+    if hasattr(lib, "jdaGatherSamplesCpp"):
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        lib.jdaBoostScoresCpp.argtypes = [dp, C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp]
+        lib.jdaSampleOrderCpp.argtypes = [dp, C.c_int, ip, dp]
+        lib.jdaScoreThresholdCpp.argtypes = [dp, C.c_int, C.c_int, dp]
+        lib.jdaScoreCutCpp.argtypes = [dp, C.c_int, C.c_double, ip, ip]
+        lib.jdaUpdateWeightsCpp.argtypes = [dp, C.c_int, dp, C.c_int, dp, dp]
+        lib.jdaGatherRowsCpp.argtypes = [C.POINTER(C.c_void_p), ip, C.c_int, C.c_size_t, ip, C.c_int, C.c_void_p]
+        lib.jdaGatherSamplesCpp.argtypes = [C.c_void_p, C.POINTER(jdaGatherSegCpp), C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int,
+                                            C.c_void_p, C.c_int, C.POINTER(jdaGatherStatsCpp)]
     return lib
 
 
@@ -325,6 +347,102 @@ def mean_error_cpp(gt_shapes, cur_shapes, left_pupils, right_pupils):
                            C.byref(out)) != 0:
         raise JdaError(last_error())
     return out.value
+
+
+# -- from one cart to the next (include/jda.h, "Dialect CPP: from one cart to the next"): host only, no cascador ----
+
+def _dvec(a):
+    a = np.ascontiguousarray(a, np.float64).reshape(-1)
+    return a, (a.ctypes.data_as(C.POINTER(C.c_double)) if a.size else None)
+
+
+def boost_scores_cpp(cart_scores, pos_leaf, neg_leaf, pos_scores, neg_scores, normalize=False):
+    """DataSet::UpdateScores for both sets and, with normalize, CalcMeanAndStd / ApplyMeanAndStd (reference data.cpp:305-317,
+    420-448; jdaBoostScoresCpp) -> dict(pos_scores, neg_scores, pos_last, neg_last, mean, std).  The inputs are not changed.
+    The sums run over the order the arrays have now, before the sort."""
+    cs, csp = _dvec(cart_scores)
+    kp, pl = _ivec(pos_leaf)
+    kn, nl = _ivec(neg_leaf)
+    ps, psp = _dvec(np.array(pos_scores, np.float64))
+    ns, nsp = _dvec(np.array(neg_scores, np.float64))
+    assert ps.size == np.asarray(pos_leaf).size and ns.size == np.asarray(neg_leaf).size, "one leaf per sample"
+    plast, plp = _dvec(np.zeros(ps.size))
+    nlast, nlp = _dvec(np.zeros(ns.size))
+    mean, std = C.c_double(), C.c_double()
+    if lib.jdaBoostScoresCpp(csp, cs.size, pl if ps.size else None, ps.size, nl if ns.size else None, ns.size, 1 if normalize else 0,
+                             psp, nsp, plp, nlp, C.byref(mean), C.byref(std)) != 0:
+        raise JdaError(last_error())
+    return dict(pos_scores=ps, neg_scores=ns, pos_last=plast, neg_last=nlast, mean=mean.value, std=std.value)
+
+
+def sample_order_cpp(scores):
+    """DataSet::_QSort_ (reference data.cpp:385-410; jdaSampleOrderCpp) on one set's scores -> (order int32 [n], sorted
+    scores [n]): order[i] is the original index of the sample now at position i.  Not a stable sort; NaN is refused."""
+    sc, scp = _dvec(scores)
+    order = np.zeros(sc.size, np.int32)
+    out = np.zeros(sc.size, np.float64)
+    if lib.jdaSampleOrderCpp(scp, sc.size, order.ctypes.data_as(C.POINTER(C.c_int)), out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise JdaError(last_error())
+    return order, out
+
+
+def score_threshold_cpp(sorted_scores, drop_n):
+    """DataSet::CalcThresholdByNumber (reference data.cpp:340-345; jdaScoreThresholdCpp) on sorted scores -> th."""
+    sc, scp = _dvec(sorted_scores)
+    th = C.c_double()
+    if lib.jdaScoreThresholdCpp(scp, sc.size, int(drop_n), C.byref(th)) != 0:
+        raise JdaError(last_error())
+    return th.value
+
+
+def score_cut_cpp(sorted_scores, th):
+    """DataSet::PreRemove / Remove (reference data.cpp:347-378; jdaScoreCutCpp) on sorted scores -> (keep, will_removed)."""
+    sc, scp = _dvec(sorted_scores)
+    keep, gone = C.c_int(), C.c_int()
+    if lib.jdaScoreCutCpp(scp, sc.size, float(th), C.byref(keep), C.byref(gone)) != 0:
+        raise JdaError(last_error())
+    return keep.value, gone.value
+
+
+def update_weights_cpp(pos_scores, neg_scores):
+    """DataSet::UpdateWeights(pos, neg) (reference data.cpp:255-303; jdaUpdateWeightsCpp) with the host C library's exp ->
+    (pos_weights, neg_weights)."""
+    ps, psp = _dvec(pos_scores)
+    ns, nsp = _dvec(neg_scores)
+    pw, pwp = _dvec(np.zeros(ps.size))
+    nw, nwp = _dvec(np.zeros(ns.size))
+    if lib.jdaUpdateWeightsCpp(psp, ps.size, nsp, ns.size, pwp, nwp) != 0:
+        raise JdaError(last_error())
+    return pw, nw
+
+
+def gather_rows_cpp(rows, index, keep=None):
+    """The per-sample rows that travel with the patches (jdaGatherRowsCpp, host only): rows is one array [n, ...] or a list
+    of up to 8 of them with equal row shape and dtype (their concatenation is the source); -> [keep, ...] with row i the
+    source row index[i]."""
+    segs = [np.ascontiguousarray(a) for a in (rows if isinstance(rows, (list, tuple)) else [rows])]
+    assert segs and all(a.ndim >= 1 and a.shape[1:] == segs[0].shape[1:] and a.dtype == segs[0].dtype for a in segs)
+    idx = np.ascontiguousarray(index, np.int32).reshape(-1)
+    keep = idx.size if keep is None else int(keep)
+    assert keep <= idx.size
+    row_bytes = int(np.prod(segs[0].shape[1:], dtype=np.int64)) * segs[0].dtype.itemsize
+    out = np.zeros((max(keep, 0),) + segs[0].shape[1:], segs[0].dtype)
+    ptrs = (C.c_void_p * len(segs))(*[a.ctypes.data if a.size else None for a in segs])
+    ns = (C.c_int * len(segs))(*[a.shape[0] for a in segs])
+    if lib.jdaGatherRowsCpp(ptrs, ns, len(segs), row_bytes, idx.ctypes.data_as(C.POINTER(C.c_int)) if idx.size else None, keep,
+                            out.ctypes.data if out.size else None) != 0:
+        raise JdaError(last_error())
+    return out
+
+
+def _byte_buffer(a, what):
+    """A numpy uint8 array or a torch uint8 device tensor (any view with a byte offset: its data pointer is what counts) ->
+    (pointer, on_device, bytes)."""
+    if hasattr(a, "is_cuda"):
+        assert a.is_cuda and a.dtype.itemsize == 1 and a.is_contiguous(), "%s: a contiguous uint8 device tensor" % what
+        return (a.data_ptr() if a.numel() else None), 1, a.numel()
+    assert isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.flags.c_contiguous, "%s: a contiguous uint8 array" % what
+    return (a.ctypes.data if a.size else None), 0, a.size
 
 
 def _stage_carts(features, thresholds, inner, K=None):
@@ -1128,6 +1246,34 @@ class Cascador:
             raise JdaError(last_error())
         res = (out,) + ((olbf,) if want_lbf else ()) + ((st.asdict(),) if stats else ())
         return res[0] if len(res) == 1 else res
+
+    # -- from one cart to the next (include/jda.h, "Dialect CPP: from one cart to the next") -----------------------
+    def gather_samples_cpp(self, segments, index, dst, keep=None, origin_size=48, half_size=36, quarter_size=24, stats=False):
+        """A new dense sample set (jdaGatherSamplesCpp): dst record i = record index[i] of the concatenation of `segments`
+        (one buffer or a list of up to 8; each a numpy uint8 array -- a host segment -- or a torch uint8 device tensor, read
+        in place, of n * (o*o + h*h + q*q) bytes) for i < keep (default: len(index)).  dst: the caller's buffer of at least
+        keep records, a torch device tensor or a writable numpy array; it must not overlap a segment.  Views at any byte
+        offset work: the data pointer is what is passed.  -> dst, or (dst, stats dict)."""
+        pb = _patch_bytes(origin_size, half_size, quarter_size)
+        bufs = list(segments) if isinstance(segments, (list, tuple)) else [segments]
+        segs = (jdaGatherSegCpp * max(len(bufs), 1))()
+        for i, b in enumerate(bufs):
+            ptr, dev, nbytes = _byte_buffer(b, "segment %d" % i)
+            assert nbytes % pb == 0, "segment %d does not hold whole records" % i
+            segs[i].patches, segs[i].on_device, segs[i].n = ptr, dev, nbytes // pb
+        idx = np.ascontiguousarray(index, np.int32).reshape(-1)
+        keep = idx.size if keep is None else int(keep)
+        assert keep <= idx.size
+        dptr, ddev, dbytes = _byte_buffer(dst, "dst")
+        assert dbytes >= max(keep, 0) * pb, "dst is too small for keep records"
+        assert ddev or dst.flags.writeable
+        st = jdaGatherStatsCpp()
+        rc = lib.jdaGatherSamplesCpp(self.h, segs, len(bufs), origin_size, half_size, quarter_size,
+                                     idx.ctypes.data_as(C.POINTER(C.c_int)) if idx.size else None, keep, dptr, ddev, C.byref(st))
+        del bufs
+        if rc != 0:
+            raise JdaError(last_error())
+        return (dst, st.asdict()) if stats else dst
 
     def trace_cpp(self, frames, minimum_size=20, step=5, factor=1.2):
         frames = np.ascontiguousarray(frames, np.uint8)

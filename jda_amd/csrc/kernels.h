@@ -471,6 +471,22 @@ struct LbfLaunch { int lds, waves, lds_bytes; };   // how it ran: staged in LDS 
 // kernel reads everything from global memory.
 hipError_t launch_lbf(const LbfArgs& a, int lds_budget, LbfLaunch* how, hipStream_t stream);
 
+// ---- dialect CPP: a sample set from one cart to the next (k_gather.hip, boost.cpp; reference src/jda/data.cpp:319-410) ----
+constexpr int kGatherSegs = 8;           // source segments of one launch at most
+constexpr int kGatherWaves = 4;          // destination records (waves) of a workgroup per round of its grid-stride loop
+// Records [first, first + n) of the source set (the concatenation of the caller's segments) at `base` (device), P bytes each.
+struct GatherSeg { const uint8_t* base; long long first, n; };
+struct GatherItem { int dst, src; };     // destination record <- source record (index into the source set)
+// One launch: items[0 .. n_items), every item's src inside one of seg[0 .. n_segs) and its dst inside
+// [dst_first, dst_first + dst_n); destination record r starts at dst + (r - dst_first) * P.  No alignment is assumed.
+struct GatherArgs {
+  GatherSeg seg[kGatherSegs]; int n_segs;
+  const GatherItem* items; long long n_items;
+  uint8_t* dst; long long dst_first, dst_n;
+  int P;
+};
+hipError_t launch_gather(const GatherArgs& a, hipStream_t stream);
+
 // Hardware-queue probe (k_misc.hip): a one-wave spin of `ticks` wall-clock ticks (100 MHz) that leaves its end time in
 // *out (mapped pinned host memory), and a kernel that leaves the time it ran.
 hipError_t launch_hwq_spin(long long ticks, unsigned long long* out, hipStream_t stream);
