@@ -562,7 +562,9 @@ JDA_API long long jdaMineWindowList(int w, int h, int origin_size, int step, dou
  * (tests/train_ref.py), not against the reference.  Out of scope: BoostCart::Train's loop and its restart policy (one step
  * of that loop -- scores, order, cut, weights and the move of the surviving samples -- is the block "from one cart to the
  * next" at the end of this file), liblinear's fit of the global regression (what goes into it and what comes out of it:
- * the block "closing a stage" below), writing the cart into a model file, data loading.
+ * the block "closing a stage" below), writing the cart into a model file, reading image files (file and JPEG reading and
+ * cvtColor stay the caller's; what LoadPositiveDataSet does with the decoded images is the block "the positive sample set" at
+ * the end of this file).
  *
  * Samples.  One struct describes a set of n samples.  origin_size / half_size / quarter_size are call arguments, each in
  * [1, 128]; the landmark count L and tree_depth come from the cascador (it also supplies the device, the "workspace_mb"
@@ -858,6 +860,107 @@ typedef struct {
 JDA_API int jdaGatherSamplesCpp(void *cascador, const jdaGatherSegCpp *segs, int n_segs, int origin_size, int half_size,
                                 int quarter_size, const int *index, int keep, unsigned char *dst, int dst_on_device,
                                 jdaGatherStatsCpp *stats);
+
+/* ---- Dialect CPP: the positive sample set -----------------------------------------------------------------------------
+ * What DataSet::LoadPositiveDataSet (reference src/jda/data.cpp:567-678) does once the images are decoded: getFace
+ * (data.cpp:542-565) cuts every face box out of its image, three cv::resize calls make the o, h and q patches
+ * (data.cpp:630-632), the landmarks are normalised to the box (625-628), face_augment_on adds the mirrored copy of every
+ * sample (637-662), CalcMeanShape (210-223) and RandomShapes (237-253) give the mean and the initial shapes; later
+ * CalcShapeResidual (175-208) is what jdaSamplesCpp.residual asks for.  The outputs are jdaSamplesCpp's layout: they go
+ * into the training entries as they are.  PARITY UNPINNED like every dialect-CPP entry: src/jda needs OpenCV and cannot be
+ * built here; these entries are bit-exact against a restatement written from the reference's source
+ * (tests/positives_ref.py), not against the reference.  Out of scope: reading the list file, decoding images and cvtColor
+ * (the caller hands in 8-bit grey images), liblinear's fit and the training loop.
+ *
+ * The face.  getFace(image, bbox) is a w x h crop of the cols x rows image in which every pixel outside the image is 0.
+ * The reference takes its clone-the-crop path only when bbox.x >= 0, bbox.y >= 0, bbox.x + w < cols and bbox.y + h < rows
+ * -- A STRICT TEST: a face with x + w == cols goes through the padded canvas although it lies inside the image.  The bytes
+ * are the same either way, and here both are one path (a pixel is read from the image, or is 0).  The padded canvas is
+ * 3 cols x 3 rows with the image at (cols / 2, rows / 2) (integer halves); a box that leaves THE CANVAS makes OpenCV throw,
+ * and the entries refuse it: -1 when  x + cols/2 < 0,  y + rows/2 < 0,  x + cols/2 + w > 3 cols  or  y + rows/2 + h > 3 rows,
+ * and when w <= 0 or h <= 0.  Everything is validated before the device is touched and before a byte of dst is written.
+ *
+ * The three patches.  Each is cv::resize(INTER_LINEAR), as restated in this library (jdaResizeCv), OF THE FACE ITSELF:
+ * face -> o, face -> h, face -> q.  This is not mining's chain (o -> h, o -> q, resize_mode 0); it is what resize_mode 1
+ * computes for a crop inside its image.  The resize clamps to the face's w x h, not to the image; a box that is not square
+ * is resized with separate x and y scales; a box of exactly twice a patch side takes OpenCV's 2x2 box average (zeros from
+ * outside the image enter it) and a box of the patch's size is copied.
+ *
+ * Augmentation.  With augment = 1 the set has size = 2 n_faces records and record i + n_faces is cv::flip(patch, 1) of
+ * record i's RESIZED o, h and q patches (data.cpp:638-640): the horizontal mirror of the bytes, NOT a resize of the
+ * mirrored face (the two differ where the resize is not symmetric under the mirror).
+ *
+ * Images use jdaValidateCpp's conventions: host images of widths[i]*heights[i] bytes, rows back to back, or
+ * (jdaBuildPositivesCppDevice) resident ones at d_base + offsets[i].  faces: n_faces rows of 5 ints (image, x, y, w, h).
+ * dst receives size records of P = o*o + h*h + q*q bytes (any alignment, P may be odd), on the device (dst_on_device = 1,
+ * written in place) or on the host (the records come back through the workspace in chunks): jdaGatherSamplesCpp's
+ * convention for its dst.  Host images are uploaded in chunks that fit the cascador's "workspace_mb" (a chunk holds at
+ * least one image); an image no face references is not uploaded.  A device dst must not overlap a referenced resident image
+ * (refused).  The cascador supplies the device, the workspace limit and the error state only -- no model is read, so the
+ * entries work with jdaSetSimilarityTransform on or off.  n_faces == 0 returns 0 without touching the device.
+ * -1 with jdaGetLastError(): NULL where data is needed, a patch size outside [1, 128], augment outside {0, 1}, an image index
+ * outside [0, n_images), an empty or NULL referenced image, more than INT_MAX records, the box refusals above, an overlap. */
+
+typedef struct {
+  double call_ms;            /* wall clock of the call                                                          */
+  double upload_ms;          /* ... the face rows and the chunks of host images to the device                   */
+  double device_ms;          /* ... the k_faces launches, HIP events, summed                                    */
+  double download_ms;        /* ... a host dst: the records back                                                */
+  long long bytes;           /* size * P: the bytes written to dst                                              */
+  int image_chunks;          /* chunks the referenced host images were uploaded in (0: images resident)         */
+  int images_uploaded;       /* host images uploaded: the referenced ones                                       */
+  int chunks;                /* batches of faces that went through the workspace                                */
+  int launches;              /* k_faces launches                                                                */
+} jdaPositivesStatsCpp;
+
+JDA_API int jdaBuildPositivesCpp(void *cascador, const unsigned char *const *images, const int *widths, const int *heights,
+                                 int n_images, const int *faces, int n_faces, int origin_size, int half_size,
+                                 int quarter_size, int augment, unsigned char *dst, int dst_on_device,
+                                 jdaPositivesStatsCpp *stats);
+JDA_API int jdaBuildPositivesCppDevice(void *cascador, const unsigned char *d_base, const size_t *offsets, const int *widths,
+                                       const int *heights, int n_images, const int *faces, int n_faces, int origin_size,
+                                       int half_size, int quarter_size, int augment, unsigned char *dst, int dst_on_device,
+                                       jdaPositivesStatsCpp *stats);
+
+/* Host only (no GPU, no cascador): ground-truth shapes, masks and the mean shape, literally data.cpp:589-598, 625-628,
+ * 641-661 and CalcMeanShape (210-223).  faces: the n_faces rows given to jdaBuildPositivesCpp (x, y, w, h are read);
+ * landmarks: n_faces * 2L doubles in image coordinates (x0, y0, x1, y1, ...).  With size = augment ? 2 n_faces : n_faces:
+ *   shape_mask[i] = -1 when ALL 2L raw values are negative (`>= 0` fails for every one: a NaN counts as negative), else 1;
+ *     such shapes are still normalised and mirrored like the others;
+ *   gt_shapes[i][2j] = (v - x) / w,  gt_shapes[i][2j + 1] = (v - y) / h   (x, y, w, h converted to double);
+ *   augment: gt_shapes[i + n] = gt_shapes[i] with every x replaced by 1 - x, then the pairs (left[j], right[j]),
+ *     j = 0 .. sym_n - 1, swapped SEQUENTIALLY IN LIST ORDER -- a landmark named in two pairs is swapped twice;
+ *     shape_mask[i + n] = shape_mask[i];
+ *   mean_shape = gt_shapes[0] WHATEVER ITS MASK, + gt_shapes[i] for i = 1 .. size - 1 with shape_mask[i] > 0 in order,
+ *     valid_n = the number of those (sample 0 is summed but NOT counted: the reference's quirk, kept); then
+ *     mean_shape[j] = mean_shape[j] * (1. / (double)valid_n) + 0.  -- `Mat /= double` in the multiply-by-reciprocal form it
+ *     has everywhere in this library (a fourth OpenCV-decided detail, FROM MEMORY AND UNCHECKED).  valid_n == 0 follows from
+ *     the same IEEE expression (inf and NaN) and the call succeeds.
+ * Outputs: gt_shapes [size * 2L], shape_mask [size], mean_shape [2L].  -1: n_faces < 1 (CalcMeanShape reads sample 0),
+ * L < 1, NULL, augment outside {0, 1}, w <= 0 or h <= 0, a pair id outside [0, L). */
+JDA_API int jdaPositiveShapesCpp(const int *faces, const double *landmarks, int n_faces, int landmark_n, int augment,
+                                 const int *left, const int *right, int sym_n, double *gt_shapes, int *shape_mask,
+                                 double *mean_shape);
+
+/* Host only: DataSet::RandomShapes (data.cpp:237-253) on the counter-based generator of the mining block: sample i has
+ * key = first_key + i and draws x = g(2 key), y = g(2 key + 1); shapes[i][2j] = mean_shape[2j] + x,
+ * shapes[i][2j + 1] = mean_shape[2j + 1] + y.  shift_size == 0 gives mean_shape + 0. and draws nothing.  A set built in
+ * pieces (first_key = the number of samples before the piece) equals one built at once.  -1: NULL, n < 0, L < 1, a
+ * shift_size that is negative or not finite. */
+JDA_API int jdaRandomShapesCpp(const double *mean_shape, int landmark_n, int n, double shift_size, uint64_t seed,
+                               uint64_t first_key, double *shapes);
+
+/* Host only: both DataSet::CalcShapeResidual overloads (data.cpp:175-208) with the identity STParameter (the training
+ * entries refuse the similarity transform): over the index list idx[0 .. n) into sets of `size` samples,
+ *   landmark_id == -1:  residual[i][j] = gt_shapes[idx[i]][j] - cur_shapes[idx[i]][j], j < 2L       (n * 2L doubles)
+ *   landmark_id >= 0:   residual[i] = the (x, y) of that landmark only                             (n * 2 doubles:
+ *                       what jdaSamplesCpp.residual takes)
+ * and has_gt[i] = shape_mask[idx[i]] > 0 (DataSet::HasGtShape; jdaSamplesCpp.has_gt).  residual or has_gt may be NULL
+ * (shape_mask may be NULL when has_gt is).  -1: NULL where data is needed, an index outside [0, size), a landmark_id
+ * outside [-1, L). */
+JDA_API int jdaShapeResidualCpp(const double *gt_shapes, const double *cur_shapes, const int *shape_mask, int size,
+                                int landmark_n, const int *idx, int n, int landmark_id, double *residual,
+                                unsigned char *has_gt);
 
 #ifdef __cplusplus
 }

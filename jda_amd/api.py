@@ -110,6 +110,15 @@ class jdaGatherStatsCpp(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class jdaPositivesStatsCpp(C.Structure):
+    _fields_ = [("call_ms", C.c_double), ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double),
+                ("bytes", C.c_longlong), ("image_chunks", C.c_int), ("images_uploaded", C.c_int), ("chunks", C.c_int),
+                ("launches", C.c_int)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # numpy view of jdaFeatureCpp arrays (same layout: three ints, four bytes of padding, four doubles)
 FEATURE_DTYPE = np.dtype([("scale", np.int32), ("landmark_id1", np.int32), ("landmark_id2", np.int32), ("pad", np.int32),
                           ("offset1_x", np.float64), ("offset1_y", np.float64), ("offset2_x", np.float64),
@@ -275,6 +284,14 @@ def _load():
         lib.jdaGatherRowsCpp.argtypes = [C.POINTER(C.c_void_p), ip, C.c_int, C.c_size_t, ip, C.c_int, C.c_void_p]
         lib.jdaGatherSamplesCpp.argtypes = [C.c_void_p, C.POINTER(jdaGatherSegCpp), C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int,
                                             C.c_void_p, C.c_int, C.POINTER(jdaGatherStatsCpp)]
+    if hasattr(lib, "jdaBuildPositivesCpp"):
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        faces_tail = [ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(jdaPositivesStatsCpp)]
+        lib.jdaBuildPositivesCpp.argtypes = [C.c_void_p, C.POINTER(u8p), ip, ip, C.c_int] + faces_tail
+        lib.jdaBuildPositivesCppDevice.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), ip, ip, C.c_int] + faces_tail
+        lib.jdaPositiveShapesCpp.argtypes = [ip, dp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, dp, ip, dp]
+        lib.jdaRandomShapesCpp.argtypes = [dp, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint64, dp]
+        lib.jdaShapeResidualCpp.argtypes = [dp, dp, ip, C.c_int, C.c_int, ip, C.c_int, C.c_int, dp, u8p]
     return lib
 
 
@@ -433,6 +450,68 @@ def gather_rows_cpp(rows, index, keep=None):
                             out.ctypes.data if out.size else None) != 0:
         raise JdaError(last_error())
     return out
+
+
+# -- the positive sample set (include/jda.h, "Dialect CPP: the positive sample set"): host only, no cascador ----
+
+def positive_shapes_cpp(faces, landmarks, augment=False, left=(), right=()):
+    """Ground-truth shapes, masks and the mean shape of the positive set (reference data.cpp:589-598, 625-628, 641-661,
+    CalcMeanShape 210-223; jdaPositiveShapesCpp).  faces: [n, 5] rows of (image, x, y, w, h); landmarks: [n, 2L] in image
+    coordinates; left / right: the symmetric pairs.  -> dict(gt_shapes [size, 2L], shape_mask [size] int32, mean_shape [2L]),
+    size = 2 n with augment.  CalcMeanShape's quirk is kept: sample 0 is summed whatever its mask and not counted."""
+    fa = np.ascontiguousarray(np.asarray(faces, np.int32).reshape(-1, 5))
+    n = fa.shape[0]
+    lm = np.ascontiguousarray(landmarks, np.float64).reshape(n, -1) if n else np.zeros((0, 2), np.float64)
+    assert lm.shape[1] % 2 == 0 and lm.shape[1] > 0, "landmarks must be [n, 2L]"
+    L = lm.shape[1] // 2
+    kl, lp = _ivec(left)
+    kr, rp = _ivec(right)
+    sym_n = int(np.asarray(left).size)
+    assert sym_n == int(np.asarray(right).size), "left and right must pair up"
+    size = 2 * n if augment else n
+    gt = np.zeros((max(size, 1), 2 * L), np.float64)
+    mask = np.zeros(max(size, 1), np.int32)
+    mean = np.zeros(2 * L, np.float64)
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    if lib.jdaPositiveShapesCpp(fa.ctypes.data_as(ip) if n else None, lm.ctypes.data_as(dp) if n else None, n, L, 1 if augment else 0,
+                                lp if sym_n else None, rp if sym_n else None, sym_n, gt.ctypes.data_as(dp), mask.ctypes.data_as(ip),
+                                mean.ctypes.data_as(dp)) != 0:
+        raise JdaError(last_error())
+    return dict(gt_shapes=gt[:size], shape_mask=mask[:size], mean_shape=mean)
+
+
+def random_shapes_cpp(mean_shape, n, shift_size=0.0, seed=0, first_key=0):
+    """DataSet::RandomShapes (reference data.cpp:237-253; jdaRandomShapesCpp) on include/jda.h's counter-based generator:
+    [n, 2L] initial shapes, sample i drawing with key first_key + i (a set built in pieces equals one built at once)."""
+    ms, msp = _dvec(mean_shape)
+    assert ms.size % 2 == 0 and ms.size > 0
+    out = np.zeros((max(int(n), 1), ms.size), np.float64)
+    if lib.jdaRandomShapesCpp(msp, ms.size // 2, int(n), float(shift_size), int(seed) & 0xffffffffffffffff,
+                              int(first_key) & 0xffffffffffffffff, out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise JdaError(last_error())
+    return out[:max(int(n), 0)]
+
+
+def shape_residual_cpp(gt_shapes, cur_shapes, idx=None, landmark_id=None, shape_mask=None):
+    """DataSet::CalcShapeResidual (reference data.cpp:175-208, identity transform; jdaShapeResidualCpp): gt - current over
+    the index list (default: every sample) -- [n, 2L] for all landmarks, [n, 2] for one landmark_id (what a sample set's
+    "residual" takes).  With shape_mask also has_gt [n] uint8 (DataSet::HasGtShape): -> (residual, has_gt)."""
+    gt = np.ascontiguousarray(gt_shapes, np.float64)
+    cur = np.ascontiguousarray(cur_shapes, np.float64)
+    assert gt.ndim == 2 and gt.shape == cur.shape and gt.shape[1] % 2 == 0 and gt.shape[1] > 0
+    size, L = gt.shape[0], gt.shape[1] // 2
+    ix = np.ascontiguousarray(np.arange(size) if idx is None else idx, np.int32).reshape(-1)
+    lid = -1 if landmark_id is None else int(landmark_id)
+    out = np.zeros((max(ix.size, 1), 2 * L if landmark_id is None else 2), np.float64)
+    mk = None if shape_mask is None else np.ascontiguousarray(shape_mask, np.int32).reshape(-1)
+    assert mk is None or mk.size == size
+    hg = None if mk is None else np.zeros(max(ix.size, 1), np.uint8)
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    if lib.jdaShapeResidualCpp(gt.ctypes.data_as(dp), cur.ctypes.data_as(dp), None if mk is None else mk.ctypes.data_as(ip), size, L,
+                               ix.ctypes.data_as(ip) if ix.size else None, ix.size, lid, out.ctypes.data_as(dp),
+                               None if hg is None else _u8(hg)) != 0:
+        raise JdaError(last_error())
+    return out[:ix.size] if mk is None else (out[:ix.size], hg[:ix.size])
 
 
 def _byte_buffer(a, what):
@@ -1246,6 +1325,38 @@ class Cascador:
             raise JdaError(last_error())
         res = (out,) + ((olbf,) if want_lbf else ()) + ((st.asdict(),) if stats else ())
         return res[0] if len(res) == 1 else res
+
+    # -- the positive sample set (include/jda.h, "Dialect CPP: the positive sample set") ---------------------------
+    def build_positives_cpp(self, images, faces, dst=None, augment=False, origin_size=48, half_size=36, quarter_size=24,
+                            stats=False):
+        """The patches of the positive set (reference data.cpp:542-565, 623-640; jdaBuildPositivesCpp*): per face row
+        (image, x, y, w, h) the o, h and q patches, each a cv::resize of getFace(image, box) (black outside the image),
+        and with augment their horizontal mirrors as records n .. 2n - 1.  images: a list of host images, or (torch uint8
+        CUDA buffer, offsets, widths, heights).  dst: None (a new numpy array), a writable numpy uint8 array or a torch
+        uint8 device tensor of at least size * (o*o + h*h + q*q) bytes -- jdaSamplesCpp's "patches", as train_cart_cpp
+        takes them.  -> dst as [size, P] (a view of the caller's buffer), or (dst, stats dict)."""
+        pb = _patch_bytes(origin_size, half_size, quarter_size)
+        dev, base, offs, ws, hs, n_img, keep = _image_set(images)
+        fa = np.ascontiguousarray(np.asarray(faces, np.int32).reshape(-1, 5))
+        n = fa.shape[0]
+        size = 2 * n if augment else n
+        if dst is None:
+            dst = np.zeros((size, pb), np.uint8)
+        dptr, ddev, dbytes = _byte_buffer(dst, "dst")
+        assert dbytes >= size * pb, "dst is too small for the set's records"
+        assert ddev or dst.flags.writeable
+        st = jdaPositivesStatsCpp()
+        args = (fa.ctypes.data_as(C.POINTER(C.c_int)) if n else None, n, origin_size, half_size, quarter_size, 1 if augment else 0,
+                dptr, ddev, C.byref(st))
+        if dev:
+            rc = lib.jdaBuildPositivesCppDevice(self.h, base, offs, ws, hs, n_img, *args)
+        else:
+            rc = lib.jdaBuildPositivesCpp(self.h, base, ws, hs, n_img, *args)
+        del keep
+        if rc != 0:
+            raise JdaError(last_error())
+        out = dst.reshape(-1)[:size * pb].reshape(size, pb)
+        return (out, st.asdict()) if stats else out
 
     # -- from one cart to the next (include/jda.h, "Dialect CPP: from one cart to the next") -----------------------
     def gather_samples_cpp(self, segments, index, dst, keep=None, origin_size=48, half_size=36, quarter_size=24, stats=False):

@@ -487,6 +487,20 @@ struct GatherArgs {
 };
 hipError_t launch_gather(const GatherArgs& a, hipStream_t stream);
 
+// ---- dialect CPP: the positive sample set (k_faces.hip, faces.cpp; reference src/jda/data.cpp:542-565, 623-640) ----
+// One face of a launch: its image (d_base + off, W x H, rows back to back), its box (x, y, w, h) -- which may leave the
+// image: getFace pads with black -- and the destination record of its o / h / q patches.
+struct FaceItem { unsigned long long off; int W, H, x, y, w, h; long long rec; };
+// One launch: workgroup i builds items[i]; record r starts at dst + r * P, P = os*os + hs*hs + qs*qs (no alignment is
+// assumed).  mirror > 0: the horizontal mirror of every patch (cv::flip(patch, 1)) goes to record rec + mirror as well.
+// [dst, dst + dst_n * P) is what the launch may write (checked in the bounds build).
+struct FacesArgs {
+  const uint8_t* base; const FaceItem* items; int n;
+  uint8_t* dst; long long dst_n, mirror;
+  int os, hs, qs;
+};
+hipError_t launch_faces(const FacesArgs& a, hipStream_t stream);
+
 // Hardware-queue probe (k_misc.hip): a one-wave spin of `ticks` wall-clock ticks (100 MHz) that leaves its end time in
 // *out (mapped pinned host memory), and a kernel that leaves the time it ran.
 hipError_t launch_hwq_spin(long long ticks, unsigned long long* out, hipStream_t stream);
