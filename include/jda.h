@@ -203,6 +203,11 @@ typedef struct {
                                  persistent one tripped a watchdog or covered too few windows (results are correct; see stderr) */
   int ws_regrows;             /* passes of this call that were run a second time because a queue sized from earlier passes'
                                  survivor fractions was too small (option "ws_bound"; results are correct; see stderr) */
+  int post_passes;            /* passes of this call whose frames were post-processed on the device (option "device_post": scan
+                                 order, score order, NMS and relocation by k_post); 0 in dialect CPP and with device_post = 0 */
+  int post_declined;          /* passes of this call in which k_post was launched and declined (a frame with more than 1,024
+                                 detections, ties or NaN among more than 256 scores, more rows than reserved): the host form took
+                                 the pass, the results are the same */
 } jdaStats;
 
 typedef struct {

@@ -48,7 +48,7 @@ class jdaStats(C.Structure):
                 ("scan_launches", C.c_int), ("handoff_n", C.c_longlong), ("cart_total_n", C.c_longlong),
                 ("call_ms", C.c_double), ("dense_passes", C.c_int), ("scan_lds_ms", C.c_double),
                 ("scan_lds_cart_n", C.c_longlong), ("scan_fallbacks", C.c_int),
-                ("ws_regrows", C.c_int)]
+                ("ws_regrows", C.c_int), ("post_passes", C.c_int), ("post_declined", C.c_int)]
 
     def asdict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "stage_done_n"}

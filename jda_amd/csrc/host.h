@@ -670,6 +670,8 @@ struct RunStats {
   int dense_passes = 0;
   int ws_regrows = 0;          // passes run again because a queue sized from earlier passes was too small (Pass::recover_overflow)
   int scan_fallbacks = 0;      // passes run again with k_scan because k_scan_p's launch tripped a watchdog / came back short
+  int post_passes = 0;         // passes whose frames k_post delivered (Pass::Attempt::posted)
+  int post_declined = 0;       // passes in which k_post was launched and raised its flag: the host form took the pass
 };
 
 

@@ -650,6 +650,7 @@ template <typename Real> bool Pass<Real>::after_counters() {
   at.counted = true;
   if (at.post_issued) {
     at.posted = ((const int*)ln->h_pn.p)[2 * nf] == 0;
+    if (at.posted) rs->post_passes++; else rs->post_declined++;      // (jdaStats::post_passes / post_declined)
     if (at.posted) return true;                 // (nothing else to fetch: the frames' results are in pinned memory)
   }
   if (at.n_out > at.out_copied && !issue_results(at.out_copied, at.n_out)) return false;   // the prediction fell short (or there was none)

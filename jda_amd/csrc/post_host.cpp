@@ -142,6 +142,7 @@ void fill_stats(jdaStats* st, const RunStats& rs, long long patch_n, int T, int 
   st->dense_passes = rs.dense_passes;
   st->scan_fallbacks = rs.scan_fallbacks;
   st->ws_regrows = rs.ws_regrows;
+  st->post_passes = rs.post_passes; st->post_declined = rs.post_declined;
   st->scan_lds_ms = rs.scan_lds_ms; st->scan_lds_cart_n = rs.carts_scan - rs.carts_scan_glb;
 }
 
@@ -156,6 +157,7 @@ RunStats run_stats_of(const jdaStats& st) {
   rs.dense_passes = st.dense_passes;
   rs.scan_fallbacks = st.scan_fallbacks;
   rs.ws_regrows = st.ws_regrows;
+  rs.post_passes = st.post_passes; rs.post_declined = st.post_declined;
   rs.scan_lds_ms = st.scan_lds_ms; rs.carts_scan_glb = st.scan_cart_n - st.scan_lds_cart_n;
   return rs;
 }
@@ -164,6 +166,7 @@ RunStats& operator+=(RunStats& a, const RunStats& b) {
   a.carts += b.carts; a.out += b.out; a.carts_scan += b.carts_scan; a.carts_scan_glb += b.carts_scan_glb;
   a.win_scan += b.win_scan; a.tail += b.tail; a.gpu_ms += b.gpu_ms; a.scan_ms += b.scan_ms; a.scan_lds_ms += b.scan_lds_ms;
   a.scan_launches += b.scan_launches; a.dense_passes += b.dense_passes; a.scan_fallbacks += b.scan_fallbacks; a.ws_regrows += b.ws_regrows;
+  a.post_passes += b.post_passes; a.post_declined += b.post_declined;
   for (int t = 0; t < kMaxStages; t++) a.stage_done[t] += b.stage_done[t];
   return a;
 }

@@ -58,6 +58,26 @@ int main(void) {
     assert out.stdout.split() == ["38245", "11"]
 
 
+def test_stats_struct_matches_its_ctypes_mirror(built, tmp_path):
+    """jdaStats grows at its end only (callers compiled against an older header keep their offsets): the last fields in
+    the order they were added, and every field of jda_amd.api.jdaStats at the offset a C compiler gives it."""
+    from jda_amd import api
+    names = [k for k, _ in api.jdaStats._fields_]
+    assert names[-4:] == ["scan_fallbacks", "ws_regrows", "post_passes", "post_declined"]
+    src = tmp_path / "stats.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "jda.h"\nint main(void) {\n' +
+                   "".join('  printf("%s %%zu\\n", offsetof(jdaStats, %s));\n' % (k, k) for k in names) +
+                   '  printf("sizeof %zu\\n", sizeof(jdaStats));\n  return 0;\n}\n')
+    exe = tmp_path / "stats"
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    out = dict(l.split() for l in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+    for k in names:
+        assert int(out[k]) == getattr(api.jdaStats, k).offset, k
+    assert int(out["sizeof"]) == C.sizeof(api.jdaStats)
+    st = api.jdaStats()
+    assert st.post_passes == 0 and st.post_declined == 0 and {"post_passes", "post_declined"} <= set(st.asdict())
+
+
 def test_detect_without_gpu_fails_loudly(built, model_file):
     """No CPU fallback: on a box without a HIP device the detect entry must raise, not
     quietly compute elsewhere."""

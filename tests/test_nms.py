@@ -26,6 +26,35 @@ def test_nms_turns_reference_raw_into_reference_post(built, tmp_path, name):
     assert same(_relocate(g["raw_shapes"][keep], g["raw_bboxes"][keep]), g["post_shapes"])
 
 
+def _literal_keep(bb, sc, overlap=0.3):
+    """Literal restatement of the reference loops in Python: exchange sort under a strict `<` (c/jda.c:256-264), greedy
+    suppression in that order (c/jda.c:267-284).  Scores as Python floats: NaN compares false, -0.0 == +0.0, like C."""
+    n = len(sc)
+    s = [float(v) for v in sc]
+    box = [tuple(int(v) for v in b) for b in bb]
+    idx = list(range(n))
+    for i in range(n - 1):
+        for j in range(i + 1, n):
+            if s[idx[i]] < s[idx[j]]:
+                idx[i], idx[j] = idx[j], idx[i]
+    keep = np.ones(n, bool)
+    for i in range(n - 1):
+        a = idx[i]
+        if not keep[a]:
+            continue
+        for j in range(i + 1, n):
+            b = idx[j]
+            if not keep[b]:
+                continue
+            x1, y1 = max(box[a][0], box[b][0]), max(box[a][1], box[b][1])
+            x2 = min(box[a][0] + box[a][2], box[b][0] + box[b][2]); y2 = min(box[a][1] + box[a][2], box[b][1] + box[b][2])
+            w, h = max(0, x2 - x1), max(0, y2 - y1)
+            ov = np.float32(w * h) / np.float32(box[a][2] ** 2 + box[b][2] ** 2 - w * h)
+            if ov > np.float32(overlap):
+                keep[b] = False
+    return keep
+
+
 def test_ties_replay_the_exchange_sort(built):
     """Equal scores: the survivor set depends on the exchange sort's permutation (c/jda.c:256-264)."""
     from jda_amd import api
@@ -34,28 +63,35 @@ def test_ties_replay_the_exchange_sort(built):
         n = int(rng.integers(2, 60))
         bb = np.c_[rng.integers(0, 40, n), rng.integers(0, 40, n), rng.integers(20, 40, n)].astype(np.int32)
         sc = rng.integers(0, 4, n).astype(np.float32)          # many ties
-        # literal restatement of the reference loop in Python
-        idx = list(range(n))
-        for i in range(n - 1):
-            for j in range(i + 1, n):
-                if sc[idx[i]] < sc[idx[j]]:
-                    idx[i], idx[j] = idx[j], idx[i]
-        keep = np.ones(n, bool)
-        for i in range(n - 1):
-            a = idx[i]
-            if not keep[a]:
-                continue
-            for j in range(i + 1, n):
-                b = idx[j]
-                if not keep[b]:
-                    continue
-                x1, y1 = max(bb[a, 0], bb[b, 0]), max(bb[a, 1], bb[b, 1])
-                x2 = min(bb[a, 0] + bb[a, 2], bb[b, 0] + bb[b, 2]); y2 = min(bb[a, 1] + bb[a, 2], bb[b, 1] + bb[b, 2])
-                w, h = max(0, x2 - x1), max(0, y2 - y1)
-                ov = np.float32(w * h) / np.float32(bb[a, 2] ** 2 + bb[b, 2] ** 2 - w * h)
-                if ov > np.float32(0.3):
-                    keep[b] = False
-        assert np.array_equal(api.nms_c(bb, sc, 0.3), keep), trial
+        assert np.array_equal(api.nms_c(bb, sc, 0.3), _literal_keep(bb, sc)), trial
+
+
+@pytest.mark.parametrize("n", [256, 257, 1024])
+@pytest.mark.parametrize("alphabet", ["ties", "nan_and_zeros"])
+def test_literal_order_at_the_device_limits(built, n, alphabet):
+    """The host form at the sizes where k_post hands over to it or stops replaying the sort itself (256 and 257 tied
+    detections, 1,024 detections; tests/test_device_post.py compares the kernel with this form): scores from a small
+    alphabet -- tie groups of different sizes, and with NaN, +0.0 and -0.0 among them (NaN is never `<` anything, the
+    two zeros are equal: the permutation of the strict-`<` exchange sort decides who suppresses whom) -- on a window
+    grid like a scan's (step 3, size 30: neighbours overlap by more than 0.3)."""
+    from jda_amd import api
+    rng = np.random.default_rng(n)
+    nx = 16 if n <= 256 else (257 if n == 257 else 32)
+    ix = np.arange(n)
+    bb = np.c_[(ix % nx) * 3, (ix // nx) * 3, np.full(n, 30)].astype(np.int32)
+    if alphabet == "ties":
+        values = np.array([-1.0, -0.5, 0.25, 0.25, 0.5, 1.0, 2.0], np.float32)
+        pr = [0.3, 0.05, 0.2, 0.1, 0.2, 0.1, 0.05]
+    else:
+        values = np.array([np.nan, 0.0, -0.0, 0.5, 0.5, -1.0, 1.0], np.float32)
+        pr = [0.2, 0.15, 0.15, 0.15, 0.1, 0.15, 0.1]
+    sc = values[rng.choice(len(values), n, p=pr)]
+    if alphabet == "nan_and_zeros":
+        assert np.isnan(sc).any() and (sc.view(np.uint32) == 0x80000000).any() and (sc.view(np.uint32) == 0).any()
+    want = _literal_keep(bb, sc)
+    got = api.nms_c(bb, sc, 0.3)
+    assert np.array_equal(got, want)
+    assert 0 < want.sum() < n
 
 
 def test_nms_edge_cases(built):
