@@ -566,8 +566,8 @@ JDA_API long long jdaMineWindowList(int w, int h, int origin_size, int step, dou
  * cannot be built here; these entries are bit-exact against a sequential restatement written from the reference's source
  * (tests/train_ref.py), not against the reference.  Out of scope: BoostCart::Train's loop and its restart policy (one step
  * of that loop -- scores, order, cut, weights and the move of the surviving samples -- is the block "from one cart to the
- * next" at the end of this file), liblinear's fit of the global regression (what goes into it and what comes out of it:
- * the block "closing a stage" below), writing the cart into a model file, reading image files (file and JPEG reading and
+ * next" at the end of this file), the global regression that closes a stage (the blocks "closing a stage" and "a stage's
+ * global regression" below), writing the cart into a model file, reading image files (file and JPEG reading and
  * cvtColor stay the caller's; what LoadPositiveDataSet does with the decoded images is the block "the positive sample set" at
  * the end of this file).
  *
@@ -689,9 +689,8 @@ JDA_API int jdaTrainCartCpp(void *cascador, const jdaSamplesCpp *pos, const jdaS
  * set, with the stage's carts and weights as caller arrays -- the form jdaTrainCartCpp hands carts out in.  Nothing is
  * written into a model.  PARITY UNPINNED like every dialect-CPP entry: src/jda needs OpenCV and cannot be built here; these
  * entries are bit-exact against a sequential restatement written from the reference's source (tests/stage_ref.py), not
- * against the reference.  Out of scope: the fit itself (liblinear's L2R_L2LOSS_SVR_DUAL draws from rand(); INTEGRATION.md
- * says what it consumes and returns), BoostCart::Train's loop (one step of it: the last block of this file), writing into a
- * model file.
+ * against the reference.  The fit between the walk and the update is the next block, "a stage's global regression".  Out
+ * of scope: BoostCart::Train's loop (one step of it: the last block of this file), writing into a model file.
  *
  * Sizes.  nodes_n = 2^tree_depth and the landmark count L come from the cascador, as in the training block (it also
  * supplies the device, the LDS budget "lbf_lds_kb" and the "workspace_mb" limit of the per-call workspace: the samples are
@@ -758,6 +757,88 @@ JDA_API int jdaStageUpdateShapesCpp(void *cascador, const jdaSamplesCpp *samples
  * n == 0 gives 0. / 0. = NaN, like the reference.  -1: NULL arguments, n < 0, L < 1, an empty pupil list, an id outside [0, L). */
 JDA_API int jdaMeanErrorCpp(const double *gt_shapes, const double *cur_shapes, int n, int L, const int *left_pupils,
                             int n_left, const int *right_pupils, int n_right, double *out);
+
+/* ---- Dialect CPP: a stage's global regression ---------------------------------------------------------------------------
+ * BoostCart::GlobalRegression (reference src/jda/btcart.cpp:328-388): the leaf indicators jdaGenLbfCpp writes and the
+ * residuals jdaShapeResidualCpp writes go in, the weight matrix w that jdaStageUpdateShapesCpp consumes comes out -- 2L
+ * independent regressions, one per shape coordinate, each of them epochs of dual coordinate descent over every used sample.
+ * The reference hands each to liblinear (L2R_L2LOSS_SVR_DUAL, p = 0, bias = -1).  Its solver shuffles with rand() and the
+ * reference calls it from an OpenMP loop (btcart.cpp:367), so the draws of different landmarks interleave differently on
+ * every run: no run of the reference is reproducible against another, and nothing here could be bit-faithful to one.  THE
+ * FIT IS THEREFORE DEFINED HERE, to the bit, on the counter-based generator of the mining block above.
+ *
+ * Arguments.  lbf: n * K ints as jdaGenLbfCpp writes them (zero-based, k * leafNum + leaf).  residual: n * 2L doubles,
+ * row-major, as jdaShapeResidualCpp writes them.  rows: the reference's valid_pos_idx (btcart.cpp:273-281), n_rows indices
+ * into both arrays in the order the samples enter the problem; a row named twice is two samples; NULL: all n rows in order
+ * (n_rows is then not read).  L and leafNum = 2^(tree_depth - 1) come from the cascador, which also supplies the device,
+ * "workspace_mb", the options "fit_lds_kb" / "fit_ahead" and the error state; no model table is read, so
+ * jdaSetSimilarityTransform does not matter (as for jdaGatherSamplesCpp).  w: K * leafNum rows of 2L doubles, row-major --
+ * exactly what jdaStageUpdateShapesCpp takes.  out_iters (2L ints: epochs run per coordinate), out_gnorm1 ([2][2L]:
+ * Gnorm1_init, then the last Gnorm1_new), stats and params (NULL: every default, seed 0) may be NULL.
+ *
+ * The fit of coordinate j.  y[s] = residual[row(s)][j], x_s = the K ones at lbf[row(s)][.], lambda = 0.5 / C,
+ * H = (double)K + lambda (QD is K times 1.*1.); every operation an IEEE double operation, no contraction:
+ *     beta[s] = 0., w_j[:] = 0., index[s] = s                                  (s = 0 .. n_rows-1)
+ *     for iter = 0, 1, ... < max_iter:
+ *         jdaFitShuffleCpp(index, n_rows, seed, iter)       -- continues from the array the previous epoch left
+ *         Gnorm1 = 0.
+ *         for s = 0 .. n_rows-1:  i = index[s]
+ *             G = -y[i] + lambda*beta[i];   G = G + dot(i)
+ *             violation = beta[i] == 0 ? (G < 0 ? -G : G > 0 ? G : 0.) : fabs(G);   Gnorm1 += violation
+ *             d = G < H*beta[i] ? -G/H : G > H*beta[i] ? -G/H : -beta[i]
+ *             if fabs(d) < 1.0e-12: continue
+ *             old = beta[i]; beta[i] = old + d; d = beta[i] - old;  if d != 0: w_j[lbf[i][k]] += d  for every k
+ *         if iter == 0: Gnorm1_init = Gnorm1
+ *         if Gnorm1 <= eps*Gnorm1_init: stop (iters = iter + 1)
+ * dot(i): 64 partial sums p[c], c = 0 .. 63, each from 0. adding w_j[lbf[i][k]] for k = c, c + 64, .. ascending; then for
+ * h = 32, 16, 8, 4, 2, 1: p[c] += p[c + h] for c < h; dot = p[0].
+ * jdaFitShuffleCpp: for s = 0 .. n-1: t = s + r(iter, s) % (n - s), swap index[s] and index[t], with
+ *     r(iter, s) = splitmix64(splitmix64(seed + (iter + 1) * G) + (s + 1) * G)        (G, splitmix64: the mining block)
+ *
+ * (a) Origin.  The body is solve_l2r_l1l2_svr for L2R_L2LOSS_SVR_DUAL with p = 0 and bias = -1 AS REMEMBERED from liblinear
+ *     2.x: the library's source is not in the reference tree (its submodule is empty), so this is UNCHECKED, like cv::resize.
+ *     It is reached through train()'s regression branch, which calls the solver once on the problem as given;
+ *     get_decfun_coef(model, j + 1, 0) is w[j].
+ * (b) Shrinking.  liblinear's shrinking branch is unreachable at p = 0: it needs G + p > Gmax_old and G - p < -Gmax_old at
+ *     once with Gmax_old >= 0.  active_size therefore never changes and the branch is omitted.
+ * (c) Deliberate differences.  The shuffle's draws.  ONE index array shared by all 2L coordinates (in the reference every
+ *     problem draws its own from the raced rand()).  The shape of dot: liblinear adds the K terms one after the other; since
+ *     nothing can reproduce liblinear's result anyway that order protects no parity, and it would cost K dependent fp64 adds
+ *     per sample.
+ * (d) PARITY UNPINNED like every dialect-CPP entry: bit-exact against a sequential restatement of the text above
+ *     (tests/fit_ref.py), which is also checked against the closed-form primal solution; not against the reference.
+ *
+ * Refused with -1 and jdaGetLastError() before the device is touched: NULL where data is needed, K <= 0, negative n or
+ * n_rows, a rows entry outside [0, n), an lbf entry of a used row outside its cart's leaves
+ * (0 <= lbf - k*leafNum < leafNum), a non-finite residual in a used row, NULL w, n_rows above 2^30.  n_rows == 0: w zeroed,
+ * iters 0, returns 0 without touching the device.  A problem whose device arrays -- the used rows of lbf (n_rows * K ints),
+ * y and beta (2 * 2L * n_rows doubles), the weights (2L * K * leafNum doubles) and fit_ahead + 1 orders (n_rows ints each) --
+ * do not fit "workspace_mb" is refused with that reason: the fit is one serial pass per epoch, chunks would buy nothing.
+ * Out of scope: BoostCart::Train's loop and restarts, writing w into a model file, L1-loss or p != 0 solvers, a bias term,
+ * any attempt to match a particular liblinear run. */
+
+typedef struct {
+  double C;        /* <= 0: 1. / n_rows (btcart.cpp:363) */
+  double eps;      /* <= 0: 0.0001 (btcart.cpp:365)      */
+  int max_iter;    /* <= 0: 1000 (liblinear's)           */
+  uint64_t seed;
+} jdaFitParamsCpp;
+
+typedef struct {
+  double call_ms;            /* wall clock of the call                                                              */
+  double shuffle_ms;         /* ... the host's shuffles, summed over the epochs                                     */
+  double upload_ms;          /* ... lbf, residuals and the epochs' orders to the device                             */
+  double device_ms;          /* ... the k_fit launches, HIP events, summed                                          */
+  int epochs_launched;       /* launches queued (>= the largest iters: "fit_ahead" queues past a stop, as no-ops)   */
+  int lds_path;              /* 1: a coordinate's column of w in LDS; 0: in global memory ("fit_lds_kb")            */
+  int lds_bytes;             /* LDS of a workgroup                                                                  */
+} jdaFitStatsCpp;
+
+JDA_API int jdaGlobalRegressionCpp(void *cascador, const int *lbf, const double *residual, int n, int K,
+                                   const int *rows, int n_rows, const jdaFitParamsCpp *params,
+                                   double *w, int *out_iters, double *out_gnorm1, jdaFitStatsCpp *stats);
+/* Host only (no cascador, no GPU): one epoch's shuffle of index[0 .. n) as specified above.  -1: n < 0, iter < 0, NULL. */
+JDA_API int jdaFitShuffleCpp(int *index, int n, uint64_t seed, int iter);
 
 /* ---- Dialect CPP: from one cart to the next ---------------------------------------------------------------------------
  * What BoostCart::Train does between two carts (reference src/jda/btcart.cpp:146-253 with src/jda/data.cpp:255-448): the new

@@ -98,6 +98,18 @@ class jdaStageStatsCpp(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class jdaFitParamsCpp(C.Structure):
+    _fields_ = [("C", C.c_double), ("eps", C.c_double), ("max_iter", C.c_int), ("seed", C.c_uint64)]
+
+
+class jdaFitStatsCpp(C.Structure):
+    _fields_ = [("call_ms", C.c_double), ("shuffle_ms", C.c_double), ("upload_ms", C.c_double), ("device_ms", C.c_double),
+                ("epochs_launched", C.c_int), ("lds_path", C.c_int), ("lds_bytes", C.c_int)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class jdaGatherSegCpp(C.Structure):
     _fields_ = [("patches", C.c_void_p), ("on_device", C.c_int), ("n", C.c_int)]
 
@@ -274,6 +286,11 @@ def _load():
         lib.jdaStageUpdateShapesCpp.argtypes = [C.c_void_p, sp, C.c_int, C.c_int, C.c_int, cp, dp, ip, dp, ip,
                                                 C.POINTER(jdaStageStatsCpp)]
         lib.jdaMeanErrorCpp.argtypes = [dp, dp, C.c_int, C.c_int, ip, C.c_int, ip, C.c_int, dp]
+    if hasattr(lib, "jdaGlobalRegressionCpp"):
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        lib.jdaGlobalRegressionCpp.argtypes = [C.c_void_p, ip, dp, C.c_int, C.c_int, ip, C.c_int, C.POINTER(jdaFitParamsCpp), dp, ip, dp,
+                                               C.POINTER(jdaFitStatsCpp)]
+        lib.jdaFitShuffleCpp.argtypes = [ip, C.c_int, C.c_uint64, C.c_int]
     if hasattr(lib, "jdaGatherSamplesCpp"):
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
         lib.jdaBoostScoresCpp.argtypes = [dp, C.c_int, ip, C.c_int, ip, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp]
@@ -364,6 +381,17 @@ def mean_error_cpp(gt_shapes, cur_shapes, left_pupils, right_pupils):
                            C.byref(out)) != 0:
         raise JdaError(last_error())
     return out.value
+
+
+def fit_shuffle_cpp(index, seed, iter):
+    """One epoch's shuffle of the global regression's sample order (jdaFitShuffleCpp, host only): index (int32, any
+    length) -> a new array, the epoch-`iter` permutation step of include/jda.h applied to it.  Epochs chain: feed the
+    result of epoch iter - 1 in."""
+    a = np.array(index, np.int32).reshape(-1)
+    if lib.jdaFitShuffleCpp(a.ctypes.data_as(C.POINTER(C.c_int)) if a.size else None, int(a.size), int(seed) & 0xffffffffffffffff,
+                            int(iter)) != 0:
+        raise JdaError(last_error())
+    return a
 
 
 # -- from one cart to the next (include/jda.h, "Dialect CPP: from one cart to the next"): host only, no cascador ----
@@ -1325,6 +1353,32 @@ class Cascador:
             raise JdaError(last_error())
         res = (out,) + ((olbf,) if want_lbf else ()) + ((st.asdict(),) if stats else ())
         return res[0] if len(res) == 1 else res
+
+    # -- a stage's global regression (include/jda.h, "Dialect CPP: a stage's global regression") -------------------
+    def global_regression_cpp(self, lbf, residual, rows=None, C=0., eps=0., max_iter=0, seed=0):
+        """BoostCart::GlobalRegression (reference btcart.cpp:328-388) as include/jda.h defines the fit: lbf [n, K] int32 as
+        gen_lbf_cpp writes it, residual [n, 2L] as shape_residual_cpp writes it, rows the used samples in the order they
+        enter the problem (None: all n).  C, eps, max_iter <= 0: the reference's defaults (1 / n_rows, 1e-4, 1000).
+        -> (w [K * leafNum, 2L] as stage_update_shapes_cpp takes it, iters [2L] int32, gnorm1 [2, 2L], stats dict)."""
+        import ctypes                                                   # (the parameter C, named like the reference's, hides the module's alias)
+        la = np.ascontiguousarray(lbf, np.int32)
+        ra = np.ascontiguousarray(residual, np.float64)
+        assert la.ndim == 2 and ra.ndim == 2 and la.shape[0] == ra.shape[0] and ra.shape[1] == self.dim
+        n, K = la.shape
+        ia = None if rows is None else np.ascontiguousarray(rows, np.int32).reshape(-1)
+        n_rows = n if ia is None else int(ia.size)
+        par = jdaFitParamsCpp(float(C), float(eps), int(max_iter), int(seed) & 0xffffffffffffffff)
+        w = np.zeros((max(K, 0) * (1 << (self.D - 1)), self.dim), np.float64)
+        iters = np.zeros(self.dim, np.int32)
+        gn = np.zeros((2, self.dim), np.float64)
+        st = jdaFitStatsCpp()
+        ip, dp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
+        rc = lib.jdaGlobalRegressionCpp(self.h, la.ctypes.data_as(ip) if la.size else None, ra.ctypes.data_as(dp) if ra.size else None,
+                                        n, K, None if ia is None else (ia if ia.size else np.zeros(1, np.int32)).ctypes.data_as(ip), n_rows, ctypes.byref(par),
+                                        w.ctypes.data_as(dp), iters.ctypes.data_as(ip), gn.ctypes.data_as(dp), ctypes.byref(st))
+        if rc != 0:
+            raise JdaError(last_error())
+        return w, iters, gn, st.asdict()
 
     # -- the positive sample set (include/jda.h, "Dialect CPP: the positive sample set") ---------------------------
     def build_positives_cpp(self, images, faces, dst=None, augment=False, origin_size=48, half_size=36, quarter_size=24,

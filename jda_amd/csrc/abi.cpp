@@ -538,7 +538,7 @@ namespace jda {
 void jda_bc_read_k_scan(unsigned long long*); void jda_bc_read_k_scan_d(unsigned long long*); void jda_bc_read_k_scan_r(unsigned long long*);
 void jda_bc_read_k_scan_dr(unsigned long long*); void jda_bc_read_k_scan_p(unsigned long long*); void jda_bc_read_k_finish(unsigned long long*);
 void jda_bc_read_k_wide(unsigned long long*); void jda_bc_read_k_stage(unsigned long long*); void jda_bc_read_k_mine(unsigned long long*); void jda_bc_read_k_train(unsigned long long*); void jda_bc_read_k_lbf(unsigned long long*);
-void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*);
+void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*); void jda_bc_read_k_fit(unsigned long long*);
 }
 // bounds-check build only (libjda_bounds.so): per translation unit {first violation: site << 32 | source line, violations}
 // since the last call -- out[16]; returns the total number of violations (kernels_common.h: Bc)
@@ -548,9 +548,9 @@ __attribute__((visibility("default"))) long long jdaDebugBoundsReport(unsigned l
                                         jda_bc_read_k_scan_p, jda_bc_read_k_finish, jda_bc_read_k_wide, jda_bc_read_k_stage};
   long long total = 0;
   for (int i = 0; i < 8; i++) { unsigned long long v[2] = {0, 0}; rd[i](v); if (out) { out[2 * i] = v[0]; out[2 * i + 1] = v[1]; } total += (long long)v[1]; }
-  // k_mine's, k_train's, k_lbf's, k_gather's and k_faces' words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file or in cpp_patch.h
-  const struct { void (*rd)(unsigned long long*); const char* tu; } more[5] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
-                                                                                {jda_bc_read_k_gather, "k_gather"}, {jda_bc_read_k_faces, "k_faces"}};
+  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces' and k_fit's words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file or in cpp_patch.h
+  const struct { void (*rd)(unsigned long long*); const char* tu; } more[6] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
+                                                                                {jda_bc_read_k_gather, "k_gather"}, {jda_bc_read_k_faces, "k_faces"}, {jda_bc_read_k_fit, "k_fit"}};
   for (const auto& t : more) {
     unsigned long long v[2] = {0, 0};
     t.rd(v);
@@ -639,6 +639,17 @@ int jdaDetectBatchCppRaggedDeviceRows(void* cascador, const unsigned char* d_bas
 } JDA_ABI_CATCH_SYNC(-1)
 
 void jdaRowsDRelease(double* rows) { std::free(rows); }
+
+int jdaGlobalRegressionCpp(void* cascador, const int* lbf, const double* residual, int n, int K, const int* rows, int n_rows,
+                           const jdaFitParamsCpp* params, double* w, int* out_iters, double* out_gnorm1, jdaFitStatsCpp* stats) try {
+  g_err.clear();
+  return fit_entry(cascador, lbf, residual, n, K, rows, n_rows, params, w, out_iters, out_gnorm1, stats);
+} JDA_ABI_CATCH_SYNC(-1)
+
+int jdaFitShuffleCpp(int* index, int n, uint64_t seed, int iter) try {
+  g_err.clear();
+  return fit_shuffle(index, n, seed, iter);
+} JDA_ABI_CATCH(-1)
 
 int jdaResultsDPack(const jdaResultD* results, int n, int frame_offset, double* rows, int capacity_rows) try {
   return results && n >= 0 ? (int)pack<DialectCpp>(results, n, frame_offset, rows, capacity_rows) : -1;

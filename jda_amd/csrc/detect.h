@@ -35,6 +35,11 @@ inline bool check_patch_sizes(int os, int hs, int qs) {
 bool check_set(const jdaSamplesCpp* s, const char* name, bool need_weights);
 bool check_pool(const jdaFeatureCpp* pool, size_t count, int L);
 
+// fit.cpp: a stage's global regression (jdaGlobalRegressionCpp) and its host-only shuffle (jdaFitShuffleCpp)
+int fit_entry(void* cascador, const int* lbf, const double* residual, int n, int K, const int* rows, int n_rows,
+              const jdaFitParamsCpp* params, double* w, int* out_iters, double* out_gnorm1, jdaFitStatsCpp* stats);
+int fit_shuffle(int* index, int n, uint64_t seed, int iter);
+
 // detect_cpp.cpp: dialect CPP, method 1 (cascador.cpp:310-376,431-477) on a uniform batch; frames on the device
 // (d_frames) or, with host_frames set, in host memory
 struct CppCall { int minimum_size, step; double factor, overlap; int nms; };

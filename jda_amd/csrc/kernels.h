@@ -501,6 +501,28 @@ struct FacesArgs {
 };
 hipError_t launch_faces(const FacesArgs& a, hipStream_t stream);
 
+// ---- dialect CPP: a stage's global regression (k_fit.hip, fit.cpp; reference src/jda/btcart.cpp:328-388) ----
+// What a coordinate's fit carries from one epoch (launch) to the next; `done` set: the coordinate's wave returns at once.
+struct FitState { double gnorm_init, gnorm_last; int iters, done; };
+constexpr int kFitPrefetch = 4;          // samples whose rows of lbf are in registers ahead of the one being stepped
+constexpr int kFitMaxRounds = 16;        // rounds of 64 carts (K <= 1024) whose gathered weights stay in registers for the scatter;
+                                         // beyond, the scatter reads the weights again
+// One epoch of every coordinate that has not stopped (device pointers).  lbf [n_rows][K] and y [dim][n_rows] are only
+// read; index [n_rows] is this epoch's order; beta [dim][n_rows], w [dim][f] (the weights TRANSPOSED) and state [dim] are
+// read and written, launch after launch.
+struct FitArgs {
+  const int* lbf; const double* y; const int* index;
+  double* beta; double* w; FitState* state;
+  int n_rows, K, f, dim;
+  double lambda, H, eps;
+};
+struct FitLaunch { int lds, lds_bytes; };   // how it ran: the coordinate's column of w in LDS (1) or in global memory (0)
+// plan_fit, once per call: where one column (f doubles) fits lds_budget -- the LDS bytes a workgroup may take -- the launches
+// keep it in LDS (and the instantiation is told its dynamic LDS size), otherwise the same body works on the column in global
+// memory.  launch_fit: one epoch as planned.
+hipError_t plan_fit(const FitArgs& a, int lds_budget, FitLaunch* how);
+hipError_t launch_fit(const FitArgs& a, const FitLaunch& how, hipStream_t stream);
+
 // Hardware-queue probe (k_misc.hip): a one-wave spin of `ticks` wall-clock ticks (100 MHz) that leaves its end time in
 // *out (mapped pinned host memory), and a kernel that leaves the time it ran.
 hipError_t launch_hwq_spin(long long ticks, unsigned long long* out, hipStream_t stream);
