@@ -154,6 +154,9 @@ JDA_API int jdaSetDevice(void *cascador, int device);
  *                   the streams the host program created before; the library probes which of its streams share a queue and
  *                   hands them out by queue.  0: wherever the runtime puts them (1).  Read-only, what the pool found:
  *                   "hwq_queues", "hwq_streams", "hwq_probes", "hwq_max_mains" (most lanes whose main streams share a queue)
+ *   read-only, what the cascador holds on the device: "mem_device_bytes" (its model tables and its lanes' buffers, all
+ *                   grow-only; NOT the total: the scan plans' buffers are not in it) and "mem_plan_buffers" (the NUMBER of
+ *                   plan buffers in use and pooled, not their bytes); per-call workspaces live only during their call
  * (the other keys of DESIGN.md section 8 are accepted as well; they are experiment switches).
  * Returns 0, or -1 for an unknown key / a running call or pending batch.  jdaGetOption returns the value (-1: unknown key). */
 JDA_API int jdaSetOption(void *cascador, const char *key, long long value);
@@ -1047,6 +1050,80 @@ JDA_API int jdaRandomShapesCpp(const double *mean_shape, int landmark_n, int n, 
 JDA_API int jdaShapeResidualCpp(const double *gt_shapes, const double *cur_shapes, const int *shape_mask, int size,
                                 int landmark_n, const int *idx, int n, int landmark_id, double *residual,
                                 unsigned char *has_gt);
+
+/* ---- Dialect CPP: the model in training ----------------------------------------------------------------------------------
+ * The model the pieces above train, held by the cascador and grown IN PLACE: JoinCascador's status (current_stage_idx,
+ * current_cart_idx: reference src/jda/cascador.cpp:17-29, header ints 5 and 6 of the trainer's file), the carts
+ * BoostCart::Train appends one by one or trains again (btcart.cpp:146-253), the weights that close a stage
+ * (btcart.cpp:255-292) and JoinCascador::SerializeTo's f64 file (cascador.cpp:79-124).  The loop stays the caller's: mine
+ * (jdaMineNegativesCpp*: Validate under the model AS IT STANDS), train (jdaTrainCartCpp), boost (jdaBoostScoresCpp ..),
+ * PUT; per stage: indicators (jdaGenLbfCpp), fit (jdaGlobalRegressionCpp), CLOSE, serialize.  PARITY UNPINNED like every
+ * dialect-CPP entry: the writer is checked against the layout restated in Python (jda_amd/synth.py), not against a file the
+ * reference wrote.
+ *
+ * THE INVARIANT.  After any sequence of these calls the cascador behaves in every entry of this header -- detect in both
+ * dialects, validate, mining, the training and stage entries, jdaCascadorInfo (multi_scale), work counters included --
+ * exactly as a cascador created from the file jdaCascadorSerializeToCpp would write at that moment.  At status (s, K - 1),
+ * where that entry refuses, the comparison file is the same content with header (s, K - 1), which the loader accepts.
+ *
+ * A training cascador starts as the reference's constructors leave a model: status (0, -1); in every cart every split node
+ * Feature() (scale 0, both landmark ids 0, offsets 0.: common.hpp:76-81) with threshold 0, every leaf score 0., mean 0., std 1.
+ * (cart.cpp:23-37); every w 0. (btcart.cpp:104-116).  Cart::th is left UNINITIALISED by the reference and is 0. here.
+ *
+ * Node order of jdaModelPutCartCpp: with nodes_n = 2^tree_depth, features[i - 1] / thresholds[i - 1] are node i = 1 ..
+ * nodes_n/2 - 1 of Cart::features (the root is 1, the children of i are 2i and 2i + 1) and leaf_scores[j] is Cart::scores[j],
+ * j = 0 .. nodes_n/2 - 1: jdaTrainCartCpp's out_features / out_thresholds / out_scores as they are, and the order
+ * Cart::SerializeTo writes them in (cart.cpp:429-450), followed by th, mean, std.
+ *
+ * The four mutating entries also work on a cascador loaded from a trainer (f64) snapshot -- that is resuming -- and refuse one
+ * read from an f32 file.  Like jdaSetOption they refuse while a call runs or a submitted batch is pending on the cascador;
+ * starting a call on another thread while one of them runs is the caller's error.  Every refusal returns -1 with
+ * jdaGetLastError() and leaves model and status untouched. */
+
+/* A cascador on JoinCascador::JoinCascador()'s model, status (stage 0, cart -1); mean_shape: 2 * landmark_n doubles.  The
+ * dimension limits are the loader's (T in [1, 16], K in [1, 2^20], landmark_n in [1, 4096], tree_depth in [2, 12]).  NULL with
+ * jdaGetLastError() otherwise.  Released with jdaCascadorRelease. */
+JDA_API void *jdaCascadorCreateTrainingCpp(int T, int K, int landmark_n, int tree_depth, const double *mean_shape);
+
+/* The status: (s, c) with s < T = carts [0, c] of stage s are written and stages [0, s) closed; (T, -1) = complete (a float file
+ * reports the (T + 1, -1) it carries).  Either pointer may be NULL. */
+JDA_API int jdaModelStatusCpp(void *cascador, int *stage, int *cart);
+
+/* Writes cart k of the stage in training.  k == cart + 1 (< K) appends and moves the status to (stage, k); k == cart >= 0
+ * replaces the last cart (the restart path, btcart.cpp:204-206) and leaves the status as it is.  Refused: any other k, a
+ * complete model, a scale outside 0..2, a landmark id outside [0, landmark_n), a std that is 0 or not finite, NULL arrays. */
+JDA_API int jdaModelPutCartCpp(void *cascador, int k, const jdaFeatureCpp *features, const int *thresholds,
+                               const double *leaf_scores, double th, double mean, double std);
+
+/* Closes the stage in training, which must hold all its carts (cart == K - 1): stores its K * leafNum rows of 2 * landmark_n
+ * weights (row-major: jdaGlobalRegressionCpp's w) and moves the status to (stage + 1, -1); after stage T - 1 the model is
+ * complete, (T, -1). */
+JDA_API int jdaModelCloseStageCpp(void *cascador, const double *w);
+
+/* JoinCascador::Validate (cascador.cpp:166-211) on every record of a RESIDENT sample set, under the model as it stands: what a
+ * trainer resuming from a model snapshot without a data snapshot, a trainer admitting extra patches, and the check "the
+ * model written is the model trained" need (the scores and shapes carried from cart to cart by jdaBoostScoresCpp /
+ * jdaStageUpdateShapesCpp must equal what this returns).  The o, h and q patches are taken AS STORED (jdaSamplesCpp's layout,
+ * host or device memory as in jdaGenLbfCpp); nothing is resized.  A trainer snapshot runs Validate's own loop bounds: stages
+ * [0, s) in full, then carts [0, c] of stage s without its regression.  The initial shape of sample i is samples->shapes[i]:
+ * a caller who wants Validate's own start passes mean_shape + 0., a trainer the jdaRandomShapesCpp shapes its positives
+ * started from; weights, residual and has_gt are ignored.  Outputs are host arrays of n entries (shape: n * 2L doubles), any
+ * may be NULL; shape is written for rejected samples too (the shape as it stood), as jdaValidateCpp does; carts_n is
+ * Validate's n.  The samples go through the device in chunks within "workspace_mb".  Option "reval_form": 0 (default) a wave
+ * per sample (k_reval: lane = cart, the score chain replayed in cart order, the first failing cart by ballot), 1 the
+ * lane-per-sample walk of jdaValidateCpp over the same records; both return identical bits.  "reval_lds_kb": the LDS a
+ * workgroup of form 0 may take (a sample's patches, shape and indicators; 0: global memory).  stats (may be NULL): as for
+ * jdaStageUpdateShapesCpp.  Refused with -1: jdaSetSimilarityTransform(1) (as the training entries), a patch size outside
+ * [1, 128], NULL samples / patches / shapes with n > 0, a negative n.  n == 0 returns 0 without touching the device.
+ * PARITY UNPINNED like every dialect-CPP entry: bit-exact against a sequential restatement (tests/model_ref.py). */
+JDA_API int jdaValidateSamplesCpp(void *cascador, const jdaSamplesCpp *samples, int origin_size, int half_size,
+                                  int quarter_size, unsigned char *is_face, double *score, int *carts_n, double *shape,
+                                  jdaStageStatsCpp *stats);
+
+/* JoinCascador::SerializeTo's f64 file with the status in its header.  Refused at (s, K - 1): the reference's writer would
+ * turn that into (s + 1, -1), a regression that was never fit, and the reference never writes there (btcart.cpp:243).
+ * jdaCascadorSerializeTo (the f32 file) is unchanged. */
+JDA_API int jdaCascadorSerializeToCpp(void *cascador, const char *path);
 
 #ifdef __cplusplus
 }

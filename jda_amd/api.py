@@ -309,6 +309,18 @@ def _load():
         lib.jdaPositiveShapesCpp.argtypes = [ip, dp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, dp, ip, dp]
         lib.jdaRandomShapesCpp.argtypes = [dp, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint64, dp]
         lib.jdaShapeResidualCpp.argtypes = [dp, dp, ip, C.c_int, C.c_int, ip, C.c_int, C.c_int, dp, u8p]
+    if hasattr(lib, "jdaModelPutCartCpp"):
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        lib.jdaCascadorCreateTrainingCpp.restype = C.c_void_p
+        lib.jdaCascadorCreateTrainingCpp.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, dp]
+        lib.jdaModelStatusCpp.argtypes = [C.c_void_p, ip, ip]
+        lib.jdaModelPutCartCpp.argtypes = [C.c_void_p, C.c_int, C.POINTER(jdaFeatureCpp), ip, dp, C.c_double, C.c_double, C.c_double]
+        lib.jdaModelCloseStageCpp.argtypes = [C.c_void_p, dp]
+        lib.jdaCascadorSerializeToCpp.argtypes = [C.c_void_p, C.c_char_p]
+    if hasattr(lib, "jdaValidateSamplesCpp"):
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        lib.jdaValidateSamplesCpp.argtypes = [C.c_void_p, C.POINTER(jdaSamplesCpp), C.c_int, C.c_int, C.c_int, u8p, dp, ip, dp,
+                                              C.POINTER(jdaStageStatsCpp)]
     return lib
 
 
@@ -765,13 +777,84 @@ class Cascador:
             self.h = lib.jdaCascadorCreate(p)
         if not self.h:
             raise JdaError("cannot load model %s: %s" % (model_path, last_error()))
+        self._read_info()
+        if device is not None and lib.jdaSetDevice(self.h, int(device)) != 0:
+            raise JdaError(last_error())
+
+    def _read_info(self):
         info = jdaModelInfo()
         lib.jdaCascadorInfo(self.h, C.byref(info))
         self.T, self.K, self.L, self.D = info.T, info.K, info.landmark_n, info.tree_depth
         self.multi_scale = bool(info.multi_scale)
         self.source_real_bytes = info.source_real_bytes
         self.dim = 2 * self.L
+
+    # -- the model in training (include/jda.h, "Dialect CPP: the model in training") ---------------------------------
+    @classmethod
+    def create_training_cpp(cls, T, K, L, D, mean_shape, device=None):
+        """jdaCascadorCreateTrainingCpp: a cascador on JoinCascador::JoinCascador()'s model, status (0, -1), that
+        put_cart_cpp / close_stage_cpp grow in place."""
+        ms = np.ascontiguousarray(mean_shape, np.float64).reshape(-1)
+        assert ms.size == 2 * int(L), "mean_shape must hold 2L doubles"
+        self = cls.__new__(cls)
+        self.h = lib.jdaCascadorCreateTrainingCpp(int(T), int(K), int(L), int(D), ms.ctypes.data_as(C.POINTER(C.c_double)))
+        if not self.h:
+            raise JdaError("cannot create a training cascador: %s" % last_error())
+        self._read_info()
         if device is not None and lib.jdaSetDevice(self.h, int(device)) != 0:
+            raise JdaError(last_error())
+        return self
+
+    def model_status_cpp(self):
+        """(stage, cart): carts [0, cart] of `stage` are written, stages [0, stage) closed; (T, -1) is the complete model."""
+        s, c = C.c_int(), C.c_int()
+        if lib.jdaModelStatusCpp(self.h, C.byref(s), C.byref(c)) != 0:
+            raise JdaError(last_error())
+        return s.value, c.value
+
+    def put_cart_cpp(self, k, features, thresholds, leaf_scores, th, mean=0., std=1.):
+        """jdaModelPutCartCpp: cart k of the stage in training from train_cart_cpp's features, thresholds and scores as they
+        are; k == cart + 1 appends, k == cart replaces the last cart."""
+        inner, half = (1 << (self.D - 1)) - 1, 1 << (self.D - 1)
+        fa, fp = _features(features)
+        ta = np.ascontiguousarray(thresholds, np.int32).reshape(-1)
+        la = np.ascontiguousarray(leaf_scores, np.float64).reshape(-1)
+        assert len(fa) == inner and ta.size == inner and la.size == half, "one cart: nodes_n/2 - 1 split nodes, nodes_n/2 leaves"
+        if lib.jdaModelPutCartCpp(self.h, int(k), fp, ta.ctypes.data_as(C.POINTER(C.c_int)), la.ctypes.data_as(C.POINTER(C.c_double)),
+                                  float(th), float(mean), float(std)) != 0:
+            raise JdaError(last_error())
+        self._read_info()
+
+    def close_stage_cpp(self, w):
+        """jdaModelCloseStageCpp: the stage's [K * leafNum, 2L] weights (global_regression_cpp's w); status -> (stage + 1, -1)."""
+        wa = np.ascontiguousarray(w, np.float64).reshape(-1)
+        assert wa.size == self.K * (1 << (self.D - 1)) * self.dim, "w must hold K * leafNum rows of 2L doubles"
+        if lib.jdaModelCloseStageCpp(self.h, wa.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+            raise JdaError(last_error())
+
+    def validate_samples_cpp(self, samples, origin_size=48, half_size=36, quarter_size=24):
+        """jdaValidateSamplesCpp: Validate (reference cascador.cpp:166-211) under the model as it stands on every record of a
+        resident sample set -- dict(patches=[n, o*o + h*h + q*q] uint8 numpy array or torch CUDA tensor, shapes=[n, 2L] the
+        start shapes) -> dict of is_face, score, carts_n, shape, stats."""
+        pb = _patch_bytes(origin_size, half_size, quarter_size)
+        s, keep = _samples(samples, self.dim, pb)
+        n = s.n
+        face = np.zeros(max(n, 1), np.uint8)
+        score = np.zeros(max(n, 1), np.float64)
+        carts = np.zeros(max(n, 1), np.int32)
+        shape = np.zeros((max(n, 1), self.dim), np.float64)
+        st = jdaStageStatsCpp()
+        rc = lib.jdaValidateSamplesCpp(self.h, C.byref(s), origin_size, half_size, quarter_size, _u8(face),
+                                       score.ctypes.data_as(C.POINTER(C.c_double)), carts.ctypes.data_as(C.POINTER(C.c_int)),
+                                       shape.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st))
+        del keep
+        if rc != 0:
+            raise JdaError(last_error())
+        return dict(is_face=face[:n], score=score[:n], carts_n=carts[:n], shape=shape[:n], stats=st.asdict())
+
+    def serialize_to_cpp(self, path):
+        """jdaCascadorSerializeToCpp: the trainer's f64 file with the status in its header (refused at (s, K - 1))."""
+        if lib.jdaCascadorSerializeToCpp(self.h, os.fsencode(path)) != 0:
             raise JdaError(last_error())
 
     def close(self):

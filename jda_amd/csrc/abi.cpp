@@ -59,6 +59,43 @@ void jdaCascadorSerializeTo(void* cascador, const char* model) try {
   (void)save_model_f32(((Cascador*)cascador)->hm, model);
 } JDA_ABI_CATCH_VOID
 
+void* jdaCascadorCreateTrainingCpp(int T, int K, int landmark_n, int tree_depth, const double* mean_shape) {
+  try {
+    g_err.clear();
+    return grow_create(T, K, landmark_n, tree_depth, mean_shape);
+  } catch (...) {      // the tables of a big model did not fit: NULL like jdaCascadorCreate
+    abi_exception("jdaCascadorCreateTrainingCpp", false);
+    return nullptr;
+  }
+}
+
+int jdaModelStatusCpp(void* cascador, int* stage, int* cart) try {
+  g_err.clear();
+  return grow_status((Cascador*)cascador, stage, cart);
+} JDA_ABI_CATCH(-1)
+
+int jdaModelPutCartCpp(void* cascador, int k, const jdaFeatureCpp* features, const int* thresholds, const double* leaf_scores,
+                       double th, double mean, double std) try {
+  g_err.clear();
+  return grow_put_cart((Cascador*)cascador, k, features, thresholds, leaf_scores, th, mean, std);
+} JDA_ABI_CATCH(-1)
+
+int jdaModelCloseStageCpp(void* cascador, const double* w) try {
+  g_err.clear();
+  return grow_close_stage((Cascador*)cascador, w);
+} JDA_ABI_CATCH(-1)
+
+int jdaValidateSamplesCpp(void* cascador, const jdaSamplesCpp* samples, int origin_size, int half_size, int quarter_size,
+                          unsigned char* is_face, double* score, int* carts_n, double* shape, jdaStageStatsCpp* stats) try {
+  g_err.clear();
+  return reval_entry((Cascador*)cascador, samples, origin_size, half_size, quarter_size, is_face, score, carts_n, shape, stats);
+} JDA_ABI_CATCH_SYNC(-1)
+
+int jdaCascadorSerializeToCpp(void* cascador, const char* path) try {
+  g_err.clear();
+  return grow_serialize((Cascador*)cascador, path);
+} JDA_ABI_CATCH(-1)
+
 void jdaCascadorRelease(void* cascador) try {
   Cascador* c = (Cascador*)cascador;
   if (!c) return;
@@ -148,6 +185,18 @@ long long jdaGetOption(void* cascador, const char* key) try {
     if (std::strcmp(key, "hwq_streams") == 0) return c->streams.created;
     if (std::strcmp(key, "hwq_probes") == 0) return c->streams.probes;
     if (std::strcmp(key, "hwq_max_mains") == 0) { int m = 0; for (int x : c->streams.mains) m = std::max(m, x); return m; }
+  }
+  if (c && key && std::strncmp(key, "mem_", 4) == 0) {
+    // read-only: what the cascador holds on the device -- bytes of its model tables (both dialects' and the mining tables) and
+    // of its lanes' buffers, all grow-only, and the plan buffers in the plan map and the pool together (a test of "nothing
+    // leaks" compares them across rounds)
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (std::strcmp(key, "mem_device_bytes") == 0) {
+      size_t b = c->mf.buf.bytes + c->md.buf.bytes + c->mine_buf.bytes;
+      for (auto& l : c->lanes) b += l->ws.bytes + l->frames.bytes + l->pyr.bytes + l->rag_frames.bytes + l->rag_raw.bytes + l->rag_tab.bytes;
+      return (long long)b;
+    }
+    if (std::strcmp(key, "mem_plan_buffers") == 0) return (long long)(c->plans.size() + c->plan_pool.size());
   }
   if (!c || !key || !c->kn.get(key, &v)) { fail("jdaGetOption: unknown option"); return -1; }
   return v;
@@ -538,7 +587,7 @@ namespace jda {
 void jda_bc_read_k_scan(unsigned long long*); void jda_bc_read_k_scan_d(unsigned long long*); void jda_bc_read_k_scan_r(unsigned long long*);
 void jda_bc_read_k_scan_dr(unsigned long long*); void jda_bc_read_k_scan_p(unsigned long long*); void jda_bc_read_k_finish(unsigned long long*);
 void jda_bc_read_k_wide(unsigned long long*); void jda_bc_read_k_stage(unsigned long long*); void jda_bc_read_k_mine(unsigned long long*); void jda_bc_read_k_train(unsigned long long*); void jda_bc_read_k_lbf(unsigned long long*);
-void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*); void jda_bc_read_k_fit(unsigned long long*);
+void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*); void jda_bc_read_k_fit(unsigned long long*); void jda_bc_read_k_reval(unsigned long long*);
 }
 // bounds-check build only (libjda_bounds.so): per translation unit {first violation: site << 32 | source line, violations}
 // since the last call -- out[16]; returns the total number of violations (kernels_common.h: Bc)
@@ -548,9 +597,9 @@ __attribute__((visibility("default"))) long long jdaDebugBoundsReport(unsigned l
                                         jda_bc_read_k_scan_p, jda_bc_read_k_finish, jda_bc_read_k_wide, jda_bc_read_k_stage};
   long long total = 0;
   for (int i = 0; i < 8; i++) { unsigned long long v[2] = {0, 0}; rd[i](v); if (out) { out[2 * i] = v[0]; out[2 * i + 1] = v[1]; } total += (long long)v[1]; }
-  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces' and k_fit's words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file or in cpp_patch.h
-  const struct { void (*rd)(unsigned long long*); const char* tu; } more[6] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
-                                                                                {jda_bc_read_k_gather, "k_gather"}, {jda_bc_read_k_faces, "k_faces"}, {jda_bc_read_k_fit, "k_fit"}};
+  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces', k_fit's and k_reval's words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file or in cpp_patch.h
+  const struct { void (*rd)(unsigned long long*); const char* tu; } more[7] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
+                                                                                {jda_bc_read_k_gather, "k_gather"}, {jda_bc_read_k_faces, "k_faces"}, {jda_bc_read_k_fit, "k_fit"}, {jda_bc_read_k_reval, "k_reval"}};
   for (const auto& t : more) {
     unsigned long long v[2] = {0, 0};
     t.rd(v);

@@ -40,6 +40,20 @@ int fit_entry(void* cascador, const int* lbf, const double* residual, int n, int
               const jdaFitParamsCpp* params, double* w, int* out_iters, double* out_gnorm1, jdaFitStatsCpp* stats);
 int fit_shuffle(int* index, int n, uint64_t seed, int iter);
 
+// model_grow.cpp: the model in training (jdaCascadorCreateTrainingCpp, jdaModel*Cpp, jdaCascadorSerializeToCpp)
+Cascador* grow_create(int T, int K, int L, int D, const double* mean_shape);
+int grow_status(Cascador* c, int* stage, int* cart);
+int grow_put_cart(Cascador* c, int k, const jdaFeatureCpp* features, const int* thresholds, const double* leaf_scores, double th,
+                  double mean, double stddev);
+int grow_close_stage(Cascador* c, const double* w);
+int grow_serialize(Cascador* c, const char* path);
+
+// mine.cpp: Validate's own tables on the device
+bool mine_model(Cascador* c, MineModel* out);
+// reval.cpp: Validate on a resident sample set (jdaValidateSamplesCpp)
+int reval_entry(Cascador* c, const jdaSamplesCpp* samples, int os, int hs, int qs, unsigned char* is_face, double* score, int* carts_n,
+                double* shape, jdaStageStatsCpp* stats);
+
 // detect_cpp.cpp: dialect CPP, method 1 (cascador.cpp:310-376,431-477) on a uniform batch; frames on the device
 // (d_frames) or, with host_frames set, in host memory
 struct CppCall { int minimum_size, step; double factor, overlap; int nms; };

@@ -6,7 +6,8 @@
 //   detect.cpp     dialect-C batch entry
 //   post_host.cpp  sort, NMS, relocation, jdaResult, statistics     tickets.cpp  submit / wait
 //   ragged.cpp     images of different sizes as one job             abi.cpp      the extern "C" entry points of include/jda.h
-//   fit.cpp        a stage's global regression (dialect CPP)
+//   fit.cpp        a stage's global regression (dialect CPP)       model_grow.cpp  the model in training: put a cart, close a stage, the f64 file
+//   reval.cpp      Validate on a resident sample set (dialect CPP)
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -133,6 +134,8 @@ inline long long env_ll(const char* name, long long dflt) {
   X(mine_chunk_windows, "JDA_MINE_CHUNK_WINDOWS", 4194304) /* windows per chunk of a mining call at most (mine.cpp) */ \
   X(lbf_lds_kb, "JDA_LBF_LDS_KB", 160)      /* LDS in KB a workgroup of k_lbf (closing a stage, stage.cpp) may take; where one sample's slice does not fit it, the kernel reads from global memory (0: always) */ \
   X(fit_lds_kb, "JDA_FIT_LDS_KB", 160)      /* LDS in KB a workgroup of k_fit (a stage's global regression, fit.cpp) may take, counted in granules; where one coordinate's column of w does not fit it, the kernel works on the column in global memory (0: always) */ \
+  X(reval_form, "JDA_REVAL_FORM", 0)        /* jdaValidateSamplesCpp (reval.cpp): 0 a wave per sample (k_reval), 1 a lane per sample (k_mine_walk on the same records): identical bits, for A/B and as a check */ \
+  X(reval_lds_kb, "JDA_REVAL_LDS_KB", 160)  /* LDS in KB a workgroup of k_reval may take; where one sample's slice (patches, shape, a stage's indicators) does not fit it, the kernel works in global memory (0: always) */ \
   X(fit_ahead, "JDA_FIT_AHEAD", 2)          /* ... epochs queued ahead of the one whose state words the host inspects (fit_ahead + 1 rotating order buffers; results do not depend on it) */ \
   X(ragged_chunk_min_windows, "JDA_RAGGED_CHUNK_MIN_WINDOWS", 1500000) /* ... and at least, where a small job is cut into ragged_split chunks */ \
   X(ragged_split, "JDA_RAGGED_SPLIT", 3)    /* chunks a job smaller than that many full chunks is cut into */ \
@@ -216,7 +219,7 @@ struct Knobs {
     static const char* const non_negative[] = {"workspace_mb", "handoff", "plan_cache", "lanes", "ragged_chunk_windows", "ragged_chunk_windows_cpp", "mine_chunk_windows",
                                                "ragged_chunk_min_windows", "h2d_min_bytes", "merge_blocks", "wide_max", "lanes_min_windows", "ragged_single_windows",
                                                "scan_p_handoff", "scan_p_slots", "max_lanes", "lane_idle_calls", "scan_p_tile_kb", "scan_p_grid",
-                                               "ws_min_entries", "ws_factor_pct", "lbf_lds_kb", "fit_lds_kb", "fit_ahead"};
+                                               "ws_min_entries", "ws_factor_pct", "lbf_lds_kb", "fit_lds_kb", "fit_ahead", "reval_lds_kb", "reval_form"};
     for (const char* k : non_negative) if (std::strcmp(key, k) == 0 && v < 0) return false;
     if (std::strcmp(key, "workspace_mb") == 0 && v < 1) return false;
 #define X(name, env, dflt) if (std::strcmp(key, #name) == 0) { name = v; return true; }

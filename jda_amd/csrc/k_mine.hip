@@ -193,7 +193,8 @@ __global__ __launch_bounds__(64) void k_mine_walk(MineModel m, MineSizes z, cons
                                                   const uint8_t* __restrict__ patches, int pbytes, int similarity,
                                                   uint8_t* __restrict__ face, int* __restrict__ carts_n,
                                                   double* __restrict__ score_out, double* __restrict__ shape_out,
-                                                  int* __restrict__ lbf_ws, double* __restrict__ t1_ws, double* __restrict__ t2_ws) {
+                                                  int* __restrict__ lbf_ws, double* __restrict__ t1_ws, double* __restrict__ t2_ws,
+                                                  const double* __restrict__ init) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int dim = m.dim, K = m.K;
@@ -202,9 +203,13 @@ __global__ __launch_bounds__(64) void k_mine_walk(MineModel m, MineSizes z, cons
   int* lbf = lbf_ws + (size_t)i * K;
   double* t1 = t1_ws + (size_t)i * dim;
   double* t2 = t2_ws + (size_t)i * dim;
-  double dx, dy;
-  mine_shift(z, items[i].key, &dx, &dy);
-  for (int j = 0; j < dim; j++) sh[j] = m.mean[j] + ((j & 1) ? dy : dx);      // RandomShape, data.cpp:231-234
+  if (init) {                                           // a resident sample's own start shape (jdaValidateSamplesCpp, form 1)
+    for (int j = 0; j < dim; j++) sh[j] = init[(size_t)i * dim + j];
+  } else {
+    double dx, dy;
+    mine_shift(z, items[i].key, &dx, &dy);
+    for (int j = 0; j < dim; j++) sh[j] = m.mean[j] + ((j & 1) ? dy : dx);    // RandomShape, data.cpp:231-234
+  }
   Stp<double> stp; stp.scale = 1.; stp.r00 = 1.; stp.r01 = 0.; stp.r10 = 0.; stp.r11 = 1.;
   bool apply = false;
   double score = 0.;
@@ -266,10 +271,10 @@ __global__ __launch_bounds__(64) void k_mine_walk(MineModel m, MineSizes z, cons
 
 hipError_t launch_mine_walk(const MineModel& m, const MineSizes& z, const MineItem* items, int n, const uint8_t* patches,
                             int pbytes, int similarity, uint8_t* face, int* carts_n, double* score, double* shape, int* lbf,
-                            double* t1, double* t2, hipStream_t stream) {
+                            double* t1, double* t2, hipStream_t stream, const double* init) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_mine_walk, dim3((n + 63) / 64), dim3(64), 0, stream, m, z, items, n, patches, pbytes, similarity, face,
-                     carts_n, score, shape, lbf, t1, t2);
+                     carts_n, score, shape, lbf, t1, t2, init);
   return hipGetLastError();
 }
 

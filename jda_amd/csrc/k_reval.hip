@@ -1,0 +1,184 @@
+// HIP kernel of dialect CPP's Validate on a resident sample set for gfx950 (reference src/jda/cascador.cpp:166-211;
+// jdaValidateSamplesCpp, reval.cpp): every record's stored o / h / q patches through the model as it stands, from the
+// record's own start shape.
+//   k_reval  wave = sample, the form DESIGN section 11 names and k_lbf.hip uses for one stage.  The sample's patch bytes,
+//            its 2L shape doubles and a stage's K leaf indicators live in the wave's own slice of LDS (LDS = true: k_lbf's
+//            layout), or in global memory where a slice does not fit (LDS = false: the same arithmetic on the same values;
+//            the shape lives in the output array, the indicators in a scratch row).  Per stage:
+//            walk     lane = cart, 64 carts at a time: Cart::Forward (cart.cpp:392-404) on the split node of cpp_patch.h
+//                     with the identity STParameter; the lane keeps its cart's leaf score, mean, std and threshold
+//            replay   the score chain of those 64 carts IN CART ORDER, the non-associative chain of Validate:
+//                     score += leaf; score = (score - mean) / std -- one fp64 add, one subtract and one IEEE division per
+//                     cart, the operands handed from the cart's lane to the whole wave by v_readlane; lane l keeps the
+//                     score as it stood after cart l
+//            reject   `score < th` per lane, one ballot: the first set bit is the first failing cart -- it fixes carts_n,
+//                     the score where the walk stopped and the shape as it stood.  A NaN score fails no comparison.
+//            regress  a sample that passed the stage: lane = shape coordinate, delta from 0. + w[lbf[k]][j] for k = 0 .. K-1
+//                     in cart order (btcart.cpp:407-424, the order and form of k_lbf's phase 2), then shape += delta
+//            The partial stage of a snapshot runs its `part` carts and no regression (cascador.cpp:198-209).
+// Whole waves only: no workgroup barrier, no atomics, no spinning, nothing between waves.  The model's tables are the
+// mining tables, patched in place between launches (model_grow.cpp): every read of them has a lane-dependent address --
+// lane = cart in the walk, lane = coordinate in the regression -- so they are vector loads; nothing of them is read
+// through the scalar cache.
+#include <limits>
+
+#include "cpp_patch.h"
+
+namespace jda {
+
+namespace {
+
+__device__ __forceinline__ int reval_align16(int v) { return (v + 15) & ~15; }
+
+// This wave's writes to global memory before its later reads of them by OTHER lanes of the same wave (LDS = false).
+__device__ __forceinline__ void reval_global_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+
+// n bytes global -> LDS by one wave (k_lbf.hip's): dst keeps the source's offset inside a dword, so the body is aligned
+// on both sides; the head and the tail (at most three bytes each) go bytewise.
+__device__ __forceinline__ uint8_t* reval_stage_bytes(uint8_t* lds, const uint8_t* __restrict__ src, int n, int lane) {
+  const int sh = (int)((uintptr_t)src & 3);
+  uint8_t* dst = lds + sh;
+  const int head = min(n, (4 - sh) & 3);
+  const int body = (n - head) >> 2, tail = n - head - 4 * body;
+  if (lane < head) dst[lane] = src[lane];
+  const uint32_t* s4 = (const uint32_t*)(src + head);
+  uint32_t* d4 = (uint32_t*)(dst + head);
+  for (int d = lane; d < body; d += 64) d4[d] = s4[d];
+  if (lane < tail) dst[head + 4 * body + lane] = src[head + 4 * body + lane];
+  return dst;
+}
+
+// lane l's double for the whole wave (l wave-uniform): two v_readlane_b32
+__device__ __forceinline__ double reval_readlane(double v, int l) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+  return __hiloint2double(hi, lo);
+}
+
+}  // namespace
+
+template <bool LDS>
+__global__ __launch_bounds__(64 * kRevalWaves) void k_reval(RevalArgs a, int wave_bytes) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char reval_lds[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * (blockDim.x >> 6) + wave;
+  if (i >= a.n) return;                                  // (whole waves; no workgroup barrier below)
+  JDA_BC(Bc(0, a.n), i, 1, kBcQueue);
+  const MineModel& m = a.m;
+  const int K = m.K, dim = m.dim, leaf_n = m.leaf_n, node_n = m.node_n;
+  const int pbytes = a.os * a.os + a.hs * a.hs + a.qs * a.qs;
+  const uint8_t* pat_g = a.patches + (size_t)i * pbytes;
+  const double* start = a.start + (size_t)i * dim;
+  double* sh_g = a.shape + (size_t)i * dim;
+  int* lbf_g = a.lbf + (size_t)i * K;
+  // the wave's slice: shape [dim] doubles, lbf [K] ints, patches (pbytes + 3) bytes
+  double* sh_l = (double*)(reval_lds + (size_t)wave * wave_bytes);
+  int* lbf_l = (int*)((unsigned char*)sh_l + reval_align16(dim * 8));
+  double* sh = sh_g;
+  int* lbf = lbf_g;
+  const uint8_t* pat_p = pat_g;
+  if (LDS) {
+    sh = sh_l; lbf = lbf_l;
+    pat_p = reval_stage_bytes((uint8_t*)lbf_l + reval_align16(K * 4), pat_g, pbytes, lane);
+  }
+  for (int j = lane; j < dim; j += 64) sh[j] = start[j];
+  if (LDS) wave_lds_sync(); else reval_global_sync();
+  const PatchSet pat{pat_p, a.os, a.hs, a.qs};
+
+  double score = 0.;                                     // wave-uniform: every lane runs the same chain
+  int nn = 0;
+  bool is_face = true;
+  const int stages = m.full + (m.part > 0 ? 1 : 0);
+  [[maybe_unused]] const long long nodes_all = (long long)m.T * K * node_n, leaves_all = (long long)m.T * K * leaf_n;
+  for (int t = 0; t < stages && is_face; t++) {
+    const bool partial = t == m.full;                    // the stage in training: `part` carts, no regression
+    const int Kt = partial ? m.part : K;
+    for (int k0 = 0; k0 < Kt && is_face; k0 += 64) {
+      const int k = k0 + lane;
+      const bool active = k < Kt;
+      double lf = 0., mu = 0., sd = 1., th = -std::numeric_limits<double>::infinity();
+      if (active) {
+        const size_t ck = (size_t)t * K + k;
+        int node = 0;
+        for (int d = 0; d < m.D - 1; d++) {
+          JDA_BC(Bc(0, nodes_all), (long long)(ck * node_n + node), 1, kBcNodeTable);
+          const NodeD nd = m.nodes[ck * node_n + node];
+          JDA_BC(Bc(0, dim), nd.lm1x2, 2, kBcLandmark); JDA_BC(Bc(0, dim), nd.lm2x2, 2, kBcLandmark);
+          const int v = pat.feature(nd, sh[nd.lm1x2], sh[nd.lm1x2 + 1], sh[nd.lm2x2], sh[nd.lm2x2 + 1]);
+          node = (v <= nd.th) ? 2 * node + 1 : 2 * node + 2;   // cart.cpp:398-401, zero-based
+        }
+        const int leaf = node - node_n;
+        JDA_BC(Bc(0, leaves_all), (long long)(ck * leaf_n + leaf), 1, kBcNodeTable);
+        lbf[k] = k * leaf_n + leaf;                      // cascador.cpp:192
+        lf = m.leaf[ck * leaf_n + leaf]; mu = m.cmean[ck]; sd = m.cstd[ck]; th = m.cth[ck];
+      }
+      const int cnt = min(64, Kt - k0);
+      double mine = 0.;
+      for (int l = 0; l < cnt; l++) {                    // cascador.cpp:185-186, in cart order
+        score = score + reval_readlane(lf, l);
+        score = (score - reval_readlane(mu, l)) / reval_readlane(sd, l);
+        if (lane == l) mine = score;
+      }
+      const unsigned long long failed = __ballot(active && mine < th);      // cascador.cpp:188
+      if (failed) {
+        const int first = __ffsll((long long)failed) - 1;
+        score = reval_readlane(mine, first);
+        nn += first + 1;
+        is_face = false;
+      } else {
+        nn += cnt;
+      }
+    }
+    if (!is_face || partial) break;
+    if (LDS) wave_lds_sync(); else reval_global_sync();  // the stage's indicators, written by their carts' lanes
+    // ---- GenDeltaShape (btcart.cpp:407-424) and shape += delta (cascador.cpp:196): lane = coordinate, rows in cart order
+    [[maybe_unused]] const long long rows = (long long)K * leaf_n;
+    const double* wt = m.w + (size_t)t * K * leaf_n * dim;
+    for (int j = lane; j < dim; j += 64) {
+      double delta = 0.;
+      for (int k0 = 0; k0 < K; k0 += 8) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+          const int r = lbf[min(k0 + u, K - 1)];
+          JDA_BC(Bc(0, rows), r, 1, kBcWRow);
+          v[u] = wt[(size_t)r * dim + j];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++)
+          if (k0 + u < K) delta += v[u];
+      }
+      sh[j] = sh[j] + delta;                             // (coordinate j is read and written by this lane alone)
+    }
+    if (LDS) wave_lds_sync(); else reval_global_sync();  // the next stage's walk reads every coordinate
+  }
+  if (LDS) for (int j = lane; j < dim; j += 64) sh_g[j] = sh_l[j];
+  if (lane == 0) { a.face[i] = is_face ? 1 : 0; a.carts_n[i] = nn; a.score[i] = score; }
+}
+
+hipError_t launch_reval(const RevalArgs& a, int lds_budget, LbfLaunch* how, hipStream_t stream) {
+  if (how) *how = LbfLaunch{0, kRevalWaves, 0};
+  if (a.n <= 0) return hipSuccess;
+  if (a.m.K < 1 || a.m.D < 1 || a.m.D > 20 || a.m.dim < 2) return hipErrorInvalidValue;
+  const long long pbytes = (long long)a.os * a.os + (long long)a.hs * a.hs + (long long)a.qs * a.qs;
+  const long long wave_bytes = (((long long)a.m.dim * 8 + 15) & ~15ll) + (((long long)a.m.K * 4 + 15) & ~15ll) + ((pbytes + 3 + 15) & ~15ll);
+  const long long budget = std::min<long long>(std::max(0, lds_budget), 160 * 1024);
+  const int waves = (int)std::min<long long>(kRevalWaves, budget / wave_bytes);
+  if (waves >= 1) {
+    const int total = (int)(waves * wave_bytes);
+    if (total > 48 * 1024)
+      (void)hipFuncSetAttribute((const void*)k_reval<true>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
+    hipLaunchKernelGGL(k_reval<true>, dim3((unsigned)((a.n + waves - 1) / waves)), dim3(64 * waves), total, stream, a, (int)wave_bytes);
+    if (how) *how = LbfLaunch{1, waves, total};
+  } else {
+    hipLaunchKernelGGL(k_reval<false>, dim3((unsigned)((a.n + kRevalWaves - 1) / kRevalWaves)), dim3(64 * kRevalWaves), 0, stream, a, 0);
+  }
+  return hipGetLastError();
+}
+
+JDA_BC_READER(k_reval)
+
+}  // namespace jda

@@ -421,9 +421,10 @@ hipError_t launch_mine_patches(const MineSizes& z, const uint8_t* base, const Mi
                                uint8_t* patches, int pbytes, hipStream_t stream);
 // Validate on the patches of n crops, a lane per crop: face[i], n[i], score[i], shape[i*dim ..] (also the walk's state);
 // lbf / t1 / t2: per-crop scratch of K ints and 2 x dim doubles.
+// init != nullptr: crop i starts from init[i*dim ..] instead of mean + its key's shift, and items is not read (reval.cpp).
 hipError_t launch_mine_walk(const MineModel& m, const MineSizes& z, const MineItem* items, int n, const uint8_t* patches,
                             int pbytes, int similarity, uint8_t* face, int* carts_n, double* score, double* shape, int* lbf,
-                            double* t1, double* t2, hipStream_t stream);
+                            double* t1, double* t2, hipStream_t stream, const double* init = nullptr);
 // Sum of status[0, n) over the rejected entries (status > 0): out[0] += count, out[1] += sum.
 hipError_t launch_mine_sum(const int* status, unsigned long long n, unsigned long long* out, hipStream_t stream);
 
@@ -470,6 +471,20 @@ struct LbfLaunch { int lds, waves, lds_bytes; };   // how it ran: staged in LDS 
 // lds_budget: the LDS bytes a workgroup may take (at most the CU's 160 KB); where one sample's slice does not fit, the
 // kernel reads everything from global memory.
 hipError_t launch_lbf(const LbfArgs& a, int lds_budget, LbfLaunch* how, hipStream_t stream);
+
+// ---- dialect CPP: Validate on a resident sample set (k_reval.hip, reval.cpp; reference src/jda/cascador.cpp:166-211) ----
+constexpr int kRevalWaves = 4;           // samples (waves) of a workgroup at most
+// One chunk of a resident sample set (device pointers): record i's patches at patches + i * (os*os + hs*hs + qs*qs), its start
+// shape at start + i*dim; outputs face [n], carts_n [n], score [n], shape [n][dim] (also the walk's state where it runs
+// from global memory) and the scratch lbf [n][K] (the same).  m: the mining tables (mine.cpp), Validate's loop bounds in them.
+struct RevalArgs {
+  MineModel m;
+  const uint8_t* patches; const double* start;
+  uint8_t* face; int* carts_n; double* score; double* shape; int* lbf;
+  int n, os, hs, qs;
+};
+// lds_budget as launch_lbf's; how: staged in LDS (1) or from global memory (0), waves and LDS bytes per workgroup.
+hipError_t launch_reval(const RevalArgs& a, int lds_budget, LbfLaunch* how, hipStream_t stream);
 
 // ---- dialect CPP: a sample set from one cart to the next (k_gather.hip, boost.cpp; reference src/jda/data.cpp:319-410) ----
 constexpr int kGatherSegs = 8;           // source segments of one launch at most

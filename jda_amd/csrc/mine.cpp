@@ -34,6 +34,9 @@ bool mine_levels(int W, int H, int os, int step, double factor, std::vector<Mine
 constexpr int kTf[8] = {0, kMineSwap | kMineFlipY, kMineFlipX | kMineFlipY, kMineSwap | kMineFlipX, kMineFlipX,
                         kMineSwap | kMineFlipX | kMineFlipY, kMineFlipY, kMineSwap};   // data.cpp:930-963, see k_mine.hip
 
+}  // namespace
+
+// The mining tables of the model as it stands (built on first use, patched in place by model_grow.cpp); also reval.cpp's.
 bool mine_model(Cascador* c, MineModel* out) {
   if (!cpp_model_complete(c)) return false;
   std::lock_guard<std::mutex> lk(c->mu);
@@ -76,6 +79,8 @@ bool mine_model(Cascador* c, MineModel* out) {
   *out = c->mine_m;
   return true;
 }
+
+namespace {
 
 bool check_sizes(int os, int hs, int qs, int mode, double shift) {
   if (!check_patch_sizes(os, hs, qs)) return false;

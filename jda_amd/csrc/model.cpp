@@ -44,11 +44,11 @@ struct Cursor {
   }
 };
 
-bool sane_dims(int T, int K, int L, int D) {
+}  // namespace
+
+bool model_dims_ok(int T, int K, int L, int D) {
   return T >= 1 && T <= 16 && K >= 1 && K <= (1 << 20) && L >= 1 && L <= 4096 && D >= 2 && D <= 12;
 }
-
-}  // namespace
 
 bool load_model(const char* path, int real_bytes, HostModel* out, std::string* err) {
   FILE* f = path ? std::fopen(path, "rb") : nullptr;
@@ -67,7 +67,7 @@ bool load_model(const char* path, int real_bytes, HostModel* out, std::string* e
   HostModel m;
   m.T = c.i32(); m.K = c.i32(); m.L = c.i32(); m.D = c.i32();
   m.hdr_stage = c.i32(); m.hdr_cart = c.i32();
-  if (!sane_dims(m.T, m.K, m.L, m.D)) {
+  if (!model_dims_ok(m.T, m.K, m.L, m.D)) {
     if (err) *err = "model header holds implausible dimensions (T,K,landmark_n,tree_depth)";
     return false;
   }
@@ -154,6 +154,36 @@ bool save_model_f32(const HostModel& m, const char* path) {
   const bool ok = std::fwrite(buf.data(), 1, buf.size(), f) == buf.size();
   std::fclose(f);
   return ok;
+}
+
+bool save_model_f64(const HostModel& m, const char* path) {
+  FILE* f = path ? std::fopen(path, "wb") : nullptr;
+  if (!f) return false;
+  std::vector<unsigned char> buf;
+  buf.reserve((size_t)model_stream_bytes(m.T, m.K, m.L, m.D, 8));
+  auto put_i = [&](int32_t v) { unsigned char b[4]; std::memcpy(b, &v, 4); buf.insert(buf.end(), b, b + 4); };
+  auto put_d = [&](const double* v, size_t n) { const unsigned char* b = (const unsigned char*)v; buf.insert(buf.end(), b, b + 8 * n); };
+  const int node_n = m.node_n(), leaf_n = m.leaf_n(), dim = m.dim();
+  put_i(0); put_i(m.T); put_i(m.K); put_i(m.L); put_i(m.D);
+  put_i(m.hdr_stage); put_i(m.hdr_cart);
+  put_d(m.mean_shape.data(), dim);
+  for (int t = 0; t < m.T; t++) {
+    for (int k = 0; k < m.K; k++) {
+      const long long ci = (long long)t * m.K + k;
+      for (int i = 0; i < node_n; i++) {
+        const SplitNode& n = m.nodes[ci * node_n + i];
+        put_i(n.scale); put_i(n.lm1); put_i(n.lm2);
+        put_d(n.off, 4);
+        put_i(n.th);
+      }
+      put_d(&m.leaf_score[ci * leaf_n], leaf_n);
+      put_d(&m.cart_th[ci], 1); put_d(&m.cart_mean[ci], 1); put_d(&m.cart_std[ci], 1);
+    }
+    put_d(&m.w[(size_t)t * m.K * leaf_n * dim], (size_t)m.K * leaf_n * dim);
+  }
+  put_i(0);
+  const bool ok = std::fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+  return std::fclose(f) == 0 && ok;
 }
 
 }  // namespace jda

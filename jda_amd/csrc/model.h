@@ -54,4 +54,11 @@ bool load_model(const char* path, int real_bytes, HostModel* out, std::string* e
 // Float layout with the header convention of reference c/jda.c:652-665.
 bool save_model_f32(const HostModel& m, const char* path);
 
+// The trainer's f64 layout (JoinCascador::SerializeTo, cascador.cpp:79-124) with the model's own status in header ints 5
+// and 6, written from the layout above.  The caller decides which statuses may be written (model_grow.cpp).
+bool save_model_f64(const HostModel& m, const char* path);
+
+// The dimension limits load_model enforces on a header.
+bool model_dims_ok(int T, int K, int L, int D);
+
 }  // namespace jda
