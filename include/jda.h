@@ -317,6 +317,41 @@ JDA_API int jdaTraceBatch(void *cascador, const unsigned char *const *frames, in
                           int width, int height, float scale, int min_size, int max_size,
                           int *carts_n, float *score, unsigned int *path_hash, float *shapes);
 
+/* The cascade on windows the CALLER names (a tracker re-checking last frame's boxes, a proposal stage in front of the
+ * cascade, a float model scored on annotated boxes): the body of the reference's window loop, c/jda.c:340-414, for each
+ * of n_windows windows, 4 ints per window: (frame, x, y, size).  There is no grid, no minimum size of 24, no NMS.
+ *   views      o at (x, y); h at ((int)(x*r), (int)(y*r)), r = 1.f / sqrtf(2.f), the product in float; q at (x/2, y/2); all
+ *              three patch sides are `size` (c/jda.c:340-354).  Half and quarter images are jdaBuildPyramid's pair of
+ *              the frame, built only for a model with a scale != 0 split node; a read that leaves them is clamped into the
+ *              image, like every dialect-C entry's (the documented divergence from the reference's out-of-bounds read).
+ *   walk       from the stored mean shape, score = (score + leaf - mean) / std in cart order in fp32, reject at the first
+ *              score < cart threshold, the K-row regression after each completed stage (c/jda.c:361-412).
+ * Outputs are HOST arrays of n_windows entries in the caller's order, any may be NULL; carts_n, score, path_hash and
+ * shapes are defined as jdaTraceBatch defines them (shapes also for rejected windows):
+ *   is_face    no cart rejected the window (carts_n == T*K and the last cart passed it) && !(score < th)   (c/jda.c:414)
+ *   landmarks  2L floats, shapes[2j] * size + x and shapes[2j+1] * size + y in fp32, a multiply and then an add
+ *              (c/jda.c:471-472), for every window
+ *   stats      patch_n, face_patch_n, nonface_patch_n, cart_gothrough_n (non-faces only), average_cart_n, call_ms -- as
+ *              jdaValidateCpp fills them -- and gpu_ms, the kernels' device time; everything else 0
+ * A cascador created from a double file or from a trainer snapshot behaves as in jdaTraceBatch.  Returns 0; or -1 with
+ * jdaGetLastError() naming the offending window (its index and four values), nothing launched and no output touched, for:
+ * a needed pointer that is NULL; n < 0 or n_windows < 0; frame outside [0, n); size < 1, x < 0, y < 0, x + size > width or
+ * y + size > height; a frame size the other dialect-C entries refuse.  n_windows == 0 returns 0 and touches nothing;
+ * duplicate windows and frames no window names are fine.  Re-entrant on one cascador like the other entries.  Windows
+ * up to the side jdaGetOption("windows_tile_limit") reports walk from a copy of their pixels in LDS, larger ones (and
+ * every window with option "windows_tile" = 0) read the frame: identical bits.  The list goes through the device in
+ * chunks that fit option "workspace_mb". */
+JDA_API int jdaValidateWindows(void *cascador, const unsigned char *const *frames, int n, int width, int height,
+                               const int *windows, int n_windows, float th,
+                               unsigned char *is_face, float *score, int *carts_n, unsigned int *path_hash,
+                               float *shapes, float *landmarks, jdaStats *stats);
+/* Same, frames already resident in device memory: frame i starts at d_frames + i*frame_stride
+ * (frame_stride >= width*height). */
+JDA_API int jdaValidateWindowsDevice(void *cascador, const unsigned char *d_frames, size_t frame_stride, int n,
+                                     int width, int height, const int *windows, int n_windows, float th,
+                                     unsigned char *is_face, float *score, int *carts_n, unsigned int *path_hash,
+                                     float *shapes, float *landmarks, jdaStats *stats);
+
 /* The image pair of reference c/jda.c:450-457 (half = 1/sqrt(2), quarter =
  * 1/2) built by the device resize kernel; exposed for the parity tests.
  * half/quarter are HOST buffers of hw*hh and qw*qh bytes. */

@@ -222,6 +222,11 @@ def _load():
     lib.jdaDetectBatchWait.argtypes = [C.c_void_p, C.c_int, C.POINTER(jdaStats), C.POINTER(jdaResult)]
     lib.jdaTraceBatch.argtypes = [C.c_void_p, C.POINTER(u8p), C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                   C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint), C.POINTER(C.c_float)]
+    if hasattr(lib, "jdaValidateWindows"):          # (older builds, loaded through JDA_LIB_PATH for A/B runs, lack it)
+        win_tail = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_float, u8p, C.POINTER(C.c_float), C.POINTER(C.c_int),
+                    C.POINTER(C.c_uint), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(jdaStats)]
+        lib.jdaValidateWindows.argtypes = [C.c_void_p, C.POINTER(u8p)] + win_tail
+        lib.jdaValidateWindowsDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + win_tail
     lib.jdaBuildPyramid.argtypes = [C.c_void_p, u8p, C.c_int, C.c_int, u8p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     u8p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.jdaResultDRelease.restype = None
@@ -1102,6 +1107,46 @@ class Cascador:
         if rc != 0:
             raise JdaError(last_error())
         return dict(carts_n=carts, score=score, path_hash=hsh, shapes=shapes)
+
+    def validate_windows(self, frames, windows, th=-0.5, device=False, stats=False):
+        """The cascade on caller-given windows, rows of (frame, x, y, size) (jdaValidateWindows; the body of the reference's
+        window loop, c/jda.c:340-414, with the relocation of c/jda.c:471-472).  frames: [n, h, w] uint8, a numpy array (host
+        entry) or a torch CUDA tensor (jdaValidateWindowsDevice); device=True with a numpy array stages it on the device
+        first (torch) and calls the device entry.  -> dict of is_face, score, carts_n, path_hash, shapes, landmarks (numpy,
+        the caller's order)."""
+        if not hasattr(lib, "jdaValidateWindows"):
+            raise JdaError("this libjda.so has no jdaValidateWindows (a build from before the entry, loaded through JDA_LIB_PATH)")
+        if device and isinstance(frames, np.ndarray):
+            import torch
+            frames = torch.from_numpy(np.ascontiguousarray(frames, np.uint8)).cuda()
+        dev = not isinstance(frames, np.ndarray)
+        if dev:
+            assert frames.is_cuda and frames.dtype.itemsize == 1 and frames.is_contiguous()
+        else:
+            frames = np.ascontiguousarray(frames, np.uint8)
+        if frames.ndim == 2:
+            frames = frames[None]
+        n, h, w = frames.shape
+        win = np.ascontiguousarray(np.asarray(windows, np.int32).reshape(-1, 4))
+        nw = win.shape[0]
+        face = np.zeros(max(nw, 1), np.uint8)
+        score = np.zeros(max(nw, 1), np.float32)
+        carts = np.zeros(max(nw, 1), np.int32)
+        hsh = np.zeros(max(nw, 1), np.uint32)
+        shapes = np.zeros((max(nw, 1), self.dim), np.float32)
+        lms = np.zeros((max(nw, 1), self.dim), np.float32)
+        st = jdaStats()
+        tail = (n, w, h, win.ctypes.data_as(C.POINTER(C.c_int)), nw, th, _u8(face), score.ctypes.data_as(C.POINTER(C.c_float)),
+                carts.ctypes.data_as(C.POINTER(C.c_int)), hsh.ctypes.data_as(C.POINTER(C.c_uint)),
+                shapes.ctypes.data_as(C.POINTER(C.c_float)), lms.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st))
+        if dev:
+            rc = lib.jdaValidateWindowsDevice(self.h, C.c_void_p(frames.data_ptr()), h * w, *tail)
+        else:
+            rc = lib.jdaValidateWindows(self.h, _frame_ptrs(frames), *tail)
+        if rc != 0:
+            raise JdaError(last_error())
+        out = dict(is_face=face[:nw], score=score[:nw], carts_n=carts[:nw], path_hash=hsh[:nw], shapes=shapes[:nw], landmarks=lms[:nw])
+        return (out, st.asdict()) if stats else out
 
     def build_pyramid(self, img):
         img = np.ascontiguousarray(img, np.uint8)

@@ -186,6 +186,11 @@ long long jdaGetOption(void* cascador, const char* key) try {
     if (std::strcmp(key, "hwq_probes") == 0) return c->streams.probes;
     if (std::strcmp(key, "hwq_max_mains") == 0) { int m = 0; for (int x : c->streams.mains) m = std::max(m, x); return m; }
   }
+  // read-only: the largest window side k_windows walks from an LDS copy of the window's pixels with this model (0: none)
+  if (c && key && std::strcmp(key, "windows_tile_limit") == 0) {
+    std::lock_guard<std::mutex> lk(c->mu);             // (multi_scale() caches its answer in the model on first use)
+    return c->hm.multi_scale() ? 0 : windows_tile_limit(c->hm.dim(), c->hm.K);
+  }
   if (c && key && std::strncmp(key, "mem_", 4) == 0) {
     // read-only: what the cascador holds on the device -- bytes of its model tables (both dialects' and the mining tables) and
     // of its lanes' buffers, all grow-only, and the plan buffers in the plan map and the pool together (a test of "nothing
@@ -193,7 +198,7 @@ long long jdaGetOption(void* cascador, const char* key) try {
     std::lock_guard<std::mutex> lk(c->mu);
     if (std::strcmp(key, "mem_device_bytes") == 0) {
       size_t b = c->mf.buf.bytes + c->md.buf.bytes + c->mine_buf.bytes;
-      for (auto& l : c->lanes) b += l->ws.bytes + l->frames.bytes + l->pyr.bytes + l->rag_frames.bytes + l->rag_raw.bytes + l->rag_tab.bytes;
+      for (auto& l : c->lanes) b += l->ws.bytes + l->frames.bytes + l->pyr.bytes + l->win.bytes + l->rag_frames.bytes + l->rag_raw.bytes + l->rag_tab.bytes;
       return (long long)b;
     }
     if (std::strcmp(key, "mem_plan_buffers") == 0) return (long long)(c->plans.size() + c->plan_pool.size());
@@ -361,6 +366,22 @@ int jdaTraceBatch(void* cascador, const unsigned char* const* frames, int n, int
   if (!run_device<float>(c, lanes, pe, (const uint8_t*)lanes.v[0]->frames.p, stride, n, false, 0.f, nullptr, nullptr, &tr, &rs,
                          HostFrames{frames, (size_t)width * height})) return -1;
   return 0;
+} JDA_ABI_CATCH_SYNC(-1)
+
+int jdaValidateWindows(void* cascador, const unsigned char* const* frames, int n, int width, int height, const int* windows,
+                       int n_windows, float th, unsigned char* is_face, float* score, int* carts_n, unsigned int* path_hash,
+                       float* shapes, float* landmarks, jdaStats* stats) try {
+  g_err.clear();
+  return windows_entry((Cascador*)cascador, "jdaValidateWindows", frames, nullptr, 0, n, width, height, windows, n_windows, th,
+                       WindowsOut{is_face, score, carts_n, path_hash, shapes, landmarks, stats});
+} JDA_ABI_CATCH_SYNC(-1)
+
+int jdaValidateWindowsDevice(void* cascador, const unsigned char* d_frames, size_t frame_stride, int n, int width, int height,
+                             const int* windows, int n_windows, float th, unsigned char* is_face, float* score, int* carts_n,
+                             unsigned int* path_hash, float* shapes, float* landmarks, jdaStats* stats) try {
+  g_err.clear();
+  return windows_entry((Cascador*)cascador, "jdaValidateWindowsDevice", nullptr, d_frames, frame_stride, n, width, height, windows,
+                       n_windows, th, WindowsOut{is_face, score, carts_n, path_hash, shapes, landmarks, stats});
 } JDA_ABI_CATCH_SYNC(-1)
 
 int jdaBuildPyramid(void* cascador, const unsigned char* data, int width, int height,
@@ -587,7 +608,7 @@ namespace jda {
 void jda_bc_read_k_scan(unsigned long long*); void jda_bc_read_k_scan_d(unsigned long long*); void jda_bc_read_k_scan_r(unsigned long long*);
 void jda_bc_read_k_scan_dr(unsigned long long*); void jda_bc_read_k_scan_p(unsigned long long*); void jda_bc_read_k_finish(unsigned long long*);
 void jda_bc_read_k_wide(unsigned long long*); void jda_bc_read_k_stage(unsigned long long*); void jda_bc_read_k_mine(unsigned long long*); void jda_bc_read_k_train(unsigned long long*); void jda_bc_read_k_lbf(unsigned long long*);
-void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*); void jda_bc_read_k_fit(unsigned long long*); void jda_bc_read_k_reval(unsigned long long*);
+void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*); void jda_bc_read_k_fit(unsigned long long*); void jda_bc_read_k_reval(unsigned long long*); void jda_bc_read_k_windows(unsigned long long*);
 }
 // bounds-check build only (libjda_bounds.so): per translation unit {first violation: site << 32 | source line, violations}
 // since the last call -- out[16]; returns the total number of violations (kernels_common.h: Bc)
@@ -597,9 +618,10 @@ __attribute__((visibility("default"))) long long jdaDebugBoundsReport(unsigned l
                                         jda_bc_read_k_scan_p, jda_bc_read_k_finish, jda_bc_read_k_wide, jda_bc_read_k_stage};
   long long total = 0;
   for (int i = 0; i < 8; i++) { unsigned long long v[2] = {0, 0}; rd[i](v); if (out) { out[2 * i] = v[0]; out[2 * i + 1] = v[1]; } total += (long long)v[1]; }
-  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces', k_fit's and k_reval's words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file or in cpp_patch.h
-  const struct { void (*rd)(unsigned long long*); const char* tu; } more[7] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
-                                                                                {jda_bc_read_k_gather, "k_gather"}, {jda_bc_read_k_faces, "k_faces"}, {jda_bc_read_k_fit, "k_fit"}, {jda_bc_read_k_reval, "k_reval"}};
+  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces', k_fit's, k_reval's and k_windows' words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file or in cpp_patch.h
+  const struct { void (*rd)(unsigned long long*); const char* tu; } more[8] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
+                                                                                {jda_bc_read_k_gather, "k_gather"}, {jda_bc_read_k_faces, "k_faces"}, {jda_bc_read_k_fit, "k_fit"}, {jda_bc_read_k_reval, "k_reval"},
+                                                                                {jda_bc_read_k_windows, "k_windows"}};
   for (const auto& t : more) {
     unsigned long long v[2] = {0, 0};
     t.rd(v);

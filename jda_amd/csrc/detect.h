@@ -54,6 +54,12 @@ bool mine_model(Cascador* c, MineModel* out);
 int reval_entry(Cascador* c, const jdaSamplesCpp* samples, int os, int hs, int qs, unsigned char* is_face, double* score, int* carts_n,
                 double* shape, jdaStageStatsCpp* stats);
 
+// windows.cpp: the cascade on caller-given windows (jdaValidateWindows / jdaValidateWindowsDevice); frames on the device
+// (d_frames) or, with host_frames set, in host memory
+struct WindowsOut { unsigned char* is_face; float* score; int* carts_n; unsigned int* path_hash; float* shapes; float* landmarks; jdaStats* stats; };
+int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_frames, const uint8_t* d_frames, size_t stride, int n,
+                  int width, int height, const int* windows, int n_windows, float th, const WindowsOut& out);
+
 // detect_cpp.cpp: dialect CPP, method 1 (cascador.cpp:310-376,431-477) on a uniform batch; frames on the device
 // (d_frames) or, with host_frames set, in host memory
 struct CppCall { int minimum_size, step; double factor, overlap; int nms; };

@@ -107,6 +107,9 @@ __device__ __forceinline__ int node_feature(typename DL::Node nd, const typename
   const int y2 = clamp_win(DL::coord(s2y, nd.o2y, pw), pw);
   const int gx1 = min(v.ox + x1, v.w - 1), gy1 = min(v.oy + y1, v.h - 1);
   const int gx2 = min(v.ox + x2, v.w - 1), gy2 = min(v.oy + y2, v.h - 1);
+  // (v.bc: the range the view's image lies in where the kernel sets it -- k_windows; everything otherwise)
+  JDA_BC_ADDR(v.bc, v.img + (unsigned)(gy1 * v.w + gx1), 1, nd.scale == 0 ? kBcFinishPix : kBcWinPyramid);
+  JDA_BC_ADDR(v.bc, v.img + (unsigned)(gy2 * v.w + gx2), 1, nd.scale == 0 ? kBcFinishPix : kBcWinPyramid);
   const int a = v.img[(unsigned)(gy1 * v.w + gx1)];
   const int b = v.img[(unsigned)(gy2 * v.w + gx2)];
   return a - b;
@@ -194,7 +197,10 @@ __device__ __forceinline__ void walk_carts(const NodeOff<typename DL::Real>* __r
                                            const View& v0, const View& v1, const View& v2,
                                            const Stp<typename DL::Real>& stp, bool apply_st, int* leaf,
                                            const uint8_t* tile = nullptr, int tpitch = 0,
-                                           const typename DL::Node* __restrict__ stage_deep = nullptr, int split = 1 << 20) {
+                                           const typename DL::Node* __restrict__ stage_deep = nullptr, int split = 1 << 20,
+                                           const Bc& bc_lm = Bc(), const Bc& bc_deep = Bc()) {
+  // bc_lm / bc_deep (bounds-check build): the records of the stage in stage_off / stage_meta and in stage_deep, where the
+  // kernel says (k_windows); everything otherwise
   int node[G];
 #pragma unroll
   for (int g = 0; g < G; g++) node[g] = 0;
@@ -207,6 +213,7 @@ __device__ __forceinline__ void walk_carts(const NodeOff<typename DL::Real>* __r
 #pragma unroll
     for (int g = 0; g < G; g++) {
       const unsigned o = lvl + ((unsigned)k[g] << d) + (unsigned)node[g];
+      JDA_BC(bc_lm, o, 1, kBcNodeTable);
       const NodeOff<typename DL::Real> f = stage_off[o];
       const uint2 mt = stage_meta[o];
       nd[g].o1x = f.o1x; nd[g].o1y = f.o1y; nd[g].o2x = f.o2x; nd[g].o2y = f.o2y;
@@ -224,8 +231,10 @@ __device__ __forceinline__ void walk_carts(const NodeOff<typename DL::Real>* __r
   for (int d = shallow; d < levels; d++) {
     typename DL::Node nd[G];
 #pragma unroll
-    for (int g = 0; g < G; g++)
+    for (int g = 0; g < G; g++) {
+      JDA_BC(bc_deep, lm_deep_index((unsigned)k[g], (unsigned)d, (unsigned)node[g], (unsigned)levels, (unsigned)split), 1, kBcNodeTable);
       nd[g] = stage_deep[lm_deep_index((unsigned)k[g], (unsigned)d, (unsigned)node[g], (unsigned)levels, (unsigned)split)];
+    }
     int feat[G];
 #pragma unroll
     for (int g = 0; g < G; g++) feat[g] = node_feature<DL, MULTI, ST, TILE>(nd[g], sh, win, v0, v1, v2, stp, apply_st, tile, tpitch);

@@ -7,7 +7,7 @@
 //   post_host.cpp  sort, NMS, relocation, jdaResult, statistics     tickets.cpp  submit / wait
 //   ragged.cpp     images of different sizes as one job             abi.cpp      the extern "C" entry points of include/jda.h
 //   fit.cpp        a stage's global regression (dialect CPP)       model_grow.cpp  the model in training: put a cart, close a stage, the f64 file
-//   reval.cpp      Validate on a resident sample set (dialect CPP)
+//   reval.cpp      Validate on a resident sample set (dialect CPP)   windows.cpp  the cascade on caller-given windows (dialect C)
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -136,6 +136,7 @@ inline long long env_ll(const char* name, long long dflt) {
   X(fit_lds_kb, "JDA_FIT_LDS_KB", 160)      /* LDS in KB a workgroup of k_fit (a stage's global regression, fit.cpp) may take, counted in granules; where one coordinate's column of w does not fit it, the kernel works on the column in global memory (0: always) */ \
   X(reval_form, "JDA_REVAL_FORM", 0)        /* jdaValidateSamplesCpp (reval.cpp): 0 a wave per sample (k_reval), 1 a lane per sample (k_mine_walk on the same records): identical bits, for A/B and as a check */ \
   X(reval_lds_kb, "JDA_REVAL_LDS_KB", 160)  /* LDS in KB a workgroup of k_reval may take; where one sample's slice (patches, shape, a stage's indicators) does not fit it, the kernel works in global memory (0: always) */ \
+  X(windows_tile, "JDA_WINDOWS_TILE", -1)   /* jdaValidateWindows (windows.cpp): windows up to this side walk from an LDS copy of their pixels, within the finishing kernels' LDS budget (-1: as large as that budget allows, 0: every pixel is read from the frame): identical bits */ \
   X(fit_ahead, "JDA_FIT_AHEAD", 2)          /* ... epochs queued ahead of the one whose state words the host inspects (fit_ahead + 1 rotating order buffers; results do not depend on it) */ \
   X(ragged_chunk_min_windows, "JDA_RAGGED_CHUNK_MIN_WINDOWS", 1500000) /* ... and at least, where a small job is cut into ragged_split chunks */ \
   X(ragged_split, "JDA_RAGGED_SPLIT", 3)    /* chunks a job smaller than that many full chunks is cut into */ \
@@ -426,6 +427,7 @@ struct Lane {
   WorkT<double> wd{};
   DevBuf frames;                             // staging of host frames (the call's first lane holds the whole batch)
   DevBuf pyr;                                // half + quarter images (multi-scale models), method-0 levels
+  DevBuf win;                                // jdaValidateWindows: a chunk's window list and its per-window outputs (windows.cpp)
   // ragged passes: images at the common pitch, tight images, tables (segments, block map, image records)
   DevBuf rag_frames, rag_raw, rag_tab;
   HostPinned h_tab, h_raw;
@@ -461,7 +463,7 @@ struct Lane {
     ~Bag() { for (void* p : dev) (void)hipFree(p); for (void* p : host) (void)hipHostFree(p); }
   };
   void trim(Bag* bag = nullptr) {
-    DevBuf* db[] = {&ws, &frames, &pyr, &rag_frames, &rag_raw, &rag_tab};
+    DevBuf* db[] = {&ws, &frames, &pyr, &win, &rag_frames, &rag_raw, &rag_tab};
     HostPinned* hb[] = {&h_gid, &h_score, &h_shape, &h_tab, &h_raw, &h_pn, &h_pbb, &h_psc, &h_psh};
     for (DevBuf* b : db) { if (bag && b->p) { bag->dev.push_back(b->p); b->p = nullptr; b->bytes = 0; } else b->release(); }
     for (HostPinned* b : hb) { if (bag && b->p) { bag->host.push_back(b->p); b->p = nullptr; b->bytes = 0; } else b->release(); }

@@ -486,6 +486,26 @@ struct RevalArgs {
 // lds_budget as launch_lbf's; how: staged in LDS (1) or from global memory (0), waves and LDS bytes per workgroup.
 hipError_t launch_reval(const RevalArgs& a, int lds_budget, LbfLaunch* how, hipStream_t stream);
 
+// ---- dialect C: the cascade on caller-given windows (k_windows.hip, windows.cpp; reference c/jda.c:340-414, 471-472) ----
+// One chunk of a caller's window list (device pointers): window i is windows[i] = (frame, x, y, size), validated by the host
+// (inside its frame, frame inside [0, n_frames)).  Outputs by window index, any may be null: face [n], score [n], carts_n [n],
+// hash [n], shapes [n][dim] (window-normalised), landmarks [n][dim] (relocated, c/jda.c:471-472).  half / quarter: the
+// jdaBuildPyramid pair of every frame (multi-scale models only, null otherwise).  tile_win: windows up to this side walk from
+// an LDS copy of their pixels (single-scale models; 0: every pixel is read from the frame).
+struct WinArgs {
+  const uint8_t* frames; size_t frame_stride; int n_frames, width, height;
+  const uint8_t* half; size_t half_stride; int hw, hh;
+  const uint8_t* quarter; size_t quarter_stride; int qw, qh;
+  const int4* windows; int n;
+  float th;
+  uint8_t* face; float* score; int* carts_n; uint32_t* hash; float* shapes; float* landmarks;
+  int tile_win;
+};
+// The largest window side whose pixels fit next to the walk's state within the finishing kernels' LDS budget
+// (kFinishLdsPerGroup); 0: none does.
+int windows_tile_limit(int dim, int K);
+hipError_t launch_windows(const DevModelT<float>& m, const WinArgs& a, hipStream_t stream);
+
 // ---- dialect CPP: a sample set from one cart to the next (k_gather.hip, boost.cpp; reference src/jda/data.cpp:319-410) ----
 constexpr int kGatherSegs = 8;           // source segments of one launch at most
 constexpr int kGatherWaves = 4;          // destination records (waves) of a workgroup per round of its grid-stride loop
