@@ -618,7 +618,7 @@ __attribute__((visibility("default"))) long long jdaDebugBoundsReport(unsigned l
                                         jda_bc_read_k_scan_p, jda_bc_read_k_finish, jda_bc_read_k_wide, jda_bc_read_k_stage};
   long long total = 0;
   for (int i = 0; i < 8; i++) { unsigned long long v[2] = {0, 0}; rd[i](v); if (out) { out[2 * i] = v[0]; out[2 * i + 1] = v[1]; } total += (long long)v[1]; }
-  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces', k_fit's, k_reval's and k_windows' words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file or in cpp_patch.h
+  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces', k_fit's, k_reval's and k_windows' words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file, cpp_patch.h or cpp_wave.h
   const struct { void (*rd)(unsigned long long*); const char* tu; } more[8] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
                                                                                 {jda_bc_read_k_gather, "k_gather"}, {jda_bc_read_k_faces, "k_faces"}, {jda_bc_read_k_fit, "k_fit"}, {jda_bc_read_k_reval, "k_reval"},
                                                                                 {jda_bc_read_k_windows, "k_windows"}};
@@ -626,7 +626,7 @@ __attribute__((visibility("default"))) long long jdaDebugBoundsReport(unsigned l
     unsigned long long v[2] = {0, 0};
     t.rd(v);
     if (!v[1]) continue;
-    std::fprintf(stderr, "libjda: bounds check: %s: %llu violation(s), first at site %llu line %llu (of the .hip file or cpp_patch.h)\n", t.tu, v[1], v[0] >> 32, v[0] & 0xffffffffull);
+    std::fprintf(stderr, "libjda: bounds check: %s: %llu violation(s), first at site %llu line %llu (of the .hip file, cpp_patch.h or cpp_wave.h)\n", t.tu, v[1], v[0] >> 32, v[0] & 0xffffffffull);
     if (out) { if (!out[11]) out[10] = v[0]; out[11] += v[1]; }
     total += (long long)v[1];
   }

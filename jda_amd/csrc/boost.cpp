@@ -126,9 +126,8 @@ bool run_gather(GatherCall& x) {
         d_items = cv.take<GatherItem>((size_t)n_items);
         d_stage = staged ? cv.take<uint8_t>((size_t)nc * P) : nullptr;
       })) return false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-  if (x.stats) for (auto& e : ev) JDA_HIP(hipEventCreate(&e));
+  EvTimer timer;
+  if (!timer.open(x.stats)) return false;
 
   double t = now_ms();
   JDA_HIP(hipMemcpyAsync(d_items, items.data(), (size_t)n_items * sizeof(GatherItem), hipMemcpyHostToDevice, st));
@@ -136,11 +135,11 @@ bool run_gather(GatherCall& x) {
   upload_ms += now_ms() - t;
 
   auto launch = [&](GatherArgs& a) -> bool {
-    if (x.stats) JDA_HIP(hipEventRecord(ev[0], st));
+    if (!timer.begin(st)) return false;
     JDA_HIP(launch_gather(a, st));
-    if (x.stats) JDA_HIP(hipEventRecord(ev[1], st));
+    if (!timer.end(st)) return false;
     JDA_HIP(hipStreamSynchronize(st));
-    if (x.stats) { float ms = 0; JDA_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); device_ms += ms; }
+    if (!timer.add(&device_ms)) return false;
     launches++;
     return true;
   };

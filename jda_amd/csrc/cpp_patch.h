@@ -1,5 +1,7 @@
 // Patch numerics of dialect CPP, once, for k_misc.hip (pyramid and ROI resizes), k_mine.hip (Validate on crops, mining),
-// k_train.hip (feature pool values) and k_lbf.hip (a stage's carts over the sample set): one pixel of cv::resize(INTER_LINEAR), the split-node feature on o / h / q patches.
+// k_train.hip (feature pool values), k_faces.hip (the positive set's patches) and, through cpp_wave.h, k_lbf.hip and
+// k_reval.hip (a stage's / the model's carts over the sample set): one pixel of cv::resize(INTER_LINEAR), the split-node
+// feature on o / h / q patches.
 #pragma once
 #include "kernels_common.h"
 

@@ -123,9 +123,8 @@ bool run_faces(FacesCall& x) {
         d_imgs = x.host_imgs ? cv.take<uint8_t>(stage_bytes) : nullptr;
         d_stage = x.dst_dev ? nullptr : cv.take<uint8_t>(nb_max * mult * P);
       })) return false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-  if (x.stats) for (auto& e : ev) JDA_HIP(hipEventCreate(&e));
+  EvTimer timer;
+  if (!timer.open(x.stats)) return false;
 
   std::vector<FaceItem> items(cap);
   for (size_t k = 0; k < chunk_imgs.size(); k++) {
@@ -151,9 +150,9 @@ bool run_faces(FacesCall& x) {
       a.base = x.host_imgs ? d_imgs : x.d_base; a.items = d_items; a.n = nb; a.os = x.os; a.hs = x.hs; a.qs = x.qs;
       if (x.dst_dev) { a.dst = x.dst; a.dst_n = (long long)n * mult; a.mirror = x.augment ? n : 0; }
       else { a.dst = d_stage; a.dst_n = (long long)nb * mult; a.mirror = x.augment ? nb : 0; }
-      if (x.stats) JDA_HIP(hipEventRecord(ev[0], st));
+      if (!timer.begin(st)) return false;
       JDA_HIP(launch_faces(a, st));
-      if (x.stats) JDA_HIP(hipEventRecord(ev[1], st));
+      if (!timer.end(st)) return false;
       t = now_ms();
       if (!x.dst_dev) {
         // runs of consecutive faces come back in one copy each (and one more for their mirrors)
@@ -168,7 +167,7 @@ bool run_faces(FacesCall& x) {
       }
       JDA_HIP(hipStreamSynchronize(st));
       if (!x.dst_dev) download_ms += now_ms() - t;
-      if (x.stats) { float ms = 0; JDA_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); device_ms += ms; }
+      if (!timer.add(&device_ms)) return false;
       chunks++;
       t = now_ms();
     }

@@ -63,6 +63,18 @@ inline double now_ms() {
   return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
+// A pair of events around one launch at a time, for a caller that asked for statistics (`wanted`; otherwise every step
+// does nothing and no event exists): begin / end record on the launch's stream, add -- once that stream has been waited
+// for -- adds the span between them to *device_ms.  Each step is false after fail(), like JDA_HIP.
+struct EvTimer {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~EvTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  bool open(bool wanted) { if (wanted) for (auto& e : ev) JDA_HIP(hipEventCreate(&e)); return true; }
+  bool begin(hipStream_t st) { if (ev[0]) JDA_HIP(hipEventRecord(ev[0], st)); return true; }
+  bool end(hipStream_t st) { if (ev[1]) JDA_HIP(hipEventRecord(ev[1], st)); return true; }
+  bool add(double* device_ms) { if (ev[0]) { float ms = 0; JDA_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); *device_ms += ms; } return true; }
+};
+
 // ---- exception barrier -------------------------------------------------------------------------------------------
 // No C++ exception may cross `extern "C"`: the host side allocates (std::vector growth in the post-processing, the
 // 512 MB of a big model's tables, std::string in the error channel, std::thread) and a std::bad_alloc that left

@@ -12,7 +12,7 @@
 //                   for the state words), never through the scalar cache.
 //           column  the coordinate's column w_j (f doubles) sits in LDS for the epoch (LDS = true), or stays in global
 //                   memory where it does not fit (LDS = false: the same body on the same values, the wave's writes ordered
-//                   before its next reads the way k_lbf orders its indicator writes).
+//                   before its next reads by wave_global_sync, kernels_common.h).
 //           sample  lanes = carts: lane c gathers w_j[lbf[i][k]] for k = c, c + 64, .. and keeps the values; their sum in
 //                   ascending k is the partial sum p[c] of the contract, the six steps h = 32 .. 1 are cross-lane adds in
 //                   the contract's pairing (h = 32, 16 through the LDS crossbar, h = 8 .. 1 by DPP row shifts); G, the
@@ -30,13 +30,6 @@
 namespace jda {
 
 namespace {
-
-// This wave's writes to global memory before its later reads of them by OTHER lanes of the same wave (LDS = false).
-__device__ __forceinline__ void fit_global_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
 
 // lane c <- lane (c + h) & 63, through the LDS crossbar (no LDS memory is touched)
 __device__ __forceinline__ double fit_from_above(double v, int lane, int h) {
@@ -167,7 +160,7 @@ __global__ __launch_bounds__(64) void k_fit(FitArgs a) {
 #pragma unroll
         for (int r = 0; r < NR; r++)
           if (lane + 64 * r < K) wl[cur[r]] = v[r] + d;
-        if constexpr (LDS) wave_lds_sync(); else fit_global_sync();
+        if constexpr (LDS) wave_lds_sync(); else wave_global_sync();
       }
     } else {                                             // K above 64 * kFitMaxRounds: the row is read where it is used
       const int* __restrict__ row = a.lbf + (size_t)rl(iA, s) * K;
@@ -185,7 +178,7 @@ __global__ __launch_bounds__(64) void k_fit(FitArgs a) {
       bA = lane == s ? nb : bA;
       if (d != 0.) {
         for (int k = lane; k < K; k += 64) { const int at = row[k]; wl[at] = wl[at] + d; }
-        if constexpr (LDS) wave_lds_sync(); else fit_global_sync();
+        if constexpr (LDS) wave_lds_sync(); else wave_global_sync();
       }
     }
   };

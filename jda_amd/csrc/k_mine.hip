@@ -7,7 +7,7 @@
 //   k_mine_walk     lane = crop: Validate, literally, on the patches (fp64, snapshot loop bounds, similarity transform,
 //                   initial shape shift)
 //   k_mine_sum      reject lengths of a range of windows (NegGenerator's carts_n / nega_n, data.cpp:1001-1004)
-#include "cpp_patch.h"
+#include "cpp_wave.h"
 #include "finish_common.h"
 #include "splitmix.h"
 
@@ -214,23 +214,17 @@ __global__ __launch_bounds__(64) void k_mine_walk(MineModel m, MineSizes z, cons
   bool apply = false;
   double score = 0.;
   int nn = 0;
-  // one cart: Cart::Forward (cart.cpp:392-404) -> leaf index; false = rejected
+  // one cart: cart_forward (cpp_wave.h) on the cart-major heap -> leaf index; false = rejected
   auto cart = [&](int t, int k, int* leaf) -> bool {
     const size_t ck = (size_t)t * K + k;
     const NodeD* nodes = m.nodes + ck * m.node_n;
-    int node = 0;
-    for (int d = 0; d < m.D - 1; d++) {
-      NodeD nd = nodes[node];
-      if (apply) {                                      // stp_mc.Apply on both offsets, data.cpp:33-34
-        double ax, ay, bx, by;
-        stp_apply<double>(stp, nd.o1x, nd.o1y, &ax, &ay);
-        stp_apply<double>(stp, nd.o2x, nd.o2y, &bx, &by);
-        nd.o1x = ax; nd.o1y = ay; nd.o2x = bx; nd.o2y = by;
-      }
-      const int v = pat.feature(nd, sh[nd.lm1x2], sh[nd.lm1x2 + 1], sh[nd.lm2x2], sh[nd.lm2x2 + 1]);
-      node = (v <= nd.th) ? 2 * node + 1 : 2 * node + 2;
-    }
-    *leaf = node - m.node_n;
+    *leaf = cart_forward(pat, sh, m.D, dim, [&](int, int node) { return nodes[node - 1]; }, [&](NodeD& nd) {
+      if (!apply) return;                               // stp_mc.Apply on both offsets, data.cpp:33-34
+      double ax, ay, bx, by;
+      stp_apply<double>(stp, nd.o1x, nd.o1y, &ax, &ay);
+      stp_apply<double>(stp, nd.o2x, nd.o2y, &bx, &by);
+      nd.o1x = ax; nd.o1y = ay; nd.o2x = bx; nd.o2y = by;
+    });
     score += m.leaf[ck * m.leaf_n + *leaf];
     score = (score - m.cmean[ck]) / m.cstd[ck];
     nn++;

@@ -1,20 +1,20 @@
 // HIP kernel of dialect CPP's Validate on a resident sample set for gfx950 (reference src/jda/cascador.cpp:166-211;
 // jdaValidateSamplesCpp, reval.cpp): every record's stored o / h / q patches through the model as it stands, from the
 // record's own start shape.
-//   k_reval  wave = sample, the form DESIGN section 11 names and k_lbf.hip uses for one stage.  The sample's patch bytes,
-//            its 2L shape doubles and a stage's K leaf indicators live in the wave's own slice of LDS (LDS = true: k_lbf's
-//            layout), or in global memory where a slice does not fit (LDS = false: the same arithmetic on the same values;
+//   k_reval  wave = sample, the form of cpp_wave.h, which k_lbf.hip uses for one stage.  The sample's
+//            patch bytes, its 2L shape doubles and a stage's K leaf indicators live in the wave's own slice of LDS (LDS = true:
+//            WaveSlice), or in global memory where a slice does not fit (LDS = false: the same arithmetic on the same values;
 //            the shape lives in the output array, the indicators in a scratch row).  Per stage:
-//            walk     lane = cart, 64 carts at a time: Cart::Forward (cart.cpp:392-404) on the split node of cpp_patch.h
-//                     with the identity STParameter; the lane keeps its cart's leaf score, mean, std and threshold
+//            walk     lane = cart, 64 carts at a time: cart_forward on the mining tables' cart-major heap with the
+//                     identity STParameter; the lane keeps its cart's leaf score, mean, std and threshold
 //            replay   the score chain of those 64 carts IN CART ORDER, the non-associative chain of Validate:
 //                     score += leaf; score = (score - mean) / std -- one fp64 add, one subtract and one IEEE division per
 //                     cart, the operands handed from the cart's lane to the whole wave by v_readlane; lane l keeps the
 //                     score as it stood after cart l
 //            reject   `score < th` per lane, one ballot: the first set bit is the first failing cart -- it fixes carts_n,
 //                     the score where the walk stopped and the shape as it stood.  A NaN score fails no comparison.
-//            regress  a sample that passed the stage: lane = shape coordinate, delta from 0. + w[lbf[k]][j] for k = 0 .. K-1
-//                     in cart order (btcart.cpp:407-424, the order and form of k_lbf's phase 2), then shape += delta
+//            regress  a sample that passed the stage: lane = shape coordinate, gen_delta -- w[lbf[k]][j] for k = 0 .. K-1
+//                     in cart order (btcart.cpp:407-424) -- then shape += delta
 //            The partial stage of a snapshot runs its `part` carts and no regression (cascador.cpp:198-209).
 // Whole waves only: no workgroup barrier, no atomics, no spinning, nothing between waves.  The model's tables are the
 // mining tables, patched in place between launches (model_grow.cpp): every read of them has a lane-dependent address --
@@ -22,23 +22,14 @@
 // through the scalar cache.
 #include <limits>
 
-#include "cpp_patch.h"
+#include "cpp_wave.h"
 
 namespace jda {
 
 namespace {
 
-__device__ __forceinline__ int reval_align16(int v) { return (v + 15) & ~15; }
-
-// This wave's writes to global memory before its later reads of them by OTHER lanes of the same wave (LDS = false).
-__device__ __forceinline__ void reval_global_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-
-// n bytes global -> LDS by one wave (k_lbf.hip's): dst keeps the source's offset inside a dword, so the body is aligned
-// on both sides; the head and the tail (at most three bytes each) go bytewise.
+// n bytes global -> LDS by one wave, wave_stage_bytes' contract (cpp_wave.h) as a plain loop: k_reval keeps its own copy,
+// because with the batched one reval_bench's complete model measured slower than before (profiles/cpp_wave_ab.json).
 __device__ __forceinline__ uint8_t* reval_stage_bytes(uint8_t* lds, const uint8_t* __restrict__ src, int n, int lane) {
   const int sh = (int)((uintptr_t)src & 3);
   uint8_t* dst = lds + sh;
@@ -52,16 +43,10 @@ __device__ __forceinline__ uint8_t* reval_stage_bytes(uint8_t* lds, const uint8_
   return dst;
 }
 
-// lane l's double for the whole wave (l wave-uniform): two v_readlane_b32
-__device__ __forceinline__ double reval_readlane(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-
 }  // namespace
 
 template <bool LDS>
-__global__ __launch_bounds__(64 * kRevalWaves) void k_reval(RevalArgs a, int wave_bytes) {
+__global__ __launch_bounds__(64 * kSampleWaves) void k_reval(RevalArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char reval_lds[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const long long i = (long long)blockIdx.x * (blockDim.x >> 6) + wave;
@@ -74,18 +59,19 @@ __global__ __launch_bounds__(64 * kRevalWaves) void k_reval(RevalArgs a, int wav
   const double* start = a.start + (size_t)i * dim;
   double* sh_g = a.shape + (size_t)i * dim;
   int* lbf_g = a.lbf + (size_t)i * K;
-  // the wave's slice: shape [dim] doubles, lbf [K] ints, patches (pbytes + 3) bytes
-  double* sh_l = (double*)(reval_lds + (size_t)wave * wave_bytes);
-  int* lbf_l = (int*)((unsigned char*)sh_l + reval_align16(dim * 8));
+  const WaveSlice slice(dim, K, pbytes, true);
+  unsigned char* mine_l = reval_lds + (size_t)wave * slice.bytes;
+  double* sh_l = (double*)mine_l;
+  int* lbf_l = (int*)(mine_l + slice.lbf);
   double* sh = sh_g;
   int* lbf = lbf_g;
   const uint8_t* pat_p = pat_g;
   if (LDS) {
     sh = sh_l; lbf = lbf_l;
-    pat_p = reval_stage_bytes((uint8_t*)lbf_l + reval_align16(K * 4), pat_g, pbytes, lane);
+    pat_p = reval_stage_bytes(mine_l + slice.pat, pat_g, pbytes, lane);
   }
   for (int j = lane; j < dim; j += 64) sh[j] = start[j];
-  if (LDS) wave_lds_sync(); else reval_global_sync();
+  if (LDS) wave_lds_sync(); else wave_global_sync();
   const PatchSet pat{pat_p, a.os, a.hs, a.qs};
 
   double score = 0.;                                     // wave-uniform: every lane runs the same chain
@@ -102,15 +88,10 @@ __global__ __launch_bounds__(64 * kRevalWaves) void k_reval(RevalArgs a, int wav
       double lf = 0., mu = 0., sd = 1., th = -std::numeric_limits<double>::infinity();
       if (active) {
         const size_t ck = (size_t)t * K + k;
-        int node = 0;
-        for (int d = 0; d < m.D - 1; d++) {
-          JDA_BC(Bc(0, nodes_all), (long long)(ck * node_n + node), 1, kBcNodeTable);
-          const NodeD nd = m.nodes[ck * node_n + node];
-          JDA_BC(Bc(0, dim), nd.lm1x2, 2, kBcLandmark); JDA_BC(Bc(0, dim), nd.lm2x2, 2, kBcLandmark);
-          const int v = pat.feature(nd, sh[nd.lm1x2], sh[nd.lm1x2 + 1], sh[nd.lm2x2], sh[nd.lm2x2 + 1]);
-          node = (v <= nd.th) ? 2 * node + 1 : 2 * node + 2;   // cart.cpp:398-401, zero-based
-        }
-        const int leaf = node - node_n;
+        const int leaf = cart_forward(pat, sh, m.D, dim, [&](int, int node) {   // (heap node `node`, 1-based, is record node - 1)
+          JDA_BC(Bc(0, nodes_all), (long long)(ck * node_n + node - 1), 1, kBcNodeTable);
+          return m.nodes[ck * node_n + node - 1];
+        });
         JDA_BC(Bc(0, leaves_all), (long long)(ck * leaf_n + leaf), 1, kBcNodeTable);
         lbf[k] = k * leaf_n + leaf;                      // cascador.cpp:192
         lf = m.leaf[ck * leaf_n + leaf]; mu = m.cmean[ck]; sd = m.cstd[ck]; th = m.cth[ck];
@@ -118,14 +99,14 @@ __global__ __launch_bounds__(64 * kRevalWaves) void k_reval(RevalArgs a, int wav
       const int cnt = min(64, Kt - k0);
       double mine = 0.;
       for (int l = 0; l < cnt; l++) {                    // cascador.cpp:185-186, in cart order
-        score = score + reval_readlane(lf, l);
-        score = (score - reval_readlane(mu, l)) / reval_readlane(sd, l);
+        score = score + rl(lf, l);
+        score = (score - rl(mu, l)) / rl(sd, l);
         if (lane == l) mine = score;
       }
       const unsigned long long failed = __ballot(active && mine < th);      // cascador.cpp:188
       if (failed) {
         const int first = __ffsll((long long)failed) - 1;
-        score = reval_readlane(mine, first);
+        score = rl(mine, first);
         nn += first + 1;
         is_face = false;
       } else {
@@ -133,50 +114,24 @@ __global__ __launch_bounds__(64 * kRevalWaves) void k_reval(RevalArgs a, int wav
       }
     }
     if (!is_face || partial) break;
-    if (LDS) wave_lds_sync(); else reval_global_sync();  // the stage's indicators, written by their carts' lanes
+    if (LDS) wave_lds_sync(); else wave_global_sync();  // the stage's indicators, written by their carts' lanes
     // ---- GenDeltaShape (btcart.cpp:407-424) and shape += delta (cascador.cpp:196): lane = coordinate, rows in cart order
-    [[maybe_unused]] const long long rows = (long long)K * leaf_n;
     const double* wt = m.w + (size_t)t * K * leaf_n * dim;
-    for (int j = lane; j < dim; j += 64) {
-      double delta = 0.;
-      for (int k0 = 0; k0 < K; k0 += 8) {
-        double v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-          const int r = lbf[min(k0 + u, K - 1)];
-          JDA_BC(Bc(0, rows), r, 1, kBcWRow);
-          v[u] = wt[(size_t)r * dim + j];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++)
-          if (k0 + u < K) delta += v[u];
-      }
-      sh[j] = sh[j] + delta;                             // (coordinate j is read and written by this lane alone)
-    }
-    if (LDS) wave_lds_sync(); else reval_global_sync();  // the next stage's walk reads every coordinate
+    for (int j = lane; j < dim; j += 64)                 // (coordinate j is read and written by this lane alone)
+      sh[j] = sh[j] + gen_delta(lbf, wt, dim, K, j, (long long)K * leaf_n);
+    if (LDS) wave_lds_sync(); else wave_global_sync();  // the next stage's walk reads every coordinate
   }
   if (LDS) for (int j = lane; j < dim; j += 64) sh_g[j] = sh_l[j];
   if (lane == 0) { a.face[i] = is_face ? 1 : 0; a.carts_n[i] = nn; a.score[i] = score; }
 }
 
-hipError_t launch_reval(const RevalArgs& a, int lds_budget, LbfLaunch* how, hipStream_t stream) {
-  if (how) *how = LbfLaunch{0, kRevalWaves, 0};
+hipError_t launch_reval(const RevalArgs& a, int lds_budget, WaveLaunch* how, hipStream_t stream) {
+  *how = WaveLaunch{0, kSampleWaves, 0};
   if (a.n <= 0) return hipSuccess;
   if (a.m.K < 1 || a.m.D < 1 || a.m.D > 20 || a.m.dim < 2) return hipErrorInvalidValue;
   const long long pbytes = (long long)a.os * a.os + (long long)a.hs * a.hs + (long long)a.qs * a.qs;
-  const long long wave_bytes = (((long long)a.m.dim * 8 + 15) & ~15ll) + (((long long)a.m.K * 4 + 15) & ~15ll) + ((pbytes + 3 + 15) & ~15ll);
-  const long long budget = std::min<long long>(std::max(0, lds_budget), 160 * 1024);
-  const int waves = (int)std::min<long long>(kRevalWaves, budget / wave_bytes);
-  if (waves >= 1) {
-    const int total = (int)(waves * wave_bytes);
-    if (total > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_reval<true>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
-    hipLaunchKernelGGL(k_reval<true>, dim3((unsigned)((a.n + waves - 1) / waves)), dim3(64 * waves), total, stream, a, (int)wave_bytes);
-    if (how) *how = LbfLaunch{1, waves, total};
-  } else {
-    hipLaunchKernelGGL(k_reval<false>, dim3((unsigned)((a.n + kRevalWaves - 1) / kRevalWaves)), dim3(64 * kRevalWaves), 0, stream, a, 0);
-  }
-  return hipGetLastError();
+  *how = plan_wave_slices(WaveSlice(a.m.dim, a.m.K, pbytes, true).bytes, kSampleWaves, lds_budget);
+  return launch_wave_slices(k_reval<true>, k_reval<false>, a, a.n, *how, stream);
 }
 
 JDA_BC_READER(k_reval)

@@ -455,25 +455,23 @@ hipError_t launch_train_var(const short* values, size_t stride, int F, const int
 
 // ---- dialect CPP: closing a stage (k_lbf.hip, stage.cpp; reference src/jda/btcart.cpp:255-292, 390-424) ----
 
-// One split node of a stage's carts as k_lbf reads it: jdaFeatureCpp's fields with the landmark ids doubled, and the threshold.
-struct LbfNode { int scale, lm1x2, lm2x2, th; double o1x, o1y, o2x, o2y; };
-// The table is level-major: node i (1-based, children 2i and 2i + 1) of cart k, on level d = floor(log2 i), sits at
+// A stage's carts as k_lbf reads them: NodeD records (jdaFeatureCpp's fields with the landmark ids doubled, and the threshold),
+// level-major: node i (1-based, children 2i and 2i + 1) of cart k, on level d = floor(log2 i), sits at
 inline size_t lbf_node_at(int K, int k, int i, int d) { return (size_t)K * (((size_t)1 << d) - 1) + ((size_t)k << d) + ((size_t)i - ((size_t)1 << d)); }
-constexpr int kLbfWaves = 4;             // samples (waves) of a workgroup at most
+constexpr int kSampleWaves = 4;          // samples (waves) of a workgroup at most, in the wave-per-sample kernels (cpp_wave.h)
 // One chunk of a resident sample set (device pointers).  walk = 1: the carts are walked and lbf [n][K] is written;
 // walk = 0: lbf is read.  w != nullptr: out_shapes [n][dim] = shapes + the K rows of w [K * 2^(D-1)][dim] in cart order.
 struct LbfArgs {
-  const uint8_t* patches; const double* shapes; const LbfNode* nodes; const double* w;
+  const uint8_t* patches; const double* shapes; const NodeD* nodes; const double* w;
   int* lbf; double* out_shapes;
   int n, K, D, dim, os, hs, qs, walk;
 };
-struct LbfLaunch { int lds, waves, lds_bytes; };   // how it ran: staged in LDS (1) or from global memory (0), waves and LDS bytes per workgroup
+struct WaveLaunch { int lds, waves, lds_bytes; };  // how a wave-per-sample kernel ran: staged in LDS (1) or from global memory (0), waves and LDS bytes per workgroup
 // lds_budget: the LDS bytes a workgroup may take (at most the CU's 160 KB); where one sample's slice does not fit, the
-// kernel reads everything from global memory.
-hipError_t launch_lbf(const LbfArgs& a, int lds_budget, LbfLaunch* how, hipStream_t stream);
+// kernel reads everything from global memory.  how (never null): what was launched.
+hipError_t launch_lbf(const LbfArgs& a, int lds_budget, WaveLaunch* how, hipStream_t stream);
 
 // ---- dialect CPP: Validate on a resident sample set (k_reval.hip, reval.cpp; reference src/jda/cascador.cpp:166-211) ----
-constexpr int kRevalWaves = 4;           // samples (waves) of a workgroup at most
 // One chunk of a resident sample set (device pointers): record i's patches at patches + i * (os*os + hs*hs + qs*qs), its start
 // shape at start + i*dim; outputs face [n], carts_n [n], score [n], shape [n][dim] (also the walk's state where it runs
 // from global memory) and the scratch lbf [n][K] (the same).  m: the mining tables (mine.cpp), Validate's loop bounds in them.
@@ -483,8 +481,8 @@ struct RevalArgs {
   uint8_t* face; int* carts_n; double* score; double* shape; int* lbf;
   int n, os, hs, qs;
 };
-// lds_budget as launch_lbf's; how: staged in LDS (1) or from global memory (0), waves and LDS bytes per workgroup.
-hipError_t launch_reval(const RevalArgs& a, int lds_budget, LbfLaunch* how, hipStream_t stream);
+// lds_budget and how (never null) as launch_lbf's.
+hipError_t launch_reval(const RevalArgs& a, int lds_budget, WaveLaunch* how, hipStream_t stream);
 
 // ---- dialect C: the cascade on caller-given windows (k_windows.hip, windows.cpp; reference c/jda.c:340-414, 471-472) ----
 // One chunk of a caller's window list (device pointers): window i is windows[i] = (frame, x, y, size), validated by the host

@@ -153,6 +153,14 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The same for global memory: this wave's writes to global memory before its later reads of them by OTHER lanes of the
+// same wave (what a wave-per-sample kernel does where its state does not fit LDS: k_lbf, k_reval, k_fit).
+__device__ __forceinline__ void wave_global_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+
 __device__ __forceinline__ unsigned long long lanes_below(int lane) {
   return lane == 0 ? 0ull : (~0ull >> (64 - lane));
 }

@@ -51,11 +51,10 @@ int reval_entry(Cascador* c, const jdaSamplesCpp* s, int os, int hs, int qs, uns
           d_face = cv.take<uint8_t>(nc);
           if (host_patches) d_pat = cv.take<uint8_t>((size_t)nc * pbytes);
         })) return false;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-    if (stats) for (auto& e : ev) JDA_HIP(hipEventCreate(&e));
+    EvTimer timer;
+    if (!timer.open(stats)) return false;
     const int lds_budget = (int)std::min<long long>(160, std::max<long long>(0, c->kn.reval_lds_kb)) * 1024;
-    LbfLaunch how{0, lane_form ? 1 : kRevalWaves, 0};
+    WaveLaunch how{0, lane_form ? 1 : kSampleWaves, 0};
     std::vector<uint8_t> f(nc);
     int chunks = 0;
     for (int i0 = 0; i0 < n; i0 += nc, chunks++) {
@@ -66,7 +65,7 @@ int reval_entry(Cascador* c, const jdaSamplesCpp* s, int os, int hs, int qs, uns
       JDA_HIP(hipStreamSynchronize(st));
       upload_ms += now_ms() - t;
       const uint8_t* pat = host_patches ? d_pat : s->patches + (size_t)i0 * pbytes;
-      if (stats) JDA_HIP(hipEventRecord(ev[0], st));
+      if (!timer.begin(st)) return false;
       if (lane_form) {
         const MineSizes z{os, hs, qs, 0, 0., 0ull};
         JDA_HIP(launch_mine_walk(m, z, nullptr, cn, pat, (int)pbytes, 0, d_face, d_carts, d_score, d_shape, d_lbf, d_t1, d_t2, st, d_start));
@@ -76,9 +75,9 @@ int reval_entry(Cascador* c, const jdaSamplesCpp* s, int os, int hs, int qs, uns
         a.lbf = d_lbf; a.n = cn; a.os = os; a.hs = hs; a.qs = qs;
         JDA_HIP(launch_reval(a, lds_budget, &how, st));
       }
-      if (stats) JDA_HIP(hipEventRecord(ev[1], st));
+      if (!timer.end(st)) return false;
       JDA_HIP(hipStreamSynchronize(st));
-      if (stats) { float ms = 0; JDA_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); device_ms += ms; }
+      if (!timer.add(&device_ms)) return false;
       t = now_ms();
       if (is_face) JDA_HIP(hipMemcpyAsync(is_face + i0, d_face, cn, hipMemcpyDeviceToHost, st));
       if (score) JDA_HIP(hipMemcpyAsync(score + i0, d_score, (size_t)cn * sizeof(double), hipMemcpyDeviceToHost, st));

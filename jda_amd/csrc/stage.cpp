@@ -91,7 +91,7 @@ bool run_call(StageCall& x) {
   hipStream_t st = one.stream;
 
   // the stage's carts, level-major (kernels.h: lbf_node_at), and its weights
-  std::vector<LbfNode> nodes;
+  std::vector<NodeD> nodes;
   if (walk && inner > 0) {
     nodes.resize((size_t)K * inner);
     for (int k = 0; k < K; k++)
@@ -99,40 +99,39 @@ bool run_call(StageCall& x) {
         for (int i = 1 << d; i < (2 << d); i++) {
           const size_t src = (size_t)k * inner + (i - 1);
           const jdaFeatureCpp& f = x.carts->features[src];
-          LbfNode& nd = nodes[lbf_node_at(K, k, i, d)];
+          NodeD& nd = nodes[lbf_node_at(K, k, i, d)];
           nd.scale = f.scale; nd.lm1x2 = 2 * f.landmark_id1; nd.lm2x2 = 2 * f.landmark_id2; nd.th = x.carts->thresholds[src];
           nd.o1x = f.offset1_x; nd.o1y = f.offset1_y; nd.o2x = f.offset2_x; nd.o2y = f.offset2_y;
         }
   }
   const size_t w_count = update ? (size_t)K * leaf_n * dim : 0;
-  const size_t fixed = nodes.size() * sizeof(LbfNode) + w_count * sizeof(double) + 4096;
+  const size_t fixed = nodes.size() * sizeof(NodeD) + w_count * sizeof(double) + 4096;
   const size_t per = (size_t)dim * 8 * (update ? 2 : 1) + (size_t)K * 4 + (host_patches ? pbytes : 0) + 64;
   const size_t budget = (size_t)std::max<long long>(1, c->kn.workspace_mb) << 20;
   const size_t room = budget > fixed ? budget - fixed : 0;
   const int nc = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, room / per));
 
   CallBuf buf;
-  LbfNode* d_nodes; double* d_w; double* d_sh; double* d_out; int* d_lbf; uint8_t* d_pat;
+  NodeD* d_nodes; double* d_w; double* d_sh; double* d_out; int* d_lbf; uint8_t* d_pat;
   if (!carve_into(buf, [&](Carver& cv) {
-        d_nodes = cv.take<LbfNode>(std::max<size_t>(nodes.size(), 1));
+        d_nodes = cv.take<NodeD>(std::max<size_t>(nodes.size(), 1));
         d_w = update ? cv.take<double>(w_count) : nullptr;
         d_sh = cv.take<double>((size_t)nc * dim);
         d_out = update ? cv.take<double>((size_t)nc * dim) : nullptr;
         d_lbf = cv.take<int>((size_t)nc * K);
         d_pat = host_patches ? cv.take<uint8_t>((size_t)nc * pbytes) : nullptr;
       })) return false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-  if (x.stats) for (auto& e : ev) JDA_HIP(hipEventCreate(&e));
+  EvTimer timer;
+  if (!timer.open(x.stats)) return false;
 
   double t = now_ms();
-  if (!nodes.empty()) JDA_HIP(hipMemcpyAsync(d_nodes, nodes.data(), nodes.size() * sizeof(LbfNode), hipMemcpyHostToDevice, st));
+  if (!nodes.empty()) JDA_HIP(hipMemcpyAsync(d_nodes, nodes.data(), nodes.size() * sizeof(NodeD), hipMemcpyHostToDevice, st));
   if (update) JDA_HIP(hipMemcpyAsync(d_w, x.w, w_count * sizeof(double), hipMemcpyHostToDevice, st));
   JDA_HIP(hipStreamSynchronize(st));
   upload_ms += now_ms() - t;
 
   const int lds_budget = (int)std::min<long long>(160, std::max<long long>(0, c->kn.lbf_lds_kb)) * 1024;
-  LbfLaunch how{0, kLbfWaves, 0};
+  WaveLaunch how{0, kSampleWaves, 0};
   int chunks = 0;
   for (int i0 = 0; i0 < n; i0 += nc, chunks++) {
     const int cn = std::min(nc, n - i0);
@@ -146,11 +145,11 @@ bool run_call(StageCall& x) {
     a.patches = walk ? (host_patches ? d_pat : s->patches + (size_t)i0 * pbytes) : nullptr;
     a.shapes = d_sh; a.nodes = d_nodes; a.w = d_w; a.lbf = d_lbf; a.out_shapes = d_out;
     a.n = cn; a.K = K; a.D = D; a.dim = dim; a.os = x.os; a.hs = x.hs; a.qs = x.qs; a.walk = walk ? 1 : 0;
-    if (x.stats) JDA_HIP(hipEventRecord(ev[0], st));
+    if (!timer.begin(st)) return false;
     JDA_HIP(launch_lbf(a, lds_budget, &how, st));
-    if (x.stats) JDA_HIP(hipEventRecord(ev[1], st));
+    if (!timer.end(st)) return false;
     JDA_HIP(hipStreamSynchronize(st));
-    if (x.stats) { float ms = 0; JDA_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); device_ms += ms; }
+    if (!timer.add(&device_ms)) return false;
     t = now_ms();
     if (update) JDA_HIP(hipMemcpyAsync(x.out_shapes + (size_t)i0 * dim, d_out, (size_t)cn * dim * sizeof(double), hipMemcpyDeviceToHost, st));
     if (x.out_lbf) JDA_HIP(hipMemcpyAsync(x.out_lbf + (size_t)i0 * K, d_lbf, (size_t)cn * K * sizeof(int), hipMemcpyDeviceToHost, st));

@@ -87,9 +87,8 @@ int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_
           d_win = cv.take<int4>(nc); d_face = cv.take<uint8_t>(nc); d_score = cv.take<float>(nc); d_carts = cv.take<int>(nc);
           d_hash = cv.take<uint32_t>(nc); d_shapes = cv.take<float>((size_t)nc * dim); d_lm = cv.take<float>((size_t)nc * dim);
         })) return false;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-    if (out.stats) for (auto& e : ev) JDA_HIP(hipEventCreate(&e));
+    EvTimer timer;
+    if (!timer.open(out.stats)) return false;
     std::vector<uint8_t> f(nc);
     std::vector<int> cn(nc);
     for (int i0 = 0; i0 < n_windows; i0 += nc) {
@@ -99,9 +98,9 @@ int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_
       // (face and carts_n always: the statistics count them; the rest only where the caller takes it)
       a.face = d_face; a.carts_n = d_carts; a.score = out.score ? d_score : nullptr; a.hash = out.path_hash ? d_hash : nullptr;
       a.shapes = out.shapes ? d_shapes : nullptr; a.landmarks = out.landmarks ? d_lm : nullptr;
-      if (out.stats) JDA_HIP(hipEventRecord(ev[0], st));
+      if (!timer.begin(st)) return false;
       JDA_HIP(launch_windows(m, a, st));
-      if (out.stats) JDA_HIP(hipEventRecord(ev[1], st));
+      if (!timer.end(st)) return false;
       JDA_HIP(hipMemcpyAsync(f.data(), d_face, cnw, hipMemcpyDeviceToHost, st));
       JDA_HIP(hipMemcpyAsync(cn.data(), d_carts, (size_t)cnw * sizeof(int), hipMemcpyDeviceToHost, st));
       if (out.score) JDA_HIP(hipMemcpyAsync(out.score + i0, d_score, (size_t)cnw * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -109,7 +108,7 @@ int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_
       if (out.shapes) JDA_HIP(hipMemcpyAsync(out.shapes + (size_t)i0 * dim, d_shapes, (size_t)cnw * dim * sizeof(float), hipMemcpyDeviceToHost, st));
       if (out.landmarks) JDA_HIP(hipMemcpyAsync(out.landmarks + (size_t)i0 * dim, d_lm, (size_t)cnw * dim * sizeof(float), hipMemcpyDeviceToHost, st));
       JDA_HIP(hipStreamSynchronize(st));
-      if (out.stats) { float ms = 0; JDA_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); device_ms += ms; }
+      if (!timer.add(&device_ms)) return false;
       for (int i = 0; i < cnw; i++) {
         if (out.is_face) out.is_face[i0 + i] = f[i];
         if (out.carts_n) out.carts_n[i0 + i] = cn[i];

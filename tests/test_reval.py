@@ -76,13 +76,20 @@ def _both_forms(c, samples, want, sizes, forms=(0, 1)):
 def test_lane_and_chunk_edges(built, gpu, tmp_path, K, n, D, L, sizes):
     """Carts at and around the 64 lanes of a wave, samples at and around the waves of a workgroup, tree depths with 1, 3 and
     5 node levels, shapes of 2 to 136 coordinates (more than one round of lane = coordinate), two stages so that stage 1 walks
-    on regressed shapes.  A constant threshold cuts some samples somewhere."""
+    on regressed shapes.  A constant threshold cuts some samples somewhere.
+    Two rows run once more from global memory (reval_lds_kb 0), the path k_reval shares with k_lbf: (65, 65, 6, 5) -- a second
+    round of carts of one lane, K % 8 = 1 rows in the regression's last batch, odd patch offsets -- and (130, 65, 4, 68) -- three
+    rounds of carts, three of coordinates, K % 8 = 2."""
     m = _model(2, K, L, D, seed=K + n, th=-0.4 * np.sqrt(K))
     c, blob = _cascador(tmp_path, m)
     patches, starts = _records(m, n, sizes, seed=n)
     want = _reference(blob, patches, starts, sizes)
     got = _both_forms(c, dict(patches=patches, shapes=starts), want, sizes)
     assert got["stats"]["lds_path"] == 1 and got["stats"]["chunks"] == 1
+    if (K, n, D, L) in ((65, 65, 6, 5), (130, 65, 4, 68)):
+        c.set_option("reval_lds_kb", 0)
+        got = _both_forms(c, dict(patches=patches, shapes=starts), want, sizes, forms=(0,))
+        assert got["stats"]["lds_path"] == 0 and got["stats"]["chunks"] == 1
     c.close()
 
 
