@@ -615,9 +615,24 @@ JDA_API long long jdaMineWindowList(int w, int h, int origin_size, int step, dou
  *
  * Feature values.  Feature::CalcFeatureValue (data.cpp:18-58) with the identity STParameter, evaluated exactly as the
  * dialect-CPP split node is everywhere in this library: fp64 (shape + offset) * side of the patch of the feature's scale,
- * round (halves away from zero), clamp into the patch, pixel difference in [-255, 255].  With jdaSetSimilarityTransform(1)
- * every entry below refuses (-1): CalcFeatureValues indexes the per-sample transform by the FEATURE index (data.cpp:168,
- * stp_mc[i]), which reads past the array whenever the pool is larger than the set -- there is no behaviour to reproduce.
+ * round (halves away from zero), clamp into the patch, pixel difference in [-255, 255].
+ *
+ * Similarity transform.  With jdaSetSimilarityTransform(1) every entry below refuses (-1) by default: CalcFeatureValues
+ * indexes the per-sample transform by the FEATURE index (data.cpp:168, stp_mc[i]), which reads past the array whenever the
+ * pool is larger than the set -- that line has no behaviour to reproduce.  Every OTHER consumer of a trained split node uses
+ * the sample's own parameter: DataSet::UpdateScores (data.cpp:312), BoostCart::GenLBF (btcart.cpp:399) and Validate
+ * (cascador.cpp:180), and the contract below -- a training sample's leaf IS Cart::Forward's -- holds only if feature f on
+ * sample j is evaluated with sample j's parameter.  THAT READING IS DEFINED HERE, a deliberate difference from the reference:
+ * stp_mc[idx[j]], with stp_mc[s] = STParameter::Calc(shape of s, mean_shape), the mean shape the cascador's.  Because it is
+ * this library's definition and not the reference's behaviour the caller opts in: jdaSetOption(cascador, "train_similarity",
+ * 1) (environment JDA_TRAIN_SIMILARITY, default 0).  With the option AND jdaSetSimilarityTransform(1) the six device entries
+ * of this block, of "closing a stage" and jdaValidateSamplesCpp run under the per-sample transform; with the transform off
+ * the option has no effect; it is the only option that turns a refusal into a result and changes no result that exists
+ * without it.  The stored parameter of the reference always equals Calc(current shape, mean_shape) where it is used
+ * (CalcSTParameters runs at each stage start, cascador.cpp:45-46, and after MoreNegSamples, data.cpp:531; shapes change only
+ * when a stage closes), so every entry derives it from samples->shapes (DataSet::CalcSTParameters, data.cpp:131-146, on the
+ * device) and jdaSamplesCpp carries no parameter array.  Outside the contract: a sample whose landmarks all coincide has
+ * scale1 == 0 and NaN parameters (jdaValidateCpp has the same gap).
  *
  * Randomness is the caller's.  The reference seeds from getTickCount() and per-thread cv::RNGs; none of it is reproducible
  * and none of it is a goal.  The caller passes, per internal node, the pool, the mode (1 classification, 0 regression: the
@@ -653,7 +668,8 @@ JDA_API long long jdaMineWindowList(int w, int h, int origin_size, int step, dou
  * sums, the host runs the sweep.  A training sample's leaf is what Cart::Forward returns for it (same feature, threshold and
  * value), so pos_leaf / neg_leaf ARE DataSet::UpdateScores (data.cpp:305-317): the caller adds out_scores[leaf].
  *
- * Reference quirks kept or avoided: stp_mc[i] indexed by feature (avoided: refused); threshold -256 sends every sample
+ * Reference quirks kept or avoided: stp_mc[i] indexed by feature (avoided: refused, or with "train_similarity" read as
+ * stp_mc[idx[j]], above); threshold -256 sends every sample
  * right (kept); the classification gates use counts while the criterion uses weights (kept); regression takes its order
  * statistic over all positives but the variance over the has_gt ones (kept). */
 
@@ -698,6 +714,15 @@ typedef struct {
 JDA_API int jdaGenFeaturePoolCpp(int F, int landmark_n, double radius, int multi_scale, uint64_t seed, uint64_t key,
                                  jdaFeatureCpp *out_features, double *out_u);
 
+/* DataSet::CalcSTParameters (data.cpp:131-146) for n shapes (n * 2L doubles, host): stp_mc[i] = STParameter::Calc(shapes[i],
+ * mean_shape) and stp_cm[i] = Calc(mean_shape, shapes[i]), each n rows of five doubles (scale, rot00, rot01, rot10, rot11);
+ * either may be NULL.  The mean shape is the cascador's.  With jdaSetSimilarityTransform off every row is STParameter's
+ * default (1, 1, 0, 0, 1; data.cpp:68-70) and the device is not touched.  No opt-in is needed: the entry trains nothing.
+ * Calc is data.cpp:72-112 in its own order, on the device (cv::norm and Mat /= double as restated for Validate: unpinned).
+ * stp_cm is what jdaShapeResidualStCpp takes.  n == 0 returns 0 without touching the device; -1: a NULL cascador, NULL
+ * shapes with n > 0, a negative n. */
+JDA_API int jdaCalcSTParametersCpp(void *cascador, const double *shapes, int n, double *stp_mc, double *stp_cm);
+
 /* CalcFeatureValues over the whole set: out[f * n + j] = value of pool[f] on sample j (F * n ints, row = feature). */
 JDA_API int jdaCalcFeatureValuesCpp(void *cascador, const jdaSamplesCpp *samples, int origin_size, int half_size,
                                     int quarter_size, const jdaFeatureCpp *pool, int F, int *out);
@@ -739,9 +764,12 @@ JDA_API int jdaTrainCartCpp(void *cascador, const jdaSamplesCpp *pos, const jdaS
  * by the resize_mode-0 chain (data.cpp:987-990, o -> h, o -> q) those are the h / q bytes the set already stores, the layout
  * of jdaSamplesCpp.patches.  The entries READ THE STORED PATCHES and resize nothing.
  *
- * Similarity transform.  With jdaSetSimilarityTransform(1) all three device entries refuse (-1): the training entries
- * refuse too, so a sample set for them cannot exist with it on.  The split node is evaluated with the identity STParameter
- * and GenDeltaShape's Apply is the identity.
+ * Similarity transform.  With jdaSetSimilarityTransform(1) the two device entries refuse (-1) unless the caller opted in with
+ * the option "train_similarity" (the training block, "Similarity transform"): the training entries refuse too, so a sample
+ * set for them cannot exist.  Without the transform the split node is evaluated with the identity STParameter and
+ * GenDeltaShape's Apply is the identity.  With both, every sample runs under stp_mc = STParameter::Calc(its shape,
+ * mean_shape) (btcart.cpp:399): the walk applies it to both offsets of every split node, and out_shapes = shapes +
+ * stp_mc.Apply(delta) (btcart.cpp:422) -- also when lbf_in is given and nothing is walked.
  *
  * Refused with -1 and jdaGetLastError(), never a crash: NULL where data is needed, K <= 0, a scale outside 0..2, a landmark
  * id outside [0, L), a patch size outside [1, 128], an lbf_in entry outside its cart's leaves.  n == 0 returns 0 without
@@ -892,7 +920,8 @@ JDA_API int jdaFitShuffleCpp(int *index, int n, uint64_t seed, int iter);
  * (tests/boost_ref.py), not against the reference.  Out of scope: the loop itself and the restart decision
  * (btcart.cpp:189-232: the caller compares will_removed with its own policy and, to restart, copies `last` back --
  * ResetScores), the call into mining (the caller invokes jdaMineNegativesCpp* and passes the result as a segment),
- * CalcSTParameters (the training entries refuse the similarity transform), snapshots, writing carts or weights into a
+ * CalcSTParameters (with "train_similarity" every entry derives the parameters from the shapes it is given;
+ * jdaCalcSTParametersCpp returns them), snapshots, writing carts or weights into a
  * model, liblinear.
  *
  * All of it is fp64 in the reference's own order.  The host entries take no cascador, use no GPU and never crash: bad
@@ -1074,8 +1103,8 @@ JDA_API int jdaPositiveShapesCpp(const int *faces, const double *landmarks, int 
 JDA_API int jdaRandomShapesCpp(const double *mean_shape, int landmark_n, int n, double shift_size, uint64_t seed,
                                uint64_t first_key, double *shapes);
 
-/* Host only: both DataSet::CalcShapeResidual overloads (data.cpp:175-208) with the identity STParameter (the training
- * entries refuse the similarity transform): over the index list idx[0 .. n) into sets of `size` samples,
+/* Host only: both DataSet::CalcShapeResidual overloads (data.cpp:175-208) with the identity STParameter (the similarity
+ * transform: jdaShapeResidualStCpp below): over the index list idx[0 .. n) into sets of `size` samples,
  *   landmark_id == -1:  residual[i][j] = gt_shapes[idx[i]][j] - cur_shapes[idx[i]][j], j < 2L       (n * 2L doubles)
  *   landmark_id >= 0:   residual[i] = the (x, y) of that landmark only                             (n * 2 doubles:
  *                       what jdaSamplesCpp.residual takes)
@@ -1085,6 +1114,15 @@ JDA_API int jdaRandomShapesCpp(const double *mean_shape, int landmark_n, int n, 
 JDA_API int jdaShapeResidualCpp(const double *gt_shapes, const double *cur_shapes, const int *shape_mask, int size,
                                 int landmark_n, const int *idx, int n, int landmark_id, double *residual,
                                 unsigned char *has_gt);
+
+/* Host only: jdaShapeResidualCpp under the similarity transform.  stp_cm: `size` rows of five doubles (scale, rot00, rot01,
+ * rot10, rot11), jdaCalcSTParametersCpp's stp_cm of the set's current shapes; row idx[i] is applied to sample i's residual as
+ * data.cpp:185 (every landmark's (x, y)) and data.cpp:203 (the one landmark) do: Apply (data.hpp:42-45) is
+ * x2 = scale * (rot00 * x + rot01 * y), y2 = scale * (rot10 * x + rot11 * y).  stp_cm == NULL gives jdaShapeResidualCpp's
+ * bits.  Refusals as jdaShapeResidualCpp's. */
+JDA_API int jdaShapeResidualStCpp(const double *gt_shapes, const double *cur_shapes, const int *shape_mask, int size,
+                                  int landmark_n, const int *idx, int n, int landmark_id, const double *stp_cm,
+                                  double *residual, unsigned char *has_gt);
 
 /* ---- Dialect CPP: the model in training ----------------------------------------------------------------------------------
  * The model the pieces above train, held by the cascador and grown IN PLACE: JoinCascador's status (current_stage_idx,
@@ -1148,7 +1186,11 @@ JDA_API int jdaModelCloseStageCpp(void *cascador, const double *w);
  * per sample (k_reval: lane = cart, the score chain replayed in cart order, the first failing cart by ballot), 1 the
  * lane-per-sample walk of jdaValidateCpp over the same records; both return identical bits.  "reval_lds_kb": the LDS a
  * workgroup of form 0 may take (a sample's patches, shape and indicators; 0: global memory).  stats (may be NULL): as for
- * jdaStageUpdateShapesCpp.  Refused with -1: jdaSetSimilarityTransform(1) (as the training entries), a patch size outside
+ * jdaStageUpdateShapesCpp.  Similarity transform: with jdaSetSimilarityTransform(1) and the option "train_similarity" (the
+ * training block) every FULL stage starts with STParameter::Calc(shape as it stands, mean_shape) (cascador.cpp:180), applied to
+ * the offsets of its walk and to its delta before the add; the partial stage of a snapshot walks with the stage before's
+ * parameter, or STParameter's default when it is stage 0 (cascador.cpp:198-209), as jdaValidateCpp does; both forms return
+ * identical bits.  Refused with -1: jdaSetSimilarityTransform(1) without that option (as the training entries), a patch size outside
  * [1, 128], NULL samples / patches / shapes with n > 0, a negative n.  n == 0 returns 0 without touching the device.
  * PARITY UNPINNED like every dialect-CPP entry: bit-exact against a sequential restatement (tests/model_ref.py). */
 JDA_API int jdaValidateSamplesCpp(void *cascador, const jdaSamplesCpp *samples, int origin_size, int half_size,

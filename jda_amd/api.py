@@ -314,6 +314,10 @@ def _load():
         lib.jdaPositiveShapesCpp.argtypes = [ip, dp, C.c_int, C.c_int, C.c_int, ip, ip, C.c_int, dp, ip, dp]
         lib.jdaRandomShapesCpp.argtypes = [dp, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint64, dp]
         lib.jdaShapeResidualCpp.argtypes = [dp, dp, ip, C.c_int, C.c_int, ip, C.c_int, C.c_int, dp, u8p]
+    if hasattr(lib, "jdaCalcSTParametersCpp"):      # (older builds, loaded through JDA_LIB_PATH for A/B runs, lack them)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        lib.jdaCalcSTParametersCpp.argtypes = [C.c_void_p, dp, C.c_int, dp, dp]
+        lib.jdaShapeResidualStCpp.argtypes = [dp, dp, ip, C.c_int, C.c_int, ip, C.c_int, C.c_int, dp, dp, u8p]
     if hasattr(lib, "jdaModelPutCartCpp"):
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
         lib.jdaCascadorCreateTrainingCpp.restype = C.c_void_p
@@ -537,10 +541,12 @@ def random_shapes_cpp(mean_shape, n, shift_size=0.0, seed=0, first_key=0):
     return out[:max(int(n), 0)]
 
 
-def shape_residual_cpp(gt_shapes, cur_shapes, idx=None, landmark_id=None, shape_mask=None):
-    """DataSet::CalcShapeResidual (reference data.cpp:175-208, identity transform; jdaShapeResidualCpp): gt - current over
-    the index list (default: every sample) -- [n, 2L] for all landmarks, [n, 2] for one landmark_id (what a sample set's
-    "residual" takes).  With shape_mask also has_gt [n] uint8 (DataSet::HasGtShape): -> (residual, has_gt)."""
+def shape_residual_cpp(gt_shapes, cur_shapes, idx=None, landmark_id=None, shape_mask=None, stp_cm=None):
+    """DataSet::CalcShapeResidual (reference data.cpp:175-208; jdaShapeResidualCpp): gt - current over the index list
+    (default: every sample) -- [n, 2L] for all landmarks, [n, 2] for one landmark_id (what a sample set's "residual"
+    takes).  With shape_mask also has_gt [n] uint8 (DataSet::HasGtShape): -> (residual, has_gt).  stp_cm ([size, 5],
+    Cascador.calc_st_parameters_cpp's): row idx[i] is applied to sample i's residual (jdaShapeResidualStCpp); None: the
+    identity transform."""
     gt = np.ascontiguousarray(gt_shapes, np.float64)
     cur = np.ascontiguousarray(cur_shapes, np.float64)
     assert gt.ndim == 2 and gt.shape == cur.shape and gt.shape[1] % 2 == 0 and gt.shape[1] > 0
@@ -552,9 +558,16 @@ def shape_residual_cpp(gt_shapes, cur_shapes, idx=None, landmark_id=None, shape_
     assert mk is None or mk.size == size
     hg = None if mk is None else np.zeros(max(ix.size, 1), np.uint8)
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
-    if lib.jdaShapeResidualCpp(gt.ctypes.data_as(dp), cur.ctypes.data_as(dp), None if mk is None else mk.ctypes.data_as(ip), size, L,
-                               ix.ctypes.data_as(ip) if ix.size else None, ix.size, lid, out.ctypes.data_as(dp),
-                               None if hg is None else _u8(hg)) != 0:
+    head = (gt.ctypes.data_as(dp), cur.ctypes.data_as(dp), None if mk is None else mk.ctypes.data_as(ip), size, L,
+            ix.ctypes.data_as(ip) if ix.size else None, ix.size, lid)
+    tail = (out.ctypes.data_as(dp), None if hg is None else _u8(hg))
+    if stp_cm is None:
+        rc = lib.jdaShapeResidualCpp(*head, *tail)
+    else:
+        cm = np.ascontiguousarray(stp_cm, np.float64)
+        assert cm.shape == (size, 5), "stp_cm must be [size, 5]"
+        rc = lib.jdaShapeResidualStCpp(*head, cm.ctypes.data_as(dp), *tail)
+    if rc != 0:
         raise JdaError(last_error())
     return out[:ix.size] if mk is None else (out[:ix.size], hg[:ix.size])
 
@@ -1363,6 +1376,18 @@ class Cascador:
         return out
 
     # -- training one CART (include/jda.h, "Dialect CPP: training one CART") ------------------------------------
+    def calc_st_parameters_cpp(self, shapes):
+        """jdaCalcSTParametersCpp: DataSet::CalcSTParameters (reference data.cpp:131-146) for [n, 2L] shapes against the
+        cascador's mean shape -> (stp_mc, stp_cm), each [n, 5] rows of (scale, rot00, rot01, rot10, rot11); the default
+        parameter (1, 1, 0, 0, 1) with the similarity transform off."""
+        sh = np.ascontiguousarray(shapes, np.float64).reshape(-1, self.dim)
+        n = sh.shape[0]
+        mc, cm = np.zeros((max(n, 1), 5), np.float64), np.zeros((max(n, 1), 5), np.float64)
+        dp = C.POINTER(C.c_double)
+        if lib.jdaCalcSTParametersCpp(self.h, sh.ctypes.data_as(dp) if n else None, n, mc.ctypes.data_as(dp), cm.ctypes.data_as(dp)) != 0:
+            raise JdaError(last_error())
+        return mc[:n], cm[:n]
+
     def calc_feature_values_cpp(self, samples, pool, origin_size=48, half_size=36, quarter_size=24):
         """DataSet::CalcFeatureValues (reference data.cpp:148-173): [F, n] int32, row = feature.  samples: dict of patches
         ([n, o*o + h*h + q*q] uint8, numpy or a torch CUDA tensor -- the layout mine_negatives_cpp returns), shapes

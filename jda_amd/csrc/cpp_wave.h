@@ -2,10 +2,12 @@
 // (Validate on a resident set) and, for the cart descent, k_mine.hip: one wave per sample, the sample's state in the wave's own
 // slice of LDS or -- where a slice does not fit -- in global memory, the same arithmetic on the same values.  Here: the
 // slice's layout for device and host, the patch copy into it, Cart::Forward on the split node of cpp_patch.h,
-// GenDeltaShape's sum, and the launch of such a kernel (wave_lds_sync / wave_global_sync: kernels_common.h).  k_mine.hip
+// GenDeltaShape's sum, the similarity transform of a sample (stp_calc_uniform, finish_common.h) on its walk and its sum, and
+// the launch of such a kernel (wave_lds_sync / wave_global_sync: kernels_common.h).  k_mine.hip
 // uses cart_forward alone; k_reval.hip everything but wave_stage_bytes (it keeps a plain loop of its own).
 #pragma once
 #include "cpp_patch.h"
+#include "finish_common.h"
 
 namespace jda {
 
@@ -82,6 +84,13 @@ __device__ __forceinline__ double gen_delta(const int* lbf, const double* wt, in
       if (k0 + u < K) delta += v[u];                     // btcart.cpp:414-420
   }
   return delta;
+}
+
+// stp_mc.Apply on GenDeltaShape's sum (btcart.cpp:422, data.cpp:116-126) with lane = coordinate: `mine` is delta[j], its
+// partner delta[j ^ 1] sits in the neighbouring lane (dim is even: both in the same round; every lane of the wave calls this).
+__device__ __forceinline__ double stp_apply_lane(const Stp<double>& p, double mine, int j) {
+  const double other = __shfl_xor(mine, 1, 64);
+  return (j & 1) ? p.scale * (p.r10 * other + p.r11 * mine) : p.scale * (p.r00 * mine + p.r01 * other);   // data.hpp:42-45
 }
 
 // How many samples (waves) of a workgroup get a slice of wave_bytes within lds_budget -- the LDS bytes a workgroup may

@@ -31,6 +31,11 @@ inline bool check_patch_sizes(int os, int hs, int qs) {
   return true;
 }
 
+// The trainer-side entries (train.cpp, stage.cpp, reval.cpp) run under the per-sample similarity transform: the transform is on
+// AND the caller opted into this library's reading of data.cpp:168 (option "train_similarity", include/jda.h).  On without the
+// option: they refuse.
+inline bool train_similarity(const Cascador* c) { return c->similarity && c->kn.train_similarity; }
+
 // train.cpp: a caller's sample set / pool features as the trainer-side entries accept them (fail() says what is wrong)
 bool check_set(const jdaSamplesCpp* s, const char* name, bool need_weights);
 bool check_pool(const jdaFeatureCpp* pool, size_t count, int L);

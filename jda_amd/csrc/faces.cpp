@@ -188,6 +188,33 @@ int build_positives(FacesCall x) {
   return run_faces(x) ? 0 : -1;
 }
 
+// DataSet::CalcShapeResidual (data.cpp:175-208); stp_cm: null -- the identity transform, nothing is applied -- or size rows of
+// (scale, rot00, rot01, rot10, rot11), row idx[i] applied to sample i's residual (data.cpp:185, 203; Apply: data.hpp:42-45).
+int shape_residual(const double* gt_shapes, const double* cur_shapes, const int* shape_mask, int size, int landmark_n, const int* idx,
+                   int n, int landmark_id, const double* stp_cm, double* residual, unsigned char* has_gt) {
+  if (size < 0 || n < 0 || landmark_n < 1 || (n > 0 && (!gt_shapes || !cur_shapes || !idx))) { fail("bad arguments"); return -1; }
+  if (landmark_id < -1 || landmark_id >= landmark_n) { fail("landmark_id must be -1 (all landmarks) or in [0, landmark_n)"); return -1; }
+  if (has_gt && !shape_mask) { fail("bad arguments: has_gt needs shape_mask"); return -1; }
+  for (int i = 0; i < n; i++)
+    if (idx[i] < 0 || idx[i] >= size) { fail("idx[" + std::to_string(i) + "] = " + std::to_string(idx[i]) + " is outside [0, " + std::to_string(size) + ")"); return -1; }
+  const size_t dim = 2 * (size_t)landmark_n;
+  for (int i = 0; i < n; i++) {
+    const double* g = gt_shapes + (size_t)idx[i] * dim;
+    const double* s = cur_shapes + (size_t)idx[i] * dim;
+    const double* p = stp_cm ? stp_cm + 5 * (size_t)idx[i] : nullptr;
+    auto put = [&](double x, double y, double* out) {
+      if (p) { out[0] = p[0] * (p[1] * x + p[2] * y); out[1] = p[0] * (p[3] * x + p[4] * y); }
+      else { out[0] = x; out[1] = y; }
+    };
+    if (residual) {
+      if (landmark_id < 0) for (size_t j = 0; j < dim; j += 2) put(g[j] - s[j], g[j + 1] - s[j + 1], residual + (size_t)i * dim + j);   // data.cpp:184-185
+      else put(g[2 * landmark_id] - s[2 * landmark_id], g[2 * landmark_id + 1] - s[2 * landmark_id + 1], residual + 2 * (size_t)i);     // data.cpp:199-205
+    }
+    if (has_gt) has_gt[i] = shape_mask[idx[i]] > 0 ? 1 : 0;                                               // DataSet::HasGtShape
+  }
+  return 0;
+}
+
 }  // namespace
 }  // namespace jda
 
@@ -294,25 +321,13 @@ int jdaRandomShapesCpp(const double* mean_shape, int landmark_n, int n, double s
 int jdaShapeResidualCpp(const double* gt_shapes, const double* cur_shapes, const int* shape_mask, int size, int landmark_n,
                         const int* idx, int n, int landmark_id, double* residual, unsigned char* has_gt) try {
   g_err.clear();
-  if (size < 0 || n < 0 || landmark_n < 1 || (n > 0 && (!gt_shapes || !cur_shapes || !idx))) { fail("bad arguments"); return -1; }
-  if (landmark_id < -1 || landmark_id >= landmark_n) { fail("landmark_id must be -1 (all landmarks) or in [0, landmark_n)"); return -1; }
-  if (has_gt && !shape_mask) { fail("bad arguments: has_gt needs shape_mask"); return -1; }
-  for (int i = 0; i < n; i++)
-    if (idx[i] < 0 || idx[i] >= size) { fail("idx[" + std::to_string(i) + "] = " + std::to_string(idx[i]) + " is outside [0, " + std::to_string(size) + ")"); return -1; }
-  const size_t dim = 2 * (size_t)landmark_n;
-  for (int i = 0; i < n; i++) {
-    const double* g = gt_shapes + (size_t)idx[i] * dim;
-    const double* s = cur_shapes + (size_t)idx[i] * dim;
-    if (residual) {
-      if (landmark_id < 0) for (size_t j = 0; j < dim; j++) residual[(size_t)i * dim + j] = g[j] - s[j];      // data.cpp:184
-      else {                                                                                              // data.cpp:199-205
-        residual[2 * (size_t)i] = g[2 * landmark_id] - s[2 * landmark_id];
-        residual[2 * (size_t)i + 1] = g[2 * landmark_id + 1] - s[2 * landmark_id + 1];
-      }
-    }
-    if (has_gt) has_gt[i] = shape_mask[idx[i]] > 0 ? 1 : 0;                                               // DataSet::HasGtShape
-  }
-  return 0;
+  return shape_residual(gt_shapes, cur_shapes, shape_mask, size, landmark_n, idx, n, landmark_id, nullptr, residual, has_gt);
+} JDA_ABI_CATCH(-1)
+
+int jdaShapeResidualStCpp(const double* gt_shapes, const double* cur_shapes, const int* shape_mask, int size, int landmark_n,
+                          const int* idx, int n, int landmark_id, const double* stp_cm, double* residual, unsigned char* has_gt) try {
+  g_err.clear();
+  return shape_residual(gt_shapes, cur_shapes, shape_mask, size, landmark_n, idx, n, landmark_id, stp_cm, residual, has_gt);
 } JDA_ABI_CATCH(-1)
 
 }  // extern "C"

@@ -52,6 +52,73 @@ __device__ __forceinline__ Stp<double> stp_calc(const double* s1, const double* 
   return p;
 }
 
+// STParameter::Calc without scratch, in two parts, for the trainer's kernels (k_stp: a lane per sample; k_lbf, k_reval: every
+// lane of a sample's wave runs the same chain, so the parameter is wave-uniform): the centred values are recomputed where
+// stp_calc stores them -- the same operations on the same values in the same order, so the bits are stp_calc's.
+// One shape's side of data.cpp:72-98: its centre, cv::norm of the centred vector, the reciprocal `Mat_ /= s` multiplies by.
+struct StpSide { double cx, cy, scale, inv; };
+template <typename Load>                     // s(i): coordinate i of the shape, i < 2L
+__device__ __forceinline__ StpSide stp_side(const Load& s, int L) {
+  StpSide a;
+  double xc = 0., yc = 0.;
+  for (int i = 0; i < L; i++) { xc += s(2 * i); yc += s(2 * i + 1); }
+  xc /= (double)L; yc /= (double)L;
+  double q = 0.;
+  int i = 0;                                 // (i stays even: v0, v2 are x, v1, v3 are y)
+  for (; i <= 2 * L - 4; i += 4) {
+    const double v0 = s(i) - xc, v1 = s(i + 1) - yc, v2 = s(i + 2) - xc, v3 = s(i + 3) - yc;
+    q += v0 * v0 + v1 * v1 + v2 * v2 + v3 * v3;
+  }
+  if (i < 2 * L) { const double v0 = s(i) - xc, v1 = s(i + 1) - yc; q += v0 * v0; q += v1 * v1; }   // (2L mod 4 is 0 or 2: the tail is one x, one y)
+  a.cx = xc; a.cy = yc; a.scale = sqrt(q); a.inv = 1. / a.scale;
+  return a;
+}
+// one coordinate centred and normalised (data.cpp:89-98): c is the side's cx for an x, its cy for a y
+__device__ __forceinline__ double stp_unit(double v, double c, double inv) { return (v - c) * inv + 0.; }
+// data.cpp:96, 100-111 from the two normalised vectors -- n1(i, &x, &y), n2(i, &x, &y): landmark i of each -- *mc = Calc(shape1,
+// shape2) and, CM, *cm = Calc(shape2, shape1) from the same pass (DataSet::CalcSTParameters' pair, data.cpp:134-135), each
+// with add chains of its own.
+template <bool CM, typename N1, typename N2>
+__device__ __forceinline__ void stp_rot(const N1& n1, double scale1, const N2& n2, double scale2, int L, Stp<double>* mc, Stp<double>* cm) {
+  double num = 0., den = 0., num2 = 0., den2 = 0.;
+  for (int i = 0; i < L; i++) {
+    double ax, ay, bx, by;
+    n1(i, &ax, &ay); n2(i, &bx, &by);
+    num += ay * bx - ax * by;
+    den += ax * bx + ay * by;
+    if (CM) { num2 += by * ax - bx * ay; den2 += bx * ax + by * ay; }
+  }
+  mc->scale = scale1 / scale2;
+  const double norm = sqrt(num * num + den * den);
+  const double sn = num / norm, cs = den / norm;
+  mc->r00 = cs; mc->r01 = -sn; mc->r10 = sn; mc->r11 = cs;
+  if (CM) {
+    cm->scale = scale2 / scale1;
+    const double norm2 = sqrt(num2 * num2 + den2 * den2);
+    const double sn2 = num2 / norm2, cs2 = den2 / norm2;
+    cm->r00 = cs2; cm->r01 = -sn2; cm->r10 = sn2; cm->r11 = cs2;
+  }
+}
+// Calc(shape, mean) whole, for the kernels that hold one sample per wave: s(c) coordinate c of the shape, mean [2L] as stored.
+template <typename Load>
+__device__ __forceinline__ Stp<double> stp_calc_uniform(const Load& s, const double* __restrict__ mean, int L) {
+  const auto m = [&](int c) { return mean[c]; };
+  const StpSide a = stp_side(s, L), b = stp_side(m, L);
+  Stp<double> p;
+  stp_rot<false>([&](int i, double* x, double* y) { *x = stp_unit(s(2 * i), a.cx, a.inv); *y = stp_unit(s(2 * i + 1), a.cy, a.inv); }, a.scale,
+                 [&](int i, double* x, double* y) { *x = stp_unit(m(2 * i), b.cx, b.inv); *y = stp_unit(m(2 * i + 1), b.cy, b.inv); }, b.scale,
+                 L, &p, (Stp<double>*)nullptr);
+  return p;
+}
+// stp_mc.Apply on both offsets of a split node (data.cpp:41-42)
+template <typename Node>
+__device__ __forceinline__ void stp_apply_offsets(const Stp<double>& p, Node& nd) {
+  double ax, ay, bx, by;
+  stp_apply<double>(p, nd.o1x, nd.o1y, &ax, &ay);
+  stp_apply<double>(p, nd.o2x, nd.o2y, &bx, &by);
+  nd.o1x = ax; nd.o1y = ay; nd.o2x = bx; nd.o2y = by;
+}
+
 // Where a window reads its pixels for one feature scale.
 struct View {
   const uint8_t* img; int w, h, ox, oy;

@@ -148,6 +148,7 @@ inline long long env_ll(const char* name, long long dflt) {
   X(fit_lds_kb, "JDA_FIT_LDS_KB", 160)      /* LDS in KB a workgroup of k_fit (a stage's global regression, fit.cpp) may take, counted in granules; where one coordinate's column of w does not fit it, the kernel works on the column in global memory (0: always) */ \
   X(reval_form, "JDA_REVAL_FORM", 0)        /* jdaValidateSamplesCpp (reval.cpp): 0 a wave per sample (k_reval), 1 a lane per sample (k_mine_walk on the same records): identical bits, for A/B and as a check */ \
   X(reval_lds_kb, "JDA_REVAL_LDS_KB", 160)  /* LDS in KB a workgroup of k_reval may take; where one sample's slice (patches, shape, a stage's indicators) does not fit it, the kernel works in global memory (0: always) */ \
+  X(train_similarity, "JDA_TRAIN_SIMILARITY", 0) /* with jdaSetSimilarityTransform(1): 1 lets the trainer entries (train.cpp, stage.cpp, reval.cpp) run under the per-sample STParameter of the sample's own shape -- this library's reading of data.cpp:168, include/jda.h; 0: they refuse.  The only option that turns a refusal into a result; no effect with the transform off */ \
   X(windows_tile, "JDA_WINDOWS_TILE", -1)   /* jdaValidateWindows (windows.cpp): windows up to this side walk from an LDS copy of their pixels, within the finishing kernels' LDS budget (-1: as large as that budget allows, 0: every pixel is read from the frame): identical bits */ \
   X(fit_ahead, "JDA_FIT_AHEAD", 2)          /* ... epochs queued ahead of the one whose state words the host inspects (fit_ahead + 1 rotating order buffers; results do not depend on it) */ \
   X(ragged_chunk_min_windows, "JDA_RAGGED_CHUNK_MIN_WINDOWS", 1500000) /* ... and at least, where a small job is cut into ragged_split chunks */ \
@@ -232,7 +233,7 @@ struct Knobs {
     static const char* const non_negative[] = {"workspace_mb", "handoff", "plan_cache", "lanes", "ragged_chunk_windows", "ragged_chunk_windows_cpp", "mine_chunk_windows",
                                                "ragged_chunk_min_windows", "h2d_min_bytes", "merge_blocks", "wide_max", "lanes_min_windows", "ragged_single_windows",
                                                "scan_p_handoff", "scan_p_slots", "max_lanes", "lane_idle_calls", "scan_p_tile_kb", "scan_p_grid",
-                                               "ws_min_entries", "ws_factor_pct", "lbf_lds_kb", "fit_lds_kb", "fit_ahead", "reval_lds_kb", "reval_form"};
+                                               "ws_min_entries", "ws_factor_pct", "lbf_lds_kb", "fit_lds_kb", "fit_ahead", "reval_lds_kb", "reval_form", "train_similarity"};
     for (const char* k : non_negative) if (std::strcmp(key, k) == 0 && v < 0) return false;
     if (std::strcmp(key, "workspace_mb") == 0 && v < 1) return false;
 #define X(name, env, dflt) if (std::strcmp(key, #name) == 0) { name = v; return true; }

@@ -16,6 +16,10 @@
 //            regress  a sample that passed the stage: lane = shape coordinate, gen_delta -- w[lbf[k]][j] for k = 0 .. K-1
 //                     in cart order (btcart.cpp:407-424) -- then shape += delta
 //            The partial stage of a snapshot runs its `part` carts and no regression (cascador.cpp:198-209).
+//            ST = true (train_similarity, include/jda.h): at the start of every full stage every lane runs STParameter::Calc(shape
+//            as it stands, mean_shape) (cascador.cpp:180; stp_calc_uniform: no scratch, wave-uniform); the walk applies it to the
+//            node's offsets, the regression to the sum before the add (btcart.cpp:422).  The partial stage walks with the stage
+//            before's parameter, the first stage with STParameter's default -- as k_mine_walk.  ST = false is the code it was.
 // Whole waves only: no workgroup barrier, no atomics, no spinning, nothing between waves.  The model's tables are the
 // mining tables, patched in place between launches (model_grow.cpp): every read of them has a lane-dependent address --
 // lane = cart in the walk, lane = coordinate in the regression -- so they are vector loads; nothing of them is read
@@ -45,7 +49,7 @@ __device__ __forceinline__ uint8_t* reval_stage_bytes(uint8_t* lds, const uint8_
 
 }  // namespace
 
-template <bool LDS>
+template <bool LDS, bool ST>
 __global__ __launch_bounds__(64 * kSampleWaves) void k_reval(RevalArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char reval_lds[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -78,10 +82,13 @@ __global__ __launch_bounds__(64 * kSampleWaves) void k_reval(RevalArgs a) {
   int nn = 0;
   bool is_face = true;
   const int stages = m.full + (m.part > 0 ? 1 : 0);
+  [[maybe_unused]] Stp<double> stp;
+  [[maybe_unused]] bool apply = false;                   // (false: STParameter's default, the offsets as stored)
   [[maybe_unused]] const long long nodes_all = (long long)m.T * K * node_n, leaves_all = (long long)m.T * K * leaf_n;
   for (int t = 0; t < stages && is_face; t++) {
     const bool partial = t == m.full;                    // the stage in training: `part` carts, no regression
     const int Kt = partial ? m.part : K;
+    if (ST && !partial) { stp = stp_calc_uniform([&](int c) { return sh[c]; }, m.mean, dim >> 1); apply = true; }   // cascador.cpp:180
     for (int k0 = 0; k0 < Kt && is_face; k0 += 64) {
       const int k = k0 + lane;
       const bool active = k < Kt;
@@ -91,7 +98,7 @@ __global__ __launch_bounds__(64 * kSampleWaves) void k_reval(RevalArgs a) {
         const int leaf = cart_forward(pat, sh, m.D, dim, [&](int, int node) {   // (heap node `node`, 1-based, is record node - 1)
           JDA_BC(Bc(0, nodes_all), (long long)(ck * node_n + node - 1), 1, kBcNodeTable);
           return m.nodes[ck * node_n + node - 1];
-        });
+        }, [&](NodeD& nd) { if (ST && apply) stp_apply_offsets(stp, nd); });
         JDA_BC(Bc(0, leaves_all), (long long)(ck * leaf_n + leaf), 1, kBcNodeTable);
         lbf[k] = k * leaf_n + leaf;                      // cascador.cpp:192
         lf = m.leaf[ck * leaf_n + leaf]; mu = m.cmean[ck]; sd = m.cstd[ck]; th = m.cth[ck];
@@ -117,8 +124,16 @@ __global__ __launch_bounds__(64 * kSampleWaves) void k_reval(RevalArgs a) {
     if (LDS) wave_lds_sync(); else wave_global_sync();  // the stage's indicators, written by their carts' lanes
     // ---- GenDeltaShape (btcart.cpp:407-424) and shape += delta (cascador.cpp:196): lane = coordinate, rows in cart order
     const double* wt = m.w + (size_t)t * K * leaf_n * dim;
-    for (int j = lane; j < dim; j += 64)                 // (coordinate j is read and written by this lane alone)
-      sh[j] = sh[j] + gen_delta(lbf, wt, dim, K, j, (long long)K * leaf_n);
+    if (ST) {
+      for (int j0 = 0; j0 < dim; j0 += 64) {             // (whole rounds: a coordinate's partner is a lane of this round)
+        const int j = j0 + lane;
+        const double delta = stp_apply_lane(stp, j < dim ? gen_delta(lbf, wt, dim, K, j, (long long)K * leaf_n) : 0., j);
+        if (j < dim) sh[j] = sh[j] + delta;
+      }
+    } else {
+      for (int j = lane; j < dim; j += 64)               // (coordinate j is read and written by this lane alone)
+        sh[j] = sh[j] + gen_delta(lbf, wt, dim, K, j, (long long)K * leaf_n);
+    }
     if (LDS) wave_lds_sync(); else wave_global_sync();  // the next stage's walk reads every coordinate
   }
   if (LDS) for (int j = lane; j < dim; j += 64) sh_g[j] = sh_l[j];
@@ -131,7 +146,8 @@ hipError_t launch_reval(const RevalArgs& a, int lds_budget, WaveLaunch* how, hip
   if (a.m.K < 1 || a.m.D < 1 || a.m.D > 20 || a.m.dim < 2) return hipErrorInvalidValue;
   const long long pbytes = (long long)a.os * a.os + (long long)a.hs * a.hs + (long long)a.qs * a.qs;
   *how = plan_wave_slices(WaveSlice(a.m.dim, a.m.K, pbytes, true).bytes, kSampleWaves, lds_budget);
-  return launch_wave_slices(k_reval<true>, k_reval<false>, a, a.n, *how, stream);
+  if (a.st) return launch_wave_slices(k_reval<true, true>, k_reval<false, true>, a, a.n, *how, stream);
+  return launch_wave_slices(k_reval<true, false>, k_reval<false, false>, a, a.n, *how, stream);
 }
 
 JDA_BC_READER(k_reval)

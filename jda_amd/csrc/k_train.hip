@@ -1,14 +1,18 @@
 // HIP kernels of dialect CPP's CART training for gfx950 (reference src/jda/cart.cpp:41-350, Cart::Train / SplitNode /
 // SplitNodeWithClassification / SplitNodeWithRegression, and DataSet::CalcFeatureValues, data.cpp:148-173):
 //   k_train_transpose  shapes [n][2L] -> [2L][n]
-//   k_train_values     lane = sample of a node's list, loop over a tile of the pool: Feature::CalcFeatureValue with the
-//                      identity STParameter (data.cpp:18-58) -> 16-bit values [feature][position in the list]
+//   k_stp_mean / k_stp DataSet::CalcSTParameters (data.cpp:131-146): the mean shape's side of STParameter::Calc once per call,
+//                      then lane = sample over the transposed shapes -> stp_mc (and stp_cm) as five planes [5][n]
+//   k_train_values     lane = sample of a node's list, loop over a tile of the pool: Feature::CalcFeatureValue (data.cpp:18-58)
+//                      with the identity STParameter (ST = false) or the sample's own stp_mc (ST = true: train_similarity,
+//                      include/jda.h) -> 16-bit values [feature][position in the list]
 //   k_train_hist       wave = feature: the 511-bin count histogram and the weighted one, every bin's weights added in
 //                      list order (cart.cpp:199-208) -- the order decides bits
 //   k_train_var        lane = feature: the order statistic from the counts (cart.cpp:314-320), then the eight sums of
 //                      the left / right residuals in list order (cart.cpp:321-334)
 // No log() here: the entropy sweep and the leaf scores are host work on these kernels' outputs (train.cpp).
 #include "cpp_patch.h"
+#include "finish_common.h"
 
 namespace jda {
 
@@ -38,6 +42,7 @@ hipError_t launch_train_transpose(const double* in, int n, int dim, double* out,
 
 constexpr int kTrainFeatTile = 64;
 
+template <bool ST>
 __global__ __launch_bounds__(256) void k_train_values(TrainSet set, const int* __restrict__ list, int count,
                                                       const TrainFeat* __restrict__ pool, int F, short* __restrict__ out,
                                                       size_t stride) {
@@ -47,9 +52,15 @@ __global__ __launch_bounds__(256) void k_train_values(TrainSet set, const int* _
   const PatchSet pat{set.patches + (size_t)s * (size_t)(set.os * set.os + set.hs * set.hs + set.qs * set.qs), set.os, set.hs, set.qs};
   const double* sh = set.shapes_t + s;
   const size_t n = (size_t)set.n;
+  Stp<double> stp;
+  if (ST) {                                             // the sample's own stp_mc, once (k_stp's planes)
+    JDA_BC(Bc(0, set.n), s, 1, kBcQueue);
+    stp.scale = set.stp[s]; stp.r00 = set.stp[n + s]; stp.r01 = set.stp[2 * n + s]; stp.r10 = set.stp[3 * n + s]; stp.r11 = set.stp[4 * n + s];
+  }
   const int f0 = blockIdx.y * kTrainFeatTile, f1 = min(F, f0 + kTrainFeatTile);
   for (int f = f0; f < f1; f++) {
-    const TrainFeat ft = pool[f];                       // wave-uniform: scalar loads
+    TrainFeat ft = pool[f];                             // wave-uniform: scalar loads
+    if (ST) stp_apply_offsets(stp, ft);                 // data.cpp:41-42
     out[(size_t)f * stride + j] = (short)pat.feature(ft, sh[(size_t)(2 * ft.lm1) * n], sh[(size_t)(2 * ft.lm1 + 1) * n],
                                                      sh[(size_t)(2 * ft.lm2) * n], sh[(size_t)(2 * ft.lm2 + 1) * n]);
   }
@@ -58,8 +69,52 @@ __global__ __launch_bounds__(256) void k_train_values(TrainSet set, const int* _
 hipError_t launch_train_values(const TrainSet& set, const int* list, int count, const TrainFeat* pool, int F, short* out,
                                size_t stride, hipStream_t stream) {
   if (count <= 0 || F <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_train_values, dim3((count + 255) / 256, (F + kTrainFeatTile - 1) / kTrainFeatTile), dim3(256), 0, stream, set,
-                     list, count, pool, F, out, stride);
+  const dim3 grid((count + 255) / 256, (F + kTrainFeatTile - 1) / kTrainFeatTile);
+  if (set.stp) hipLaunchKernelGGL(k_train_values<true>, grid, dim3(256), 0, stream, set, list, count, pool, F, out, stride);
+  else hipLaunchKernelGGL(k_train_values<false>, grid, dim3(256), 0, stream, set, list, count, pool, F, out, stride);
+  return hipGetLastError();
+}
+
+// =============================================================================
+// k_stp_mean, k_stp: DataSet::CalcSTParameters
+// =============================================================================
+// The mean shape's side of STParameter::Calc is the same for every sample: one wave forms it once per call -- every lane the
+// same chain, on the device, so that sqrt and the division are the ones the samples' side uses -- and leaves
+// ms[0 .. 4) = centre x, centre y, cv::norm, its reciprocal and ms[4 + i] = coordinate i centred and normalised.
+__global__ __launch_bounds__(64) void k_stp_mean(const double* __restrict__ mean, int L, double* __restrict__ ms) {
+  const int lane = threadIdx.x;
+  const StpSide b = stp_side([&](int i) { return mean[i]; }, L);
+  if (lane == 0) { ms[0] = b.cx; ms[1] = b.cy; ms[2] = b.scale; ms[3] = b.inv; }
+  for (int l = lane; l < L; l += 64) { ms[4 + 2 * l] = stp_unit(mean[2 * l], b.cx, b.inv); ms[5 + 2 * l] = stp_unit(mean[2 * l + 1], b.cy, b.inv); }
+}
+
+// lane = sample i over shapes_t [2L][n] (coalesced): stp_mc = Calc(shape, mean_shape) and stp_cm = Calc(mean_shape, shape)
+// (data.cpp:134-135) as planes [5][n] -- scale, rot00, rot01, rot10, rot11 -- either may be null.  The centred values are
+// recomputed, not stored: no scratch.  stp_cm is a second pair of add chains in the same pass, not derived from stp_mc:
+// negating the sine turns a +0. into a -0. where Calc gives +0. (a shape that equals the mean shape; tests/test_train_st_host.py).
+__global__ __launch_bounds__(256) void k_stp(const double* __restrict__ shapes_t, int n, int L, const double* __restrict__ ms,
+                                             double* __restrict__ stp_mc, double* __restrict__ stp_cm) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t N = (size_t)n;
+  const auto s = [&](int c) {
+    JDA_BC(Bc(0, (long long)2 * L * n), (size_t)c * N + i, 1, kBcLandmark);
+    return shapes_t[(size_t)c * N + i];
+  };
+  const StpSide a = stp_side(s, L);
+  Stp<double> mc, cm;
+  stp_rot<true>([&](int l, double* x, double* y) { *x = stp_unit(s(2 * l), a.cx, a.inv); *y = stp_unit(s(2 * l + 1), a.cy, a.inv); }, a.scale,
+                [&](int l, double* x, double* y) { *x = ms[4 + 2 * l]; *y = ms[5 + 2 * l]; }, ms[2], L, &mc, &cm);
+  if (stp_mc) { stp_mc[i] = mc.scale; stp_mc[N + i] = mc.r00; stp_mc[2 * N + i] = mc.r01; stp_mc[3 * N + i] = mc.r10; stp_mc[4 * N + i] = mc.r11; }
+  if (stp_cm) { stp_cm[i] = cm.scale; stp_cm[N + i] = cm.r00; stp_cm[2 * N + i] = cm.r01; stp_cm[3 * N + i] = cm.r10; stp_cm[4 * N + i] = cm.r11; }
+}
+
+hipError_t launch_stp(const double* shapes_t, int n, int L, const double* mean, double* ms, double* stp_mc, double* stp_cm,
+                      hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  if (L < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_stp_mean, dim3(1), dim3(64), 0, stream, mean, L, ms);
+  hipLaunchKernelGGL(k_stp, dim3((n + 255) / 256), dim3(256), 0, stream, shapes_t, n, L, (const double*)ms, stp_mc, stp_cm);
   return hipGetLastError();
 }
 

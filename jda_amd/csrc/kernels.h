@@ -433,14 +433,20 @@ hipError_t launch_mine_sum(const int* status, unsigned long long n, unsigned lon
 // One pool feature: the fields of Feature (include/jda/common.hpp), jdaFeatureCpp's layout.
 struct TrainFeat { int scale, lm1, lm2, pad; double o1x, o1y, o2x, o2y; };
 // A sample set on the device: patches tight (o, h, q back to back per sample), shapes TRANSPOSED [2L][n] so that the
-// lanes of a wave (lane = sample, the landmark wave-uniform) read neighbouring doubles.
-struct TrainSet { const uint8_t* patches; const double* shapes_t; int n, os, hs, qs; };
+// lanes of a wave (lane = sample, the landmark wave-uniform) read neighbouring doubles.  stp: nullptr -- the identity
+// STParameter -- or every sample's stp_mc as launch_stp writes it, five planes [5][n] (train_similarity, include/jda.h).
+struct TrainSet { const uint8_t* patches; const double* shapes_t; int n, os, hs, qs; const double* stp; };
 constexpr int kTrainBins = 511;          // value + 255, cart.cpp:197-198
 // Per-feature ordered sums of the regression split (cart.cpp:321-334): left / right x, x*x, y, y*y and the counts.
 struct TrainVar { double s[8]; int n_left, n_right, th, pad; };
 
 // shapes [n][dim] -> [dim][n]
 hipError_t launch_train_transpose(const double* in, int n, int dim, double* out, hipStream_t stream);
+// DataSet::CalcSTParameters (data.cpp:131-146) over shapes_t [2L][n]: stp_mc = Calc(shape, mean), stp_cm = Calc(mean, shape) as
+// planes [5][n] (scale, rot00, rot01, rot10, rot11; either may be null).  mean [2L] as stored; ms: 4 + 2L doubles of scratch
+// (the mean shape's side of Calc, formed once).
+hipError_t launch_stp(const double* shapes_t, int n, int L, const double* mean, double* ms, double* stp_mc, double* stp_cm,
+                      hipStream_t stream);
 // CalcFeatureValues: out[f * stride + j] = value of pool feature f on sample list[j] (list == nullptr: sample j), j < count.
 hipError_t launch_train_values(const TrainSet& set, const int* list, int count, const TrainFeat* pool, int F, short* out,
                                size_t stride, hipStream_t stream);
@@ -461,10 +467,13 @@ inline size_t lbf_node_at(int K, int k, int i, int d) { return (size_t)K * (((si
 constexpr int kSampleWaves = 4;          // samples (waves) of a workgroup at most, in the wave-per-sample kernels (cpp_wave.h)
 // One chunk of a resident sample set (device pointers).  walk = 1: the carts are walked and lbf [n][K] is written;
 // walk = 0: lbf is read.  w != nullptr: out_shapes [n][dim] = shapes + the K rows of w [K * 2^(D-1)][dim] in cart order.
+// mean != nullptr (train_similarity, include/jda.h): the mean shape [dim] as stored -- every sample walks and updates under
+// its own STParameter::Calc(shape, mean) (btcart.cpp:399, 422).
 struct LbfArgs {
   const uint8_t* patches; const double* shapes; const NodeD* nodes; const double* w;
   int* lbf; double* out_shapes;
   int n, K, D, dim, os, hs, qs, walk;
+  const double* mean;
 };
 struct WaveLaunch { int lds, waves, lds_bytes; };  // how a wave-per-sample kernel ran: staged in LDS (1) or from global memory (0), waves and LDS bytes per workgroup
 // lds_budget: the LDS bytes a workgroup may take (at most the CU's 160 KB); where one sample's slice does not fit, the
@@ -480,6 +489,7 @@ struct RevalArgs {
   const uint8_t* patches; const double* start;
   uint8_t* face; int* carts_n; double* score; double* shape; int* lbf;
   int n, os, hs, qs;
+  int st;                      // 1: the similarity transform (train_similarity, include/jda.h), per full stage from the shape as it stands
 };
 // lds_budget and how (never null) as launch_lbf's.
 hipError_t launch_reval(const RevalArgs& a, int lds_budget, WaveLaunch* how, hipStream_t stream);

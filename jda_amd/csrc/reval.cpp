@@ -15,7 +15,7 @@ int reval_entry(Cascador* c, const jdaSamplesCpp* s, int os, int hs, int qs, uns
   if (stats) std::memset(stats, 0, sizeof *stats);
   if (!c) { fail("bad arguments"); return -1; }
   if (!check_patch_sizes(os, hs, qs)) return -1;
-  if (c->similarity) {
+  if (c->similarity && !c->kn.train_similarity) {        // (refused unless the caller opted in: include/jda.h)
     fail(std::string(fn) + ": refused with jdaSetSimilarityTransform(1): the training entries refuse with it on (data.cpp:168), "
          "so a sample set for this entry cannot exist");
     return -1;
@@ -29,6 +29,7 @@ int reval_entry(Cascador* c, const jdaSamplesCpp* s, int os, int hs, int qs, uns
   const size_t pbytes = (size_t)os * os + (size_t)hs * hs + (size_t)qs * qs;
   const bool host_patches = !s->patches_on_device;
   const bool lane_form = c->kn.reval_form == 1;
+  const int st_on = train_similarity(c) ? 1 : 0;         // cascador.cpp:180: every full stage under Calc(shape as it stands, mean_shape)
   double upload_ms = 0, device_ms = 0, download_ms = 0;
 
   OneLane one(c);
@@ -68,11 +69,11 @@ int reval_entry(Cascador* c, const jdaSamplesCpp* s, int os, int hs, int qs, uns
       if (!timer.begin(st)) return false;
       if (lane_form) {
         const MineSizes z{os, hs, qs, 0, 0., 0ull};
-        JDA_HIP(launch_mine_walk(m, z, nullptr, cn, pat, (int)pbytes, 0, d_face, d_carts, d_score, d_shape, d_lbf, d_t1, d_t2, st, d_start));
+        JDA_HIP(launch_mine_walk(m, z, nullptr, cn, pat, (int)pbytes, st_on, d_face, d_carts, d_score, d_shape, d_lbf, d_t1, d_t2, st, d_start));
       } else {
         RevalArgs a{};
         a.m = m; a.patches = pat; a.start = d_start; a.face = d_face; a.carts_n = d_carts; a.score = d_score; a.shape = d_shape;
-        a.lbf = d_lbf; a.n = cn; a.os = os; a.hs = hs; a.qs = qs;
+        a.lbf = d_lbf; a.n = cn; a.os = os; a.hs = hs; a.qs = qs; a.st = st_on;
         JDA_HIP(launch_reval(a, lds_budget, &how, st));
       }
       if (!timer.end(st)) return false;

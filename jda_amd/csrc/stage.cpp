@@ -30,7 +30,7 @@ bool check_call(StageCall& x, const char* fn, bool* empty) {
   Cascador* c = x.c;
   if (!c) { fail("bad arguments"); return false; }
   if (!check_patch_sizes(x.os, x.hs, x.qs)) return false;
-  if (c->similarity) {
+  if (c->similarity && !c->kn.train_similarity) {        // (refused unless the caller opted in: include/jda.h)
     fail(std::string(fn) + ": refused with jdaSetSimilarityTransform(1): the training entries refuse with it on (data.cpp:168), "
          "so a sample set for this entry cannot exist");
     return false;
@@ -82,6 +82,7 @@ bool run_call(StageCall& x) {
   const int n = s->n, K = x.K, D = c->hm.D, L = c->hm.L, dim = 2 * L;
   const int leaf_n = 1 << (D - 1), inner = leaf_n - 1;
   const bool walk = x.lbf_in == nullptr, update = x.out_shapes != nullptr;
+  const bool st_on = train_similarity(c);                // every sample under STParameter::Calc(its shape, mean_shape), btcart.cpp:399, 422
   const size_t pbytes = (size_t)x.os * x.os + (size_t)x.hs * x.hs + (size_t)x.qs * x.qs;
   const bool host_patches = walk && !s->patches_on_device;
   double upload_ms = 0, device_ms = 0, download_ms = 0;
@@ -112,8 +113,9 @@ bool run_call(StageCall& x) {
   const int nc = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, room / per));
 
   CallBuf buf;
-  NodeD* d_nodes; double* d_w; double* d_sh; double* d_out; int* d_lbf; uint8_t* d_pat;
+  NodeD* d_nodes; double* d_w; double* d_sh; double* d_out; int* d_lbf; uint8_t* d_pat; double* d_mean = nullptr;
   if (!carve_into(buf, [&](Carver& cv) {
+        if (st_on) d_mean = cv.take<double>(dim);
         d_nodes = cv.take<NodeD>(std::max<size_t>(nodes.size(), 1));
         d_w = update ? cv.take<double>(w_count) : nullptr;
         d_sh = cv.take<double>((size_t)nc * dim);
@@ -127,6 +129,7 @@ bool run_call(StageCall& x) {
   double t = now_ms();
   if (!nodes.empty()) JDA_HIP(hipMemcpyAsync(d_nodes, nodes.data(), nodes.size() * sizeof(NodeD), hipMemcpyHostToDevice, st));
   if (update) JDA_HIP(hipMemcpyAsync(d_w, x.w, w_count * sizeof(double), hipMemcpyHostToDevice, st));
+  if (st_on) JDA_HIP(hipMemcpyAsync(d_mean, c->hm.mean_shape.data(), (size_t)dim * sizeof(double), hipMemcpyHostToDevice, st));
   JDA_HIP(hipStreamSynchronize(st));
   upload_ms += now_ms() - t;
 
@@ -145,6 +148,7 @@ bool run_call(StageCall& x) {
     a.patches = walk ? (host_patches ? d_pat : s->patches + (size_t)i0 * pbytes) : nullptr;
     a.shapes = d_sh; a.nodes = d_nodes; a.w = d_w; a.lbf = d_lbf; a.out_shapes = d_out;
     a.n = cn; a.K = K; a.D = D; a.dim = dim; a.os = x.os; a.hs = x.hs; a.qs = x.qs; a.walk = walk ? 1 : 0;
+    a.mean = d_mean;
     if (!timer.begin(st)) return false;
     JDA_HIP(launch_lbf(a, lds_budget, &how, st));
     if (!timer.end(st)) return false;

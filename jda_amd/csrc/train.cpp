@@ -50,13 +50,17 @@ struct DevSet {
   CallBuf buf;
 };
 
-bool upload_set(const jdaSamplesCpp* s, int L, int os, int hs, int qs, DevSet* d, hipStream_t st) {
+// mean != nullptr (train_similarity): the cascador's mean shape [2L] -- every sample's stp_mc = STParameter::Calc(its shape,
+// mean), DataSet::CalcSTParameters (data.cpp:131-146), is made after the transpose (k_stp) and the values kernel applies it.
+bool upload_set(const jdaSamplesCpp* s, int L, int os, int hs, int qs, DevSet* d, hipStream_t st, const double* mean = nullptr) {
   d->host = s;
   const size_t n = (size_t)s->n, dim = 2 * (size_t)L, pt = (size_t)os * os + (size_t)hs * hs + (size_t)qs * qs;
   d->ts.n = s->n; d->ts.os = os; d->ts.hs = hs; d->ts.qs = qs;
   if (n == 0) return true;
   uint8_t* pa; double* raw; double* tr; double* w; double* res; uint8_t* gt;
+  double* ms = nullptr; double* stp = nullptr;
   if (!carve_into(d->buf, [&](Carver& cv) {
+        if (mean) { ms = cv.take<double>(4 + 2 * dim); stp = cv.take<double>(5 * n); }
         pa = s->patches_on_device ? nullptr : cv.take<uint8_t>(n * pt);
         raw = cv.take<double>(n * dim); tr = cv.take<double>(n * dim);
         w = s->weights ? cv.take<double>(n) : nullptr;
@@ -69,9 +73,13 @@ bool upload_set(const jdaSamplesCpp* s, int L, int os, int hs, int qs, DevSet* d
   if (res) JDA_HIP(hipMemcpyAsync(res, s->residual, 2 * n * sizeof(double), hipMemcpyHostToDevice, st));
   if (gt) JDA_HIP(hipMemcpyAsync(gt, s->has_gt, n, hipMemcpyHostToDevice, st));
   JDA_HIP(launch_train_transpose(raw, s->n, (int)dim, tr, st));
+  if (mean) {                             // (ms: the mean shape as stored at [4 + dim, 4 + 2 dim), its side of Calc in front)
+    JDA_HIP(hipMemcpyAsync(ms + 4 + dim, mean, dim * sizeof(double), hipMemcpyHostToDevice, st));
+    JDA_HIP(launch_stp(tr, s->n, L, ms + 4 + dim, ms, stp, nullptr, st));
+  }
   JDA_HIP(hipStreamSynchronize(st));      // (the host arrays are the caller's: done with them before anything else)
   d->ts.patches = pa ? pa : s->patches;
-  d->ts.shapes_t = tr; d->weights = w; d->residual = res; d->has_gt = gt;
+  d->ts.shapes_t = tr; d->ts.stp = stp; d->weights = w; d->residual = res; d->has_gt = gt;
   return true;
 }
 
@@ -149,7 +157,8 @@ struct Ctx {
   bool open(const jdaSamplesCpp* p, const jdaSamplesCpp* n, int os, int hs, int qs, int F_) {
     if (!one.open()) return false;
     st = one.stream; L = c->hm.L;
-    return upload_set(p, L, os, hs, qs, &pos, st) && upload_set(n, L, os, hs, qs, &neg, st) && reserve(F_);
+    const double* mean = train_similarity(c) ? c->hm.mean_shape.data() : nullptr;
+    return upload_set(p, L, os, hs, qs, &pos, st, mean) && upload_set(n, L, os, hs, qs, &neg, st, mean) && reserve(F_);
   }
 
   void carve(Carver& cv) {
@@ -278,7 +287,7 @@ bool feature_row(Ctx& x, const DevSet& set, const int* d_list, int count, int f,
 bool begin(Cascador* c, int os, int hs, int qs, const char* fn) {
   if (!c) { fail("bad arguments"); return false; }
   if (!check_patch_sizes(os, hs, qs)) return false;
-  if (c->similarity) {
+  if (c->similarity && !c->kn.train_similarity) {                            // (refused unless the caller opted in: include/jda.h)
     fail(std::string(fn) + ": refused with jdaSetSimilarityTransform(1): the reference's CalcFeatureValues indexes the per-sample "
          "transform by the feature index (data.cpp:168), there is no behaviour to reproduce");
     return false;
@@ -326,6 +335,47 @@ int jdaGenFeaturePoolCpp(int F, int landmark_n, double radius, int multi_scale, 
   }
   return 0;
 } JDA_ABI_CATCH(-1)
+
+int jdaCalcSTParametersCpp(void* cascador, const double* shapes, int n, double* stp_mc, double* stp_cm) try {
+  g_err.clear();
+  Cascador* c = (Cascador*)cascador;
+  if (!c || n < 0 || (n > 0 && !shapes)) { fail("bad arguments"); return -1; }
+  if (n == 0 || (!stp_mc && !stp_cm)) return 0;
+  if (!c->similarity) {                                                       // STParameter's default, data.cpp:68-70
+    for (double* out : {stp_mc, stp_cm})
+      for (int i = 0; out && i < n; i++) { double* p = out + 5 * (size_t)i; p[0] = 1.; p[1] = 1.; p[2] = 0.; p[3] = 0.; p[4] = 1.; }
+    return 0;
+  }
+  const int L = c->hm.L;
+  const size_t N = (size_t)n, dim = 2 * (size_t)L;
+  OneLane one(c);
+  CallBuf buf;
+  auto body = [&]() -> bool {
+    if (!one.open()) return false;
+    hipStream_t st = one.stream;
+    double* raw; double* tr; double* ms; double* mc; double* cm;
+    if (!carve_into(buf, [&](Carver& cv) {
+          raw = cv.take<double>(N * dim); tr = cv.take<double>(N * dim); ms = cv.take<double>(4 + 2 * dim);
+          mc = stp_mc ? cv.take<double>(5 * N) : nullptr; cm = stp_cm ? cv.take<double>(5 * N) : nullptr;
+        })) return false;
+    JDA_HIP(hipMemcpyAsync(raw, shapes, N * dim * sizeof(double), hipMemcpyHostToDevice, st));
+    JDA_HIP(hipMemcpyAsync(ms + 4 + dim, c->hm.mean_shape.data(), dim * sizeof(double), hipMemcpyHostToDevice, st));
+    JDA_HIP(launch_train_transpose(raw, n, (int)dim, tr, st));
+    JDA_HIP(launch_stp(tr, n, L, ms + 4 + dim, ms, mc, cm, st));
+    std::vector<double> planes(5 * N);
+    for (int which = 0; which < 2; which++) {                                 // planes [5][n] -> rows of (scale, rot00, rot01, rot10, rot11)
+      const double* dev = which ? cm : mc;
+      double* out = which ? stp_cm : stp_mc;
+      if (!out) continue;
+      JDA_HIP(hipMemcpyAsync(planes.data(), dev, 5 * N * sizeof(double), hipMemcpyDeviceToHost, st));
+      JDA_HIP(hipStreamSynchronize(st));
+      for (size_t i = 0; i < N; i++)
+        for (int k = 0; k < 5; k++) out[5 * i + k] = planes[(size_t)k * N + i];
+    }
+    return true;
+  };
+  return body() ? 0 : -1;
+} JDA_ABI_CATCH_SYNC(-1)
 
 int jdaCalcFeatureValuesCpp(void* cascador, const jdaSamplesCpp* samples, int origin_size, int half_size, int quarter_size,
                             const jdaFeatureCpp* pool, int F, int* out) try {

@@ -13,6 +13,8 @@ sample walks everything, at statuses (1, -1), (2, 269) and complete, reval_form 
 device_ms, one warm-up, then median (min - max) of 3.
 
     python tools/reval_bench.py [--out profiles/reval_bench.json]
+    python tools/reval_bench.py --reval-only [--similarity]     (part 2 alone; --similarity: jdaSetSimilarityTransform(1) with the
+                                                                  option train_similarity)
 """
 import argparse
 import json
@@ -37,7 +39,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reval_bench.json"))
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--reval-only", action="store_true")
+    ap.add_argument("--similarity", action="store_true")
     args = ap.parse_args()
+    assert not args.similarity or args.reval_only, "--similarity times part 2 only: give --reval-only"
     from jda_amd import api, synth
     import model_ref
     T, K, L, D = 5, 540, 27, 4
@@ -46,56 +51,57 @@ def main():
     ref.m, ref.stage, ref.cart = src, 2, 268
     tmp = tempfile.mkdtemp()
     snap = ref.save(os.path.join(tmp, "snap.model"))
-    imgs = [synth.make_frames(1, 320, 240, seed=3, first=i)[0] for i in range(4)]
-    cart = model_ref.cart_of(src, 2, 269)
+    if not args.reval_only:
+        imgs = [synth.make_frames(1, 320, 240, seed=3, first=i)[0] for i in range(4)]
+        cart = model_ref.cart_of(src, 2, 269)
 
-    def mine(c):
-        return c.mine_negatives_cpp(imgs, [5] * 4, [1.2] * 4, [0] * 4, size=2048, patches=False)
+        def mine(c):
+            return c.mine_negatives_cpp(imgs, [5] * 4, [1.2] * 4, [0] * 4, size=2048, patches=False)
 
-    a = api.Cascador(snap, "double", device=0)
-    mine(a)                                                          # builds the mining tables
-    a.put_cart_cpp(269, *cart)                                       # append: status (2, 269)
-    want = mine(a)
-    put_ms, mine_ms, both_ms = [], [], []
-    for r in range(args.reps + 1):
-        t0 = time.perf_counter()
-        a.put_cart_cpp(269, *cart)                                   # replace: the same work as an append
-        t1 = time.perf_counter()
-        got = mine(a)
-        t2 = time.perf_counter()
-        assert np.array_equal(got["hits"], want["hits"]) and np.array_equal(got["score"].view(np.uint64), want["score"].view(np.uint64))
-        if r:
-            put_ms.append((t1 - t0) * 1e3); mine_ms.append((t2 - t1) * 1e3); both_ms.append((t2 - t0) * 1e3)
-    ser_ms, create_ms, fmine_ms, trip_ms = [], [], [], []
-    path = os.path.join(tmp, "trip.model")
-    for r in range(args.reps + 1):
-        t0 = time.perf_counter()
-        a.serialize_to_cpp(path)
-        t1 = time.perf_counter()
-        b = api.Cascador(path, "double", device=0)
-        t2 = time.perf_counter()
-        got = mine(b)
-        t3 = time.perf_counter()
-        b.close()
-        assert np.array_equal(got["hits"], want["hits"]) and np.array_equal(got["score"].view(np.uint64), want["score"].view(np.uint64))
-        if r:
-            ser_ms.append((t1 - t0) * 1e3); create_ms.append((t2 - t1) * 1e3); fmine_ms.append((t3 - t2) * 1e3); trip_ms.append((t3 - t0) * 1e3)
-    a.close()
-    # close + the first mining call after it: stage 2 complete but open, (2, 539)
-    ref.cart = K - 1
-    full = ref.save(os.path.join(tmp, "full.model"))
-    close_ms, cmine_ms = [], []
-    for r in range(args.reps + 1):
-        b = api.Cascador(full, "double", device=0)
-        mine(b)
-        t0 = time.perf_counter()
-        b.close_stage_cpp(src.w[2])
-        t1 = time.perf_counter()
-        mine(b)
-        t2 = time.perf_counter()
-        b.close()
-        if r:
-            close_ms.append((t1 - t0) * 1e3); cmine_ms.append((t2 - t1) * 1e3)
+        a = api.Cascador(snap, "double", device=0)
+        mine(a)                                                          # builds the mining tables
+        a.put_cart_cpp(269, *cart)                                       # append: status (2, 269)
+        want = mine(a)
+        put_ms, mine_ms, both_ms = [], [], []
+        for r in range(args.reps + 1):
+            t0 = time.perf_counter()
+            a.put_cart_cpp(269, *cart)                                   # replace: the same work as an append
+            t1 = time.perf_counter()
+            got = mine(a)
+            t2 = time.perf_counter()
+            assert np.array_equal(got["hits"], want["hits"]) and np.array_equal(got["score"].view(np.uint64), want["score"].view(np.uint64))
+            if r:
+                put_ms.append((t1 - t0) * 1e3); mine_ms.append((t2 - t1) * 1e3); both_ms.append((t2 - t0) * 1e3)
+        ser_ms, create_ms, fmine_ms, trip_ms = [], [], [], []
+        path = os.path.join(tmp, "trip.model")
+        for r in range(args.reps + 1):
+            t0 = time.perf_counter()
+            a.serialize_to_cpp(path)
+            t1 = time.perf_counter()
+            b = api.Cascador(path, "double", device=0)
+            t2 = time.perf_counter()
+            got = mine(b)
+            t3 = time.perf_counter()
+            b.close()
+            assert np.array_equal(got["hits"], want["hits"]) and np.array_equal(got["score"].view(np.uint64), want["score"].view(np.uint64))
+            if r:
+                ser_ms.append((t1 - t0) * 1e3); create_ms.append((t2 - t1) * 1e3); fmine_ms.append((t3 - t2) * 1e3); trip_ms.append((t3 - t0) * 1e3)
+        a.close()
+        # close + the first mining call after it: stage 2 complete but open, (2, 539)
+        ref.cart = K - 1
+        full = ref.save(os.path.join(tmp, "full.model"))
+        close_ms, cmine_ms = [], []
+        for r in range(args.reps + 1):
+            b = api.Cascador(full, "double", device=0)
+            mine(b)
+            t0 = time.perf_counter()
+            b.close_stage_cpp(src.w[2])
+            t1 = time.perf_counter()
+            mine(b)
+            t2 = time.perf_counter()
+            b.close()
+            if r:
+                close_ms.append((t1 - t0) * 1e3); cmine_ms.append((t2 - t1) * 1e3)
     # Validate on 10^5 resident records
     import torch
     n = 100000
@@ -107,6 +113,9 @@ def main():
     for tag, hdr in (("1_-1", (1, -1)), ("2_269", (2, 269)), ("complete", (T, -1))):
         ref.stage, ref.cart = hdr
         c = api.Cascador(ref.save(os.path.join(tmp, "reval.model")), "double", device=0)
+        if args.similarity:
+            c.set_similarity_transform(True)
+            c.set_option("train_similarity", 1)
         res, keep = {}, {}
         for form in (0, 1):
             c.set_option("reval_form", form)
@@ -122,6 +131,13 @@ def main():
         res["carts_per_sample"] = int(keep[0]["carts_n"][0]); res["faces"] = int(keep[0]["is_face"].sum())
         reval[tag] = res
         c.close()
+    if args.reval_only:
+        out = dict(model=dict(T=T, K=K, L=L, D=D, all_pass=True), similarity=bool(args.similarity),
+                   validate_samples_cpp=dict(records=n, sizes=[48, 36, 24], statuses=reval))
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+        print(json.dumps({t: {f: (v[f]["call"]["median_ms"], v[f]["device"]["median_ms"]) for f in ("form0", "form1")} for t, v in reval.items()}))
+        return
     out = dict(model=dict(T=T, K=K, L=L, D=D, status=[2, 269], all_pass=True), images="4 x 320x240, step 5, factor 1.2, size 2048",
                hits=int(len(want["hits"])), windows=int(want["stats"]["windows"]),
                in_place=dict(put_cart_cpp=med(put_ms), first_mine_after_put=med(mine_ms), total=med(both_ms)),

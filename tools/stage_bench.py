@@ -9,6 +9,8 @@ liblinear and cannot be built here, and the parent commit has no such entry.
 
     python tools/stage_bench.py [--n 200000] [--K 540] [--repeats 3] [--out profiles/stage_close_bench.json]
     python tools/stage_bench.py --once fused_multi        (one call of one configuration: for a kernel trace)
+    python tools/stage_bench.py --similarity              (jdaSetSimilarityTransform(1) with the option train_similarity: every
+                                                           sample under its own STParameter)
 """
 import argparse
 import json
@@ -34,6 +36,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--once", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--similarity", action="store_true")
     a = ap.parse_args()
     import torch
     from jda_amd import api, synth
@@ -41,6 +44,9 @@ def main():
     path = os.path.join(synth.cache_dir(), "stage_bench_1_2_%d_%d.model" % (L, D))
     synth.make_model(1, 2, L, D, seed=1).save(path, 8)
     c = api.Cascador(path, "double", device=0)
+    if a.similarity:
+        c.set_similarity_transform(True)
+        c.set_option("train_similarity", 1)
     n, K, dim, leaf_n, inner = a.n, a.K, 2 * L, 1 << (D - 1), (1 << (D - 1)) - 1
     pbytes = OS * OS + HS * HS + QS * QS
     g = torch.Generator(device="cuda").manual_seed(1)
@@ -54,7 +60,7 @@ def main():
     traffic = dict(patch_bytes=n * pbytes, shape_bytes_in=n * dim * 8, shape_bytes_out=n * dim * 8, lbf_bytes=n * K * 4,
                    w_row_bytes_read=n * K * dim * 8, w_table_bytes=K * leaf_n * dim * 8, node_table_bytes=K * inner * 48,
                    node_evaluations=n * K * (D - 1), fp64_adds=n * K * dim)
-    res = dict(n=n, K=K, depth=D, landmarks=L, sizes=[OS, HS, QS], repeats=a.repeats, traffic=traffic, configs={})
+    res = dict(n=n, K=K, depth=D, landmarks=L, sizes=[OS, HS, QS], repeats=a.repeats, similarity=bool(a.similarity), traffic=traffic, configs={})
     lbf = None
     for name, (what, multi) in CONFIGS.items():
         if a.once and name != a.once:

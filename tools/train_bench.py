@@ -7,6 +7,8 @@ needs OpenCV and cannot be built here, and the parent commit has no such entry.
 
     python tools/train_bench.py [--n 100000] [--features 2000] [--repeats 3] [--out profiles/train_bench.json]
     python tools/train_bench.py --once cls_scale0        (one call of one configuration: for a kernel trace)
+    python tools/train_bench.py --similarity             (jdaSetSimilarityTransform(1) with the option train_similarity: every
+                                                          sample under its own STParameter)
 """
 import argparse
 import json
@@ -40,15 +42,19 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--once", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--similarity", action="store_true")
     a = ap.parse_args()
     import torch
     from jda_amd import api, synth
     path = os.path.join(synth.cache_dir(), "train_bench_1_2_%d_%d.model" % (L, D))
     synth.make_model(1, 2, L, D, seed=1).save(path, 8)
     c = api.Cascador(path, "double", device=0)
+    if a.similarity:
+        c.set_similarity_transform(True)
+        c.set_option("train_similarity", 1)
     pos, neg = sample_set(torch, a.n, 1), sample_set(torch, a.n, 2)
     inner = (1 << (D - 1)) - 1
-    res = dict(n_pos=a.n, n_neg=a.n, features=a.features, depth=D, landmarks=L, sizes=[OS, HS, QS], repeats=a.repeats, configs={})
+    res = dict(n_pos=a.n, n_neg=a.n, features=a.features, depth=D, landmarks=L, sizes=[OS, HS, QS], repeats=a.repeats, similarity=bool(a.similarity), configs={})
     for name, (mode, multi) in CONFIGS.items():
         if a.once and name != a.once:
             continue
