@@ -605,9 +605,9 @@ JDA_API long long jdaMineWindowList(int w, int h, int origin_size, int step, dou
  * (tests/train_ref.py), not against the reference.  Out of scope: BoostCart::Train's loop and its restart policy (one step
  * of that loop -- scores, order, cut, weights and the move of the surviving samples -- is the block "from one cart to the
  * next" at the end of this file), the global regression that closes a stage (the blocks "closing a stage" and "a stage's
- * global regression" below), writing the cart into a model file, reading image files (file and JPEG reading and
- * cvtColor stay the caller's; what LoadPositiveDataSet does with the decoded images is the block "the positive sample set" at
- * the end of this file).
+ * global regression" below), writing the cart into a model file, reading image files (file and JPEG reading stay the
+ * caller's; the colour conversion is the block "frames as they arrive", what LoadPositiveDataSet does with the decoded images
+ * the block "the positive sample set", both at the end of this file).
  *
  * Samples.  One struct describes a set of n samples.  origin_size / half_size / quarter_size are call arguments, each in
  * [1, 128]; the landmark count L and tree_depth come from the cascador (it also supplies the device, the "workspace_mb"
@@ -1022,8 +1022,9 @@ JDA_API int jdaGatherSamplesCpp(void *cascador, const jdaGatherSegCpp *segs, int
  * CalcShapeResidual (175-208) is what jdaSamplesCpp.residual asks for.  The outputs are jdaSamplesCpp's layout: they go
  * into the training entries as they are.  PARITY UNPINNED like every dialect-CPP entry: src/jda needs OpenCV and cannot be
  * built here; these entries are bit-exact against a restatement written from the reference's source
- * (tests/positives_ref.py), not against the reference.  Out of scope: reading the list file, decoding images and cvtColor
- * (the caller hands in 8-bit grey images), liblinear's fit and the training loop.
+ * (tests/positives_ref.py), not against the reference.  Out of scope: reading the list file and decoding images (the
+ * caller hands in 8-bit grey images; jdaPackGray[Device], "frames as they arrive", makes them from decoded colour images),
+ * liblinear's fit and the training loop.
  *
  * The face.  getFace(image, bbox) is a w x h crop of the cols x rows image in which every pixel outside the image is 0.
  * The reference takes its clone-the-crop path only when bbox.x >= 0, bbox.y >= 0, bbox.x + w < cols and bbox.y + h < rows
@@ -1201,6 +1202,61 @@ JDA_API int jdaValidateSamplesCpp(void *cascador, const jdaSamplesCpp *samples, 
  * turn that into (s + 1, -1), a regression that was never fit, and the reference never writes there (btcart.cpp:243).
  * jdaCascadorSerializeTo (the f32 file) is unchanged. */
 JDA_API int jdaCascadorSerializeToCpp(void *cascador, const char *path);
+
+/* ------------------------------------------------------------------------ */
+/* Frames as they arrive                                                    */
+/* ------------------------------------------------------------------------ */
+/* Every entry above takes 8-bit gray, rows back to back.  None of the reference's callers has that in hand: src/live.cpp:32,
+ * src/test.cpp:40 and 134 and src/jda/data.cpp:621 each hold a decoded BGR image and call cvtColor(..., CV_BGR2GRAY) just
+ * before the line this library replaces; a hardware JPEG or video decoder leaves interleaved RGB / BGR(A) or a pitched luma
+ * plane in device memory.  These two entries take such images -- any of the formats below, any row pitch, any rectangle --
+ * and write the dense gray images the other entries take.  Decoding stays the caller's.
+ *
+ * Gray value.  gray = (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14 in integer arithmetic: OpenCV 2.4's 8-bit CV_BGR2GRAY
+ * (0.114 / 0.587 / 0.299 in Q14, rounded to nearest), the version the reference is written against.  Later OpenCV SIMD
+ * paths use a 15-bit form of the same weights, which differs in the last bit for some colours; THIS LIBRARY'S DEFINITION
+ * IS THE 14-BIT ONE ABOVE, on the host and on the device, to the bit.  RGB formats swap the outer weights; alpha is
+ * ignored (and never read); GRAY8 is a copy (it serves a pitch or a rectangle).
+ *
+ * Output layout.  Image i is written at dst + dst_offsets[i] as w * h bytes, rows back to back: exactly what
+ * jdaDetectBatchRaggedDevice, jdaDetectBatchCppRaggedDevice, jdaValidateCppDevice, jdaMineNegativesCppDevice and
+ * jdaBuildPositivesCppDevice take (d_base = dst, offsets = dst_offsets, widths / heights = the rectangles'), and with
+ * dst_offsets[i] = i * frame_stride what jdaDetectBatchDevice, jdaDetectBatchSubmit and jdaValidateWindowsDevice take.
+ * RESULTS OF A LATER DETECT CALL ARE IN THE RECTANGLE'S COORDINATES: add (x, y) to get back to the source image; there is no
+ * relocation entry.
+ *
+ * jdaPackGray needs no cascador and no GPU: a plain loop over host memory, what a jdaDetect caller with a cv::Mat of BGR
+ * uses.  jdaPackGrayDevice makes ONE kernel launch for all n images, of whatever sizes and formats (k_pack.hip); the
+ * cascador supplies the device, the error state and a lane, whose grow-only buffer holds the image table -- no model is
+ * read.  It runs on hip_stream if given (a hipStream_t: the stream the caller produced the pixels on), otherwise on the
+ * lane's own stream, and returns when d_dst is complete, like every entry without a ticket.  Re-entrant on one cascador
+ * like the other entries.  stats (may be NULL): pixels written, bytes read (w * h * bytes per pixel) and written, kernel
+ * launches (1), the kernel's time between two events and the call's wall time.
+ *
+ * Refused with -1, jdaGetLastError() naming the image index and the offending values, nothing launched and no byte of dst
+ * written: a NULL pointer where one is needed (images, dst, dst_offsets, an image's data; the cascador), n < 0, an unknown
+ * format, width / height / w / h below 1 (except w == h == 0: the whole image), a rectangle that leaves the image,
+ * pitch < width * bytes per pixel, two destination images that overlap, a destination image that overlaps the bytes the
+ * rectangle takes of any source row of any image.  n == 0 returns 0 and touches nothing. */
+#define JDA_PIX_GRAY8  0   /* 1 byte per pixel: a copy (pitch / rectangle only); the Y plane of NV12 is this */
+#define JDA_PIX_BGR24  1
+#define JDA_PIX_RGB24  2
+#define JDA_PIX_BGRA32 3   /* alpha ignored */
+#define JDA_PIX_RGBA32 4   /* alpha ignored */
+
+typedef struct {
+  const unsigned char *data; /* pixel (0,0) of the SOURCE image: host memory for jdaPackGray, device for jdaPackGrayDevice */
+  long long pitch;           /* bytes from one row to the next, >= width * bytes per pixel, any alignment */
+  int width, height;         /* of the source image */
+  int format;                /* JDA_PIX_* */
+  int x, y, w, h;            /* rectangle to take; w == 0 && h == 0 means the whole image */
+} jdaPixels;
+
+typedef struct { long long pixels, bytes_in, bytes_out; int launches; double device_ms, call_ms; } jdaPackStats;
+
+JDA_API int jdaPackGray(const jdaPixels *images, int n, unsigned char *dst, const size_t *dst_offsets);
+JDA_API int jdaPackGrayDevice(void *cascador, const jdaPixels *images, int n, unsigned char *d_dst,
+                              const size_t *dst_offsets, void *hip_stream, jdaPackStats *stats);
 
 #ifdef __cplusplus
 }

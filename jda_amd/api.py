@@ -131,6 +131,26 @@ class jdaPositivesStatsCpp(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class jdaPixels(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("pitch", C.c_longlong), ("width", C.c_int), ("height", C.c_int), ("format", C.c_int),
+                ("x", C.c_int), ("y", C.c_int), ("w", C.c_int), ("h", C.c_int)]
+
+
+class jdaPackStats(C.Structure):
+    _fields_ = [("pixels", C.c_longlong), ("bytes_in", C.c_longlong), ("bytes_out", C.c_longlong), ("launches", C.c_int),
+                ("device_ms", C.c_double), ("call_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# include/jda.h, "frames as they arrive": JDA_PIX_* and their bytes per pixel
+JDA_PIX_GRAY8, JDA_PIX_BGR24, JDA_PIX_RGB24, JDA_PIX_BGRA32, JDA_PIX_RGBA32 = range(5)
+PIX_FORMATS = {"gray8": JDA_PIX_GRAY8, "bgr24": JDA_PIX_BGR24, "rgb24": JDA_PIX_RGB24, "bgra32": JDA_PIX_BGRA32,
+               "rgba32": JDA_PIX_RGBA32}
+PIX_BYTES = {JDA_PIX_GRAY8: 1, JDA_PIX_BGR24: 3, JDA_PIX_RGB24: 3, JDA_PIX_BGRA32: 4, JDA_PIX_RGBA32: 4}
+
+
 # numpy view of jdaFeatureCpp arrays (same layout: three ints, four bytes of padding, four doubles)
 FEATURE_DTYPE = np.dtype([("scale", np.int32), ("landmark_id1", np.int32), ("landmark_id2", np.int32), ("pad", np.int32),
                           ("offset1_x", np.float64), ("offset1_y", np.float64), ("offset2_x", np.float64),
@@ -330,6 +350,10 @@ def _load():
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
         lib.jdaValidateSamplesCpp.argtypes = [C.c_void_p, C.POINTER(jdaSamplesCpp), C.c_int, C.c_int, C.c_int, u8p, dp, ip, dp,
                                               C.POINTER(jdaStageStatsCpp)]
+    if hasattr(lib, "jdaPackGrayDevice"):           # (older builds, loaded through JDA_LIB_PATH for A/B runs, lack them)
+        lib.jdaPackGray.argtypes = [C.POINTER(jdaPixels), C.c_int, C.c_void_p, C.POINTER(C.c_size_t)]
+        lib.jdaPackGrayDevice.argtypes = [C.c_void_p, C.POINTER(jdaPixels), C.c_int, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p,
+                                          C.POINTER(jdaPackStats)]
     return lib
 
 
@@ -675,6 +699,57 @@ def _pack_images_device(images):
     for i, a in enumerate(imgs):
         host[int(offs[i]):int(offs[i]) + a.size] = a.ravel()
     return torch.from_numpy(host).cuda(), offs, [a.shape[1] for a in imgs], [a.shape[0] for a in imgs]
+
+
+def _pixel_format(f):
+    return PIX_FORMATS[f.lower()] if isinstance(f, str) else int(f)
+
+
+def _pixel_table(images, formats, rects, address, strides):
+    """jdaPixels[n] for arrays / tensors of shape [H, W, C] or [H, W] (strides in BYTES; a view's row stride is the pitch)
+    and the (w, h) every image's rectangle comes out as.  What the library refuses is left to it; only what a jdaPixels
+    cannot say is refused here: pixels whose bytes do not lie back to back inside a row."""
+    n = len(images)
+    if isinstance(formats, (str, int)):
+        formats = [formats] * n
+    if len(formats) != n or (rects is not None and len(rects) != n):
+        raise ValueError("pack_gray: one format (and one rectangle) per image")
+    px = (jdaPixels * max(n, 1))()
+    sizes = []
+    for i, im in enumerate(images):
+        f = _pixel_format(formats[i])
+        st, shape = strides(im), tuple(im.shape)
+        chans = shape[2] if len(shape) == 3 else 1
+        if len(shape) not in (2, 3) or chans != PIX_BYTES.get(f, chans):
+            raise ValueError("pack_gray: image %d has shape %s, format %d needs [H, W%s]" % (i, shape, f, ", %d" % PIX_BYTES[f] if PIX_BYTES[f] > 1 else ""))
+        if (len(shape) == 3 and chans > 1 and st[2] != 1) or (shape[1] > 1 and st[1] != chans) or (shape[0] > 1 and st[0] < 0):
+            raise ValueError("pack_gray: image %d: a pixel's bytes and a row's pixels must lie back to back (strides %s)" % (i, st))
+        r = (0, 0, 0, 0) if rects is None or rects[i] is None else tuple(int(v) for v in rects[i])
+        pitch = st[0] if shape[0] > 1 else shape[1] * chans
+        px[i] = jdaPixels(address(im), pitch, shape[1], shape[0], f, *r)
+        sizes.append((shape[1], shape[0]) if r[2] == 0 and r[3] == 0 else (r[2], r[3]))
+    return px, sizes
+
+
+def pack_gray(images, formats, rects=None):
+    """jdaPackGray: numpy uint8 arrays [H, W, C] or [H, W] (row-strided views allowed) of the given formats ("bgr24", ... or
+    JDA_PIX_*; one for all or one per image), each cut to its rectangle (x, y, w, h) (None: the whole image) -> a list of
+    uint8 [h, w] gray arrays.  Host only: no cascador, no GPU."""
+    images = [np.asarray(im) for im in images]
+    for im in images:
+        if im.dtype != np.uint8:
+            raise ValueError("pack_gray: uint8 images")
+    px, sizes = _pixel_table(images, formats, rects, lambda a: a.ctypes.data, lambda a: a.strides)
+    sizes = [(max(w, 0), max(h, 0)) for w, h in sizes]
+    offs = np.zeros(max(len(images), 1), np.uint64)
+    tot = 0
+    for i, (w, h) in enumerate(sizes):
+        offs[i] = tot
+        tot += w * h
+    dst = np.empty(max(tot, 1), np.uint8)
+    if lib.jdaPackGray(px, len(images), dst.ctypes.data, offs.ctypes.data_as(C.POINTER(C.c_size_t))) != 0:
+        raise JdaError(last_error())
+    return [dst[int(offs[i]):int(offs[i]) + w * h].reshape(h, w) for i, (w, h) in enumerate(sizes)]
 
 
 def count_windows(width, height, scale=1.25, min_size=40, max_size=-1):
@@ -1038,6 +1113,44 @@ class Cascador:
             raise JdaError(last_error())
         out = self._collect(res, n, keep_results, frame_offset)
         return (out, st.asdict()) if stats else out
+
+    # -- frames as they arrive: colour / pitched / cropped device images -> dense gray ----------
+    def pack_gray_device(self, images, formats, rects=None, frame_stride=None, stats=False, hip_stream=None, out=None):
+        """jdaPackGrayDevice: torch uint8 CUDA tensors [H, W, C] or [H, W] (strided views allowed: a view's row stride is the
+        pitch) of the given formats, each cut to its rectangle (x, y, w, h) (None: the whole image), packed to gray by ONE
+        kernel launch.  -> (buffer, offsets, widths, heights): a torch uint8 CUDA tensor and where every image lies in it --
+        the arguments of detect_ragged_packed / detect_ragged_cpp_packed and the device image set of validate_cpp,
+        mine_negatives_cpp and build_positives_cpp.  Image i starts at a multiple of 256 bytes, or with frame_stride at
+        i * frame_stride: buffer.view(n, h, w) then goes into detect_batch_device / submit_batch_device where frame_stride ==
+        w * h.  hip_stream: a hipStream_t handle (torch.cuda.Stream().cuda_stream) the pixels were produced on.
+        out = (buffer, offsets): the caller's own destination.  stats=True: (that tuple, jdaPackStats as a dict)."""
+        import torch
+        images = list(images)
+        for im in images:
+            if not (im.is_cuda and im.dtype == torch.uint8):
+                raise ValueError("pack_gray_device: torch uint8 CUDA tensors")
+        px, sizes = _pixel_table(images, formats, rects, lambda t: t.data_ptr(), lambda t: tuple(t.stride()))
+        n = len(images)
+        sizes = [(max(w, 0), max(h, 0)) for w, h in sizes]
+        if out is not None:
+            buf, offs = out[0], np.ascontiguousarray(out[1], np.uint64)
+            assert buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous() and len(offs) == n
+        else:
+            offs = np.zeros(max(n, 1), np.uint64)
+            tot = 0
+            for i, (w, h) in enumerate(sizes):
+                offs[i] = tot if frame_stride is None else i * int(frame_stride)
+                tot = int(offs[i]) + (w * h if frame_stride is None else max(w * h, int(frame_stride)))
+                if frame_stride is None:
+                    tot = (tot + 255) // 256 * 256
+            buf = torch.empty(max(tot, 1), dtype=torch.uint8, device=images[0].device if n else "cuda")
+        st = jdaPackStats() if stats else None
+        rc = lib.jdaPackGrayDevice(self.h, px, n, C.c_void_p(buf.data_ptr()), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
+                                   C.c_void_p(hip_stream) if hip_stream is not None else None, C.byref(st) if stats else None)
+        if rc != 0:
+            raise JdaError(last_error())
+        res = (buf, offs[:n], [w for w, _ in sizes], [h for _, h in sizes])
+        return (res, st.asdict()) if stats else res
 
     # -- two batches in flight from one thread -----------------------------------
     def submit_batch_device(self, d_frames, scale=1.25, min_size=40, max_size=-1, th=-0.5, nms=True, stats=False):

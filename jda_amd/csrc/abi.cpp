@@ -384,6 +384,17 @@ int jdaValidateWindowsDevice(void* cascador, const unsigned char* d_frames, size
                        n_windows, th, WindowsOut{is_face, score, carts_n, path_hash, shapes, landmarks, stats});
 } JDA_ABI_CATCH_SYNC(-1)
 
+int jdaPackGray(const jdaPixels* images, int n, unsigned char* dst, const size_t* dst_offsets) try {
+  g_err.clear();
+  return pack_host(images, n, dst, dst_offsets);
+} JDA_ABI_CATCH(-1)
+
+int jdaPackGrayDevice(void* cascador, const jdaPixels* images, int n, unsigned char* d_dst, const size_t* dst_offsets,
+                      void* hip_stream, jdaPackStats* stats) try {
+  g_err.clear();
+  return pack_device((Cascador*)cascador, images, n, d_dst, dst_offsets, (hipStream_t)hip_stream, stats);
+} JDA_ABI_CATCH_SYNC(-1)
+
 int jdaBuildPyramid(void* cascador, const unsigned char* data, int width, int height,
                     unsigned char* half, int* hw, int* hh, unsigned char* quarter, int* qw, int* qh) try {
   g_err.clear();
@@ -608,7 +619,7 @@ namespace jda {
 void jda_bc_read_k_scan(unsigned long long*); void jda_bc_read_k_scan_d(unsigned long long*); void jda_bc_read_k_scan_r(unsigned long long*);
 void jda_bc_read_k_scan_dr(unsigned long long*); void jda_bc_read_k_scan_p(unsigned long long*); void jda_bc_read_k_finish(unsigned long long*);
 void jda_bc_read_k_wide(unsigned long long*); void jda_bc_read_k_stage(unsigned long long*); void jda_bc_read_k_mine(unsigned long long*); void jda_bc_read_k_train(unsigned long long*); void jda_bc_read_k_lbf(unsigned long long*);
-void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*); void jda_bc_read_k_fit(unsigned long long*); void jda_bc_read_k_reval(unsigned long long*); void jda_bc_read_k_windows(unsigned long long*);
+void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*); void jda_bc_read_k_fit(unsigned long long*); void jda_bc_read_k_reval(unsigned long long*); void jda_bc_read_k_windows(unsigned long long*); void jda_bc_read_k_pack(unsigned long long*);
 }
 // bounds-check build only (libjda_bounds.so): per translation unit {first violation: site << 32 | source line, violations}
 // since the last call -- out[16]; returns the total number of violations (kernels_common.h: Bc)
@@ -618,10 +629,10 @@ __attribute__((visibility("default"))) long long jdaDebugBoundsReport(unsigned l
                                         jda_bc_read_k_scan_p, jda_bc_read_k_finish, jda_bc_read_k_wide, jda_bc_read_k_stage};
   long long total = 0;
   for (int i = 0; i < 8; i++) { unsigned long long v[2] = {0, 0}; rd[i](v); if (out) { out[2 * i] = v[0]; out[2 * i + 1] = v[1]; } total += (long long)v[1]; }
-  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces', k_fit's, k_reval's and k_windows' words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file, cpp_patch.h or cpp_wave.h
-  const struct { void (*rd)(unsigned long long*); const char* tu; } more[8] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
+  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces', k_fit's, k_reval's, k_windows' and k_pack's words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file, cpp_patch.h or cpp_wave.h
+  const struct { void (*rd)(unsigned long long*); const char* tu; } more[9] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
                                                                                 {jda_bc_read_k_gather, "k_gather"}, {jda_bc_read_k_faces, "k_faces"}, {jda_bc_read_k_fit, "k_fit"}, {jda_bc_read_k_reval, "k_reval"},
-                                                                                {jda_bc_read_k_windows, "k_windows"}};
+                                                                                {jda_bc_read_k_windows, "k_windows"}, {jda_bc_read_k_pack, "k_pack"}};
   for (const auto& t : more) {
     unsigned long long v[2] = {0, 0};
     t.rd(v);

@@ -65,6 +65,11 @@ struct WindowsOut { unsigned char* is_face; float* score; int* carts_n; unsigned
 int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_frames, const uint8_t* d_frames, size_t stride, int n,
                   int width, int height, const int* windows, int n_windows, float th, const WindowsOut& out);
 
+// pack.cpp: frames as they arrive (jdaPackGray / jdaPackGrayDevice)
+int pack_host(const jdaPixels* images, int n, unsigned char* dst, const size_t* dst_offsets);
+int pack_device(Cascador* c, const jdaPixels* images, int n, unsigned char* d_dst, const size_t* dst_offsets, hipStream_t user_stream,
+                jdaPackStats* stats);
+
 // detect_cpp.cpp: dialect CPP, method 1 (cascador.cpp:310-376,431-477) on a uniform batch; frames on the device
 // (d_frames) or, with host_frames set, in host memory
 struct CppCall { int minimum_size, step; double factor, overlap; int nms; };

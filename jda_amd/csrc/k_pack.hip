@@ -1,0 +1,172 @@
+// HIP kernel for gfx950 that turns frames as they arrive -- interleaved BGR / RGB / BGRA / RGBA or 8-bit gray, any row pitch,
+// any rectangle -- into the dense 8-bit gray images every detect / validate / mining / positives entry takes (include/jda.h,
+// "frames as they arrive"; what the reference's callers do with cvtColor(..., CV_BGR2GRAY) just before the line this library
+// replaces: src/live.cpp:32, src/test.cpp:40 and 134, src/jda/data.cpp:621).
+//   gray = (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14        integer, OpenCV 2.4's 8-bit form
+//   k_pack    ONE launch for a ragged set.  An image's dense output is dealt in units (kernels.h: PackImg), not per row: a
+//             48-pixel-wide face crop fills its lanes like a frame does.  lane = unit; a workgroup takes kPackBlock *
+//             kPackRounds consecutive units of the launch and finds the image of its first one in block_img (an item per
+//             workgroup, made by the host); a lane walks on from there through the image records, whose `first` is the
+//             prefix sum of the units.  All offsets are 64-bit.
+//             - the destination decides the shape: a unit below nq is the 16 bytes at a 16-byte boundary of dst, one
+//               16-byte store; the bytes in front of the first boundary and behind the last are one byte store each;
+//             - a 16-byte unit whose pixels lie in one source row reads its 16 * bpp bytes as aligned dwords -- 4 * bpp of
+//               them, and one more where the first pixel does not start a dword -- and funnels every dword out of two
+//               neighbours by the lane's own shift (v_alignbyte_b32); BGR24 pixels are cut out of the realigned dwords the
+//               same way.  Every dword read holds a byte of a pixel of the unit: a source that ends with its allocation is safe;
+//             - a unit that straddles source rows (and the single bytes) reads pixel by pixel, byte loads;
+//             - the weights are split into their low and high bytes, so a pixel is two v_dot4_u32_u8 on the dword that holds
+//               it: the byte that is alpha, or the next pixel's, meets a zero weight.  GRAY8 is the same kernel without it.
+//             No LDS, no atomics, no inline assembly, no scratch.
+#include "kernels_common.h"
+
+namespace jda {
+
+namespace {
+
+typedef uint32_t pack_u32x4 __attribute__((ext_vector_type(4)));
+typedef pack_u32x4 pack_u32x4_a4 __attribute__((aligned(4)));          // four dwords at a dword-aligned address
+// (the image records hand out plain pointers; said to be global memory, they are read and written with global_, not flat_, instructions)
+typedef const __attribute__((address_space(1))) uint8_t* pack_src_t;
+typedef __attribute__((address_space(1))) uint8_t* pack_dst_t;
+typedef const __attribute__((address_space(1))) uint32_t* pack_src4_t;
+typedef const __attribute__((address_space(1))) pack_u32x4_a4* pack_src16_t;
+typedef __attribute__((address_space(1))) pack_u32x4* pack_dst16_t;
+
+#ifdef JDA_BOUNDS_CHECK
+// n aligned dwords from p: each must hold a byte of bc (the bytes the rectangle takes of one source row)
+#define JDA_BC_PACK_DWORDS(bc, p, n) do { for (int k_ = 0; k_ < (n); k_++) { const long long q_ = (long long)(uintptr_t)(p) + 4 * k_; \
+    if (q_ + 4 <= (bc).lo || q_ >= (bc).hi) jda_bc_fail(kBcPackSrc, __LINE__); } } while (0)
+#else
+#define JDA_BC_PACK_DWORDS(bc, p, n) do { } while (0)
+#endif
+
+// the gray value of the pixel in the low bytes of px (weights: PackImg::w_lo / w_hi)
+__device__ __forceinline__ uint32_t pack_gray(uint32_t px, uint32_t w_lo, uint32_t w_hi) {
+  const uint32_t hi = __builtin_amdgcn_udot4(px, w_hi, 0u, false);
+  return __builtin_amdgcn_udot4(px, w_lo, (hi << 8) + 8192u, false) >> 14;
+}
+
+// 16 pixels of one source row from a (any alignment) -> their 16 gray bytes
+template <int BPP>
+__device__ __forceinline__ pack_u32x4 pack_row16(pack_src_t a, uint32_t w_lo, uint32_t w_hi, const Bc& bc_row) {
+  constexpr int ND = 4 * BPP;                                    // dwords that 16 pixels fill
+  const uint32_t sh = (uint32_t)((uintptr_t)a & 3);
+  const pack_src4_t s4 = (pack_src4_t)(a - sh);                    // dword aligned
+  JDA_BC_PACK_DWORDS(bc_row, s4, sh ? ND + 1 : ND);
+  uint32_t d[ND + 1];
+#pragma unroll
+  for (int k = 0; k < ND; k += 4) {
+    const pack_u32x4 v = *(pack_src16_t)(s4 + k);
+    d[k] = v.x; d[k + 1] = v.y; d[k + 2] = v.z; d[k + 3] = v.w;
+  }
+  d[ND] = sh ? s4[ND] : 0u;                                        // (holds a byte of the last pixel only then)
+  uint32_t t[ND + 1];                                              // the 16 * BPP bytes from a on
+#pragma unroll
+  for (int k = 0; k < ND; k++) t[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);
+  t[ND] = 0u;
+  if constexpr (BPP == 1) {
+    return pack_u32x4{t[0], t[1], t[2], t[3]};
+  } else {
+    uint32_t o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      constexpr int B = BPP;
+      const int j = (B * k) >> 2, off = (B * k) & 3;               // the pixel's dword and its byte in it (constants once unrolled)
+      const uint32_t px = off ? __builtin_amdgcn_alignbyte(t[j + 1], t[j], (uint32_t)off) : t[j];
+      o[k >> 2] |= pack_gray(px, w_lo, w_hi) << (8 * (k & 3));
+    }
+    return pack_u32x4{o[0], o[1], o[2], o[3]};
+  }
+}
+
+// one pixel, byte loads (alpha is not read)
+__device__ __forceinline__ uint32_t pack_pixel(pack_src_t p, int bpp, uint32_t w_lo, uint32_t w_hi, const Bc& bc_src) {
+  JDA_BC_ADDR(bc_src, p, bpp == 1 ? 1 : 3, kBcPackSrc);
+  if (bpp == 1) return p[0];
+  return pack_gray((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16), w_lo, w_hi);
+}
+
+// pixel p of a w-wide image -> (row, column); an image below 2^32 pixels divides in 32 bits
+__device__ __forceinline__ void pack_yx(long long p, int w, long long* y, int* x) {
+  if (p <= 0xffffffffll) {
+    const uint32_t q = (uint32_t)p / (uint32_t)w;
+    *y = q; *x = (int)((uint32_t)p - q * (uint32_t)w);
+  } else {
+    const long long q = p / w;
+    *y = q; *x = (int)(p - q * w);
+  }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kPackBlock) void k_pack(PackArgs a) {
+  const long long base = (long long)blockIdx.x * (kPackBlock * kPackRounds);
+  int i = a.block_img[blockIdx.x];
+  if (i < 0 || i >= a.n) return;                                   // (the host made the list: never taken)
+  PackImg im = a.imgs[i];
+  for (int r = 0; r < kPackRounds; r++) {
+    const long long g = base + r * kPackBlock + (int)threadIdx.x;
+    if (g >= a.total) break;
+    while (g >= im.first + im.nq + im.head + im.tail && i + 1 < a.n) im = a.imgs[++i];
+    const long long u = g - im.first;
+    if (u < 0 || u >= im.nq + im.head + im.tail) {                 // (the prefix sums cover [0, total): never taken)
+#ifdef JDA_BOUNDS_CHECK
+      jda_bc_fail(kBcPackDst, __LINE__);
+#endif
+      break;
+    }
+    const long long npix = (long long)im.w * im.h;
+    [[maybe_unused]] const Bc bc_dst((long long)(uintptr_t)im.dst, (long long)(uintptr_t)im.dst + npix);
+    [[maybe_unused]] const Bc bc_src((long long)(uintptr_t)im.src, (long long)(uintptr_t)im.src + (long long)(im.h - 1) * im.pitch + (long long)im.w * im.bpp);
+    if (u < im.nq) {
+      const long long p0 = im.head + (u << 4);
+      long long y; int x;
+      pack_yx(p0, im.w, &y, &x);
+      pack_u32x4 o;
+      if (x + 16 <= im.w) {
+        const pack_src_t row = (pack_src_t)im.src + y * im.pitch;
+        [[maybe_unused]] const Bc bc_row((long long)(uintptr_t)row, (long long)(uintptr_t)row + (long long)im.w * im.bpp);
+        const pack_src_t s = row + (long long)x * im.bpp;
+        if (im.bpp == 1) o = pack_row16<1>(s, 0u, 0u, bc_row);
+        else if (im.bpp == 3) o = pack_row16<3>(s, im.w_lo, im.w_hi, bc_row);
+        else o = pack_row16<4>(s, im.w_lo, im.w_hi, bc_row);
+      } else {
+        uint32_t q[4] = {0u, 0u, 0u, 0u};
+        pack_src_t row = (pack_src_t)im.src + y * im.pitch;
+        pack_src_t s = row + (long long)x * im.bpp;
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+          q[k >> 2] |= pack_pixel(s, im.bpp, im.w_lo, im.w_hi, bc_src) << (8 * (k & 3));
+          s += im.bpp;
+          if (++x == im.w) { x = 0; row += im.pitch; s = row; }
+        }
+        o = pack_u32x4{q[0], q[1], q[2], q[3]};
+      }
+      JDA_BC_ADDR(bc_dst, im.dst + p0, 16, kBcPackDst);
+      *(pack_dst16_t)(im.dst + p0) = o;                            // 16-byte aligned: head is dst's distance to its first boundary
+    } else {
+      const long long e = u - im.nq;                               // [0, head): the bytes in front, [head, head + tail): behind
+      const long long p = e < im.head ? e : (im.nq << 4) + e;
+      long long y; int x;
+      pack_yx(p, im.w, &y, &x);
+      const uint32_t v = pack_pixel((pack_src_t)im.src + y * im.pitch + (long long)x * im.bpp, im.bpp, im.w_lo, im.w_hi, bc_src);
+      JDA_BC_ADDR(bc_dst, im.dst + p, 1, kBcPackDst);
+      ((pack_dst_t)im.dst)[p] = (uint8_t)v;
+    }
+  }
+}
+
+hipError_t launch_pack(const PackArgs& a, hipStream_t stream) {
+  if (a.n <= 0 || a.total <= 0) return hipSuccess;
+  if (!a.imgs || !a.block_img) return hipErrorInvalidValue;
+  constexpr long long per = (long long)kPackBlock * kPackRounds;
+  const long long groups = (a.total + per - 1) / per;
+  if (groups > 0x7fffffffll) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pack, dim3((unsigned)groups), dim3(kPackBlock), 0, stream, a);
+  return hipGetLastError();
+}
+
+JDA_BC_READER(k_pack)
+
+}  // namespace jda

@@ -530,6 +530,26 @@ struct GatherArgs {
 };
 hipError_t launch_gather(const GatherArgs& a, hipStream_t stream);
 
+// ---- frames as they arrive: colour / pitched / cropped images -> dense 8-bit gray (k_pack.hip, pack.cpp; include/jda.h) ----
+constexpr int kPackBlock = 256;          // lanes of a workgroup: consecutive lanes take consecutive units
+constexpr int kPackRounds = 4;           // units of a lane: a workgroup covers kPackBlock * kPackRounds consecutive units
+// One image of a launch: w x h pixels of bpp bytes from src (the rectangle's first pixel; rows `pitch` bytes apart) to the w * h
+// bytes at dst.  Its output is dealt in UNITS: nq runs of 16 bytes from dst's first 16-byte boundary on, then one unit per
+// byte in front of that boundary (head, at most 15) and behind the last run (tail, at most 15).  first: the image's first unit
+// in the launch.  w_lo / w_hi: low and high bytes of the three Q14 weights, in the pixel's byte order (0: bpp == 1, a copy).
+struct PackImg {
+  const uint8_t* src; uint8_t* dst;
+  long long pitch, first, nq;
+  int w, h, bpp, head, tail;
+  uint32_t w_lo, w_hi;
+  int pad;
+};
+static_assert(sizeof(PackImg) == 72, "PackImg is uploaded as it is");
+// One launch: imgs[0 .. n), total = the units of all of them; block_img[b] = the image that holds unit
+// b * kPackBlock * kPackRounds (a lane walks on from there).
+struct PackArgs { const PackImg* imgs; const int* block_img; int n; long long total; };
+hipError_t launch_pack(const PackArgs& a, hipStream_t stream);
+
 // ---- dialect CPP: the positive sample set (k_faces.hip, faces.cpp; reference src/jda/data.cpp:542-565, 623-640) ----
 // One face of a launch: its image (d_base + off, W x H, rows back to back), its box (x, y, w, h) -- which may leave the
 // image: getFace pads with black -- and the destination record of its o / h / q patches.

@@ -52,6 +52,17 @@ def load_gray(path):
         return None
 
 
+def load_pixels(path):
+    """-> the decoded image as uint8 [h,w,3] RGB (what jdaPackGray / jdaPackGrayDevice take as JDA_PIX_RGB24), or None where
+    load_gray returns None.  load_gray(path) == bgr2gray(load_pixels(path)) for a colour file."""
+    try:
+        from PIL import Image
+        with Image.open(path) as im:
+            return np.ascontiguousarray(np.asarray(im.convert("RGB"), np.uint8))
+    except Exception:
+        return None
+
+
 def format_entry(image_id, rects, scores):
     """One image's block of a fold-XX-out.txt (test.cpp:153,163; %lf prints 6 decimals)."""
     lines = ["%s\n%d\n" % (image_id, len(scores))]
@@ -127,6 +138,27 @@ def detect_fold_ragged_cpp(casc, grays, params=None):
     p.update(params or {})
     res, st = casc.detect_ragged_cpp(grays, p["minimum_size"], p["step"], p["factor"], p["overlap"], p["nms"], stats=True)
     return [(r["rects"], r["scores"], r["shapes"]) for r in res], st
+
+
+def detect_fold_ragged_pixels(casc, rgbs, dialect="cpp", params=None, c_call=None):
+    """The same job from the decoded RGB images (load_pixels): they go to the device as they are, one jdaPackGrayDevice launch
+    makes the gray images there, and the dialect's ragged device entry runs on them.  -> as detect_fold_ragged[_cpp]."""
+    import torch
+    packed = casc.pack_gray_device([torch.from_numpy(np.ascontiguousarray(a, np.uint8)).cuda() for a in rgbs], "rgb24")
+    if dialect == "cpp":
+        p = dict(FDDB_DEFAULTS)
+        p.update(params or {})
+        res, st = casc.detect_ragged_cpp_packed(*packed, p["minimum_size"], p["step"], p["factor"], p["overlap"], p["nms"], stats=True)
+        return [(r["rects"], r["scores"], r["shapes"]) for r in res], st
+    call = dict(scale=1.25, min_size=40, max_size=-1, th=-0.5)
+    call.update(c_call or {})
+    res, st = casc.detect_ragged_packed(*packed, call["scale"], call["min_size"], call["max_size"], call["th"], stats=True)
+    out = []
+    for r in res:
+        bb = r["bboxes"]
+        rects = np.concatenate([bb, bb[:, 2:3]], 1) if len(bb) else np.zeros((0, 4), np.int32)
+        out.append((rects, r["scores"].astype(np.float64), r["shapes"].astype(np.float64)))
+    return out, st
 
 
 def run(casc, fddb_dir, folds=range(1, 11), dialect="cpp", params=None, rank=0, world=1, device=None, log=None,
