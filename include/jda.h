@@ -1223,7 +1223,7 @@ JDA_API int jdaCascadorSerializeToCpp(void *cascador, const char *path);
  * jdaBuildPositivesCppDevice take (d_base = dst, offsets = dst_offsets, widths / heights = the rectangles'), and with
  * dst_offsets[i] = i * frame_stride what jdaDetectBatchDevice, jdaDetectBatchSubmit and jdaValidateWindowsDevice take.
  * RESULTS OF A LATER DETECT CALL ARE IN THE RECTANGLE'S COORDINATES: add (x, y) to get back to the source image; there is no
- * relocation entry.
+ * relocation entry (jdaFaceChips, "faces as they leave" below, takes the rectangle with the landmarks as they are).
  *
  * jdaPackGray needs no cascador and no GPU: a plain loop over host memory, what a jdaDetect caller with a cv::Mat of BGR
  * uses.  jdaPackGrayDevice makes ONE kernel launch for all n images, of whatever sizes and formats (k_pack.hip); the
@@ -1257,6 +1257,89 @@ typedef struct { long long pixels, bytes_in, bytes_out; int launches; double dev
 JDA_API int jdaPackGray(const jdaPixels *images, int n, unsigned char *dst, const size_t *dst_offsets);
 JDA_API int jdaPackGrayDevice(void *cascador, const jdaPixels *images, int n, unsigned char *d_dst,
                               const size_t *dst_offsets, void *hip_stream, jdaPackStats *stats);
+
+/* ------------------------------------------------------------------------ */
+/* Faces as they leave                                                      */
+/* ------------------------------------------------------------------------ */
+/* Every detect entry hands back boxes, scores and landmarks.  What a recogniser, an attribute net, a quality filter or a
+ * thumbnailer takes is the face itself, turned upright by its landmarks and resampled to a fixed size: a CHIP.  These entries
+ * fit a similarity transform to each face's landmarks and cut its chip out of the source image -- any jdaPixels: the
+ * original colour frame, at its pitch, with the rectangle a packed crop was detected on -- in one call for any number of
+ * faces of any number of images.  Like the gray value above, the chip is DEFINED here, in fp64 with a stated order of
+ * operations up to a coordinate's rounding to 1/1024 pixel and in integers from there on: host form, device form and the
+ * restatement in tests/chips_ref.py agree to the byte, the matrices to the bit.
+ *
+ * The fit (on the host in both forms; fp64, every sum strictly sequential in landmark order from 0., no fused
+ * multiply-add).  Face f has landmarks p_i = (landmarks[f][2i], landmarks[f][2i+1]), pixels in the coordinates of its
+ * image's RECTANGLE (what a detect call on the packed rectangle returned; real_bytes 4: jdaResult's floats, each widened to
+ * double; 8: jdaResultD's doubles), and the template has points q_i = (tmpl[2i], tmpl[2i+1]) in chip pixels.  Only
+ * landmarks i with use[i] != 0 take part (use == NULL: all L); m = their number.
+ *   sum_qx = 0., then sum_qx = sum_qx + qx_i for the used i in index order; sum_qy, sum_px, sum_py alike
+ *   mqx = sum_qx / m    mqy = sum_qy / m    mpx = sum_px / m    mpy = sum_py / m          (m as a double)
+ *   per used i:  cqx = qx_i - mqx   cqy = qy_i - mqy   cpx = px_i - mpx   cpy = py_i - mpy
+ *   den = 0., sa = 0., sb = 0., then per used i in index order
+ *     den = den + (cqx * cqx + cqy * cqy)
+ *     sa  = sa  + (cqx * cpx + cqy * cpy)
+ *     sb  = sb  + (cqx * cpy - cqy * cpx)
+ *   a = sa / den    b = sb / den
+ *   tx = (mpx - (a * mqx - b * mqy)) + (double)rect.x
+ *   ty = (mpy - (b * mqx + a * mqy)) + (double)rect.y
+ *   M = {a, -b, tx, b, a, ty}
+ * M maps chip pixels to pixels of the WHOLE source image (least squares over the used landmarks); matrices, if given,
+ * receives the six doubles of every face.  A face is refused if fewer than 2 landmarks are used, if den == 0 (the used
+ * template points coincide) or if a landmark or template value that is used is not finite.
+ *
+ * Supersampling.  A chip pixel is the mean of n x n bilinear samples, n per axis, from s2 = a * a + b * b (the squared
+ * reduction; no sqrt): n = 1 if s2 <= 1, 2 if s2 <= 4, 3 if s2 <= 9, else 4.  supersample = 0 takes this n, 1..4 force it.
+ * BEYOND A 4x REDUCTION ALIASING RETURNS: n stops at 4; reduce the source first (the pyramid of jdaBuildPyramid) for more.
+ *
+ * A chip pixel (u, v), u < chip_w, v < chip_h.  For j in [0, n) and i in [0, n):
+ *   cu = (double)u + (double)((2 * i + 1) - n) / (double)(2 * n)      cv = (double)v + (double)((2 * j + 1) - n) / (double)(2 * n)
+ *   sx = (M[0] * cu + M[1] * cv) + M[2]                               sy = (M[3] * cu + M[4] * cv) + M[5]
+ *   the sample is 0 unless sx > -1 && sx < W && sy > -1 && sy < H (W, H: the whole source image, not the rectangle -- a
+ *   face at a crop's edge keeps its surroundings; a NaN fails the test); otherwise
+ *   X = (int64)floor(sx * 1024 + 0.5)   Y = (int64)floor(sy * 1024 + 0.5)
+ *   x0 = X >> 10   fx = X & 1023   y0 = Y >> 10   fy = Y & 1023
+ *   the taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), each 0 where outside the image, weigh
+ *   (1024 - fx) * (1024 - fy), fx * (1024 - fy), (1024 - fx) * fy, fx * fy; tap * weight is summed over all taps of all
+ *   samples in unsigned 32-bit integers (255 * 2^20 * 16 fits).
+ *   out = ((sum + n * n * 2^19) >> 20) / (n * n)                      (unsigned integer division)
+ *
+ * Formats.  Chips are JDA_PIX_GRAY8, JDA_PIX_BGR24 or JDA_PIX_RGB24; sources any JDA_PIX_*.  Colour to colour interpolates
+ * each channel, the channel order converted, alpha never read; gray to colour replicates the value; colour to gray converts
+ * each TAP with the Q14 formula of "frames as they arrive" and then interpolates, so the gray chip of a colour image equals
+ * the gray chip of its jdaPackGray image.  No byte outside the source image's pixels is ever read (not a pitch's slack, not
+ * alpha): a source that ends with its allocation is safe.
+ *
+ * Layout.  Chip f is written at dst + f * chip_w * chip_h * bytes per chip pixel, rows back to back, chips back to back.
+ *
+ * jdaFaceChips needs no cascador and no GPU: the definition in plain loops; tmpl is required.  jdaFaceChipsDevice takes
+ * device sources and a device d_dst (landmarks, tmpl, use, face_image and matrices are host memory: the fit runs on the
+ * host) and makes ONE kernel launch for all faces of the call, whatever their images' sizes and formats (k_chips.hip); the
+ * cascador supplies the device, the error state, a lane whose grow-only buffer holds the face and image records, and with
+ * tmpl == NULL the template: its mean shape times the chip size, q_i = (mean[2i] * chip_w, mean[2i+1] * chip_h), which
+ * needs landmark_n == the model's.  It runs on hip_stream if given, otherwise on the lane's own stream, returns when d_dst
+ * is complete and is re-entrant on one cascador like every other entry.  stats (may be NULL): faces, chip bytes written,
+ * taps (4 per sample: chip pixels * n * n * 4, read or not), kernel launches (1), the kernel's time between two events and
+ * the call's wall time.  jdaCascadorMeanShape copies the model's mean shape (2 * landmark_n doubles, normalised to the
+ * detection window) -- no other entry returns it.
+ *
+ * Refused with -1, jdaGetLastError() naming the face or image index, nothing launched and no byte of dst or matrices
+ * written: a NULL pointer where one is needed (images, face_image, landmarks, dst, tmpl in the host form; the cascador), a
+ * negative count, landmark_n < 1, real_bytes other than 4 or 8, a chip format that is not one of the three, chip_w or
+ * chip_h outside 1..4096, supersample outside 0..4, a face_image outside [0, n_images), everything jdaPackGray refuses
+ * about an image, a face the fit refuses, a destination that overlaps the byte range of any source image (its first pixel
+ * to its last).  n_faces == 0 returns 0 and touches nothing. */
+typedef struct { long long faces, chip_bytes, taps; int launches; double device_ms, call_ms; } jdaChipStats;
+
+JDA_API int jdaFaceChips(const jdaPixels *images, int n_images, const int *face_image, const void *landmarks, int real_bytes,
+                         int n_faces, int landmark_n, const double *tmpl, const unsigned char *use, int chip_w, int chip_h,
+                         int chip_format, int supersample, unsigned char *dst, double *matrices);
+JDA_API int jdaFaceChipsDevice(void *cascador, const jdaPixels *images, int n_images, const int *face_image,
+                               const void *landmarks, int real_bytes, int n_faces, int landmark_n, const double *tmpl,
+                               const unsigned char *use, int chip_w, int chip_h, int chip_format, int supersample,
+                               unsigned char *d_dst, double *matrices, void *hip_stream, jdaChipStats *stats);
+JDA_API int jdaCascadorMeanShape(void *cascador, double *mean_shape);
 
 #ifdef __cplusplus
 }

@@ -144,6 +144,14 @@ class jdaPackStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class jdaChipStats(C.Structure):
+    _fields_ = [("faces", C.c_longlong), ("chip_bytes", C.c_longlong), ("taps", C.c_longlong), ("launches", C.c_int),
+                ("device_ms", C.c_double), ("call_ms", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # include/jda.h, "frames as they arrive": JDA_PIX_* and their bytes per pixel
 JDA_PIX_GRAY8, JDA_PIX_BGR24, JDA_PIX_RGB24, JDA_PIX_BGRA32, JDA_PIX_RGBA32 = range(5)
 PIX_FORMATS = {"gray8": JDA_PIX_GRAY8, "bgr24": JDA_PIX_BGR24, "rgb24": JDA_PIX_RGB24, "bgra32": JDA_PIX_BGRA32,
@@ -354,6 +362,12 @@ def _load():
         lib.jdaPackGray.argtypes = [C.POINTER(jdaPixels), C.c_int, C.c_void_p, C.POINTER(C.c_size_t)]
         lib.jdaPackGrayDevice.argtypes = [C.c_void_p, C.POINTER(jdaPixels), C.c_int, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p,
                                           C.POINTER(jdaPackStats)]
+    if hasattr(lib, "jdaFaceChipsDevice"):
+        chips = [C.POINTER(jdaPixels), C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                 C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        lib.jdaFaceChips.argtypes = chips
+        lib.jdaFaceChipsDevice.argtypes = [C.c_void_p] + chips + [C.c_void_p, C.POINTER(jdaChipStats)]
+        lib.jdaCascadorMeanShape.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     return lib
 
 
@@ -750,6 +764,67 @@ def pack_gray(images, formats, rects=None):
     if lib.jdaPackGray(px, len(images), dst.ctypes.data, offs.ctypes.data_as(C.POINTER(C.c_size_t))) != 0:
         raise JdaError(last_error())
     return [dst[int(offs[i]):int(offs[i]) + w * h].reshape(h, w) for i, (w, h) in enumerate(sizes)]
+
+
+def lib_landmarks(casc):
+    info = jdaModelInfo()
+    return info.landmark_n if lib.jdaCascadorInfo(casc.h, C.byref(info)) == 0 else 1
+
+
+def _chip_faces(faces, landmarks, n_images):
+    """(face_image int32 [n], landmarks float32 / float64 [n, 2L], real_bytes) from either form a caller has: face_image and
+    a landmark array, or -- landmarks None -- one detect() result per image (a dict with "shapes", or None for no face)."""
+    if landmarks is None:
+        if len(faces) != n_images:
+            raise ValueError("face_chips: one detect() result (or None) per image")
+        shapes = [np.zeros((0, 0)) if r is None else np.asarray(r["shapes"] if isinstance(r, dict) else r) for r in faces]
+        shapes = [s.reshape(len(s), -1) if len(s) else s.reshape(0, 0) for s in shapes]
+        full = [s for s in shapes if len(s)]
+        fi = np.concatenate([np.full(len(s), i, np.int32) for i, s in enumerate(shapes)]) if shapes else np.zeros(0, np.int32)
+        lm = np.concatenate(full) if full else np.zeros((0, 2), np.float32)
+    else:
+        fi, lm = np.asarray(faces, np.int32).reshape(-1), np.asarray(landmarks)
+        lm = lm.reshape(len(fi), -1) if len(fi) else np.zeros((0, 2), lm.dtype)
+    if lm.dtype not in (np.float32, np.float64):
+        lm = lm.astype(np.float64)
+    return np.ascontiguousarray(fi, np.int32), np.ascontiguousarray(lm), lm.dtype.itemsize
+
+
+def _chip_args(px, n_images, fi, lm, rb, L, tmpl, use, chip_w, chip_h, chip_format, supersample, dst, mats):
+    t = None if tmpl is None else np.ascontiguousarray(tmpl, np.float64).reshape(-1)
+    if t is not None and len(fi) and t.size != 2 * L:
+        raise ValueError("face_chips: the template has %d values, the landmarks %d" % (t.size, 2 * L))
+    u = None if use is None else np.ascontiguousarray(use, np.uint8).reshape(-1)
+    if u is not None and len(fi) and u.size != L:
+        raise ValueError("face_chips: one `use` byte per landmark")
+    keep = (t, u, fi, lm)
+    return keep, [px, n_images, fi.ctypes.data_as(C.POINTER(C.c_int)), lm.ctypes.data, rb, len(fi), L,
+                  None if t is None else t.ctypes.data_as(C.POINTER(C.c_double)), None if u is None else u.ctypes.data,
+                  int(chip_w), int(chip_h), _pixel_format(chip_format), int(supersample), dst,
+                  mats.ctypes.data_as(C.POINTER(C.c_double))]
+
+
+def face_chips(images, formats, faces, landmarks, tmpl, chip_w, chip_h, chip_format="gray8", rects=None, use=None, supersample=0,
+               matrices=False):
+    """jdaFaceChips (include/jda.h, "faces as they leave"): numpy uint8 images like pack_gray's, faces = the image index of
+    every face and landmarks [n, 2L] float32 / float64 in the coordinates of the image's rectangle (or faces = one detect()
+    result per image and landmarks None), tmpl [2L] chip pixels -> uint8 chips [n, chip_h, chip_w] (gray8) or
+    [n, chip_h, chip_w, 3]; matrices=True: (chips, float64 [n, 6], chip -> source pixel).  Host only: no cascador, no GPU."""
+    images = [np.asarray(im) for im in images]
+    for im in images:
+        if im.dtype != np.uint8:
+            raise ValueError("face_chips: uint8 images")
+    px, _ = _pixel_table(images, formats, rects, lambda a: a.ctypes.data, lambda a: a.strides)
+    fi, lm, rb = _chip_faces(faces, landmarks, len(images))
+    n, bpp = len(fi), PIX_BYTES.get(_pixel_format(chip_format), 1)
+    dst = np.zeros((n, int(chip_h), int(chip_w)) + ((bpp,) if bpp > 1 else ()), np.uint8)
+    mats = np.zeros((max(n, 1), 6), np.float64)
+    keep, args = _chip_args(px, len(images), fi, lm, rb, lm.shape[1] // 2, tmpl, use, chip_w, chip_h, chip_format, supersample,
+                            dst.ctypes.data, mats)
+    if lib.jdaFaceChips(*args) != 0:
+        raise JdaError(last_error())
+    del keep
+    return (dst, mats[:n]) if matrices else dst
 
 
 def count_windows(width, height, scale=1.25, min_size=40, max_size=-1):
@@ -1151,6 +1226,55 @@ class Cascador:
             raise JdaError(last_error())
         res = (buf, offs[:n], [w for w, _ in sizes], [h for _, h in sizes])
         return (res, st.asdict()) if stats else res
+
+    # -- faces as they leave: upright chips cut from device images ---------------------------------
+    def mean_shape(self):
+        """jdaCascadorMeanShape: the model's mean shape, float64 [2L], normalised to the detection window."""
+        info = jdaModelInfo()
+        if lib.jdaCascadorInfo(self.h, C.byref(info)) != 0:
+            raise JdaError("jdaCascadorInfo failed")
+        out = np.zeros(2 * info.landmark_n, np.float64)
+        if lib.jdaCascadorMeanShape(self.h, out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+            raise JdaError(last_error())
+        return out
+
+    def face_chips_device(self, images, formats, faces, landmarks=None, tmpl=None, chip_w=112, chip_h=112, chip_format="gray8",
+                          rects=None, use=None, supersample=0, matrices=False, stats=False, hip_stream=None, out=None):
+        """jdaFaceChipsDevice: torch uint8 CUDA tensors like pack_gray_device's, faces / landmarks like face_chips' (one
+        detect() result per image with landmarks None), tmpl None: the model's mean shape at the chip's size -> a torch
+        uint8 CUDA tensor [n, chip_h, chip_w(, 3)], cut by ONE kernel launch.  out: the caller's own destination, a
+        contiguous uint8 CUDA tensor of n * chip_h * chip_w * bytes per pixel elements at any address.  matrices=True /
+        stats=True append the float64 [n, 6] matrices / jdaChipStats as a dict to the returned tuple."""
+        import torch
+        images = list(images)
+        for im in images:
+            if not (im.is_cuda and im.dtype == torch.uint8):
+                raise ValueError("face_chips_device: torch uint8 CUDA tensors")
+        px, _ = _pixel_table(images, formats, rects, lambda t: t.data_ptr(), lambda t: tuple(t.stride()))
+        fi, lm, rb = _chip_faces(faces, landmarks, len(images))
+        n, bpp = len(fi), PIX_BYTES.get(_pixel_format(chip_format), 1)
+        shape = (n, int(chip_h), int(chip_w)) + ((bpp,) if bpp > 1 else ())
+        if out is not None:
+            assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == int(np.prod(shape))
+            buf = out
+        else:
+            buf = torch.empty(max(int(np.prod(shape)), 1), dtype=torch.uint8, device=images[0].device if images else "cuda")
+        mats = np.zeros((max(n, 1), 6), np.float64)
+        L = lm.shape[1] // 2 if n else lib_landmarks(self)
+        keep, args = _chip_args(px, len(images), fi, lm, rb, L, tmpl, use, chip_w, chip_h, chip_format, supersample,
+                                C.c_void_p(buf.data_ptr()), mats)
+        st = jdaChipStats() if stats else None
+        rc = lib.jdaFaceChipsDevice(self.h, *args, C.c_void_p(hip_stream) if hip_stream is not None else None,
+                                    C.byref(st) if stats else None)
+        del keep
+        if rc != 0:
+            raise JdaError(last_error())
+        res = (buf.view(-1)[:int(np.prod(shape))].view(shape),)
+        if matrices:
+            res += (mats[:n],)
+        if stats:
+            res += (st.asdict(),)
+        return res[0] if len(res) == 1 else res
 
     # -- two batches in flight from one thread -----------------------------------
     def submit_batch_device(self, d_frames, scale=1.25, min_size=40, max_size=-1, th=-0.5, nms=True, stats=False):

@@ -395,6 +395,32 @@ int jdaPackGrayDevice(void* cascador, const jdaPixels* images, int n, unsigned c
   return pack_device((Cascador*)cascador, images, n, d_dst, dst_offsets, (hipStream_t)hip_stream, stats);
 } JDA_ABI_CATCH_SYNC(-1)
 
+int jdaFaceChips(const jdaPixels* images, int n_images, const int* face_image, const void* landmarks, int real_bytes, int n_faces,
+                 int landmark_n, const double* tmpl, const unsigned char* use, int chip_w, int chip_h, int chip_format, int supersample,
+                 unsigned char* dst, double* matrices) try {
+  g_err.clear();
+  return chips_host(ChipsCall{images, n_images, face_image, landmarks, real_bytes, n_faces, landmark_n, tmpl, use, chip_w, chip_h,
+                              chip_format, supersample, dst, matrices});
+} JDA_ABI_CATCH(-1)
+
+int jdaFaceChipsDevice(void* cascador, const jdaPixels* images, int n_images, const int* face_image, const void* landmarks,
+                       int real_bytes, int n_faces, int landmark_n, const double* tmpl, const unsigned char* use, int chip_w,
+                       int chip_h, int chip_format, int supersample, unsigned char* d_dst, double* matrices, void* hip_stream,
+                       jdaChipStats* stats) try {
+  g_err.clear();
+  return chips_device((Cascador*)cascador, ChipsCall{images, n_images, face_image, landmarks, real_bytes, n_faces, landmark_n, tmpl, use,
+                                                     chip_w, chip_h, chip_format, supersample, d_dst, matrices},
+                      (hipStream_t)hip_stream, stats);
+} JDA_ABI_CATCH_SYNC(-1)
+
+int jdaCascadorMeanShape(void* cascador, double* mean_shape) try {
+  g_err.clear();
+  if (!cascador || !mean_shape) { fail("jdaCascadorMeanShape: null cascador or mean_shape"); return -1; }
+  const HostModel& h = ((Cascador*)cascador)->hm;
+  std::memcpy(mean_shape, h.mean_shape.data(), h.mean_shape.size() * sizeof(double));
+  return 0;
+} JDA_ABI_CATCH(-1)
+
 int jdaBuildPyramid(void* cascador, const unsigned char* data, int width, int height,
                     unsigned char* half, int* hw, int* hh, unsigned char* quarter, int* qw, int* qh) try {
   g_err.clear();
@@ -619,7 +645,7 @@ namespace jda {
 void jda_bc_read_k_scan(unsigned long long*); void jda_bc_read_k_scan_d(unsigned long long*); void jda_bc_read_k_scan_r(unsigned long long*);
 void jda_bc_read_k_scan_dr(unsigned long long*); void jda_bc_read_k_scan_p(unsigned long long*); void jda_bc_read_k_finish(unsigned long long*);
 void jda_bc_read_k_wide(unsigned long long*); void jda_bc_read_k_stage(unsigned long long*); void jda_bc_read_k_mine(unsigned long long*); void jda_bc_read_k_train(unsigned long long*); void jda_bc_read_k_lbf(unsigned long long*);
-void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*); void jda_bc_read_k_fit(unsigned long long*); void jda_bc_read_k_reval(unsigned long long*); void jda_bc_read_k_windows(unsigned long long*); void jda_bc_read_k_pack(unsigned long long*);
+void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*); void jda_bc_read_k_fit(unsigned long long*); void jda_bc_read_k_reval(unsigned long long*); void jda_bc_read_k_windows(unsigned long long*); void jda_bc_read_k_pack(unsigned long long*); void jda_bc_read_k_chips(unsigned long long*);
 }
 // bounds-check build only (libjda_bounds.so): per translation unit {first violation: site << 32 | source line, violations}
 // since the last call -- out[16]; returns the total number of violations (kernels_common.h: Bc)
@@ -629,10 +655,10 @@ __attribute__((visibility("default"))) long long jdaDebugBoundsReport(unsigned l
                                         jda_bc_read_k_scan_p, jda_bc_read_k_finish, jda_bc_read_k_wide, jda_bc_read_k_stage};
   long long total = 0;
   for (int i = 0; i < 8; i++) { unsigned long long v[2] = {0, 0}; rd[i](v); if (out) { out[2 * i] = v[0]; out[2 * i + 1] = v[1]; } total += (long long)v[1]; }
-  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces', k_fit's, k_reval's, k_windows' and k_pack's words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file, cpp_patch.h or cpp_wave.h
-  const struct { void (*rd)(unsigned long long*); const char* tu; } more[9] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
+  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces', k_fit's, k_reval's, k_windows', k_pack's and k_chips' words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file, cpp_patch.h or cpp_wave.h
+  const struct { void (*rd)(unsigned long long*); const char* tu; } more[10] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
                                                                                 {jda_bc_read_k_gather, "k_gather"}, {jda_bc_read_k_faces, "k_faces"}, {jda_bc_read_k_fit, "k_fit"}, {jda_bc_read_k_reval, "k_reval"},
-                                                                                {jda_bc_read_k_windows, "k_windows"}, {jda_bc_read_k_pack, "k_pack"}};
+                                                                                {jda_bc_read_k_windows, "k_windows"}, {jda_bc_read_k_pack, "k_pack"}, {jda_bc_read_k_chips, "k_chips"}};
   for (const auto& t : more) {
     unsigned long long v[2] = {0, 0};
     t.rd(v);

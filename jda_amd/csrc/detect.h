@@ -69,6 +69,21 @@ int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_
 int pack_host(const jdaPixels* images, int n, unsigned char* dst, const size_t* dst_offsets);
 int pack_device(Cascador* c, const jdaPixels* images, int n, unsigned char* d_dst, const size_t* dst_offsets, hipStream_t user_stream,
                 jdaPackStats* stats);
+// ... and what it shares with chips.cpp: everything the entries refuse about ONE jdaPixels (fail() says what, behind the
+// prefix `img`), the rectangle resolved; bytes per pixel of a JDA_PIX_* (0: unknown); the Q14 weights of a colour pixel's
+// bytes 0, 1, 2 (include/jda.h)
+struct PixelsOne { const uint8_t* src; long long pitch; int x, y, w, h, bpp, format; };   // src: the rectangle's first pixel
+bool check_pixels(const std::string& img, const jdaPixels& p, PixelsOne* out);
+int pixels_bpp(int format);
+void pack_weights(int format, int w[3]);
+
+// chips.cpp: faces as they leave (jdaFaceChips / jdaFaceChipsDevice)
+struct ChipsCall {
+  const jdaPixels* images; int n_images; const int* face_image; const void* landmarks; int real_bytes, n_faces, landmark_n;
+  const double* tmpl; const unsigned char* use; int chip_w, chip_h, chip_format, supersample; unsigned char* dst; double* matrices;
+};
+int chips_host(const ChipsCall& call);
+int chips_device(Cascador* c, const ChipsCall& call, hipStream_t user_stream, jdaChipStats* stats);
 
 // detect_cpp.cpp: dialect CPP, method 1 (cascador.cpp:310-376,431-477) on a uniform batch; frames on the device
 // (d_frames) or, with host_frames set, in host memory

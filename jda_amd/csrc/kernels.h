@@ -550,6 +550,26 @@ static_assert(sizeof(PackImg) == 72, "PackImg is uploaded as it is");
 struct PackArgs { const PackImg* imgs; const int* block_img; int n; long long total; };
 hipError_t launch_pack(const PackArgs& a, hipStream_t stream);
 
+// ---- faces as they leave: upright face chips cut from detections (k_chips.hip, chips.cpp; include/jda.h) ----
+constexpr int kChipBlock = 256;          // lanes of a workgroup: consecutive lanes take consecutive units
+// One face of a launch: M maps chip pixel centres to source pixels (sx = (m[0] * cu + m[1] * cv) + m[2], sy with m[3..5]),
+// its source image and the sub-samples per axis.
+struct ChipFace { double m[6]; int image; int n; };
+static_assert(sizeof(ChipFace) == 56, "ChipFace is uploaded as it is");
+// One source image: the WHOLE image (taps leave the rectangle, never the image); rgb: byte 0 of a colour pixel is red.
+struct ChipImg { const uint8_t* data; long long pitch; int width, height, bpp, rgb; };
+static_assert(sizeof(ChipImg) == 32, "ChipImg is uploaded as it is");
+// One launch: n_faces chips of cw x ch pixels of cbpp (1 | 3) bytes back to back from dst.  The call's `bytes` output bytes are
+// ONE run, dealt in UNITS like k_pack's: nq runs of 16 bytes from dst's first 16-byte boundary on, then one unit per byte in
+// front of that boundary (head, at most 15) and behind the last run (tail, at most 15).  A chip of 45 bytes begins anywhere
+// inside a unit.
+struct ChipArgs {
+  const ChipFace* faces; const ChipImg* imgs; uint8_t* dst;
+  long long bytes, nq;
+  int head, tail, n_faces, n_images, cw, ch, cbpp, crgb;
+};
+hipError_t launch_chips(const ChipArgs& a, hipStream_t stream);
+
 // ---- dialect CPP: the positive sample set (k_faces.hip, faces.cpp; reference src/jda/data.cpp:542-565, 623-640) ----
 // One face of a launch: its image (d_base + off, W x H, rows back to back), its box (x, y, w, h) -- which may leave the
 // image: getFace pads with black -- and the destination record of its o / h / q patches.

@@ -124,7 +124,7 @@ enum BcSite : int { kBcScanPixLds = 1, kBcScanPixGlb = 2, kBcTileLoad = 3, kBcFi
                     kBcNodeTable = 7, kBcWindowTileLoad = 8, kBcS0Table = 9, kBcStagePix = 10, kBcQueue = 11, kBcLandmark = 12,
                     kBcGatherSrc = 13, kBcGatherDst = 14, kBcFacesSrc = 15, kBcFacesDst = 16,
                     kBcFitSample = 17, kBcFitWeight = 18, kBcWinList = 19, kBcWinOut = 20, kBcWinPyramid = 21,
-                    kBcPackSrc = 22, kBcPackDst = 23 };
+                    kBcPackSrc = 22, kBcPackDst = 23, kBcChipSrc = 24, kBcChipDst = 25 };
 #ifdef JDA_BOUNDS_CHECK
 static __device__ unsigned long long jda_bc_word[2];      // [0] first violation: site << 32 | line; [1] violations
 __device__ __forceinline__ void jda_bc_fail(int site, int line) {

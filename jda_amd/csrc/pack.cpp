@@ -1,7 +1,8 @@
 // libjda.so, host side: frames as they arrive (include/jda.h) -- jdaPackGray, a plain loop over host memory, and
 // jdaPackGrayDevice on the kernel of k_pack.hip.  Both validate everything before a byte is written or anything is launched;
 // the device form builds the image table and the item list of the launch, puts them into its lane's grow-only buffer and
-// makes one launch for all images.  No model is read.
+// makes one launch for all images.  No model is read.  What the entries refuse about ONE image (check_pixels) is shared with
+// chips.cpp.
 #include "detect.h"
 
 namespace jda {
@@ -14,15 +15,6 @@ struct PackOne {                      // an image of a call, rectangle resolved
   long long pitch, npix;
   int w, h, bpp, format;
 };
-
-int pack_bpp(int format) {
-  switch (format) {
-    case JDA_PIX_GRAY8: return 1;
-    case JDA_PIX_BGR24: case JDA_PIX_RGB24: return 3;
-    case JDA_PIX_BGRA32: case JDA_PIX_RGBA32: return 4;
-  }
-  return 0;
-}
 
 // Does [d0, d1) touch a byte the rectangle takes of any source row?  Row y takes [s + y * pitch, s + y * pitch + L).
 bool touches_rows(const PackOne& s, uintptr_t d0, uintptr_t d1) {
@@ -42,31 +34,12 @@ bool check_pack(const std::string& who, const jdaPixels* images, int n, unsigned
   if (!dst_offsets) { fail(who + "null dst_offsets"); return false; }
   out->resize((size_t)n);
   for (int i = 0; i < n; i++) {
-    const jdaPixels& p = images[i];
-    const std::string img = who + "image " + std::to_string(i) + ": ";
-    if (!p.data) { fail(img + "null data"); return false; }
-    const int bpp = pack_bpp(p.format);
-    if (!bpp) { fail(img + "unknown format " + std::to_string(p.format)); return false; }
-    if (p.width < 1 || p.height < 1) { fail(img + "width x height = " + std::to_string(p.width) + " x " + std::to_string(p.height) + ": an image has at least one pixel"); return false; }
-    if (p.pitch < (long long)p.width * bpp) {
-      fail(img + "pitch " + std::to_string(p.pitch) + " is smaller than a row (width " + std::to_string(p.width) + " x " + std::to_string(bpp) + " bytes per pixel)");
-      return false;
-    }
-    int x = p.x, y = p.y, w = p.w, h = p.h;
-    const std::string rect = "rectangle (x, y, w, h) = (" + std::to_string(p.x) + ", " + std::to_string(p.y) + ", " + std::to_string(p.w) + ", " + std::to_string(p.h) + ")";
-    if (w == 0 && h == 0) {
-      if (x != 0 || y != 0) { fail(img + rect + ": w == h == 0 takes the whole image, from (0, 0)"); return false; }
-      w = p.width; h = p.height;
-    }
-    if (w < 1 || h < 1) { fail(img + rect + ": w and h must be at least 1 (or both 0 for the whole image)"); return false; }
-    if (x < 0 || y < 0 || (long long)x + w > p.width || (long long)y + h > p.height) {
-      fail(img + rect + " leaves the image of " + std::to_string(p.width) + " x " + std::to_string(p.height));
-      return false;
-    }
+    PixelsOne r;
+    if (!check_pixels(who + "image " + std::to_string(i) + ": ", images[i], &r)) return false;
     PackOne& o = (*out)[(size_t)i];
-    o.src = p.data + (long long)y * p.pitch + (long long)x * bpp;
+    o.src = r.src;
     o.dst = dst + dst_offsets[i];
-    o.pitch = p.pitch; o.npix = (long long)w * h; o.w = w; o.h = h; o.bpp = bpp; o.format = p.format;
+    o.pitch = r.pitch; o.npix = (long long)r.w * r.h; o.w = r.w; o.h = r.h; o.bpp = r.bpp; o.format = r.format;
   }
   // two destination images that overlap: neighbours in address order
   std::vector<int> by_dst((size_t)n);
@@ -105,13 +78,46 @@ bool check_pack(const std::string& who, const jdaPixels* images, int n, unsigned
   return true;
 }
 
-// the Q14 weights of the pixel's bytes 0, 1, 2 (include/jda.h)
+}  // namespace
+
+int pixels_bpp(int format) {
+  switch (format) {
+    case JDA_PIX_GRAY8: return 1;
+    case JDA_PIX_BGR24: case JDA_PIX_RGB24: return 3;
+    case JDA_PIX_BGRA32: case JDA_PIX_RGBA32: return 4;
+  }
+  return 0;
+}
+
 void pack_weights(int format, int w[3]) {
   const bool rgb = format == JDA_PIX_RGB24 || format == JDA_PIX_RGBA32;
   w[0] = rgb ? 4899 : 1868; w[1] = 9617; w[2] = rgb ? 1868 : 4899;
 }
 
-}  // namespace
+bool check_pixels(const std::string& img, const jdaPixels& p, PixelsOne* out) {
+  if (!p.data) { fail(img + "null data"); return false; }
+  const int bpp = pixels_bpp(p.format);
+  if (!bpp) { fail(img + "unknown format " + std::to_string(p.format)); return false; }
+  if (p.width < 1 || p.height < 1) { fail(img + "width x height = " + std::to_string(p.width) + " x " + std::to_string(p.height) + ": an image has at least one pixel"); return false; }
+  if (p.pitch < (long long)p.width * bpp) {
+    fail(img + "pitch " + std::to_string(p.pitch) + " is smaller than a row (width " + std::to_string(p.width) + " x " + std::to_string(bpp) + " bytes per pixel)");
+    return false;
+  }
+  int x = p.x, y = p.y, w = p.w, h = p.h;
+  const std::string rect = "rectangle (x, y, w, h) = (" + std::to_string(p.x) + ", " + std::to_string(p.y) + ", " + std::to_string(p.w) + ", " + std::to_string(p.h) + ")";
+  if (w == 0 && h == 0) {
+    if (x != 0 || y != 0) { fail(img + rect + ": w == h == 0 takes the whole image, from (0, 0)"); return false; }
+    w = p.width; h = p.height;
+  }
+  if (w < 1 || h < 1) { fail(img + rect + ": w and h must be at least 1 (or both 0 for the whole image)"); return false; }
+  if (x < 0 || y < 0 || (long long)x + w > p.width || (long long)y + h > p.height) {
+    fail(img + rect + " leaves the image of " + std::to_string(p.width) + " x " + std::to_string(p.height));
+    return false;
+  }
+  out->src = p.data + (long long)y * p.pitch + (long long)x * bpp;
+  out->pitch = p.pitch; out->x = x; out->y = y; out->w = w; out->h = h; out->bpp = bpp; out->format = p.format;
+  return true;
+}
 
 int pack_host(const jdaPixels* images, int n, unsigned char* dst, const size_t* dst_offsets) {
   std::vector<PackOne> v;
