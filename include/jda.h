@@ -1222,8 +1222,9 @@ JDA_API int jdaCascadorSerializeToCpp(void *cascador, const char *path);
  * jdaDetectBatchRaggedDevice, jdaDetectBatchCppRaggedDevice, jdaValidateCppDevice, jdaMineNegativesCppDevice and
  * jdaBuildPositivesCppDevice take (d_base = dst, offsets = dst_offsets, widths / heights = the rectangles'), and with
  * dst_offsets[i] = i * frame_stride what jdaDetectBatchDevice, jdaDetectBatchSubmit and jdaValidateWindowsDevice take.
- * RESULTS OF A LATER DETECT CALL ARE IN THE RECTANGLE'S COORDINATES: add (x, y) to get back to the source image; there is no
- * relocation entry (jdaFaceChips, "faces as they leave" below, takes the rectangle with the landmarks as they are).
+ * RESULTS OF A LATER DETECT CALL ARE IN THE RECTANGLE'S COORDINATES: add (x, y) to get back to the source image, or let
+ * jdaOrientBack ("frames in any orientation" below) do it (jdaFaceChips, "faces as they leave", takes the rectangle with the
+ * landmarks as they are).
  *
  * jdaPackGray needs no cascador and no GPU: a plain loop over host memory, what a jdaDetect caller with a cv::Mat of BGR
  * uses.  jdaPackGrayDevice makes ONE kernel launch for all n images, of whatever sizes and formats (k_pack.hip); the
@@ -1257,6 +1258,71 @@ typedef struct { long long pixels, bytes_in, bytes_out; int launches; double dev
 JDA_API int jdaPackGray(const jdaPixels *images, int n, unsigned char *dst, const size_t *dst_offsets);
 JDA_API int jdaPackGrayDevice(void *cascador, const jdaPixels *images, int n, unsigned char *d_dst,
                               const size_t *dst_offsets, void *hip_stream, jdaPackStats *stats);
+
+/* ------------------------------------------------------------------------ */
+/* Frames in any orientation                                                */
+/* ------------------------------------------------------------------------ */
+/* The cascade finds upright faces; frames do not arrive upright.  A phone or camera stores the sensor's rows and says "rotate
+ * 90 degrees to display" in a tag, a mirrored front camera delivers flipped frames, a video decoder leaves the rotation to
+ * the consumer.  These entries are jdaPackGray[Device] with ONE more step -- every image is written turned by one of the
+ * eight orientations -- and the way back: jdaOrientBack takes the boxes and landmarks a detect call found on the turned
+ * images into the source images the caller holds.
+ *
+ * The orientation.  A code t in 0..7, EXACTLY the transforms[] code of jdaMineNegativesCpp (data.cpp:930-963), as three bits:
+ *     t      0  1  2  3  4  5  6  7
+ *     swap   .  x  .  x  .  x  .  x
+ *     flipX  .  .  x  x  x  x  .  .
+ *     flipY  .  x  x  .  .  x  x  .
+ * For a source rectangle of w x h pixels the turned image is W' x H' with W' = swap ? h : w and H' = swap ? w : h
+ * (jdaOrientSize), and its pixel (column u, row v) is the rectangle's pixel (x, y):
+ *     (x, y) = swap ? (v, u) : (u, v)
+ *     then x = w - 1 - x if flipX
+ *     then y = h - 1 - y if flipY
+ * In numpy, on the rectangle's gray image a (tests/mining_ref.py: transform; tests/turn_ref.py):
+ *     0: a              1: rot90(a, -1)  (a quarter turn clockwise)     2: rot90(a, 2)     3: rot90(a, 1)  (counter-clockwise)
+ *     4: fliplr(a)      5: rot90(a, 2).T (the anti-transpose)           6: flipud(a)       7: a.T
+ * EXIF.  Turning the STORED image by t gives the image as it should be displayed, for the Orientation tag
+ *     tag  1  2  3  4  5  6  7  8
+ *     t    0  4  2  6  7  1  5  3
+ * Orientations 4, 5, 6 and 7 mirror (the swap / flip matrix has determinant -1): a left eye becomes a right eye.
+ *
+ * jdaPackGrayOriented / jdaPackGrayOrientedDevice have the contract of jdaPackGray / jdaPackGrayDevice in every respect --
+ * formats, pitch, rectangle, the Q14 gray value, the refusals, the overlap checks, the stream, the return on completion,
+ * re-entrancy, stats with launches == 1 for n > 0 -- with one difference: image i is written turned by orients[i], as
+ * W' * H' bytes (the same number as w * h: the overlap checks are those of jdaPackGray), rows of W' bytes back to back.  An
+ * orients[i] outside 0..7 (and NULL orients with n > 0) is refused like an unknown format.  With every orientation 0 the
+ * bytes are jdaPackGray[Device]'s.  The host form is plain loops over the definition; the device form makes ONE kernel launch
+ * for all n images of whatever sizes, formats and orientations (k_turn.hip: 64 x 64 tiles through LDS) and, like k_pack,
+ * never reads a byte outside the rectangle's pixels of a source row's dwords: a source that ends with its allocation is safe.
+ *
+ * jdaOrientBack (host only, in place).  Face f belongs to image face_image[f]; boxes (n_faces * box_ints ints: box_ints 3
+ * (x, y, size) as jdaResult's, 4 (x, y, w, h) as jdaResultD's; may be NULL) and landmarks (n_faces * 2 * landmark_n reals of
+ * real_bytes 4 or 8, (x, y) pairs in pixels; may be NULL) are in the coordinates of that image's TURNED rectangle -- what a
+ * detect call on the turned image returned -- and on return in those of the WHOLE source image.  With (rx, ry, w, h) the
+ * image's rectangle:
+ *   boxes, integer exact:   (x0, y0, bw, bh) = swap ? (y, x, bh, bw) : (x, y, bw, bh)
+ *                           x0 = w - bw - x0 if flipX      y0 = h - bh - y0 if flipY      then x0 += rx, y0 += ry
+ *   landmarks, a pixel's centre being its integer index (how the cascade reads shape * size), in the type's own precision,
+ *   one operation per line, no fused multiply-add:
+ *                           swap the pair if swap
+ *                           x = (real)(w - 1) - x if flipX      y = (real)(h - 1) - y if flipY
+ *                           x = x + (real)rx                    y = y + (real)ry
+ *   for the mirroring orientations 4, 5, 6, 7 additionally the landmark pairs (left[j], right[j]), j = 0 .. sym_n - 1, are
+ *   exchanged SEQUENTIALLY IN LIST ORDER, exactly as jdaPositiveShapesCpp does -- a landmark named in two pairs is swapped
+ *   twice; sym_n == 0 leaves the labels alone.  Scores are not touched.
+ * Refused with -1, jdaGetLastError() naming the index, nothing written: NULL images, orients or face_image with n_faces > 0,
+ * a negative count, box_ints other than 3 or 4 (with boxes), real_bytes other than 4 or 8 or landmark_n < 1 (with
+ * landmarks), NULL left / right with sym_n > 0, a pair id outside [0, landmark_n), a face_image outside [0, n_images),
+ * everything jdaPackGray refuses about an image, an orientation outside 0..7.  n_faces == 0 returns 0 and touches nothing. */
+JDA_API int jdaOrientSize(int w, int h, int orient, int *tw, int *th);
+JDA_API int jdaPackGrayOriented(const jdaPixels *images, const int *orients, int n, unsigned char *dst,
+                                const size_t *dst_offsets);
+JDA_API int jdaPackGrayOrientedDevice(void *cascador, const jdaPixels *images, const int *orients, int n,
+                                      unsigned char *d_dst, const size_t *dst_offsets, void *hip_stream,
+                                      jdaPackStats *stats);
+JDA_API int jdaOrientBack(const jdaPixels *images, const int *orients, int n_images, const int *face_image, int n_faces,
+                          int *boxes, int box_ints, void *landmarks, int real_bytes, int landmark_n, const int *left,
+                          const int *right, int sym_n);
 
 /* ------------------------------------------------------------------------ */
 /* Faces as they leave                                                      */

@@ -368,6 +368,14 @@ def _load():
         lib.jdaFaceChips.argtypes = chips
         lib.jdaFaceChipsDevice.argtypes = [C.c_void_p] + chips + [C.c_void_p, C.POINTER(jdaChipStats)]
         lib.jdaCascadorMeanShape.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    if hasattr(lib, "jdaPackGrayOrientedDevice"):
+        ip = C.POINTER(C.c_int)
+        lib.jdaOrientSize.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip]
+        lib.jdaPackGrayOriented.argtypes = [C.POINTER(jdaPixels), ip, C.c_int, C.c_void_p, C.POINTER(C.c_size_t)]
+        lib.jdaPackGrayOrientedDevice.argtypes = [C.c_void_p, C.POINTER(jdaPixels), ip, C.c_int, C.c_void_p, C.POINTER(C.c_size_t),
+                                                  C.c_void_p, C.POINTER(jdaPackStats)]
+        lib.jdaOrientBack.argtypes = [C.POINTER(jdaPixels), ip, C.c_int, ip, C.c_int, ip, C.c_int, C.c_void_p, C.c_int, C.c_int, ip, ip,
+                                      C.c_int]
     return lib
 
 
@@ -764,6 +772,113 @@ def pack_gray(images, formats, rects=None):
     if lib.jdaPackGray(px, len(images), dst.ctypes.data, offs.ctypes.data_as(C.POINTER(C.c_size_t))) != 0:
         raise JdaError(last_error())
     return [dst[int(offs[i]):int(offs[i]) + w * h].reshape(h, w) for i, (w, h) in enumerate(sizes)]
+
+
+# ---- frames in any orientation (include/jda.h) ------------------------------------------------------------------------------
+EXIF_ORIENT = {1: 0, 2: 4, 3: 2, 4: 6, 5: 7, 6: 1, 7: 5, 8: 3}
+
+
+def orient_from_exif(tag):
+    """The orientation code t that turns the STORED image into the image as it should be displayed, for an EXIF Orientation
+    tag 1..8 (include/jda.h, "frames in any orientation")."""
+    if int(tag) not in EXIF_ORIENT:
+        raise ValueError("orient_from_exif: EXIF Orientation is 1..8, not %r" % (tag,))
+    return EXIF_ORIENT[int(tag)]
+
+
+def orient_size(w, h, orient):
+    """jdaOrientSize: (W', H') of a w x h rectangle turned by orient."""
+    tw, th = C.c_int(), C.c_int()
+    if lib.jdaOrientSize(int(w), int(h), int(orient), C.byref(tw), C.byref(th)) != 0:
+        raise JdaError(last_error())
+    return tw.value, th.value
+
+
+def _orients(orients, n):
+    """One orientation for all images or one per image -> int32 [max(n, 1)]."""
+    o = np.full(n, int(orients), np.int32) if np.ndim(orients) == 0 else np.ascontiguousarray(orients, np.int32).reshape(-1)
+    if len(o) != n:
+        raise ValueError("orients: one orientation for all images or one per image")
+    return o if n else np.zeros(1, np.int32)
+
+
+def _turned_sizes(sizes, orients):
+    return [(max(h, 0), max(w, 0)) if int(t) & 1 else (max(w, 0), max(h, 0)) for (w, h), t in zip(sizes, orients)]   # (odd codes swap)
+
+
+def pack_gray_oriented(images, formats, orients, rects=None):
+    """jdaPackGrayOriented: pack_gray with every image written turned by its orientation (0..7: one for all or one per image)
+    -> a list of uint8 [H', W'] gray arrays.  Host only: no cascador, no GPU."""
+    images = [np.asarray(im) for im in images]
+    for im in images:
+        if im.dtype != np.uint8:
+            raise ValueError("pack_gray_oriented: uint8 images")
+    px, sizes = _pixel_table(images, formats, rects, lambda a: a.ctypes.data, lambda a: a.strides)
+    o = _orients(orients, len(images))
+    sizes = _turned_sizes(sizes, o)
+    offs = np.zeros(max(len(images), 1), np.uint64)
+    tot = 0
+    for i, (w, h) in enumerate(sizes):
+        offs[i] = tot
+        tot += w * h
+    dst = np.empty(max(tot, 1), np.uint8)
+    if lib.jdaPackGrayOriented(px, o.ctypes.data_as(C.POINTER(C.c_int)), len(images), dst.ctypes.data,
+                               offs.ctypes.data_as(C.POINTER(C.c_size_t))) != 0:
+        raise JdaError(last_error())
+    return [dst[int(offs[i]):int(offs[i]) + w * h].reshape(h, w) for i, (w, h) in enumerate(sizes)]
+
+
+def orient_back(images, formats, orients, faces, boxes=None, landmarks=None, rects=None, left=(), right=()):
+    """jdaOrientBack: what a detect call found on images TURNED by orients (pack_gray_oriented[_device]) -> the coordinates of
+    the whole source images.  images / formats / rects as the pack call got them (numpy arrays or torch tensors: only their
+    shapes are read).  Either faces = the image index of every face with boxes (int [n, 3] (x, y, size) or [n, 4]
+    (x, y, w, h), or None) and landmarks (float32 / float64 [n, 2L], or None) -> (boxes, landmarks), new arrays; or faces = one
+    detect result per image (a dict with "bboxes" or "rects", "scores", "shapes"; None: no face) -> a list of new dicts.
+    left / right: the landmark pairs a mirroring orientation (4..7) exchanges."""
+    images = list(images)
+    tensor = bool(images) and hasattr(images[0], "data_ptr")
+    px, _ = _pixel_table(images, formats, rects, (lambda t: t.data_ptr()) if tensor else (lambda a: np.asarray(a).ctypes.data),
+                         (lambda t: tuple(int(v) * t.element_size() for v in t.stride())) if tensor else (lambda a: np.asarray(a).strides))
+    n_img = len(images)
+    o = _orients(orients, n_img)
+    results = boxes is None and landmarks is None and len(faces) == n_img and all(r is None or isinstance(r, dict) for r in faces)
+    if results:
+        key = ["bboxes" if r is not None and "bboxes" in r else "rects" for r in faces]
+        full = [(i, r) for i, r in enumerate(faces) if r is not None and len(r["scores"])]
+        fi = np.concatenate([np.full(len(r["scores"]), i, np.int32) for i, r in full]) if full else np.zeros(0, np.int32)
+        boxes = np.concatenate([np.asarray(r[key[i]], np.int32) for i, r in full]) if full else np.zeros((0, 3), np.int32)
+        landmarks = np.concatenate([np.asarray(r["shapes"]) for i, r in full]) if full else np.zeros((0, 2), np.float32)
+    else:
+        fi = np.asarray(faces, np.int32).reshape(-1)
+    fi = np.ascontiguousarray(fi, np.int32)
+    n = len(fi)
+    b = None if boxes is None else np.array(boxes, np.int32).reshape(n, -1)
+    lm = None if landmarks is None else np.asarray(landmarks)
+    if lm is not None:
+        lm = np.array(lm if lm.dtype in (np.float32, np.float64) else lm.astype(np.float64)).reshape(n, -1)
+    le, ri = np.ascontiguousarray(left, np.int32).reshape(-1), np.ascontiguousarray(right, np.int32).reshape(-1)
+    if len(le) != len(ri):
+        raise ValueError("orient_back: left and right name the two landmarks of every pair")
+    ip = C.POINTER(C.c_int)
+    rc = lib.jdaOrientBack(px, o.ctypes.data_as(ip), n_img, fi.ctypes.data_as(ip), n, None if b is None else b.ctypes.data_as(ip),
+                           b.shape[1] if b is not None else 0, None if lm is None else lm.ctypes.data,
+                           lm.dtype.itemsize if lm is not None else 0, lm.shape[1] // 2 if lm is not None else 0,
+                           le.ctypes.data_as(ip) if len(le) else None, ri.ctypes.data_as(ip) if len(le) else None, len(le))
+    if rc != 0:
+        raise JdaError(last_error())
+    if not results:
+        return b, lm
+    out, at = [], 0
+    for i, r in enumerate(faces):
+        if r is None:
+            out.append(None)
+            continue
+        m = len(r["scores"])
+        d = dict(r)
+        d[key[i]], d["shapes"], d["scores"] = b[at:at + m].copy(), lm[at:at + m].copy(), np.array(r["scores"])
+        out.append(d)
+        at += m
+    return out
 
 
 def lib_landmarks(casc):
@@ -1222,6 +1337,41 @@ class Cascador:
         st = jdaPackStats() if stats else None
         rc = lib.jdaPackGrayDevice(self.h, px, n, C.c_void_p(buf.data_ptr()), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
                                    C.c_void_p(hip_stream) if hip_stream is not None else None, C.byref(st) if stats else None)
+        if rc != 0:
+            raise JdaError(last_error())
+        res = (buf, offs[:n], [w for w, _ in sizes], [h for _, h in sizes])
+        return (res, st.asdict()) if stats else res
+
+    def pack_gray_oriented_device(self, images, formats, orients, rects=None, frame_stride=None, stats=False, hip_stream=None, out=None):
+        """jdaPackGrayOrientedDevice: pack_gray_device with every image written turned by its orientation (0..7: one for all
+        or one per image; include/jda.h, "frames in any orientation") by ONE kernel launch.  -> (buffer, offsets, widths,
+        heights) of the TURNED images, like pack_gray_device's; api.orient_back takes what a detect call finds on them back
+        to the source images."""
+        import torch
+        images = list(images)
+        for im in images:
+            if not (im.is_cuda and im.dtype == torch.uint8):
+                raise ValueError("pack_gray_oriented_device: torch uint8 CUDA tensors")
+        px, sizes = _pixel_table(images, formats, rects, lambda t: t.data_ptr(), lambda t: tuple(t.stride()))
+        n = len(images)
+        o = _orients(orients, n)
+        sizes = _turned_sizes(sizes, o)
+        if out is not None:
+            buf, offs = out[0], np.ascontiguousarray(out[1], np.uint64)
+            assert buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous() and len(offs) == n
+        else:
+            offs = np.zeros(max(n, 1), np.uint64)
+            tot = 0
+            for i, (w, h) in enumerate(sizes):
+                offs[i] = tot if frame_stride is None else i * int(frame_stride)
+                tot = int(offs[i]) + (w * h if frame_stride is None else max(w * h, int(frame_stride)))
+                if frame_stride is None:
+                    tot = (tot + 255) // 256 * 256
+            buf = torch.empty(max(tot, 1), dtype=torch.uint8, device=images[0].device if n else "cuda")
+        st = jdaPackStats() if stats else None
+        rc = lib.jdaPackGrayOrientedDevice(self.h, px, o.ctypes.data_as(C.POINTER(C.c_int)), n, C.c_void_p(buf.data_ptr()),
+                                           offs.ctypes.data_as(C.POINTER(C.c_size_t)),
+                                           C.c_void_p(hip_stream) if hip_stream is not None else None, C.byref(st) if stats else None)
         if rc != 0:
             raise JdaError(last_error())
         res = (buf, offs[:n], [w for w, _ in sizes], [h for _, h in sizes])

@@ -77,6 +77,28 @@ bool check_pixels(const std::string& img, const jdaPixels& p, PixelsOne* out);
 int pixels_bpp(int format);
 void pack_weights(int format, int w[3]);
 
+// ... and with turn.cpp: an image of a call, rectangle resolved, and everything the pack entries refuse about a call
+struct PackOne {
+  const uint8_t* src;                 // the rectangle's first pixel
+  uint8_t* dst;
+  long long pitch, npix;
+  int w, h, bpp, format;
+  int tf;                             // kTf[orientation] (0 without orients)
+};
+bool check_pack(const std::string& who, const jdaPixels* images, const int* orients, bool turned, int n, unsigned char* dst,
+                const size_t* dst_offsets, std::vector<PackOne>* out);
+
+// turn.cpp: frames in any orientation (jdaOrientSize, jdaPackGrayOriented[Device], jdaOrientBack)
+int orient_size(int w, int h, int orient, int* tw, int* th);
+int turn_host(const jdaPixels* images, const int* orients, int n, unsigned char* dst, const size_t* dst_offsets);
+int turn_device(Cascador* c, const jdaPixels* images, const int* orients, int n, unsigned char* d_dst, const size_t* dst_offsets,
+                hipStream_t user_stream, jdaPackStats* stats);
+struct OrientBackCall {
+  const jdaPixels* images; const int* orients; int n_images; const int* face_image; int n_faces; int* boxes; int box_ints;
+  void* landmarks; int real_bytes, landmark_n; const int* left; const int* right; int sym_n;
+};
+int orient_back(const OrientBackCall& call);
+
 // chips.cpp: faces as they leave (jdaFaceChips / jdaFaceChipsDevice)
 struct ChipsCall {
   const jdaPixels* images; int n_images; const int* face_image; const void* landmarks; int real_bytes, n_faces, landmark_n;

@@ -9,6 +9,7 @@
 //   fit.cpp        a stage's global regression (dialect CPP)       model_grow.cpp  the model in training: put a cart, close a stage, the f64 file
 //   reval.cpp      Validate on a resident sample set (dialect CPP)   windows.cpp  the cascade on caller-given windows (dialect C)
 //   pack.cpp       colour / pitched / cropped frames -> dense gray      chips.cpp    upright face chips cut from detections
+//   turn.cpp       the same, turned by one of the eight orientations; results mapped back
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -443,6 +444,7 @@ struct Lane {
   DevBuf pyr;                                // half + quarter images (multi-scale models), method-0 levels
   DevBuf win;                                // jdaValidateWindows: a chunk's window list and its per-window outputs (windows.cpp)
   DevBuf pack;                               // jdaPackGrayDevice: the image table and the item list of its launch (pack.cpp)
+  DevBuf turn;                               // jdaPackGrayOrientedDevice: the image table and the item list of its launch (turn.cpp)
   DevBuf chips;                              // jdaFaceChipsDevice: the face and image records of its launch (chips.cpp)
   // ragged passes: images at the common pitch, tight images, tables (segments, block map, image records)
   DevBuf rag_frames, rag_raw, rag_tab;
@@ -479,7 +481,7 @@ struct Lane {
     ~Bag() { for (void* p : dev) (void)hipFree(p); for (void* p : host) (void)hipHostFree(p); }
   };
   void trim(Bag* bag = nullptr) {
-    DevBuf* db[] = {&ws, &frames, &pyr, &win, &pack, &chips, &rag_frames, &rag_raw, &rag_tab};
+    DevBuf* db[] = {&ws, &frames, &pyr, &win, &pack, &turn, &chips, &rag_frames, &rag_raw, &rag_tab};
     HostPinned* hb[] = {&h_gid, &h_score, &h_shape, &h_tab, &h_raw, &h_pn, &h_pbb, &h_psc, &h_psh};
     for (DevBuf* b : db) { if (bag && b->p) { bag->dev.push_back(b->p); b->p = nullptr; b->bytes = 0; } else b->release(); }
     for (HostPinned* b : hb) { if (bag && b->p) { bag->host.push_back(b->p); b->p = nullptr; b->bytes = 0; } else b->release(); }

@@ -18,34 +18,11 @@
 //             - the weights are split into their low and high bytes, so a pixel is two v_dot4_u32_u8 on the dword that holds
 //               it: the byte that is alpha, or the next pixel's, meets a zero weight.  GRAY8 is the same kernel without it.
 //             No LDS, no atomics, no inline assembly, no scratch.
-#include "kernels_common.h"
+#include "pack_pixel.h"   // pack_gray, pack_pixel, the pack_*_t typedefs, JDA_BC_PACK_DWORDS: shared with k_turn.hip
 
 namespace jda {
 
 namespace {
-
-typedef uint32_t pack_u32x4 __attribute__((ext_vector_type(4)));
-typedef pack_u32x4 pack_u32x4_a4 __attribute__((aligned(4)));          // four dwords at a dword-aligned address
-// (the image records hand out plain pointers; said to be global memory, they are read and written with global_, not flat_, instructions)
-typedef const __attribute__((address_space(1))) uint8_t* pack_src_t;
-typedef __attribute__((address_space(1))) uint8_t* pack_dst_t;
-typedef const __attribute__((address_space(1))) uint32_t* pack_src4_t;
-typedef const __attribute__((address_space(1))) pack_u32x4_a4* pack_src16_t;
-typedef __attribute__((address_space(1))) pack_u32x4* pack_dst16_t;
-
-#ifdef JDA_BOUNDS_CHECK
-// n aligned dwords from p: each must hold a byte of bc (the bytes the rectangle takes of one source row)
-#define JDA_BC_PACK_DWORDS(bc, p, n) do { for (int k_ = 0; k_ < (n); k_++) { const long long q_ = (long long)(uintptr_t)(p) + 4 * k_; \
-    if (q_ + 4 <= (bc).lo || q_ >= (bc).hi) jda_bc_fail(kBcPackSrc, __LINE__); } } while (0)
-#else
-#define JDA_BC_PACK_DWORDS(bc, p, n) do { } while (0)
-#endif
-
-// the gray value of the pixel in the low bytes of px (weights: PackImg::w_lo / w_hi)
-__device__ __forceinline__ uint32_t pack_gray(uint32_t px, uint32_t w_lo, uint32_t w_hi) {
-  const uint32_t hi = __builtin_amdgcn_udot4(px, w_hi, 0u, false);
-  return __builtin_amdgcn_udot4(px, w_lo, (hi << 8) + 8192u, false) >> 14;
-}
 
 // 16 pixels of one source row from a (any alignment) -> their 16 gray bytes
 template <int BPP>
@@ -78,13 +55,6 @@ __device__ __forceinline__ pack_u32x4 pack_row16(pack_src_t a, uint32_t w_lo, ui
     }
     return pack_u32x4{o[0], o[1], o[2], o[3]};
   }
-}
-
-// one pixel, byte loads (alpha is not read)
-__device__ __forceinline__ uint32_t pack_pixel(pack_src_t p, int bpp, uint32_t w_lo, uint32_t w_hi, const Bc& bc_src) {
-  JDA_BC_ADDR(bc_src, p, bpp == 1 ? 1 : 3, kBcPackSrc);
-  if (bpp == 1) return p[0];
-  return pack_gray((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16), w_lo, w_hi);
 }
 
 // pixel p of a w-wide image -> (row, column); an image below 2^32 pixels divides in 32 bits

@@ -401,6 +401,11 @@ struct MineModel {
 // data.cpp:930-963 as bits (kMineSwap: transpose, kMineFlipX / kMineFlipY: mirror the stored x / y).
 struct MineImg { unsigned long long off; int w, h, tf, pad; };
 constexpr int kMineSwap = 1, kMineFlipX = 2, kMineFlipY = 4;
+// Orientation code t in 0..7 (jdaMineNegativesCpp's transforms[], include/jda.h "frames in any orientation") -> its bits:
+// turned pixel (u, v) is stored pixel (x, y) = swap ? (v, u) : (u, v), then x = w-1-x if FlipX, then y = h-1-y if FlipY.
+// The ONE table of mine.cpp and turn.cpp.
+constexpr int kTf[8] = {0, kMineSwap | kMineFlipY, kMineFlipX | kMineFlipY, kMineSwap | kMineFlipX, kMineFlipX,
+                        kMineSwap | kMineFlipX | kMineFlipY, kMineFlipY, kMineSwap};   // data.cpp:930-963, see k_mine.hip
 // One (image, level) of the enumeration: its windows are ordinals [first, first + nx*ny), row by row.
 struct MineSeg { unsigned long long first; int image, win, step, nx; };
 // One crop Validate runs on: (x, y, w, h) in the transformed image, key of its initial-shape draw.
@@ -549,6 +554,27 @@ static_assert(sizeof(PackImg) == 72, "PackImg is uploaded as it is");
 // b * kPackBlock * kPackRounds (a lane walks on from there).
 struct PackArgs { const PackImg* imgs; const int* block_img; int n; long long total; };
 hipError_t launch_pack(const PackArgs& a, hipStream_t stream);
+
+// ---- frames in any orientation: the same, turned by one of the eight orientations (k_turn.hip, turn.cpp; include/jda.h) ----
+constexpr int kTurnBlock = 256;          // lanes of a workgroup: one tile of one image
+constexpr int kTurnTile = 64;            // a tile is at most kTurnTile x kTurnTile pixels of the TURNED image
+constexpr int kTurnPitch = 68;           // bytes from one row of the LDS tile to the next (the bank reasoning)
+// One image of a launch: the w x h pixels of bpp bytes from src (the rectangle's first pixel; rows `pitch` bytes apart), turned
+// by tf (kMineSwap | kMineFlipX | kMineFlipY), to the tw * th bytes at dst (tw = swap ? h : w).  Its tiles are the launch's
+// workgroups [first, first + ntu * ntv), row by row; tile column k covers the turned columns [64 k - off, 64 k - off + 64)
+// inside [0, tw), off = dst & 15: on the turned row 0 -- and on every row where tw is a multiple of 16 -- a tile begins at a
+// 16-byte boundary of dst.  w_lo / w_hi: PackImg's.
+struct TurnImg {
+  const uint8_t* src; uint8_t* dst;
+  long long pitch, first;
+  int w, h, bpp, tf, ntu, ntv, off;
+  uint32_t w_lo, w_hi;
+  int pad;
+};
+static_assert(sizeof(TurnImg) == 72, "TurnImg is uploaded as it is");
+// One launch: imgs[0 .. n), total = the tiles of all of them; block_img[b] = the image of tile (workgroup) b.
+struct TurnArgs { const TurnImg* imgs; const int* block_img; int n; long long total; };
+hipError_t launch_turn(const TurnArgs& a, hipStream_t stream);
 
 // ---- faces as they leave: upright face chips cut from detections (k_chips.hip, chips.cpp; include/jda.h) ----
 constexpr int kChipBlock = 256;          // lanes of a workgroup: consecutive lanes take consecutive units

@@ -31,9 +31,6 @@ bool mine_levels(int W, int H, int os, int step, double factor, std::vector<Mine
   return true;
 }
 
-constexpr int kTf[8] = {0, kMineSwap | kMineFlipY, kMineFlipX | kMineFlipY, kMineSwap | kMineFlipX, kMineFlipX,
-                        kMineSwap | kMineFlipX | kMineFlipY, kMineFlipY, kMineSwap};   // data.cpp:930-963, see k_mine.hip
-
 }  // namespace
 
 // The mining tables of the model as it stands (built on first use, patched in place by model_grow.cpp); also reval.cpp's.

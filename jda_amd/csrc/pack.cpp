@@ -2,19 +2,12 @@
 // jdaPackGrayDevice on the kernel of k_pack.hip.  Both validate everything before a byte is written or anything is launched;
 // the device form builds the image table and the item list of the launch, puts them into its lane's grow-only buffer and
 // makes one launch for all images.  No model is read.  What the entries refuse about ONE image (check_pixels) is shared with
-// chips.cpp.
+// chips.cpp, what they refuse about a call (check_pack) with turn.cpp.
 #include "detect.h"
 
 namespace jda {
 
 namespace {
-
-struct PackOne {                      // an image of a call, rectangle resolved
-  const uint8_t* src;                 // the rectangle's first pixel
-  uint8_t* dst;
-  long long pitch, npix;
-  int w, h, bpp, format;
-};
 
 // Does [d0, d1) touch a byte the rectangle takes of any source row?  Row y takes [s + y * pitch, s + y * pitch + L).
 bool touches_rows(const PackOne& s, uintptr_t d0, uintptr_t d1) {
@@ -25,12 +18,17 @@ bool touches_rows(const PackOne& s, uintptr_t d0, uintptr_t d1) {
   return y < s.h && s0 + y * s.pitch < b;
 }
 
-// Everything jdaPackGray / jdaPackGrayDevice refuse (include/jda.h); on success one PackOne per image.
-bool check_pack(const std::string& who, const jdaPixels* images, int n, unsigned char* dst, const size_t* dst_offsets, std::vector<PackOne>* out) {
+}  // namespace
+
+// Everything jdaPackGray / jdaPackGrayDevice refuse (include/jda.h); on success one PackOne per image.  With orients (turn.cpp)
+// an orientation outside 0..7 is refused like an unknown format; a turned image takes the same w * h bytes of dst.
+bool check_pack(const std::string& who, const jdaPixels* images, const int* orients, bool turned, int n, unsigned char* dst,
+                const size_t* dst_offsets, std::vector<PackOne>* out) {
   if (n < 0) { fail(who + "negative number of images (n = " + std::to_string(n) + ")"); return false; }
   if (n == 0) return true;
   if (!images) { fail(who + "null images"); return false; }
   if (!dst) { fail(who + "null destination"); return false; }
+  if (turned && !orients) { fail(who + "null orients"); return false; }
   if (!dst_offsets) { fail(who + "null dst_offsets"); return false; }
   out->resize((size_t)n);
   for (int i = 0; i < n; i++) {
@@ -39,7 +37,11 @@ bool check_pack(const std::string& who, const jdaPixels* images, int n, unsigned
     PackOne& o = (*out)[(size_t)i];
     o.src = r.src;
     o.dst = dst + dst_offsets[i];
-    o.pitch = r.pitch; o.npix = (long long)r.w * r.h; o.w = r.w; o.h = r.h; o.bpp = r.bpp; o.format = r.format;
+    o.pitch = r.pitch; o.npix = (long long)r.w * r.h; o.w = r.w; o.h = r.h; o.bpp = r.bpp; o.format = r.format; o.tf = 0;
+    if (turned) {
+      if (orients[i] < 0 || orients[i] > 7) { fail(who + "image " + std::to_string(i) + ": unknown orientation " + std::to_string(orients[i]) + " (0..7)"); return false; }
+      o.tf = kTf[orients[i]];
+    }
   }
   // two destination images that overlap: neighbours in address order
   std::vector<int> by_dst((size_t)n);
@@ -77,8 +79,6 @@ bool check_pack(const std::string& who, const jdaPixels* images, int n, unsigned
   }
   return true;
 }
-
-}  // namespace
 
 int pixels_bpp(int format) {
   switch (format) {
@@ -121,7 +121,7 @@ bool check_pixels(const std::string& img, const jdaPixels& p, PixelsOne* out) {
 
 int pack_host(const jdaPixels* images, int n, unsigned char* dst, const size_t* dst_offsets) {
   std::vector<PackOne> v;
-  if (!check_pack("jdaPackGray: ", images, n, dst, dst_offsets, &v)) return -1;
+  if (!check_pack("jdaPackGray: ", images, nullptr, false, n, dst, dst_offsets, &v)) return -1;
   for (const PackOne& o : v) {
     uint8_t* d = o.dst;
     if (o.bpp == 1) {
@@ -144,7 +144,7 @@ int pack_device(Cascador* c, const jdaPixels* images, int n, unsigned char* d_ds
   const std::string who = "jdaPackGrayDevice: ";
   if (!c) { fail(who + "null cascador"); return -1; }
   std::vector<PackOne> v;
-  if (!check_pack(who, images, n, d_dst, dst_offsets, &v)) return -1;
+  if (!check_pack(who, images, nullptr, false, n, d_dst, dst_offsets, &v)) return -1;
   if (stats) std::memset(stats, 0, sizeof *stats);
   if (n == 0) return 0;
 
