@@ -753,25 +753,68 @@ def _pixel_table(images, formats, rects, address, strides):
     return px, sizes
 
 
+def _pixels(who, images, formats, rects, device):
+    """What every pack / chips call does with its images first: numpy uint8 arrays (device: torch uint8 CUDA tensors), or a
+    ValueError in the caller's name -> (the images as a list, their jdaPixels table, the (w, h) of their rectangles)."""
+    if device:
+        import torch
+        images = list(images)
+        ok = all(im.is_cuda and im.dtype == torch.uint8 for im in images)
+        address, strides = (lambda t: t.data_ptr()), (lambda t: tuple(t.stride()))
+    else:
+        images = [np.asarray(im) for im in images]
+        ok = all(im.dtype == np.uint8 for im in images)
+        address, strides = (lambda a: a.ctypes.data), (lambda a: a.strides)
+    if not ok:
+        raise ValueError("%s: %s" % (who, "torch uint8 CUDA tensors" if device else "uint8 images"))
+    return (images,) + _pixel_table(images, formats, rects, address, strides)
+
+
+def _offsets(sizes, align=1, frame_stride=None):
+    """Where images of the given (w, h) start in one destination, uint64 [max(n, 1)], and the bytes of it: back to back, each
+    at a multiple of align, or -- with frame_stride -- image i at i * frame_stride."""
+    offs = np.zeros(max(len(sizes), 1), np.uint64)
+    tot = 0
+    for i, (w, h) in enumerate(sizes):
+        offs[i] = tot if frame_stride is None else i * int(frame_stride)
+        tot = int(offs[i]) + (w * h if frame_stride is None else max(w * h, int(frame_stride)))
+        if frame_stride is None:
+            tot = (tot + align - 1) // align * align
+    return offs, tot
+
+
+def _device_buffer(buf, tot, images):
+    """The destination of a device call: the caller's own (checked), or a new one of tot bytes on the images' device."""
+    import torch
+    if buf is None:
+        return torch.empty(max(tot, 1), dtype=torch.uint8, device=images[0].device if images else "cuda")
+    assert buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous()
+    return buf
+
+
+def _pack_gray(who, images, formats, orients, rects):
+    """pack_gray (orients None) and pack_gray_oriented."""
+    images, px, sizes = _pixels(who, images, formats, rects, False)
+    n = len(images)
+    o = None if orients is None else _orients(orients, n)
+    sizes = _turned_sizes(sizes, o)
+    offs, tot = _offsets(sizes)
+    dst = np.empty(max(tot, 1), np.uint8)
+    offp = offs.ctypes.data_as(C.POINTER(C.c_size_t))
+    if o is None:
+        rc = lib.jdaPackGray(px, n, dst.ctypes.data, offp)
+    else:
+        rc = lib.jdaPackGrayOriented(px, o.ctypes.data_as(C.POINTER(C.c_int)), n, dst.ctypes.data, offp)
+    if rc != 0:
+        raise JdaError(last_error())
+    return [dst[int(offs[i]):int(offs[i]) + w * h].reshape(h, w) for i, (w, h) in enumerate(sizes)]
+
+
 def pack_gray(images, formats, rects=None):
     """jdaPackGray: numpy uint8 arrays [H, W, C] or [H, W] (row-strided views allowed) of the given formats ("bgr24", ... or
     JDA_PIX_*; one for all or one per image), each cut to its rectangle (x, y, w, h) (None: the whole image) -> a list of
     uint8 [h, w] gray arrays.  Host only: no cascador, no GPU."""
-    images = [np.asarray(im) for im in images]
-    for im in images:
-        if im.dtype != np.uint8:
-            raise ValueError("pack_gray: uint8 images")
-    px, sizes = _pixel_table(images, formats, rects, lambda a: a.ctypes.data, lambda a: a.strides)
-    sizes = [(max(w, 0), max(h, 0)) for w, h in sizes]
-    offs = np.zeros(max(len(images), 1), np.uint64)
-    tot = 0
-    for i, (w, h) in enumerate(sizes):
-        offs[i] = tot
-        tot += w * h
-    dst = np.empty(max(tot, 1), np.uint8)
-    if lib.jdaPackGray(px, len(images), dst.ctypes.data, offs.ctypes.data_as(C.POINTER(C.c_size_t))) != 0:
-        raise JdaError(last_error())
-    return [dst[int(offs[i]):int(offs[i]) + w * h].reshape(h, w) for i, (w, h) in enumerate(sizes)]
+    return _pack_gray("pack_gray", images, formats, None, rects)
 
 
 # ---- frames in any orientation (include/jda.h) ------------------------------------------------------------------------------
@@ -803,29 +846,14 @@ def _orients(orients, n):
 
 
 def _turned_sizes(sizes, orients):
-    return [(max(h, 0), max(w, 0)) if int(t) & 1 else (max(w, 0), max(h, 0)) for (w, h), t in zip(sizes, orients)]   # (odd codes swap)
+    """The (w, h) of rectangles turned by their orientations (None: none is); odd codes swap."""
+    return [(max(h, 0), max(w, 0)) if int(t) & 1 else (max(w, 0), max(h, 0)) for (w, h), t in zip(sizes, [0] * len(sizes) if orients is None else orients)]
 
 
 def pack_gray_oriented(images, formats, orients, rects=None):
     """jdaPackGrayOriented: pack_gray with every image written turned by its orientation (0..7: one for all or one per image)
     -> a list of uint8 [H', W'] gray arrays.  Host only: no cascador, no GPU."""
-    images = [np.asarray(im) for im in images]
-    for im in images:
-        if im.dtype != np.uint8:
-            raise ValueError("pack_gray_oriented: uint8 images")
-    px, sizes = _pixel_table(images, formats, rects, lambda a: a.ctypes.data, lambda a: a.strides)
-    o = _orients(orients, len(images))
-    sizes = _turned_sizes(sizes, o)
-    offs = np.zeros(max(len(images), 1), np.uint64)
-    tot = 0
-    for i, (w, h) in enumerate(sizes):
-        offs[i] = tot
-        tot += w * h
-    dst = np.empty(max(tot, 1), np.uint8)
-    if lib.jdaPackGrayOriented(px, o.ctypes.data_as(C.POINTER(C.c_int)), len(images), dst.ctypes.data,
-                               offs.ctypes.data_as(C.POINTER(C.c_size_t))) != 0:
-        raise JdaError(last_error())
-    return [dst[int(offs[i]):int(offs[i]) + w * h].reshape(h, w) for i, (w, h) in enumerate(sizes)]
+    return _pack_gray("pack_gray_oriented", images, formats, orients, rects)
 
 
 def orient_back(images, formats, orients, faces, boxes=None, landmarks=None, rects=None, left=(), right=()):
@@ -925,11 +953,7 @@ def face_chips(images, formats, faces, landmarks, tmpl, chip_w, chip_h, chip_for
     every face and landmarks [n, 2L] float32 / float64 in the coordinates of the image's rectangle (or faces = one detect()
     result per image and landmarks None), tmpl [2L] chip pixels -> uint8 chips [n, chip_h, chip_w] (gray8) or
     [n, chip_h, chip_w, 3]; matrices=True: (chips, float64 [n, 6], chip -> source pixel).  Host only: no cascador, no GPU."""
-    images = [np.asarray(im) for im in images]
-    for im in images:
-        if im.dtype != np.uint8:
-            raise ValueError("face_chips: uint8 images")
-    px, _ = _pixel_table(images, formats, rects, lambda a: a.ctypes.data, lambda a: a.strides)
+    images, px, _ = _pixels("face_chips", images, formats, rects, False)
     fi, lm, rb = _chip_faces(faces, landmarks, len(images))
     n, bpp = len(fi), PIX_BYTES.get(_pixel_format(chip_format), 1)
     dst = np.zeros((n, int(chip_h), int(chip_w)) + ((bpp,) if bpp > 1 else ()), np.uint8)
@@ -1305,6 +1329,29 @@ class Cascador:
         return (out, st.asdict()) if stats else out
 
     # -- frames as they arrive: colour / pitched / cropped device images -> dense gray ----------
+    def _pack_gray_device(self, who, images, formats, orients, rects, frame_stride, stats, hip_stream, out):
+        """pack_gray_device (orients None) and pack_gray_oriented_device."""
+        images, px, sizes = _pixels(who, images, formats, rects, True)
+        n = len(images)
+        o = None if orients is None else _orients(orients, n)
+        sizes = _turned_sizes(sizes, o)
+        offs, tot = _offsets(sizes, 256, frame_stride)
+        if out is not None:
+            offs = np.ascontiguousarray(out[1], np.uint64)
+            assert len(offs) == n
+        buf = _device_buffer(None if out is None else out[0], tot, images)
+        st = jdaPackStats() if stats else None
+        tail = (C.c_void_p(buf.data_ptr()), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
+                C.c_void_p(hip_stream) if hip_stream is not None else None, C.byref(st) if stats else None)
+        if o is None:
+            rc = lib.jdaPackGrayDevice(self.h, px, n, *tail)
+        else:
+            rc = lib.jdaPackGrayOrientedDevice(self.h, px, o.ctypes.data_as(C.POINTER(C.c_int)), n, *tail)
+        if rc != 0:
+            raise JdaError(last_error())
+        res = (buf, offs[:n], [w for w, _ in sizes], [h for _, h in sizes])
+        return (res, st.asdict()) if stats else res
+
     def pack_gray_device(self, images, formats, rects=None, frame_stride=None, stats=False, hip_stream=None, out=None):
         """jdaPackGrayDevice: torch uint8 CUDA tensors [H, W, C] or [H, W] (strided views allowed: a view's row stride is the
         pitch) of the given formats, each cut to its rectangle (x, y, w, h) (None: the whole image), packed to gray by ONE
@@ -1314,68 +1361,14 @@ class Cascador:
         i * frame_stride: buffer.view(n, h, w) then goes into detect_batch_device / submit_batch_device where frame_stride ==
         w * h.  hip_stream: a hipStream_t handle (torch.cuda.Stream().cuda_stream) the pixels were produced on.
         out = (buffer, offsets): the caller's own destination.  stats=True: (that tuple, jdaPackStats as a dict)."""
-        import torch
-        images = list(images)
-        for im in images:
-            if not (im.is_cuda and im.dtype == torch.uint8):
-                raise ValueError("pack_gray_device: torch uint8 CUDA tensors")
-        px, sizes = _pixel_table(images, formats, rects, lambda t: t.data_ptr(), lambda t: tuple(t.stride()))
-        n = len(images)
-        sizes = [(max(w, 0), max(h, 0)) for w, h in sizes]
-        if out is not None:
-            buf, offs = out[0], np.ascontiguousarray(out[1], np.uint64)
-            assert buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous() and len(offs) == n
-        else:
-            offs = np.zeros(max(n, 1), np.uint64)
-            tot = 0
-            for i, (w, h) in enumerate(sizes):
-                offs[i] = tot if frame_stride is None else i * int(frame_stride)
-                tot = int(offs[i]) + (w * h if frame_stride is None else max(w * h, int(frame_stride)))
-                if frame_stride is None:
-                    tot = (tot + 255) // 256 * 256
-            buf = torch.empty(max(tot, 1), dtype=torch.uint8, device=images[0].device if n else "cuda")
-        st = jdaPackStats() if stats else None
-        rc = lib.jdaPackGrayDevice(self.h, px, n, C.c_void_p(buf.data_ptr()), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
-                                   C.c_void_p(hip_stream) if hip_stream is not None else None, C.byref(st) if stats else None)
-        if rc != 0:
-            raise JdaError(last_error())
-        res = (buf, offs[:n], [w for w, _ in sizes], [h for _, h in sizes])
-        return (res, st.asdict()) if stats else res
+        return self._pack_gray_device("pack_gray_device", images, formats, None, rects, frame_stride, stats, hip_stream, out)
 
     def pack_gray_oriented_device(self, images, formats, orients, rects=None, frame_stride=None, stats=False, hip_stream=None, out=None):
         """jdaPackGrayOrientedDevice: pack_gray_device with every image written turned by its orientation (0..7: one for all
         or one per image; include/jda.h, "frames in any orientation") by ONE kernel launch.  -> (buffer, offsets, widths,
         heights) of the TURNED images, like pack_gray_device's; api.orient_back takes what a detect call finds on them back
         to the source images."""
-        import torch
-        images = list(images)
-        for im in images:
-            if not (im.is_cuda and im.dtype == torch.uint8):
-                raise ValueError("pack_gray_oriented_device: torch uint8 CUDA tensors")
-        px, sizes = _pixel_table(images, formats, rects, lambda t: t.data_ptr(), lambda t: tuple(t.stride()))
-        n = len(images)
-        o = _orients(orients, n)
-        sizes = _turned_sizes(sizes, o)
-        if out is not None:
-            buf, offs = out[0], np.ascontiguousarray(out[1], np.uint64)
-            assert buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous() and len(offs) == n
-        else:
-            offs = np.zeros(max(n, 1), np.uint64)
-            tot = 0
-            for i, (w, h) in enumerate(sizes):
-                offs[i] = tot if frame_stride is None else i * int(frame_stride)
-                tot = int(offs[i]) + (w * h if frame_stride is None else max(w * h, int(frame_stride)))
-                if frame_stride is None:
-                    tot = (tot + 255) // 256 * 256
-            buf = torch.empty(max(tot, 1), dtype=torch.uint8, device=images[0].device if n else "cuda")
-        st = jdaPackStats() if stats else None
-        rc = lib.jdaPackGrayOrientedDevice(self.h, px, o.ctypes.data_as(C.POINTER(C.c_int)), n, C.c_void_p(buf.data_ptr()),
-                                           offs.ctypes.data_as(C.POINTER(C.c_size_t)),
-                                           C.c_void_p(hip_stream) if hip_stream is not None else None, C.byref(st) if stats else None)
-        if rc != 0:
-            raise JdaError(last_error())
-        res = (buf, offs[:n], [w for w, _ in sizes], [h for _, h in sizes])
-        return (res, st.asdict()) if stats else res
+        return self._pack_gray_device("pack_gray_oriented_device", images, formats, orients, rects, frame_stride, stats, hip_stream, out)
 
     # -- faces as they leave: upright chips cut from device images ---------------------------------
     def mean_shape(self):
@@ -1395,20 +1388,12 @@ class Cascador:
         uint8 CUDA tensor [n, chip_h, chip_w(, 3)], cut by ONE kernel launch.  out: the caller's own destination, a
         contiguous uint8 CUDA tensor of n * chip_h * chip_w * bytes per pixel elements at any address.  matrices=True /
         stats=True append the float64 [n, 6] matrices / jdaChipStats as a dict to the returned tuple."""
-        import torch
-        images = list(images)
-        for im in images:
-            if not (im.is_cuda and im.dtype == torch.uint8):
-                raise ValueError("face_chips_device: torch uint8 CUDA tensors")
-        px, _ = _pixel_table(images, formats, rects, lambda t: t.data_ptr(), lambda t: tuple(t.stride()))
+        images, px, _ = _pixels("face_chips_device", images, formats, rects, True)
         fi, lm, rb = _chip_faces(faces, landmarks, len(images))
         n, bpp = len(fi), PIX_BYTES.get(_pixel_format(chip_format), 1)
         shape = (n, int(chip_h), int(chip_w)) + ((bpp,) if bpp > 1 else ())
-        if out is not None:
-            assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == int(np.prod(shape))
-            buf = out
-        else:
-            buf = torch.empty(max(int(np.prod(shape)), 1), dtype=torch.uint8, device=images[0].device if images else "cuda")
+        assert out is None or out.numel() == int(np.prod(shape))
+        buf = _device_buffer(out, int(np.prod(shape)), images)
         mats = np.zeros((max(n, 1), 6), np.float64)
         L = lm.shape[1] // 2 if n else lib_landmarks(self)
         keep, args = _chip_args(px, len(images), fi, lm, rb, L, tmpl, use, chip_w, chip_h, chip_format, supersample,

@@ -170,7 +170,7 @@ int chips_host(const ChipsCall& call) {
 }
 
 int chips_device(Cascador* c, const ChipsCall& call, hipStream_t user_stream, jdaChipStats* stats) {
-  const double t0 = now_ms();
+  LaneCall lc(c);
   const std::string who = "jdaFaceChipsDevice: ";
   if (!c) { fail(who + "null cascador"); return -1; }
   const int k = check_counts(who, call);
@@ -193,42 +193,25 @@ int chips_device(Cascador* c, const ChipsCall& call, hipStream_t user_stream, jd
   if (stats) std::memset(stats, 0, sizeof *stats);
 
   ChipArgs a{};
-  a.dst = call.dst; a.bytes = pl.bytes;
-  a.head = (int)std::min<long long>(pl.bytes, (long long)((0 - (uintptr_t)call.dst) & 15));
-  a.nq = (pl.bytes - a.head) >> 4;
-  a.tail = (int)(pl.bytes - a.head - (a.nq << 4));
+  const DstUnits u = dst_units(call.dst, pl.bytes);
+  a.dst = call.dst; a.bytes = pl.bytes; a.head = u.head; a.nq = u.nq; a.tail = u.tail;
   a.n_faces = call.n_faces; a.n_images = call.n_images; a.cw = call.chip_w; a.ch = call.chip_h; a.cbpp = pl.cbpp; a.crgb = pl.crgb;
-  if ((a.nq + a.head + a.tail + kChipBlock - 1) / kChipBlock > 0x7fffffffll) { fail(who + "too many chip bytes for one launch (" + std::to_string(pl.bytes) + ")"); return -1; }
+  if ((u.total() + kChipBlock - 1) / kChipBlock > 0x7fffffffll) { fail(who + "too many chip bytes for one launch (" + std::to_string(pl.bytes) + ")"); return -1; }
 
-  OneLane one(c);
-  if (!one.open()) return -1;
-  Lane* ln = one.lane;
-  const hipStream_t st = user_stream ? user_stream : one.stream;
-  double device_ms = 0;
+  if (!lc.open(user_stream)) return -1;
+  const hipStream_t st = lc.st;
   auto body = [&]() -> bool {
     ChipFace* d_faces; ChipImg* d_imgs;
-    // (the lane's own grow-only buffer: a per-frame caller pays no allocation and no hipFree, which waits for the whole device)
-    if (!carve_into(ln->chips, [&](Carver& cv) { d_faces = cv.take<ChipFace>(pl.faces.size()); d_imgs = cv.take<ChipImg>(pl.imgs.size()); })) return false;
-    JDA_HIP(hipMemcpyAsync(d_faces, pl.faces.data(), pl.faces.size() * sizeof(ChipFace), hipMemcpyHostToDevice, st));
-    JDA_HIP(hipMemcpyAsync(d_imgs, pl.imgs.data(), pl.imgs.size() * sizeof(ChipImg), hipMemcpyHostToDevice, st));
-    EvTimer timer;
-    if (!timer.open(stats != nullptr)) return false;
+    if (!lc.upload(pl.faces, pl.imgs, &d_faces, &d_imgs) || !lc.begin()) return false;
     a.faces = d_faces; a.imgs = d_imgs;
-    if (!timer.begin(st)) return false;
     JDA_HIP(launch_chips(a, st));
-    if (!timer.end(st)) return false;
-    JDA_HIP(hipStreamSynchronize(st));
-    return timer.add(&device_ms);
+    return lc.end() && lc.sync();
   };
-  if (!body()) {
-    (void)hipStreamSynchronize(st);      // nothing of this call is in flight when its lane goes back to the pool
-    (void)hipGetLastError();
-    return -1;
-  }
+  if (!lc.run(stats != nullptr, body)) return -1;
   matrices_out(pl, call.matrices);
   if (stats) {
     stats->faces = call.n_faces; stats->chip_bytes = pl.bytes; stats->taps = pl.taps; stats->launches = 1;
-    stats->device_ms = device_ms; stats->call_ms = now_ms() - t0;
+    stats->device_ms = lc.device_ms; stats->call_ms = lc.call_ms();
   }
   return 0;
 }

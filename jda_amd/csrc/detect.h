@@ -68,8 +68,7 @@ int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_
 // pack.cpp: frames as they arrive (jdaPackGray / jdaPackGrayDevice)
 int pack_host(const jdaPixels* images, int n, unsigned char* dst, const size_t* dst_offsets);
 int pack_device(Cascador* c, const jdaPixels* images, int n, unsigned char* d_dst, const size_t* dst_offsets, hipStream_t user_stream,
-                jdaPackStats* stats);
-// ... and what it shares with chips.cpp: everything the entries refuse about ONE jdaPixels (fail() says what, behind the
+                jdaPackStats* stats);// ... and what it shares with chips.cpp: everything the entries refuse about ONE jdaPixels (fail() says what, behind the
 // prefix `img`), the rectangle resolved; bytes per pixel of a JDA_PIX_* (0: unknown); the Q14 weights of a colour pixel's
 // bytes 0, 1, 2 (include/jda.h)
 struct PixelsOne { const uint8_t* src; long long pitch; int x, y, w, h, bpp, format; };   // src: the rectangle's first pixel
@@ -87,6 +86,32 @@ struct PackOne {
 };
 bool check_pack(const std::string& who, const jdaPixels* images, const int* orients, bool turned, int n, unsigned char* dst,
                 const size_t* dst_offsets, std::vector<PackOne>* out);
+// The units of `bytes` bytes at dst (kernels.h: PackImg, ChipArgs): bytes in front of dst's first 16-byte boundary, runs of 16, bytes behind
+struct DstUnits { int head; long long nq; int tail; long long total() const { return nq + head + tail; } };
+inline DstUnits dst_units(const void* dst, long long bytes) {
+  DstUnits u;
+  u.head = (int)std::min<long long>(bytes, (long long)((0 - (uintptr_t)dst) & 15));
+  u.nq = (bytes - u.head) >> 4;
+  u.tail = (int)(bytes - u.head - (u.nq << 4));
+  return u;
+}
+// What PackImg and TurnImg have in common, the rest zero: the image, its first unit / tile in the launch and the Q14 weights,
+// split into their low and high bytes
+template <typename Img>
+void pack_img(Img* t, const PackOne& o, long long first) {
+  std::memset(t, 0, sizeof *t);
+  t->src = o.src; t->dst = o.dst; t->pitch = o.pitch; t->w = o.w; t->h = o.h; t->bpp = o.bpp; t->first = first;
+  if (o.bpp == 1) return;
+  int w[3];
+  pack_weights(o.format, w);
+  t->w_lo = (uint32_t)(w[0] & 255) | ((uint32_t)(w[1] & 255) << 8) | ((uint32_t)(w[2] & 255) << 16);
+  t->w_hi = (uint32_t)(w[0] >> 8) | ((uint32_t)(w[1] >> 8) << 8) | ((uint32_t)(w[2] >> 8) << 16);
+}
+// jdaPackStats of a call that made its one launch
+void pack_stats(jdaPackStats* stats, const std::vector<PackOne>& v, const LaneCall& call);
+// pack_device's launch, on images check_pack has passed (at least one) and in the name `who` of the entry the caller called
+// (turn.cpp: every orientation 0)
+int pack_launch(LaneCall& call, const std::string& who, const std::vector<PackOne>& v, hipStream_t user_stream, jdaPackStats* stats);
 
 // turn.cpp: frames in any orientation (jdaOrientSize, jdaPackGrayOriented[Device], jdaOrientBack)
 int orient_size(int w, int h, int orient, int* tw, int* th);

@@ -443,9 +443,7 @@ struct Lane {
   DevBuf frames;                             // staging of host frames (the call's first lane holds the whole batch)
   DevBuf pyr;                                // half + quarter images (multi-scale models), method-0 levels
   DevBuf win;                                // jdaValidateWindows: a chunk's window list and its per-window outputs (windows.cpp)
-  DevBuf pack;                               // jdaPackGrayDevice: the image table and the item list of its launch (pack.cpp)
-  DevBuf turn;                               // jdaPackGrayOrientedDevice: the image table and the item list of its launch (turn.cpp)
-  DevBuf chips;                              // jdaFaceChipsDevice: the face and image records of its launch (chips.cpp)
+  DevBuf tab;                                // the host-made tables of a frame entry's one launch (LaneCall::upload: pack.cpp, turn.cpp, chips.cpp)
   // ragged passes: images at the common pitch, tight images, tables (segments, block map, image records)
   DevBuf rag_frames, rag_raw, rag_tab;
   HostPinned h_tab, h_raw;
@@ -481,7 +479,7 @@ struct Lane {
     ~Bag() { for (void* p : dev) (void)hipFree(p); for (void* p : host) (void)hipHostFree(p); }
   };
   void trim(Bag* bag = nullptr) {
-    DevBuf* db[] = {&ws, &frames, &pyr, &win, &pack, &turn, &chips, &rag_frames, &rag_raw, &rag_tab};
+    DevBuf* db[] = {&ws, &frames, &pyr, &win, &tab, &rag_frames, &rag_raw, &rag_tab};
     HostPinned* hb[] = {&h_gid, &h_score, &h_shape, &h_tab, &h_raw, &h_pn, &h_pbb, &h_psc, &h_psh};
     for (DevBuf* b : db) { if (bag && b->p) { bag->dev.push_back(b->p); b->p = nullptr; b->bytes = 0; } else b->release(); }
     for (HostPinned* b : hb) { if (bag && b->p) { bag->host.push_back(b->p); b->p = nullptr; b->bytes = 0; } else b->release(); }
@@ -619,6 +617,45 @@ struct OneLane {
     lane = set.v[0]; stream = lane->stream;
     return true;
   }
+};
+
+// A frame entry (pack.cpp, turn.cpp, chips.cpp, windows.cpp): a call that runs on one lane, on the caller's stream or the
+// lane's, and reports device_ms and call_ms.  Made where the entry begins (t0), opened once everything is validated.
+struct LaneCall {
+  const double t0 = now_ms();
+  OneLane one;
+  Lane* lane = nullptr;
+  hipStream_t st = nullptr;
+  EvTimer timer;
+  double device_ms = 0;
+  explicit LaneCall(Cascador* c) : one(c) {}
+  bool open(hipStream_t user_stream = nullptr) {
+    if (!one.open()) return false;
+    lane = one.lane; st = user_stream ? user_stream : one.stream;
+    return true;
+  }
+  // The call's device work (each step false after fail(), like JDA_HIP), with events only where statistics are wanted.
+  template <typename Body>
+  bool run(bool timed, Body&& body) {
+    if (timer.open(timed) && body()) return true;
+    (void)hipStreamSynchronize(st);      // nothing of this call is in flight when its lane goes back to the pool
+    (void)hipGetLastError();
+    return false;
+  }
+  // Two host tables -> the lane's own grow-only buffer: a per-frame caller pays no allocation and no hipFree, which waits
+  // for the whole device.  (A lane is held by one call, and a call makes one launch: one buffer serves every such entry.)
+  template <typename A, typename B>
+  bool upload(const std::vector<A>& a, const std::vector<B>& b, A** d_a, B** d_b) {
+    if (!carve_into(lane->tab, [&](Carver& cv) { *d_a = cv.take<A>(a.size()); *d_b = cv.take<B>(b.size()); })) return false;
+    JDA_HIP(hipMemcpyAsync(*d_a, a.data(), a.size() * sizeof(A), hipMemcpyHostToDevice, st));
+    JDA_HIP(hipMemcpyAsync(*d_b, b.data(), b.size() * sizeof(B), hipMemcpyHostToDevice, st));
+    return true;
+  }
+  // begin / end around a launch; sync waits for the stream and adds the span to device_ms
+  bool begin() { return timer.begin(st); }
+  bool end() { return timer.end(st); }
+  bool sync() { JDA_HIP(hipStreamSynchronize(st)); return timer.add(&device_ms); }
+  double call_ms() const { return now_ms() - t0; }
 };
 
 // The model of dialect Real on the device (model_dev.cpp; caller holds c->mu).

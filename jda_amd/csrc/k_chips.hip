@@ -15,26 +15,20 @@
 //               lanes are neighbouring chip pixels): a tap outside the image, or one whose weight is 0, is not read, alpha
 //               is never read, so a source that ends with its allocation is safe;
 //             - all offsets are 64-bit.  No LDS, no atomics, no inline assembly, no scratch.
-#include "kernels_common.h"
+#include "pack_pixel.h"   // the pack_*_t typedefs, pack_unit, pack_divmod: shared with k_pack.hip
 
 namespace jda {
 
 namespace {
-
-typedef uint32_t chip_u32x4 __attribute__((ext_vector_type(4)));
-// (the records hand out plain pointers; said to be global memory, they are read and written with global_, not flat_, instructions)
-typedef const __attribute__((address_space(1))) uint8_t* chip_src_t;
-typedef __attribute__((address_space(1))) uint8_t* chip_dst_t;
-typedef __attribute__((address_space(1))) chip_u32x4* chip_dst16_t;
 
 // One tap of weight wgt at (x, y) into the CC channel sums: nothing outside the image.  gray: the chip is gray (CC == 1), a
 // colour tap goes through the Q14 formula first; swap: chip and source differ in their channel order.
 template <int CC>
 __device__ __forceinline__ void chip_tap(const ChipImg& im, bool swap, long long x, long long y, uint32_t wgt, uint32_t acc[CC]) {
   if (wgt == 0u || x < 0 || y < 0 || x >= im.width || y >= im.height) return;
-  const chip_src_t row = (chip_src_t)im.data + y * im.pitch;
+  const pack_src_t row = (pack_src_t)im.data + y * im.pitch;
   [[maybe_unused]] const Bc bc_row((long long)(uintptr_t)row, (long long)(uintptr_t)row + (long long)im.width * im.bpp);
-  const chip_src_t p = row + x * im.bpp;
+  const pack_src_t p = row + x * im.bpp;
   JDA_BC_ADDR(bc_row, p, im.bpp == 1 ? 1 : 3, kBcChipSrc);
   if (im.bpp == 1) {
     const uint32_t g = p[0];
@@ -44,8 +38,8 @@ __device__ __forceinline__ void chip_tap(const ChipImg& im, bool swap, long long
   }
   const uint32_t b0 = p[0], b1 = p[1], b2 = p[2];
   if constexpr (CC == 1) {
-    const uint32_t w0 = im.rgb ? 4899u : 1868u, w2 = im.rgb ? 1868u : 4899u;
-    acc[0] += wgt * ((b0 * w0 + b1 * 9617u + b2 * w2 + 8192u) >> 14);
+    const uint32_t w0 = im.rgb ? kGrayR : kGrayB, w2 = im.rgb ? kGrayB : kGrayR;
+    acc[0] += wgt * ((b0 * w0 + b1 * kGrayG + b2 * w2 + 8192u) >> 14);
   } else {
     acc[0] += wgt * (swap ? b2 : b0);
     acc[1] += wgt * b1;
@@ -90,13 +84,11 @@ __global__ __launch_bounds__(kChipBlock) void k_chips(ChipArgs a) {
   [[maybe_unused]] const Bc bc_dst((long long)(uintptr_t)a.dst, (long long)(uintptr_t)a.dst + a.bytes);
   // the unit's first byte of the call's output and its length
   long long p0; int len;
-  if (g < a.nq) { p0 = a.head + (g << 4); len = 16; }
-  else { const long long e = g - a.nq; p0 = e < a.head ? e : (a.nq << 4) + e; len = 1; }   // [0, head): in front, [head, head + tail): behind
+  pack_unit(g, a.nq, a.head, &p0, &len);
   // ... is byte c0 of pixel (u, v) of face f; a chip is below 2^26 pixels, the call's output below 2^32 bytes divides in 32 bits
   const uint32_t chip_bytes = (uint32_t)a.cw * (uint32_t)a.ch * (uint32_t)a.cbpp;
-  long long f; uint32_t r;
-  if (p0 <= 0xffffffffll) { const uint32_t q = (uint32_t)p0 / chip_bytes; f = q; r = (uint32_t)p0 - q * chip_bytes; }
-  else { f = p0 / (long long)chip_bytes; r = (uint32_t)(p0 - f * (long long)chip_bytes); }
+  const pack_qr fr = pack_divmod(p0, chip_bytes);
+  long long f = fr.q; const uint32_t r = fr.r;
   const uint32_t pix = r / (uint32_t)a.cbpp;
   int c0 = (int)(r - pix * (uint32_t)a.cbpp);
   int v = (int)(pix / (uint32_t)a.cw), u = (int)(pix - (uint32_t)v * (uint32_t)a.cw);
@@ -138,10 +130,10 @@ __global__ __launch_bounds__(kChipBlock) void k_chips(ChipArgs a) {
   }
   if (len == 16) {
     JDA_BC_ADDR(bc_dst, a.dst + p0, 16, kBcChipDst);
-    *(chip_dst16_t)(a.dst + p0) = chip_u32x4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};   // 16-byte aligned: head is dst's distance to its first boundary
+    *(pack_dst16_t)(a.dst + p0) = pack_u32x4{(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};   // 16-byte aligned: head is dst's distance to its first boundary
   } else {
     JDA_BC_ADDR(bc_dst, a.dst + p0, 1, kBcChipDst);
-    ((chip_dst_t)a.dst)[p0] = (uint8_t)lo;
+    ((pack_dst_t)a.dst)[p0] = (uint8_t)lo;
   }
 }
 

@@ -18,57 +18,9 @@
 //             - the weights are split into their low and high bytes, so a pixel is two v_dot4_u32_u8 on the dword that holds
 //               it: the byte that is alpha, or the next pixel's, meets a zero weight.  GRAY8 is the same kernel without it.
 //             No LDS, no atomics, no inline assembly, no scratch.
-#include "pack_pixel.h"   // pack_gray, pack_pixel, the pack_*_t typedefs, JDA_BC_PACK_DWORDS: shared with k_turn.hip
+#include "pack_pixel.h"   // pack_row, pack_pixel, pack_unit, pack_divmod, the pack_*_t typedefs: shared with k_turn.hip and k_chips.hip
 
 namespace jda {
-
-namespace {
-
-// 16 pixels of one source row from a (any alignment) -> their 16 gray bytes
-template <int BPP>
-__device__ __forceinline__ pack_u32x4 pack_row16(pack_src_t a, uint32_t w_lo, uint32_t w_hi, const Bc& bc_row) {
-  constexpr int ND = 4 * BPP;                                    // dwords that 16 pixels fill
-  const uint32_t sh = (uint32_t)((uintptr_t)a & 3);
-  const pack_src4_t s4 = (pack_src4_t)(a - sh);                    // dword aligned
-  JDA_BC_PACK_DWORDS(bc_row, s4, sh ? ND + 1 : ND);
-  uint32_t d[ND + 1];
-#pragma unroll
-  for (int k = 0; k < ND; k += 4) {
-    const pack_u32x4 v = *(pack_src16_t)(s4 + k);
-    d[k] = v.x; d[k + 1] = v.y; d[k + 2] = v.z; d[k + 3] = v.w;
-  }
-  d[ND] = sh ? s4[ND] : 0u;                                        // (holds a byte of the last pixel only then)
-  uint32_t t[ND + 1];                                              // the 16 * BPP bytes from a on
-#pragma unroll
-  for (int k = 0; k < ND; k++) t[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);
-  t[ND] = 0u;
-  if constexpr (BPP == 1) {
-    return pack_u32x4{t[0], t[1], t[2], t[3]};
-  } else {
-    uint32_t o[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-      constexpr int B = BPP;
-      const int j = (B * k) >> 2, off = (B * k) & 3;               // the pixel's dword and its byte in it (constants once unrolled)
-      const uint32_t px = off ? __builtin_amdgcn_alignbyte(t[j + 1], t[j], (uint32_t)off) : t[j];
-      o[k >> 2] |= pack_gray(px, w_lo, w_hi) << (8 * (k & 3));
-    }
-    return pack_u32x4{o[0], o[1], o[2], o[3]};
-  }
-}
-
-// pixel p of a w-wide image -> (row, column); an image below 2^32 pixels divides in 32 bits
-__device__ __forceinline__ void pack_yx(long long p, int w, long long* y, int* x) {
-  if (p <= 0xffffffffll) {
-    const uint32_t q = (uint32_t)p / (uint32_t)w;
-    *y = q; *x = (int)((uint32_t)p - q * (uint32_t)w);
-  } else {
-    const long long q = p / w;
-    *y = q; *x = (int)(p - q * w);
-  }
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(kPackBlock) void k_pack(PackArgs a) {
   const long long base = (long long)blockIdx.x * (kPackBlock * kPackRounds);
@@ -89,20 +41,20 @@ __global__ __launch_bounds__(kPackBlock) void k_pack(PackArgs a) {
     const long long npix = (long long)im.w * im.h;
     [[maybe_unused]] const Bc bc_dst((long long)(uintptr_t)im.dst, (long long)(uintptr_t)im.dst + npix);
     [[maybe_unused]] const Bc bc_src((long long)(uintptr_t)im.src, (long long)(uintptr_t)im.src + (long long)(im.h - 1) * im.pitch + (long long)im.w * im.bpp);
-    if (u < im.nq) {
-      const long long p0 = im.head + (u << 4);
-      long long y; int x;
-      pack_yx(p0, im.w, &y, &x);
-      pack_u32x4 o;
+    long long p0; int len;
+    pack_unit(u, im.nq, im.head, &p0, &len);
+    const pack_qr yx = pack_divmod(p0, (uint32_t)im.w);            // the unit's first pixel: row y, column x
+    const long long y = yx.q; int x = (int)yx.r;
+    if (len == 16) {
+      uint32_t q[4] = {0u, 0u, 0u, 0u};
       if (x + 16 <= im.w) {
         const pack_src_t row = (pack_src_t)im.src + y * im.pitch;
         [[maybe_unused]] const Bc bc_row((long long)(uintptr_t)row, (long long)(uintptr_t)row + (long long)im.w * im.bpp);
         const pack_src_t s = row + (long long)x * im.bpp;
-        if (im.bpp == 1) o = pack_row16<1>(s, 0u, 0u, bc_row);
-        else if (im.bpp == 3) o = pack_row16<3>(s, im.w_lo, im.w_hi, bc_row);
-        else o = pack_row16<4>(s, im.w_lo, im.w_hi, bc_row);
+        if (im.bpp == 1) pack_row<1, 16>(s, 0u, 0u, bc_row, q);
+        else if (im.bpp == 3) pack_row<3, 16>(s, im.w_lo, im.w_hi, bc_row, q);
+        else pack_row<4, 16>(s, im.w_lo, im.w_hi, bc_row, q);
       } else {
-        uint32_t q[4] = {0u, 0u, 0u, 0u};
         pack_src_t row = (pack_src_t)im.src + y * im.pitch;
         pack_src_t s = row + (long long)x * im.bpp;
 #pragma unroll
@@ -111,18 +63,13 @@ __global__ __launch_bounds__(kPackBlock) void k_pack(PackArgs a) {
           s += im.bpp;
           if (++x == im.w) { x = 0; row += im.pitch; s = row; }
         }
-        o = pack_u32x4{q[0], q[1], q[2], q[3]};
       }
       JDA_BC_ADDR(bc_dst, im.dst + p0, 16, kBcPackDst);
-      *(pack_dst16_t)(im.dst + p0) = o;                            // 16-byte aligned: head is dst's distance to its first boundary
+      *(pack_dst16_t)(im.dst + p0) = pack_u32x4{q[0], q[1], q[2], q[3]};   // 16-byte aligned: head is dst's distance to its first boundary
     } else {
-      const long long e = u - im.nq;                               // [0, head): the bytes in front, [head, head + tail): behind
-      const long long p = e < im.head ? e : (im.nq << 4) + e;
-      long long y; int x;
-      pack_yx(p, im.w, &y, &x);
       const uint32_t v = pack_pixel((pack_src_t)im.src + y * im.pitch + (long long)x * im.bpp, im.bpp, im.w_lo, im.w_hi, bc_src);
-      JDA_BC_ADDR(bc_dst, im.dst + p, 1, kBcPackDst);
-      ((pack_dst_t)im.dst)[p] = (uint8_t)v;
+      JDA_BC_ADDR(bc_dst, im.dst + p0, 1, kBcPackDst);
+      ((pack_dst_t)im.dst)[p0] = (uint8_t)v;
     }
   }
 }

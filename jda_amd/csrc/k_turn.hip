@@ -25,47 +25,7 @@ namespace jda {
 
 namespace {
 
-typedef uint32_t turn_u32x3 __attribute__((ext_vector_type(3)));
-typedef turn_u32x3 turn_u32x3_a4 __attribute__((aligned(4)));
-typedef const __attribute__((address_space(1))) turn_u32x3_a4* turn_src12_t;
-
 constexpr int kTurnLds = kTurnTile * kTurnPitch;
-
-// 4 pixels of one source row from a (any alignment) -> their 4 gray bytes
-template <int BPP>
-__device__ __forceinline__ uint32_t turn_row4(pack_src_t a, uint32_t w_lo, uint32_t w_hi, const Bc& bc_row) {
-  const uint32_t sh = (uint32_t)((uintptr_t)a & 3);
-  const pack_src4_t s4 = (pack_src4_t)(a - sh);                    // dword aligned
-  JDA_BC_PACK_DWORDS(bc_row, s4, sh ? BPP + 1 : BPP);
-  uint32_t d[BPP + 1];
-  if constexpr (BPP == 4) {
-    const pack_u32x4 v = *(pack_src16_t)s4;
-    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-  } else if constexpr (BPP == 3) {
-    const turn_u32x3 v = *(turn_src12_t)s4;
-    d[0] = v.x; d[1] = v.y; d[2] = v.z;
-  } else {
-    d[0] = s4[0];
-  }
-  d[BPP] = sh ? s4[BPP] : 0u;                                      // (holds a byte of the last pixel only then)
-  uint32_t t[BPP + 1];                                             // the 4 * BPP bytes from a on
-#pragma unroll
-  for (int k = 0; k < BPP; k++) t[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);
-  t[BPP] = 0u;
-  if constexpr (BPP == 1) {
-    return t[0];
-  } else {
-    uint32_t o = 0u;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      constexpr int B = BPP;
-      const int j = (B * k) >> 2, off = (B * k) & 3;               // the pixel's dword and its byte in it (constants once unrolled)
-      const uint32_t px = off ? __builtin_amdgcn_alignbyte(t[j + 1], t[j], (uint32_t)off) : t[j];
-      o |= pack_gray(px, w_lo, w_hi) << (8 * k);
-    }
-    return o;
-  }
-}
 
 // 16 bytes of the LDS tile from index i on, STEP bytes apart
 template <int STEP>
@@ -130,9 +90,9 @@ __global__ __launch_bounds__(kTurnBlock) void k_turn(TurnArgs a) {
       const pack_src_t s = rowp + (long long)(sx0 + 4 * q) * im.bpp;
       uint32_t o = 0u;
       if (4 * q + 4 <= t.sw) {
-        if (im.bpp == 1) o = turn_row4<1>(s, 0u, 0u, bc_row);
-        else if (im.bpp == 3) o = turn_row4<3>(s, im.w_lo, im.w_hi, bc_row);
-        else o = turn_row4<4>(s, im.w_lo, im.w_hi, bc_row);
+        if (im.bpp == 1) pack_row<1, 4>(s, 0u, 0u, bc_row, &o);
+        else if (im.bpp == 3) pack_row<3, 4>(s, im.w_lo, im.w_hi, bc_row, &o);
+        else pack_row<4, 4>(s, im.w_lo, im.w_hi, bc_row, &o);
       } else {
         for (int k = 0; 4 * q + k < t.sw; k++) o |= pack_pixel(s + k * im.bpp, im.bpp, im.w_lo, im.w_hi, bc_row) << (8 * k);
       }

@@ -536,6 +536,7 @@ struct GatherArgs {
 hipError_t launch_gather(const GatherArgs& a, hipStream_t stream);
 
 // ---- frames as they arrive: colour / pitched / cropped images -> dense 8-bit gray (k_pack.hip, pack.cpp; include/jda.h) ----
+constexpr uint32_t kGrayB = 1868, kGrayG = 9617, kGrayR = 4899;   // the Q14 weights of gray = (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14 (pack.cpp: pack_weights; k_chips.hip)
 constexpr int kPackBlock = 256;          // lanes of a workgroup: consecutive lanes take consecutive units
 constexpr int kPackRounds = 4;           // units of a lane: a workgroup covers kPackBlock * kPackRounds consecutive units
 // One image of a launch: w x h pixels of bpp bytes from src (the rectangle's first pixel; rows `pitch` bytes apart) to the w * h

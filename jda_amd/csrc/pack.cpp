@@ -91,7 +91,7 @@ int pixels_bpp(int format) {
 
 void pack_weights(int format, int w[3]) {
   const bool rgb = format == JDA_PIX_RGB24 || format == JDA_PIX_RGBA32;
-  w[0] = rgb ? 4899 : 1868; w[1] = 9617; w[2] = rgb ? 1868 : 4899;
+  w[0] = rgb ? kGrayR : kGrayB; w[1] = kGrayG; w[2] = rgb ? kGrayB : kGrayR;
 }
 
 bool check_pixels(const std::string& img, const jdaPixels& p, PixelsOne* out) {
@@ -138,36 +138,27 @@ int pack_host(const jdaPixels* images, int n, unsigned char* dst, const size_t* 
   return 0;
 }
 
-int pack_device(Cascador* c, const jdaPixels* images, int n, unsigned char* d_dst, const size_t* dst_offsets, hipStream_t user_stream,
-                jdaPackStats* stats) {
-  const double t0 = now_ms();
-  const std::string who = "jdaPackGrayDevice: ";
-  if (!c) { fail(who + "null cascador"); return -1; }
-  std::vector<PackOne> v;
-  if (!check_pack(who, images, nullptr, false, n, d_dst, dst_offsets, &v)) return -1;
-  if (stats) std::memset(stats, 0, sizeof *stats);
-  if (n == 0) return 0;
+void pack_stats(jdaPackStats* stats, const std::vector<PackOne>& v, const LaneCall& call) {
+  if (!stats) return;
+  long long pixels = 0, bytes_in = 0;
+  for (const PackOne& o : v) { pixels += o.npix; bytes_in += o.npix * o.bpp; }
+  stats->pixels = pixels; stats->bytes_in = bytes_in; stats->bytes_out = pixels; stats->launches = 1;
+  stats->device_ms = call.device_ms; stats->call_ms = call.call_ms();
+}
 
+int pack_launch(LaneCall& call, const std::string& who, const std::vector<PackOne>& v, hipStream_t user_stream, jdaPackStats* stats) {
   // the image table (units: kernels.h) and the image of every workgroup's first unit
-  std::vector<PackImg> tab((size_t)n);
-  long long total = 0, bytes_in = 0, pixels = 0;
+  const int n = (int)v.size();
+  std::vector<PackImg> tab(v.size());
+  long long total = 0, pixels = 0;
   for (int i = 0; i < n; i++) {
     const PackOne& o = v[(size_t)i];
     PackImg& t = tab[(size_t)i];
-    std::memset(&t, 0, sizeof t);
-    t.src = o.src; t.dst = o.dst; t.pitch = o.pitch; t.w = o.w; t.h = o.h; t.bpp = o.bpp;
-    t.head = (int)std::min<long long>(o.npix, (long long)((0 - (uintptr_t)o.dst) & 15));
-    t.nq = (o.npix - t.head) >> 4;
-    t.tail = (int)(o.npix - t.head - (t.nq << 4));
-    t.first = total;
-    if (o.bpp > 1) {
-      int w[3];
-      pack_weights(o.format, w);
-      t.w_lo = (uint32_t)(w[0] & 255) | ((uint32_t)(w[1] & 255) << 8) | ((uint32_t)(w[2] & 255) << 16);
-      t.w_hi = (uint32_t)(w[0] >> 8) | ((uint32_t)(w[1] >> 8) << 8) | ((uint32_t)(w[2] >> 8) << 16);
-    }
-    total += t.nq + t.head + t.tail;
-    pixels += o.npix; bytes_in += o.npix * o.bpp;
+    pack_img(&t, o, total);
+    const DstUnits u = dst_units(o.dst, o.npix);
+    t.head = u.head; t.nq = u.nq; t.tail = u.tail;
+    total += u.total();
+    pixels += o.npix;
   }
   constexpr long long per = (long long)kPackBlock * kPackRounds;
   const long long groups = (total + per - 1) / per;
@@ -178,36 +169,29 @@ int pack_device(Cascador* c, const jdaPixels* images, int n, unsigned char* d_ds
     block_img[(size_t)b] = (int)i;
   }
 
-  OneLane one(c);
-  if (!one.open()) return -1;
-  Lane* ln = one.lane;
-  const hipStream_t st = user_stream ? user_stream : one.stream;
-  double device_ms = 0;
+  if (!call.open(user_stream)) return -1;
+  const hipStream_t st = call.st;
   auto body = [&]() -> bool {
     PackImg* d_tab; int* d_blk;
-    // (the lane's own grow-only buffer: a per-frame caller pays no allocation and no hipFree, which waits for the whole device)
-    if (!carve_into(ln->pack, [&](Carver& cv) { d_tab = cv.take<PackImg>((size_t)n); d_blk = cv.take<int>((size_t)groups); })) return false;
-    JDA_HIP(hipMemcpyAsync(d_tab, tab.data(), (size_t)n * sizeof(PackImg), hipMemcpyHostToDevice, st));
-    JDA_HIP(hipMemcpyAsync(d_blk, block_img.data(), (size_t)groups * sizeof(int), hipMemcpyHostToDevice, st));
-    EvTimer timer;
-    if (!timer.open(stats != nullptr)) return false;
+    if (!call.upload(tab, block_img, &d_tab, &d_blk) || !call.begin()) return false;
     PackArgs a{d_tab, d_blk, n, total};
-    if (!timer.begin(st)) return false;
     JDA_HIP(launch_pack(a, st));
-    if (!timer.end(st)) return false;
-    JDA_HIP(hipStreamSynchronize(st));
-    return timer.add(&device_ms);
+    return call.end() && call.sync();
   };
-  if (!body()) {
-    (void)hipStreamSynchronize(st);      // nothing of this call is in flight when its lane goes back to the pool
-    (void)hipGetLastError();
-    return -1;
-  }
-  if (stats) {
-    stats->pixels = pixels; stats->bytes_in = bytes_in; stats->bytes_out = pixels; stats->launches = 1;
-    stats->device_ms = device_ms; stats->call_ms = now_ms() - t0;
-  }
+  if (!call.run(stats != nullptr, body)) return -1;
+  pack_stats(stats, v, call);
   return 0;
+}
+
+int pack_device(Cascador* c, const jdaPixels* images, int n, unsigned char* d_dst, const size_t* dst_offsets, hipStream_t user_stream,
+                jdaPackStats* stats) {
+  LaneCall call(c);
+  const std::string who = "jdaPackGrayDevice: ";
+  if (!c) { fail(who + "null cascador"); return -1; }
+  std::vector<PackOne> v;
+  if (!check_pack(who, images, nullptr, false, n, d_dst, dst_offsets, &v)) return -1;
+  if (stats) std::memset(stats, 0, sizeof *stats);
+  return n == 0 ? 0 : pack_launch(call, who, v, user_stream, stats);
 }
 
 }  // namespace jda

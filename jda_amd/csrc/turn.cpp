@@ -70,70 +70,45 @@ int turn_host(const jdaPixels* images, const int* orients, int n, unsigned char*
 
 int turn_device(Cascador* c, const jdaPixels* images, const int* orients, int n, unsigned char* d_dst, const size_t* dst_offsets,
                 hipStream_t user_stream, jdaPackStats* stats) {
-  const double t0 = now_ms();
+  LaneCall call(c);
   const std::string who = "jdaPackGrayOrientedDevice: ";
   if (!c) { fail(who + "null cascador"); return -1; }
   std::vector<PackOne> v;
   if (!check_pack(who, images, orients, true, n, d_dst, dst_offsets, &v)) return -1;
-  if (n > 0 && all_upright(orients, n)) return pack_device(c, images, n, d_dst, dst_offsets, user_stream, stats);   // the same bytes
   if (stats) std::memset(stats, 0, sizeof *stats);
   if (n == 0) return 0;
+  if (all_upright(orients, n)) return pack_launch(call, who, v, user_stream, stats);   // the same bytes
 
   // the image table (tiles: kernels.h) and the image of every workgroup's tile
   std::vector<TurnImg> tab((size_t)n);
-  long long total = 0, bytes_in = 0, pixels = 0;
+  long long total = 0, pixels = 0;
   for (int i = 0; i < n; i++) {
     const PackOne& o = v[(size_t)i];
     TurnImg& t = tab[(size_t)i];
-    std::memset(&t, 0, sizeof t);
-    t.src = o.src; t.dst = o.dst; t.pitch = o.pitch; t.w = o.w; t.h = o.h; t.bpp = o.bpp; t.tf = o.tf;
+    pack_img(&t, o, total);
+    t.tf = o.tf;
     const int TW = (o.tf & kMineSwap) ? o.h : o.w, TH = (o.tf & kMineSwap) ? o.w : o.h;
     t.off = (int)((uintptr_t)o.dst & 15);
     t.ntu = (int)(((long long)TW + t.off + kTurnTile - 1) / kTurnTile);
     t.ntv = (TH + kTurnTile - 1) / kTurnTile;
-    t.first = total;
-    if (o.bpp > 1) {
-      int w[3];
-      pack_weights(o.format, w);
-      t.w_lo = (uint32_t)(w[0] & 255) | ((uint32_t)(w[1] & 255) << 8) | ((uint32_t)(w[2] & 255) << 16);
-      t.w_hi = (uint32_t)(w[0] >> 8) | ((uint32_t)(w[1] >> 8) << 8) | ((uint32_t)(w[2] >> 8) << 16);
-    }
     total += (long long)t.ntu * t.ntv;
-    pixels += o.npix; bytes_in += o.npix * o.bpp;
+    pixels += o.npix;
   }
   if (total > 0x7fffffffll) { fail(who + "too many pixels for one launch (" + std::to_string(pixels) + ")"); return -1; }
   std::vector<int> block_img((size_t)total);
   for (int i = 0; i < n; i++) std::fill_n(block_img.begin() + tab[(size_t)i].first, (long long)tab[(size_t)i].ntu * tab[(size_t)i].ntv, i);
 
-  OneLane one(c);
-  if (!one.open()) return -1;
-  Lane* ln = one.lane;
-  const hipStream_t st = user_stream ? user_stream : one.stream;
-  double device_ms = 0;
+  if (!call.open(user_stream)) return -1;
+  const hipStream_t st = call.st;
   auto body = [&]() -> bool {
     TurnImg* d_tab; int* d_blk;
-    // (the lane's own grow-only buffer: a per-frame caller pays no allocation and no hipFree, which waits for the whole device)
-    if (!carve_into(ln->turn, [&](Carver& cv) { d_tab = cv.take<TurnImg>((size_t)n); d_blk = cv.take<int>((size_t)total); })) return false;
-    JDA_HIP(hipMemcpyAsync(d_tab, tab.data(), (size_t)n * sizeof(TurnImg), hipMemcpyHostToDevice, st));
-    JDA_HIP(hipMemcpyAsync(d_blk, block_img.data(), (size_t)total * sizeof(int), hipMemcpyHostToDevice, st));
-    EvTimer timer;
-    if (!timer.open(stats != nullptr)) return false;
+    if (!call.upload(tab, block_img, &d_tab, &d_blk) || !call.begin()) return false;
     TurnArgs a{d_tab, d_blk, n, total};
-    if (!timer.begin(st)) return false;
     JDA_HIP(launch_turn(a, st));
-    if (!timer.end(st)) return false;
-    JDA_HIP(hipStreamSynchronize(st));
-    return timer.add(&device_ms);
+    return call.end() && call.sync();
   };
-  if (!body()) {
-    (void)hipStreamSynchronize(st);      // nothing of this call is in flight when its lane goes back to the pool
-    (void)hipGetLastError();
-    return -1;
-  }
-  if (stats) {
-    stats->pixels = pixels; stats->bytes_in = bytes_in; stats->bytes_out = pixels; stats->launches = 1;
-    stats->device_ms = device_ms; stats->call_ms = now_ms() - t0;
-  }
+  if (!call.run(stats != nullptr, body)) return -1;
+  pack_stats(stats, v, call);
   return 0;
 }
 

@@ -11,7 +11,7 @@ namespace jda {
 
 int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_frames, const uint8_t* d_frames, size_t stride, int n,
                   int width, int height, const int* windows, int n_windows, float th, const WindowsOut& out) {
-  const double t0 = now_ms();
+  LaneCall call(c);
   const std::string who = std::string(fn) + ": ";
   if (!c) { fail(who + "null cascador"); return -1; }
   if (n < 0 || n_windows < 0) { fail(who + "negative number of frames or windows"); return -1; }
@@ -45,13 +45,11 @@ int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_
   }
   const DevModelT<float> m = c->mf.m;
   const int dim = m.dim;
-  LaneSet lanes(c);
-  if (!lanes.take(1)) return -1;
-  Lane* ln = lanes.v[0];
-  const hipStream_t st = ln->stream;
+  if (!call.open()) return -1;
+  Lane* ln = call.lane;
+  const hipStream_t st = call.st;
 
   long long faces = 0, nf_carts = 0;
-  double device_ms = 0;
   auto body = [&]() -> bool {
     if (host_frames) {
       if (!stage_frames(ln, host_frames, n, fbytes, &stride)) return false;
@@ -82,13 +80,10 @@ int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_
     const size_t budget = (size_t)std::max<long long>(1, c->kn.workspace_mb) << 20;
     const int nc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_windows, budget / per, (size_t)1 << 22}));
     int4* d_win; uint8_t* d_face; float* d_score; int* d_carts; uint32_t* d_hash; float* d_shapes; float* d_lm;
-    // (the lane's own grow-only buffer: a per-frame caller pays no allocation and no hipFree, which waits for the whole device)
     if (!carve_into(ln->win, [&](Carver& cv) {
           d_win = cv.take<int4>(nc); d_face = cv.take<uint8_t>(nc); d_score = cv.take<float>(nc); d_carts = cv.take<int>(nc);
           d_hash = cv.take<uint32_t>(nc); d_shapes = cv.take<float>((size_t)nc * dim); d_lm = cv.take<float>((size_t)nc * dim);
         })) return false;
-    EvTimer timer;
-    if (!timer.open(out.stats)) return false;
     std::vector<uint8_t> f(nc);
     std::vector<int> cn(nc);
     for (int i0 = 0; i0 < n_windows; i0 += nc) {
@@ -98,17 +93,16 @@ int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_
       // (face and carts_n always: the statistics count them; the rest only where the caller takes it)
       a.face = d_face; a.carts_n = d_carts; a.score = out.score ? d_score : nullptr; a.hash = out.path_hash ? d_hash : nullptr;
       a.shapes = out.shapes ? d_shapes : nullptr; a.landmarks = out.landmarks ? d_lm : nullptr;
-      if (!timer.begin(st)) return false;
+      if (!call.begin()) return false;
       JDA_HIP(launch_windows(m, a, st));
-      if (!timer.end(st)) return false;
+      if (!call.end()) return false;
       JDA_HIP(hipMemcpyAsync(f.data(), d_face, cnw, hipMemcpyDeviceToHost, st));
       JDA_HIP(hipMemcpyAsync(cn.data(), d_carts, (size_t)cnw * sizeof(int), hipMemcpyDeviceToHost, st));
       if (out.score) JDA_HIP(hipMemcpyAsync(out.score + i0, d_score, (size_t)cnw * sizeof(float), hipMemcpyDeviceToHost, st));
       if (out.path_hash) JDA_HIP(hipMemcpyAsync(out.path_hash + i0, d_hash, (size_t)cnw * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
       if (out.shapes) JDA_HIP(hipMemcpyAsync(out.shapes + (size_t)i0 * dim, d_shapes, (size_t)cnw * dim * sizeof(float), hipMemcpyDeviceToHost, st));
       if (out.landmarks) JDA_HIP(hipMemcpyAsync(out.landmarks + (size_t)i0 * dim, d_lm, (size_t)cnw * dim * sizeof(float), hipMemcpyDeviceToHost, st));
-      JDA_HIP(hipStreamSynchronize(st));
-      if (!timer.add(&device_ms)) return false;
+      if (!call.sync()) return false;
       for (int i = 0; i < cnw; i++) {
         if (out.is_face) out.is_face[i0 + i] = f[i];
         if (out.carts_n) out.carts_n[i0 + i] = cn[i];
@@ -117,18 +111,14 @@ int windows_entry(Cascador* c, const char* fn, const unsigned char* const* host_
     }
     return true;
   };
-  if (!body()) {
-    (void)hipStreamSynchronize(st);      // nothing of this call is in flight when its lane goes back to the pool
-    (void)hipGetLastError();
-    return -1;
-  }
+  if (!call.run(out.stats != nullptr, body)) return -1;
   if (jdaStats* stats = out.stats) {     // as jdaValidateCpp fills them (mine.cpp), and the kernels' device time
     std::memset(stats, 0, sizeof *stats);
     stats->patch_n = n_windows; stats->face_patch_n = faces; stats->nonface_patch_n = n_windows - faces;
     stats->cart_gothrough_n = nf_carts;
     stats->average_cart_n = stats->nonface_patch_n ? (double)nf_carts / stats->nonface_patch_n : 0.;
-    stats->gpu_ms = device_ms;
-    stats->call_ms = now_ms() - t0;
+    stats->gpu_ms = call.device_ms;
+    stats->call_ms = call.call_ms();
   }
   return 0;
 }

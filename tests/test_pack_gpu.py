@@ -50,13 +50,19 @@ def pattern(n):
     return ((np.arange(n, dtype=np.int64) * 7 + 13) % 251).astype(np.uint8)
 
 
-def run(casc, views, tensors, fmts, rects=None, dst_mis=None, hip_stream=None):
-    """Packs into a patterned buffer -- image i at the first 16-byte boundary at least 32 bytes behind image i - 1, plus
-    dst_mis[i] -- and compares the whole buffer; returns the statistics."""
+def run(casc, views, tensors, fmts, rects=None, ts=None, dst_mis=None, hip_stream=None):
+    """Packs -- with orientations ts (test_turn_gpu.py) turned -- into a patterned buffer -- image i at the first 16-byte boundary
+    at least 32 bytes behind image i - 1, plus dst_mis[i] -- and compares the whole buffer, and the host form's images; returns
+    the statistics."""
     import torch
+    from jda_amd import api
     n = len(views)
     rects = rects or [None] * n
-    want = [pr.pack(v, f, r) for v, f, r in zip(views, fmts, rects)]
+    if ts is None:
+        want = [pr.pack(v, f, r) for v, f, r in zip(views, fmts, rects)]
+    else:
+        import turn_ref as tr
+        want = [tr.turn(v, f, t, r) for v, f, t, r in zip(views, fmts, ts, rects)]
     offs, end = [], 0
     for i, g in enumerate(want):
         o = (end + 32 + 15) // 16 * 16 + (dst_mis[i] if dst_mis else (i * 5) % 16)
@@ -66,7 +72,10 @@ def run(casc, views, tensors, fmts, rects=None, dst_mis=None, hip_stream=None):
     buf = torch.from_numpy(expect.copy()).cuda()
     for o, g in zip(offs, want):
         expect[o:o + g.size] = g.ravel()
-    (b, o2, ws, hs), st = casc.pack_gray_device(tensors, fmts, rects, stats=True, hip_stream=hip_stream, out=(buf, offs))
+    if ts is None:
+        (b, o2, ws, hs), st = casc.pack_gray_device(tensors, fmts, rects, stats=True, hip_stream=hip_stream, out=(buf, offs))
+    else:
+        (b, o2, ws, hs), st = casc.pack_gray_oriented_device(tensors, fmts, ts, rects, stats=True, hip_stream=hip_stream, out=(buf, offs))
     if hip_stream is None:
         torch.cuda.synchronize()
     got = buf.cpu().numpy()
@@ -75,6 +84,9 @@ def run(casc, views, tensors, fmts, rects=None, dst_mis=None, hip_stream=None):
     assert ws == [g.shape[1] for g in want] and hs == [g.shape[0] for g in want] and list(o2) == offs
     assert st["launches"] == (1 if n else 0) and st["pixels"] == sum(g.size for g in want) == st["bytes_out"]
     assert st["bytes_in"] == sum(g.size * pr.BPP[f] for g, f in zip(want, fmts))
+    host = api.pack_gray(views, fmts, rects) if ts is None else api.pack_gray_oriented(views, fmts, ts, rects)
+    for h, g in zip(host, want):                                                 # device form == host form
+        assert h.shape == g.shape and np.array_equal(h, g)
     return st
 
 

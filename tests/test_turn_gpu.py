@@ -13,7 +13,7 @@ import pack_ref as pr
 import turn_ref as tr
 from conftest import same
 from mining_ref import transform
-from test_pack_gpu import colour_of, on_device, pattern, source
+from test_pack_gpu import colour_of, on_device, pattern, run, source
 
 pytestmark = pytest.mark.gpu
 
@@ -37,37 +37,6 @@ def casc(built, gpu, model_file):
     c.close()
 
 
-def run(casc, views, tensors, fmts, ts, rects=None, dst_mis=None, hip_stream=None):
-    """Packs into a patterned buffer -- image i at the first 16-byte boundary at least 32 bytes behind image i - 1, plus
-    dst_mis[i] -- and compares the whole buffer, and the host form's images; returns the statistics."""
-    import torch
-    from jda_amd import api
-    n = len(views)
-    rects = rects or [None] * n
-    want = [tr.turn(v, f, t, r) for v, f, t, r in zip(views, fmts, ts, rects)]
-    offs, end = [], 0
-    for i, g in enumerate(want):
-        o = (end + 32 + 15) // 16 * 16 + (dst_mis[i] if dst_mis else (i * 5) % 16)
-        offs.append(o)
-        end = o + g.size
-    expect = pattern(end + 64)
-    buf = torch.from_numpy(expect.copy()).cuda()
-    for o, g in zip(offs, want):
-        expect[o:o + g.size] = g.ravel()
-    (b, o2, ws, hs), st = casc.pack_gray_oriented_device(tensors, fmts, ts, rects, stats=True, hip_stream=hip_stream, out=(buf, offs))
-    if hip_stream is None:
-        torch.cuda.synchronize()
-    got = buf.cpu().numpy()
-    bad = np.flatnonzero(got != expect)
-    assert bad.size == 0, ("first wrong byte", int(bad[0]), "of", got.size, "image offsets", offs[:8])
-    assert ws == [g.shape[1] for g in want] and hs == [g.shape[0] for g in want] and list(o2) == offs
-    assert st["launches"] == (1 if n else 0) and st["pixels"] == sum(g.size for g in want) == st["bytes_out"]
-    assert st["bytes_in"] == sum(g.size * pr.BPP[f] for g, f in zip(want, fmts))
-    for h, g in zip(api.pack_gray_oriented(views, fmts, ts, rects), want):       # device form == host form
-        assert h.shape == g.shape and np.array_equal(h, g)
-    return st
-
-
 @pytest.mark.parametrize("shift", range(5))
 def test_shape_grid_mixed(casc, shift):
     """Every width x height x orientation in ONE call, the formats dealt round: narrower than a unit, than a tile, one tile,
@@ -79,7 +48,7 @@ def test_shape_grid_mixed(casc, shift):
             for t in tr.ORIENTS:
                 fmt = pr.FORMATS[(len(srcs) + shift) % 5]
                 srcs.append(source(rng, h, w, fmt, slack=(w + h) % 4, base=(3 * w + h + t) % 16)); fmts.append(fmt); ts.append(t)
-    run(casc, [s[0] for s in srcs], [s[1] for s in srcs], fmts, ts)
+    run(casc, [s[0] for s in srcs], [s[1] for s in srcs], fmts, ts=ts)
 
 
 @pytest.mark.parametrize("fmt", [pr.BGR24, pr.GRAY8])
@@ -90,7 +59,7 @@ def test_misalignments(casc, wh, t, fmt):
     against every head / tail length of every turned row."""
     rng = np.random.default_rng(t)
     srcs = [source(rng, wh[1], wh[0], fmt, sb % 3, sb) for sb in range(16) for _ in range(16)]
-    run(casc, [s[0] for s in srcs], [s[1] for s in srcs], [fmt] * 256, [t] * 256, dst_mis=[i % 16 for i in range(256)])
+    run(casc, [s[0] for s in srcs], [s[1] for s in srcs], [fmt] * 256, ts=[t] * 256, dst_mis=[i % 16 for i in range(256)])
 
 
 def test_rectangles(casc):
@@ -103,7 +72,7 @@ def test_rectangles(casc):
                 views.append(v); tensors.append(d); fmts.append(fmt); rects.append(pr.RECTS[name](37, 21)); ts.append(t)
     v, d = source(rng, 300, 400, pr.BGRA32)             # a crop of more than one tile out of a frame
     views.append(v); tensors.append(d); fmts.append(pr.BGRA32); rects.append((201, 107, 150, 131)); ts.append(3)
-    run(casc, views, tensors, fmts, ts, rects)
+    run(casc, views, tensors, fmts, rects, ts)
 
 
 def mixed(rng, n):
@@ -114,7 +83,7 @@ def mixed(rng, n):
         v, d = source(rng, h, w, fmt, int(rng.integers(0, 9)), int(rng.integers(0, 16)))
         views.append(v); tensors.append(d); fmts.append(fmt); ts.append(int(rng.integers(0, 8)))
         rects.append(None if i % 3 else (w // 2, h // 3, w - w // 2, h - h // 3))
-    return views, tensors, fmts, ts, rects
+    return views, tensors, fmts, rects, ts
 
 
 @pytest.mark.parametrize("n", [1, 2, 5, 130])
@@ -131,14 +100,14 @@ def test_source_ends_with_its_allocation(casc):
         for t in tr.ORIENTS:
             for w, h in ((67, 5), (5, 67)):
                 srcs.append(source(rng, h, w, fmt, 0, (t + w) % 4)); fmts.append(fmt); ts.append(t)
-    run(casc, [s[0] for s in srcs], [s[1] for s in srcs], fmts, ts)
+    run(casc, [s[0] for s in srcs], [s[1] for s in srcs], fmts, ts=ts)
 
 
 def test_upright_sets_are_pack_gray(casc):
     """Every orientation 0: jdaPackGrayDevice's bytes (and one launch); an empty set touches nothing."""
     import torch
-    views, tensors, fmts, ts, rects = mixed(np.random.default_rng(3), 7)
-    run(casc, views, tensors, fmts, [0] * 7, rects)
+    views, tensors, fmts, rects, ts = mixed(np.random.default_rng(3), 7)
+    run(casc, views, tensors, fmts, rects, [0] * 7)
     buf = torch.from_numpy(pattern(64)).cuda()
     (b, offs, ws, hs), st = casc.pack_gray_oriented_device([], [], [], stats=True, out=(buf, []))
     assert len(offs) == 0 and ws == [] and hs == [] and st["launches"] == 0 and np.array_equal(buf.cpu().numpy(), pattern(64))
@@ -146,12 +115,12 @@ def test_upright_sets_are_pack_gray(casc):
 
 def test_both_stream_forms(casc):
     import torch
-    views, tensors, fmts, ts, rects = mixed(np.random.default_rng(11), 9)
-    run(casc, views, tensors, fmts, ts, rects)                               # hip_stream NULL: the lane's own stream
+    views, tensors, fmts, rects, ts = mixed(np.random.default_rng(11), 9)
+    run(casc, views, tensors, fmts, rects, ts)                               # hip_stream NULL: the lane's own stream
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):                                               # the pixels are produced on s, just before the call
         tensors = [d.clone() if d.is_contiguous() else d for d in tensors]
-        run(casc, views, tensors, fmts, ts, rects, hip_stream=s.cuda_stream)
+        run(casc, views, tensors, fmts, rects, ts, hip_stream=s.cuda_stream)
     s.synchronize()
 
 

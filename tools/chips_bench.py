@@ -23,6 +23,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from kernel_resources import kernel_resources  # noqa: E402  (tools/kernel_resources.py)
 
 # five points (eyes, nose, mouth corners) of an upright face in a 112 x 112 chip
 TEMPLATE = np.array([38.0, 46.0, 74.0, 46.0, 56.0, 66.0, 42.0, 86.0, 70.0, 86.0])
@@ -30,22 +31,6 @@ TEMPLATE = np.array([38.0, 46.0, 74.0, 46.0, 56.0, 66.0, 42.0, 86.0, 70.0, 86.0]
 
 def summary(ms):
     return dict(median=statistics.median(ms), min=min(ms), max=max(ms), all=ms)
-
-
-def kernel_resources():
-    import re
-    import subprocess
-    import tempfile
-    from jda_amd import build as lib_build
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([lib_build.hipcc()] + lib_build.CFLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(lib_build.CSRC, "k_chips.hip"),
-                            "-o", os.path.join(d, "k_chips.o")], capture_output=True, text=True, check=True)
-    got = {}
-    for key, pat in (("vgprs", r" VGPRs: (\d+)"), ("agprs", r"AGPRs: (\d+)"), ("sgprs", r"TotalSGPRs: (\d+)"), ("scratch_bytes_per_lane", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                     ("waves_per_simd", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds_bytes_per_block", r"LDS Size \[bytes/block\]: (\d+)")):
-        got[key] = int(re.search(pat, r.stderr).group(1))
-    assert "k_chips" in r.stderr and got["scratch_bytes_per_lane"] == 0, r.stderr
-    return got
 
 
 def make_faces(n_frames, per_frame, W, H, chip, seed=0):
@@ -78,7 +63,7 @@ def main():
     if a.resources:
         with open(a.resources) as f:
             res = json.load(f)
-        res["k_chips_resources"] = kernel_resources()
+        res["k_chips_resources"] = kernel_resources("k_chips.hip", "k_chips")
         with open(a.resources, "w") as f:
             json.dump(res, f, indent=1)
         print(json.dumps(res["k_chips_resources"]))

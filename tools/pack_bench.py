@@ -22,6 +22,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from kernel_resources import kernel_resources  # noqa: E402  (tools/kernel_resources.py)
 
 
 def summary(ms):
@@ -38,22 +39,6 @@ def fddb_sizes(n=2845, seed=0, max_side=450):
     return out
 
 
-def kernel_resources():
-    import re
-    import subprocess
-    import tempfile
-    from jda_amd import build as lib_build
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([lib_build.hipcc()] + lib_build.CFLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(lib_build.CSRC, "k_pack.hip"),
-                            "-o", os.path.join(d, "k_pack.o")], capture_output=True, text=True, check=True)
-    got = {}
-    for key, pat in (("vgprs", r" VGPRs: (\d+)"), ("agprs", r"AGPRs: (\d+)"), ("sgprs", r"TotalSGPRs: (\d+)"), ("scratch_bytes_per_lane", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                     ("waves_per_simd", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds_bytes_per_block", r"LDS Size \[bytes/block\]: (\d+)")):
-        got[key] = int(re.search(pat, r.stderr).group(1))
-    assert "k_pack" in r.stderr and got["scratch_bytes_per_lane"] == 0, r.stderr
-    return got
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--resources", default=None, help="JSON file to add k_pack's compile-time resource figures to (no GPU needed)")
@@ -64,7 +49,7 @@ def main():
     if a.resources:
         with open(a.resources) as f:
             res = json.load(f)
-        res["k_pack_resources"] = kernel_resources()
+        res["k_pack_resources"] = kernel_resources("k_pack.hip", "k_pack")
         with open(a.resources, "w") as f:
             json.dump(res, f, indent=1)
         print(json.dumps(res["k_pack_resources"]))

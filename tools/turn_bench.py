@@ -12,16 +12,14 @@ import argparse
 import ctypes as C
 import json
 import os
-import re
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from kernel_resources import kernel_resources  # noqa: E402  (tools/kernel_resources.py)
 
 
 def summary(ms):
@@ -31,19 +29,6 @@ def summary(ms):
 def transform(a, t):
     """include/jda.h's numpy equivalents of the orientations timed here."""
     return np.ascontiguousarray({0: a, 4: np.fliplr(a), 1: np.rot90(a, -1), 7: a.T}[t])
-
-
-def kernel_resources():
-    from jda_amd import build as lib_build
-    with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([lib_build.hipcc()] + lib_build.CFLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(lib_build.CSRC, "k_turn.hip"),
-                            "-o", os.path.join(d, "k_turn.o")], capture_output=True, text=True, check=True)
-    got = {}
-    for key, pat in (("vgprs", r" VGPRs: (\d+)"), ("agprs", r"AGPRs: (\d+)"), ("sgprs", r"TotalSGPRs: (\d+)"), ("scratch_bytes_per_lane", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                     ("waves_per_simd", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds_bytes_per_block", r"LDS Size \[bytes/block\]: (\d+)")):
-        got[key] = int(re.search(pat, r.stderr).group(1))
-    assert "k_turn" in r.stderr and got["scratch_bytes_per_lane"] == 0, r.stderr
-    return got
 
 
 def main():
@@ -58,7 +43,7 @@ def main():
         if os.path.exists(a.resources):
             with open(a.resources) as f:
                 res = json.load(f)
-        res["k_turn_resources"] = kernel_resources()
+        res["k_turn_resources"] = kernel_resources("k_turn.hip", "k_turn")
         with open(a.resources, "w") as f:
             json.dump(res, f, indent=1)
         print(json.dumps(res["k_turn_resources"]))
