@@ -162,6 +162,29 @@ JDA_API int jdaSetDevice(void *cascador, int device);
 JDA_API int jdaSetOption(void *cascador, const char *key, long long value);
 JDA_API long long jdaGetOption(void *cascador, const char *key);
 
+/* Which finishing form the passes of a cascador took.  After the stage-0 scan a pass finishes its
+ * windows in one of these forms; the choice depends on the length of the hand-off queue (or its prediction from earlier
+ * passes on the same scan plan), on the model, on the options and on how many callers share the cascador, and never
+ * changes a result.  A test that names a finishing kernel reads here that the kernel ran. */
+enum {
+  JDA_FINISH_WIDE_CONC = 0,  /* k_finish_wide, score replay and regression side by side                          */
+  JDA_FINISH_WIDE_SEQ,       /* k_finish_wide, one after the other, the weight rows through LDS                  */
+  JDA_FINISH_MERGED,         /* one k_finish launch for every stage                                              */
+  JDA_FINISH_FILTER0,        /* k_filter0, then k_finish on its survivors                                        */
+  JDA_FINISH_MID_DIRECT,     /* the same pair, fed from the mid queue the persistent scan filled itself          */
+  JDA_FINISH_TWO_LAUNCH,     /* k_finish for stage 0, then k_finish for the other stages                         */
+  JDA_FINISH_DENSE,          /* dense mode: k_stage for every stage and level, no hand-off queue at all          */
+  JDA_FINISH_FORM_N
+};
+/* counts[f]: how often the passes of this cascador have issued form f since it was created -- every entry that runs a
+ * pass counts (batches, traces, tickets, ragged jobs, both dialects).  The counts only grow and are added atomically
+ * where the launches are issued; a caller takes the difference around its own call, which is that call's alone as long
+ * as one thread uses the cascador.  A form counts once per pass, however many launches it takes (DENSE: one per stage
+ * and level).  A pass that is issued again -- a queue was too small, or the persistent scan came back short
+ * (jdaStats ws_regrows / scan_fallbacks) -- counts again: the difference says what was launched, not what was kept.
+ * Returns 0, or -1 for a null argument. */
+JDA_API int jdaFinishForms(void *cascador, long long counts[JDA_FINISH_FORM_N]);
+
 /* Window enumeration of reference c/jda.c:320-339 without running anything:
  * number of candidate windows and pyramid levels for one frame. */
 JDA_API int jdaCountWindows(int width, int height, float scale, int min_size, int max_size,

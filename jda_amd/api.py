@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("JDA_LIB_PATH") or os.path.join(_HERE, "libjda.so")
 
 JDA_DIALECT_C = 0
 JDA_DIALECT_CPP = 1
+# include/jda.h: JDA_FINISH_*, the finishing forms a pass can take, in the order of jdaFinishForms' counts
+FINISH_FORMS = ("WIDE_CONC", "WIDE_SEQ", "MERGED", "FILTER0", "MID_DIRECT", "TWO_LAUNCH", "DENSE")
 
 
 class JdaError(RuntimeError):
@@ -207,6 +209,7 @@ def _load():
     lib.jdaSetOption.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
     lib.jdaGetOption.restype = C.c_longlong
     lib.jdaGetOption.argtypes = [C.c_void_p, C.c_char_p]
+    lib.jdaFinishForms.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.jdaCountWindows.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                     C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     lib.jdaDetectOptionsInit.restype = None
@@ -1193,6 +1196,14 @@ class Cascador:
 
     def get_option(self, key):
         return int(lib.jdaGetOption(self.h, key.encode()))
+
+    def finish_forms(self):
+        """jdaFinishForms: how often this cascador's passes have issued each finishing form since it was created
+        (include/jda.h: JDA_FINISH_*, in that order).  The counts only grow; take the difference around a call."""
+        counts = (C.c_longlong * len(FINISH_FORMS))()
+        if lib.jdaFinishForms(self.h, counts) != 0:
+            raise JdaError(last_error())
+        return dict(zip(FINISH_FORMS, (int(x) for x in counts)))
 
     def serialize(self, path):
         lib.jdaCascadorSerializeTo(self.h, os.fsencode(path))

@@ -207,6 +207,13 @@ long long jdaGetOption(void* cascador, const char* key) try {
   return v;
 } JDA_ABI_CATCH(-1)
 
+int jdaFinishForms(void* cascador, long long counts[JDA_FINISH_FORM_N]) try {
+  Cascador* c = (Cascador*)cascador;
+  if (!c || !counts) { fail("jdaFinishForms: null cascador or counts"); return -1; }
+  for (int f = 0; f < JDA_FINISH_FORM_N; f++) counts[f] = c->finish_forms[f].load(std::memory_order_relaxed);
+  return 0;
+} JDA_ABI_CATCH(-1)
+
 int jdaCountWindows(int width, int height, float scale, int min_size, int max_size,
                     long long* n_windows, int* n_levels) try {
   ScanPlan sp; std::string err;

@@ -510,6 +510,8 @@ struct Cascador {
   // them, see PlanEntry::pred_tail
   double pred_tail = -1, pred_out = -1;
   bool last_dense = false;
+  // finishing forms the passes of this cascador have issued (jdaFinishForms): counted where the launches are issued
+  std::atomic<long long> finish_forms[JDA_FINISH_FORM_N] = {};
   int similarity = 0;          // dialect CPP: Config::with_similarity_transform (reference common.cpp:214)
   int device = -1;
   int n_cus = 256;             // compute units of the device

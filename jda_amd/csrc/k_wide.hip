@@ -399,9 +399,9 @@ hipError_t launch_finish_wide_impl(bool trace, bool apply_th, typename DL::Real 
   const WideLds L(m.dim, m.K, (int)sizeof(Real), tile_bytes, budget);
   if (L.row_cap < 1 || L.total > budget) return hipErrorInvalidValue;
   const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>(n_hint, 1 << 16));
-  const int block = m.K > 512 ? 1024 : (m.K > 256 ? 512 : 256);
-  // replay and regression side by side: a wave for the replay + one per 64 shape coordinates
-  const bool conc_ok = conc && 1 + (m.dim + 63) / 64 <= block / 64;
+  const int block = finish_wide_block(m.K);
+  // replay and regression side by side: a wave for the replay + one per 64 shape coordinates (kernels.h)
+  const bool conc_ok = conc && finish_wide_conc_ok(m.dim, m.K);
   auto go = [&](auto kern) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(block), L.total, stream, d_plan, m, w, apply_th ? 1 : 0, th, s0_table,

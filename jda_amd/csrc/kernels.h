@@ -347,6 +347,12 @@ constexpr size_t kFinishLdsPerGroup = 7680;
 // final cut; reads the hand-off queue.  finish_wide_ok: the model fits (single-scale nodes, no similarity transform,
 // a weight row within the LDS row buffer).
 bool finish_wide_ok(int dim, int K, int leaf_n, int real_bytes, bool multi, bool similarity);
+// Its workgroup: a thread per cart of a stage, up to 1,024 (more carts take further rounds).
+inline int finish_wide_block(int K) { return K > 512 ? 1024 : (K > 256 ? 512 : 256); }
+// Replay and regression side by side (the concurrent form) need a wave for the replay and one per 64 shape coordinates
+// in that workgroup; a model that does not fit them takes the sequential form whatever `conc` asks for.  The launcher
+// and the record of the form that ran (Pass::launch_finishers, jdaFinishForms) both ask here.
+inline bool finish_wide_conc_ok(int dim, int K) { return 1 + (dim + 63) / 64 <= finish_wide_block(K) / 64; }
 template <typename Real>
 hipError_t launch_finish_wide(bool trace, bool apply_final_th, Real final_th, const DevPlan* d_plan,
                               const DevModelT<Real>& m, const WorkT<Real>& w, long long n_hint, const S0Node* s0_table,

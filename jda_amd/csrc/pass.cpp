@@ -131,6 +131,7 @@ template <typename Real> bool Pass<Real>::dense_ok(int* pix_cap, int* lds_max) c
 template <typename Real> bool Pass<Real>::run_dense() {
   int pix_cap, lds_max;
   (void)dense_ok(&pix_cap, &lds_max);
+  count_form(JDA_FINISH_DENSE);
   for (int t = 0; t < hm().T; t++)
     for (int l = 0; l < pe->hp.n_levels; l++)
       JDA_HIP(launch_stage<Real>(want_trace(), l, t, apply_th, th, pe->dp, pe->hp, model(), w, pix_cap, lds_max, st));
@@ -464,6 +465,7 @@ template <typename Real> bool Pass<Real>::launch_finishers(long long n_grid) {
     // then everybody goes through k_finish(survivors)
     const long long nmid = pred_mid >= 0 ? (long long)(pred_mid * (double)windows() * 1.25) + 64 : 0;
     const long long wg2 = std::min<long long>((long long)cap_m, std::max<long long>(std::max<long long>(2048, n_grid / std::max<long long>(1, kn().fin_grid_div)), nmid));
+    count_form(JDA_FINISH_MID_DIRECT);
     JDA_HIP(launch_filter0<Real>(want_trace(), pe->dp, model(), wc, n_grid, s0_tbl(), st));
     JDA_HIP(launch_finish<Real>(want_trace(), 0, T, apply_th, th, pe->dp, model(), wc, g2, wg2, s0_tbl(), (int)kn().fin_tile, st, true));
     at.finished = true;
@@ -474,6 +476,7 @@ template <typename Real> bool Pass<Real>::launch_finishers(long long n_grid) {
   if (n_grid <= kn().wide_max && busy_lanes <= kn().wide_busy_max && finish_wide_ok(hm().dim(), hm().K, hm().leaf_n(), (int)sizeof(Real), multi, Sel<Real>::dialect == JDA_DIALECT_CPP && c->similarity)) {
     // a small job (a frame or a few): the call's time is the latency of one window's chain through the stages --
     // every queued window gets a whole workgroup (k_wide.hip)
+    count_form(kn().wide_conc != 0 && finish_wide_conc_ok(hm().dim(), hm().K) ? JDA_FINISH_WIDE_CONC : JDA_FINISH_WIDE_SEQ);
     JDA_HIP(launch_finish_wide<Real>(want_trace(), apply_th, th, pe->dp, model(), w, n_grid, s0_tbl(), st, kn().wide_conc != 0));
     at.finished = true;
     return true;
@@ -484,6 +487,7 @@ template <typename Real> bool Pass<Real>::launch_finishers(long long n_grid) {
   if (T == 1 || n_grid <= kn().finish_merge || st_snapshot) {
     // few windows left: one launch walks them through every remaining stage (no balance problem,
     // one launch less)
+    count_form(JDA_FINISH_MERGED);
     JDA_HIP(launch_finish<Real>(want_trace(), 0, T, apply_th, th, pe->dp, model(), w, gm, n_grid, s0_tbl(), (int)kn().fin_tile, st));
     at.finished = true;
     return true;
@@ -492,6 +496,7 @@ template <typename Real> bool Pass<Real>::launch_finishers(long long n_grid) {
   if (filter0_ok()) {
     // the dying majority is filtered by a lean kernel (four windows per workgroup, stage 0 only); the survivors --
     // a few per cent -- go through k_finish for the regression of stage 0 and every later stage
+    count_form(JDA_FINISH_FILTER0);
     JDA_HIP(launch_filter0<Real>(want_trace(), pe->dp, model(), wc, n_grid, s0_tbl(), st));
     JDA_HIP(launch_finish<Real>(want_trace(), 0, T, apply_th, th, pe->dp, model(), wc, g2, wg2, s0_tbl(), (int)kn().fin_tile, st, true));
     at.finished = true;
@@ -502,6 +507,7 @@ template <typename Real> bool Pass<Real>::launch_finishers(long long n_grid) {
   // of the mid queue (the kernel reads it from the device counter): its grid is a quarter of the hand-off count
   // -- one workgroup per window as long as fewer than 25 % pass stage 0 (6.7 % in the cascade regime), a grid-stride
   // loop beyond that; the surplus workgroups exit at once (an empty workgroup costs ~1.3 ns of dispatcher time).
+  count_form(JDA_FINISH_TWO_LAUNCH);
   JDA_HIP(launch_finish<Real>(want_trace(), 0, 1, apply_th, th, pe->dp, model(), w, (int)kn().fin_g1, n_grid, s0_tbl(), (int)kn().fin_tile1, st));
   JDA_HIP(launch_finish<Real>(want_trace(), 1, T, apply_th, th, pe->dp, model(), w, g2, wg2, nullptr, (int)kn().fin_tile, st));
   at.finished = true;

@@ -117,6 +117,8 @@ struct Pass {
   // ... and its survivors take their stage-0 leaves along to k_finish (WorkT::m_leaf; kernels.h: carry_pack)
   bool carry_ok() const { return kn().fin_carry && filter0_ok() && carry_fits(hm().leaf_n(), hm().K); }
   long long windows() const { return rag ? rag->windows : (long long)nf * pe->sp.windows; }
+  // the finishing form this pass is about to issue, for jdaFinishForms (a pass that is issued again counts again)
+  void count_form(int form) { c->finish_forms[form].fetch_add(1, std::memory_order_relaxed); }
 
   bool dense_ok(int* pix_cap, int* lds_max) const;
   bool run_dense();

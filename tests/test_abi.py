@@ -29,6 +29,21 @@ def test_every_declared_symbol_is_exported(built):
         assert hasattr(api.lib, n), n
 
 
+def test_finish_forms_entry_and_its_python_mirror(built, model_file):
+    """jdaFinishForms (include/jda.h): exported, JDA_FINISH_FORM_N counts in the header's order, all zero on a cascador
+    that has run nothing, null arguments refused.  No GPU needed: the counts live in the host object."""
+    from jda_amd import api
+    assert "jdaFinishForms" in declared_symbols()
+    src = open(HEADER).read()
+    names = re.findall(r"\bJDA_FINISH_(\w+?)\s*(?:=\s*0\s*)?,", src[src.index("JDA_FINISH_WIDE_CONC"):src.index("JDA_FINISH_FORM_N")])
+    assert tuple(names) == api.FINISH_FORMS and len(names) == 7
+    p, _ = model_file((2, 8, 5, 3), 8, seed=1)
+    c = api.Cascador(p)
+    assert c.finish_forms() == dict.fromkeys(api.FINISH_FORMS, 0)
+    assert api.lib.jdaFinishForms(c.h, None) == -1 and api.lib.jdaFinishForms(None, (C.c_longlong * 7)()) == -1
+    c.close()
+
+
 def test_header_is_plain_c_and_links(built, tmp_path):
     """What a maintainer of the reference would do: compile a C caller against
     include/jda.h and link libjda.so (no torch, no C++)."""

@@ -117,7 +117,11 @@ def test_carry_vs_oracle_and_reference_and_with_the_carry_off(built, gpu, model_
     assert small > 0 and large > 0
     assert int((g["carts_n"] == T * K).sum()) > 0
     d = torch.from_numpy(frames).to(gpu)
+    before = c.finish_forms()
     dets, st = c.detect_batch_device(d, stats=True)
+    forms = {k: v - before[k] for k, v in c.finish_forms().items() if v != before[k]}
+    print("forms:", forms)
+    assert forms and set(forms) <= {"FILTER0", "MID_DIRECT"}, forms      # k_filter0 + k_finish(survivors): the carry's path
     assert st["handoff_n"] > FINISH_MERGE and st["dense_passes"] == 0
     ref = pyoracle.Reference(p, S_DIMS, 8) if pyoracle.reference_lib_path(*S_DIMS) else None
     for i in range(len(frames)):
@@ -175,7 +179,11 @@ def test_entries_from_the_persistent_scan_mix_with_carried_ones(built, gpu, mode
     c1 = _cascador(p, env=env)
     assert c1.get_option("scan_p_mid") == 1 and c1.get_option("fin_carry") == 1
     for rep in range(2):                                   # (the second pass sizes its launches from the first)
+        before = c1.finish_forms()
         got, st1 = c1.detect_batch_device(d, stats=True)
+        forms = {k: v - before[k] for k, v in c1.finish_forms().items() if v != before[k]}
+        print("pass", rep, "forms:", forms)
+        assert forms and set(forms) == {"MID_DIRECT"}, forms       # k_filter0 + k_finish(survivors) fed from k_scan_p's mid queue
         _same_dets(want, got)
         for k in ("cart_total_n", "face_patch_n", "stage_done_n", "patch_n"):
             assert st0[k] == st1[k], (rep, k)

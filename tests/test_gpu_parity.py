@@ -35,6 +35,14 @@ def _compare_trace(casc, orc, frames, **kw):
     assert off == len(g["carts_n"])
 
 
+def _forms(c, fn, *a, **kw):
+    """-> (what the call returned, the finishing forms its passes took: jdaFinishForms after minus before, zeros left out)."""
+    before = c.finish_forms()
+    r = fn(*a, **kw)
+    after = c.finish_forms()
+    return r, {k: after[k] - before[k] for k in after if after[k] != before[k]}
+
+
 def _compare_detect(got, want):
     for k in ("bboxes", "scores", "shapes"):
         assert same(got[k], want[k]), k
@@ -48,8 +56,11 @@ def test_golden_vectors(built, gpu, tmp_path, name):
     meta, g, mp = golden_util.load(name, tmp_path)
     scale, mn, mx, th = meta["call"]
     c = api.Cascador(mp, "double")
+    before = c.finish_forms()
     post = c.detect(g["frame"], scale, 0.1, mn, mx, th)                       # the drop-in call
     raw = c.detect_batch(g["frame"][None], scale, mn, mx, th, nms=False)[0]
+    forms = {k: v - before[k] for k, v in c.finish_forms().items() if v != before[k]}
+    print(name, "forms:", forms)            # (for the record only: the docstring claims no form, and a golden frame may hold no window)
     for k in ("bboxes", "scores"):
         assert same(raw[k], g["raw_" + k]), (name, k)
         assert same(post[k], g["post_" + k]), (name, k)
@@ -154,8 +165,14 @@ def test_shipped_dims_vs_oracle_and_reference(built, gpu, model_file):
     p, _ = model_file(S_DIMS, 8, seed=1, cart_th=-2.0)
     frames = synth.make_frames(2, 320, 240, seed=14)
     c, o = api.Cascador(p, "double"), pyoracle.Oracle(p)
+    before = c.finish_forms()
     _compare_trace(c, o, frames)
     dets = c.detect_batch(frames)
+    # two frames of 320 x 240 hand about 4,000 windows off: too many for k_finish_wide (one k_finish launch; the second
+    # call, sized 10 % up from the first one's count, may take k_filter0 first), far too few for dense mode
+    forms = {k: v - before[k] for k, v in c.finish_forms().items() if v != before[k]}
+    print("forms:", forms)
+    assert sum(forms.values()) == 2 and set(forms) <= {"MERGED", "FILTER0"}, forms
     ref = pyoracle.Reference(p, S_DIMS, 8) if pyoracle.reference_lib_path(*S_DIMS) else None
     for i in range(len(frames)):
         _compare_detect(dets[i], o.detect(frames[i]))
@@ -469,6 +486,16 @@ DIFF_KERNELS = {  # which finishing kernel a traced pass runs (options of DESIGN
     "k_finish_wide": dict(dense=0, wide_max=10_000_000),
     "k_stage": dict(dense=2),
 }
+DIFF_DIMS = {  # the model a kernel takes in place of the parametrised one.  Found by the form counts: dense mode declines 68
+    # landmarks whatever `dense` asks for (Pass::dense_ok: the shapes of a 16 x 16 tile of windows, 136 x 256 reals, do not fit
+    # LDS next to the weight rows), so that case went window by window and never ran k_stage; with 16 landmarks it does.
+    ("k_stage", (2, 64, 68, 6)): (2, 64, 16, 6),
+}
+DIFF_FORMS = {  # ... and the finishing forms (jdaFinishForms) that are launches of that kernel
+    "k_finish": {"MERGED", "FILTER0", "MID_DIRECT", "TWO_LAUNCH"},
+    "k_finish_wide": {"WIDE_CONC"},          # (18 and 136 shape coordinates: both leave a wave for the replay)
+    "k_stage": {"DENSE"},
+}
 
 
 @pytest.mark.parametrize("kernel", sorted(DIFF_KERNELS))
@@ -487,6 +514,8 @@ def test_dialects_agree_where_they_must(built, gpu, tmp_path, kernel, dims, win,
     sizes of scale != 0 nodes, cv::resize, the multimap NMS (cart.cpp:392-404, data.cpp:37-51)."""
     from jda_amd import api, synth
     from oracle.pyoracle import Oracle
+    dims = DIFF_DIMS.get((kernel, dims), dims)
+    print("model:", dims)
     m = synth.make_dyadic_model(*dims, win=win, seed=11 + win, reject=reject)
     p = str(tmp_path / "dyadic.model")
     m.save(p, 8)
@@ -495,8 +524,11 @@ def test_dialects_agree_where_they_must(built, gpu, tmp_path, kernel, dims, win,
     c = api.Cascador(p)
     for k, v in DIFF_KERNELS[kernel].items():
         c.set_option(k, v)
-    a = c.trace(frames, scale=np.float32(scale), min_size=win, max_size=win)
-    b = c.trace_cpp(frames, minimum_size=win, step=step, factor=100.0)
+    a, fa = _forms(c, c.trace, frames, scale=np.float32(scale), min_size=win, max_size=win)
+    b, fb = _forms(c, c.trace_cpp, frames, minimum_size=win, step=step, factor=100.0)
+    print(kernel, "forms:", fa, fb)
+    want = DIFF_FORMS[kernel]
+    assert fa and fb and set(fa) <= want and set(fb) <= want, (kernel, fa, fb)
     n = n_frames * ((w - win) // step + 1) * ((h - win) // step + 1)
     assert len(a["carts_n"]) == len(b["carts_n"]) == n
     if dims == (3, 70, 9, 5):
@@ -787,7 +819,7 @@ def test_dense_mode_is_a_third_implementation_of_the_walk(built, gpu, model_file
     c0 = api.Cascador(p)
     tr0 = c0.trace(frames)
     d0, s0 = c0.detect_batch(frames, stats=True)
-    assert s0["dense_passes"] == 0
+    assert s0["dense_passes"] == 0 and c0.finish_forms()["DENSE"] == 0
     for mode in ("2", "1"):
         monkeypatch.setenv("JDA_DENSE", mode)
         c = api.Cascador(p)
@@ -795,7 +827,8 @@ def test_dense_mode_is_a_third_implementation_of_the_walk(built, gpu, model_file
         tr = c.trace(frames)
         for k in tr0:
             assert same(tr0[k], tr[k]), (mode, k)
-        d, s = c.detect_batch(frames, stats=True)
+        (d, s), f = _forms(c, c.detect_batch, frames, stats=True)
+        print("dense =", mode, "forms:", f, "dense_passes", s["dense_passes"])
         for a, b in zip(d, d0):
             _compare_detect(a, b)
         for k in ("patch_n", "face_patch_n", "cart_gothrough_n", "cart_total_n"):
@@ -803,6 +836,7 @@ def test_dense_mode_is_a_third_implementation_of_the_walk(built, gpu, model_file
         assert list(s["stage_done_n"]) == list(s0["stage_done_n"])
         if mode == "2" or cart_th is None:
             assert s["dense_passes"] >= 1, "dense mode did not run"
+            assert f.get("DENSE", 0) >= 1 and (mode == "1" or set(f) == {"DENSE"}), f
 
 
 def test_dense_mode_dialect_cpp(built, gpu, model_file, monkeypatch):
@@ -812,7 +846,8 @@ def test_dense_mode_dialect_cpp(built, gpu, model_file, monkeypatch):
     frames = synth.make_frames(2, 200, 150, seed=64)
     monkeypatch.setenv("JDA_DENSE", "2")
     c, o = api.Cascador(p), Oracle(p)
-    g = c.trace_cpp(frames, 20, 5, 1.2)
+    g, f = _forms(c, c.trace_cpp, frames, 20, 5, 1.2)
+    assert f == {"DENSE": 1}, f
     off = 0
     for i in range(len(frames)):
         r = o.trace_cpp(frames[i], 20, 5, 1.2)
@@ -1040,35 +1075,55 @@ print("OK")
 
 # ---------------------------------------------------------------- small jobs: workgroup = window
 
-@pytest.mark.parametrize("dims,kw", [((3, 70, 9, 5), dict(cart_th=-0.9, norm_every=9)), ((2, 130, 27, 4), dict(cart_th=-0.6)),
-                                     ((2, 600, 5, 3), dict(cart_th=-1.5, norm_every=50)), ((3, 20, 150, 4), dict(cart_th=-0.8)),
+@pytest.mark.parametrize("dims,kw", [((3, 70, 9, 5), dict(cart_th=-0.5, norm_every=9)), ((2, 130, 27, 4), dict(cart_th=0.7)),
+                                     ((2, 600, 5, 3), dict(cart_th=-0.7, norm_every=50)), ((3, 20, 150, 4), dict(cart_th=0.2)),
                                      ((2, 64, 68, 6), dict(cart_th=-0.7))])
 def test_wide_finish_equals_wave_finish_and_the_oracle(built, gpu, model_file, dims, kw):
     """Small jobs finish with one WORKGROUP per window (k_finish_wide: thread = cart, weight rows through LDS), large
     ones with one wave per window (k_finish).  Same per-window trace (reject cart, score bits, leaf-path hash, shape
-    bits) from both, equal to the oracle's (c/jda.c:357-426; Validate, cascador.cpp:166-211), in both dialects."""
+    bits) from both, equal to the oracle's (c/jda.c:357-426; Validate, cascador.cpp:166-211), in both dialects.
+    Every call states the finishing form it took (jdaFinishForms): the wide cascador WIDE_CONC (WIDE_SEQ with 300 shape
+    coordinates, which leave no wave for the replay), the wide_conc = 0 cascador WIDE_SEQ, the wave cascador MERGED and
+    nothing else.  The thresholds and the dialect-CPP scan keep the hand-off queue under (wide_max - 64) / 1.1 = 872
+    windows, so that a call sized from the pass before it takes the same form (tests/test_finish_forms.py)."""
     from jda_amd import api, synth
     from oracle.pyoracle import Oracle
     p, _ = model_file(dims, 8, seed=91, **kw)
-    frames = synth.make_frames(2, 260, 190, seed=92)
+    frames = synth.make_frames(1 if dims == (2, 130, 27, 4) else 2, 260, 190, seed=92)     # (K = 130 keeps the most windows)
+    cpp = dict(minimum_size=40, step=6, factor=1.25)
     o = Oracle(p)
     wide, wave = api.Cascador(p), api.Cascador(p)
     wave.set_option("wide_max", 0)
     assert wide.get_option("wide_max") > 0
-    _compare_trace(wide, o, frames[:1])
-    tw, tv = wide.trace(frames), wave.trace(frames)
+    form = {"WIDE_SEQ" if dims[2] == 150 else "WIDE_CONC": 1}
+    (tw, fw), (tv, fv) = _forms(wide, wide.trace, frames), _forms(wave, wave.trace, frames)
+    print("trace:", fw, fv)
+    assert fw == form and fv == {"MERGED": 1}, (fw, fv)
+    off = 0
+    for i in range(len(frames)):
+        r = o.trace(frames[i])
+        n = len(r["carts_n"])
+        for k in ("carts_n", "score", "path_hash", "shapes"):
+            assert same(r[k], tw[k][off:off + n]), (i, k)
+        off += n
     for k in tw:
         assert same(tw[k], tv[k]), k
     # the wide kernel's two forms: replay and regression side by side (wide_conc = 1, the default) or one after the other
     seq = api.Cascador(p)
     seq.set_option("wide_conc", 0)
     assert wide.get_option("wide_conc") == 1
-    ts, tsc = seq.trace(frames), seq.trace_cpp(frames, 20, 5, 1.2)
+    (ts, fs), (tsc, fsc) = _forms(seq, seq.trace, frames), _forms(seq, seq.trace_cpp, frames, **cpp)
+    print("wide_conc = 0:", fs, fsc)
+    assert fs == {"WIDE_SEQ": 1} and fsc == {"WIDE_SEQ": 1}, (fs, fsc)
     for k in tw:
         assert same(tw[k], ts[k]), ("wide_conc", k)
-    for a, b in zip(wide.detect_batch(frames), seq.detect_batch(frames)):
+    (da, fa), (db, fb) = _forms(wide, wide.detect_batch, frames), _forms(seq, seq.detect_batch, frames)
+    assert fa == form and fb == {"WIDE_SEQ": 1}, (fa, fb)
+    for a, b in zip(da, db):
         _compare_detect(a, b)
-    (dw, sw), (dv, sv) = wide.detect_batch(frames, stats=True), wave.detect_batch(frames, stats=True)
+    ((dw, sw), fw), ((dv, sv), fv) = _forms(wide, wide.detect_batch, frames, stats=True), _forms(wave, wave.detect_batch, frames, stats=True)
+    print("detect:", fw, fv, "hand-off", sw["handoff_n"])
+    assert fw == form and fv == {"MERGED": 1}, (fw, fv)
     for a, b in zip(dw, dv):
         _compare_detect(a, b)
     for k in ("patch_n", "face_patch_n", "cart_gothrough_n", "cart_total_n", "handoff_n"):
@@ -1076,14 +1131,19 @@ def test_wide_finish_equals_wave_finish_and_the_oracle(built, gpu, model_file, d
     assert list(sw["stage_done_n"]) == list(sv["stage_done_n"])
     assert sum(len(d["scores"]) for d in dw) > 0
     # dialect CPP (fp64: the rows go through registers instead of LDS-DMA, the delta is summed from zero)
-    cw, cv = wide.trace_cpp(frames, 20, 5, 1.2), wave.trace_cpp(frames, 20, 5, 1.2)
+    (cw, fw), (cv, fv) = _forms(wide, wide.trace_cpp, frames, **cpp), _forms(wave, wave.trace_cpp, frames, **cpp)
+    print("trace_cpp:", fw, fv)
+    assert fw == form and fv == {"MERGED": 1}, (fw, fv)
     for k in cw:
         assert same(cw[k], cv[k]), ("cpp", k)
         assert same(cw[k], tsc[k]), ("cpp wide_conc", k)
-    r = o.trace_cpp(frames[0], 20, 5, 1.2)
+    r = o.trace_cpp(frames[0], **cpp)
     for k in ("carts_n", "score", "path_hash", "shapes"):
         assert same(r[k], cw[k][:len(r[k])]), ("cpp oracle", k)
-    for a, b in zip(wide.detect_batch_cpp(frames), wave.detect_batch_cpp(frames)):
+    (da, fw), (db, fv) = _forms(wide, wide.detect_batch_cpp, frames, **cpp), _forms(wave, wave.detect_batch_cpp, frames, **cpp)
+    print("detect_cpp:", fw, fv)
+    assert fw == form and fv == {"MERGED": 1}, (fw, fv)
+    for a, b in zip(da, db):
         for k in ("rects", "scores", "shapes"):
             assert same(a[k], b[k]), ("cpp", k)
 
@@ -1104,12 +1164,14 @@ def test_finish_table_layouts_do_not_change_results(built, gpu, model_file, monk
     plain = api.Cascador(p)
     plain.set_option("wide_max", 0)            # the wave-per-window kernel is the one that reads these tables
     _compare_trace(plain, Oracle(p), frames[:1])
-    want_t, want_d, want_c = plain.trace(frames), plain.detect_batch(frames), plain.trace_cpp(frames, 20, 5, 1.2)
+    (want_t, want_d, want_c), f0 = _forms(plain, lambda: (plain.trace(frames), plain.detect_batch(frames), plain.trace_cpp(frames, 20, 5, 1.2)))
+    forms = [f0]
     for pad, deep in ((1, 1), (1, 0), (0, 1)):
         monkeypatch.setenv("JDA_W_PAD", str(pad)); monkeypatch.setenv("JDA_LM_DEEP", str(deep))
         c = api.Cascador(p)
         c.set_option("wide_max", 0)
-        t, d, tc = c.trace(frames), c.detect_batch(frames), c.trace_cpp(frames, 20, 5, 1.2)
+        (t, d, tc), f = _forms(c, lambda: (c.trace(frames), c.detect_batch(frames), c.trace_cpp(frames, 20, 5, 1.2)))
+        forms.append(f)
         for k in want_t:
             assert same(want_t[k], t[k]), (pad, deep, k)
         for a, b in zip(want_d, d):
@@ -1118,6 +1180,10 @@ def test_finish_table_layouts_do_not_change_results(built, gpu, model_file, monk
             assert same(want_c[k], tc[k]), (pad, deep, "cpp", k)
         c.close()
     plain.close()
+    # k_finish is the kernel under test: three passes a cascador, none through k_finish_wide or k_stage
+    print("forms:", forms)
+    for f in forms:
+        assert sum(f.values()) == 3 and set(f) <= {"MERGED", "FILTER0", "TWO_LAUNCH"}, f
 
 
 def test_streamed_weight_rows_give_the_same_detections(built, gpu, model_file, monkeypatch):
@@ -1131,7 +1197,9 @@ def test_streamed_weight_rows_give_the_same_detections(built, gpu, model_file, m
     c = api.Cascador(p)
     c.set_option("wide_max", 0)
     o = Oracle(p)
-    got = c.detect_batch(frames)
+    got, f = _forms(c, c.detect_batch, frames)
+    print("forms:", f)
+    assert f == {"MERGED": 1}, f                # (k_finish, not k_finish_wide or k_stage)
     for i in range(len(frames)):
         _compare_detect(o.detect(frames[i]), got[i])
     assert sum(len(g["scores"]) for g in got) > 0
