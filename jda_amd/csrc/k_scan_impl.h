@@ -11,6 +11,9 @@
 // The cart tables (resolved nodes, leaf scores, cart parameters) are staged in LDS one CHUNK of
 // carts at a time; a workgroup that still has windows alive at the end of a chunk loads the next
 // one, up to `handoff` carts.
+// Shared with the persistent form k_scan_p (scan_walk.h): the tree walks, ThNorm, tile_geo, handoff_write.  The score
+// recurrence, the batch replay and the compaction are this kernel's own copies of the same arithmetic: the compaction as
+// a shared helper cost the uniform instantiations two waves per SIMD (profiles/scan_shared_isa.txt).
 //
 // This file is the kernel and its launchers; three translation units include it and instantiate one third of the
 // (Real, TRACE, MODE, BLOCK, DEPTH, RAGGED, NORM) combinations each, so that they compile side by side (one unit took
@@ -38,9 +41,6 @@ int scan_handoff_cap(int node_n, int leaf_n, int real_bytes) {
 namespace {
 
 constexpr int kScanMaxWindows = 512;     // windows per tile at most (queue capacity)
-
-template <typename Real>
-struct ThNorm { Real th, norm; };        // first half of CartPar: all the common case needs
 
 template <typename Real, bool TRACE>
 struct ScanLds {
@@ -172,14 +172,11 @@ void k_scan(const DevPlan* __restrict__ plan, DevModelT<Real> m,
     lv_ = plan->lv[level];
   }
   const DevLevel lv = lv_;
-  const int frame = frame_, trel = trel_;
+  const int frame = frame_;
   const int gid0 = RAGGED ? gid0_ : frame * plan->windows + lv.base;
   const uint8_t* img = RAGGED ? w.frames + img_off_ : w.frames + (size_t)frame * w.frame_stride;
-  const int ty = trel / lv.tiles_x, tx = trel - ty * lv.tiles_x;
-  const int wx0 = tx * lv.tw, wy0 = ty * lv.th;                 // first window of the tile
-  const int twe = min(lv.tw, lv.nx - wx0), the = min(lv.th, lv.ny - wy0);
-  const int x0 = wx0 * lv.step, y0 = wy0 * lv.step;             // tile origin in the frame
-  const int pw = lv.win + (twe - 1) * lv.step, ph = lv.win + (the - 1) * lv.step;
+  const TileGeo tg = tile_geo(trel_, lv.tiles_x, lv.tw, lv.th, lv.nx, lv.ny, lv.step, lv.win);
+  const int wx0 = tg.wx0, wy0 = tg.wy0, twe = tg.twe, the = tg.the;     // first window of the tile; its windows
 
   // ---- stage the pixel tile (LDS-DMA when the frame is 16-byte aligned) and the first table chunk ----
   const int W = plan->width;
@@ -190,8 +187,8 @@ void k_scan(const DevPlan* __restrict__ plan, DevModelT<Real> m,
 #else
   const Bc bc_fr, bc_pix;
 #endif
-  if (GLB) pix = img + (size_t)y0 * W + x0;       // window origins are offsets from the tile origin in the frame
-  else xshift = load_tile<BLOCK>(lds + L.pix, w.frames, w.frame_stride, img, W, x0, y0, pw, ph, lv.pitch, tid, bc_fr, Bc(0, (pix_bytes + 15) & ~15));
+  if (GLB) pix = img + (size_t)tg.y0 * W + tg.x0;       // window origins are offsets from the tile origin in the frame
+  else xshift = load_tile<BLOCK>(lds + L.pix, w.frames, w.frame_stride, img, W, tg.x0, tg.y0, tg.pw, tg.ph, lv.pitch, tid, bc_fr, Bc(0, (pix_bytes + 15) & ~15));
   auto load_tables = [&](int kb, int kc) {
     dma_to_lds<BLOCK>(lds + L.nodes, table + lv.s0_table + (size_t)kb * node_n, kc * node_n * (int)sizeof(S0Node), tid);
     dma_to_lds<BLOCK>(lds + L.leaf, m.leaf + (size_t)kb * leaf_n, kc * leaf_n * (int)sizeof(Real), tid);
@@ -547,16 +544,9 @@ void k_scan(const DevPlan* __restrict__ plan, DevModelT<Real> m,
     for (int i = tid; i < n_items; i += BLOCK) {
       const int widx = q_widx[cur * M_MAX + i];
       const int wy = widx / lv.tw, wx = widx - wy * lv.tw;
-      const unsigned slot = gbase + i;
-      if (slot < w.cap_q) {
-        JDA_BC(Bc(0, w.cap_q), slot, 1, kBcQueue);
-        w.q_gid[slot] = (uint32_t)(gid0 + (wy0 + wy) * lv.nx + wx0 + wx);
-        w.q_score[slot] = q_score[cur * M_MAX + i];
-        w.q_kstart[slot] = (uint32_t)K;
-        w.q_xy[slot] = (uint32_t)((wx0 + wx) * lv.step) | ((uint32_t)((wy0 + wy) * lv.step) << 16);
-        w.q_wf[slot] = (uint32_t)lv.win | ((uint32_t)frame << 16);
-        if (TRACE) w.q_hash[slot] = q_hash[cur * M_MAX + i];
-      }
+      const bool put = handoff_write(w, gbase + i, false, (uint32_t)(gid0 + (wy0 + wy) * lv.nx + wx0 + wx), q_score[cur * M_MAX + i], K,
+                                     wx0 + wx, wy0 + wy, lv.step, lv.win, frame);
+      if (TRACE && put) w.q_hash[gbase + i] = q_hash[cur * M_MAX + i];
       handed += K;
     }
   }

@@ -20,7 +20,9 @@
 //     the deepest ring that holds a full task, then fresh windows, then whatever is left (partial tasks: only when a
 //     tile is late or at the end of the launch), so a ring never holds more than a task plus what the waves in flight
 //     can add -- the ring capacity 64 * (waves + 2)
-// Same arithmetic in the same order as k_scan: bit-identical results (reject cart, score).
+// Same arithmetic in the same order as k_scan: bit-identical results (reject cart, score).  The tree walks, ThNorm,
+// tile_geo and handoff_write are k_scan's (scan_walk.h), the table copy is kernels_common.h's dma_to_lds_rt; p_apply,
+// p_uni and p_pair's replay restate k_scan's recurrence.
 #include "kernels_common.h"
 #include "scan_walk.h"
 
@@ -43,8 +45,6 @@ constexpr int kPSpinMax = 1 << 20;     // ring commit
 #define JDA_SCAN_P_IDLE_MAX (1 << 20)  // (tests build a variant with 0: every wave that idles once leaves -> the fallback runs)
 #endif
 constexpr int kPIdleMax = JDA_SCAN_P_IDLE_MAX;
-
-struct ThNormF { float th, norm; };
 
 // Control block in LDS: 16-byte records, so that a wave picks its next task from ONE ds_read_b128 -- lane i reads
 // record i, evaluates "its" slot or ring, and ballots turn the candidates into masks.  (The first version walked rings
@@ -94,25 +94,6 @@ __device__ __forceinline__ void lds_drain() { asm volatile("s_waitcnt lgkmcnt(0)
 __device__ __forceinline__ void compiler_fence() { asm volatile("" ::: "memory"); }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// global -> LDS by LDS-DMA with a run-time workgroup size (dma_to_lds, kernels_common.h, takes it as a template
-// parameter); the tail and unaligned sources go through registers.  The caller waits vmcnt(0) + barrier.
-__device__ __forceinline__ void dma_to_lds_rt(unsigned char* lds_dst, const void* __restrict__ src, int nbytes, int tid, int nthreads) {
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-  const unsigned char* g = (const unsigned char*)src;
-  int done = 0;
-  if ((((uintptr_t)g) & 15) == 0) {
-    const int chunks = nbytes >> 4;
-    const int lane = tid & 63, wv = tid >> 6;
-    for (int base = wv * 64; base < chunks; base += nthreads) {
-      if (base + lane < chunks)
-        __builtin_amdgcn_global_load_lds((gbl_ptr_t)(g + ((size_t)(base + lane) << 4)), (lds_ptr_t)(lds_dst + (base << 4)), 16, 0, 0);
-    }
-    done = chunks << 4;
-  }
-  for (int i = done + tid; i < nbytes; i += nthreads) lds_dst[i] = g[i];
-}
-
 struct PCtx {
   Bc bc;                               // bounds-check build: the LDS bytes of the pixel-tile slots (empty otherwise)
   const uint8_t* lds;                  // pixels are addressed by absolute LDS offsets
@@ -125,10 +106,10 @@ struct PCtx {
 // its branch leave the loop.
 template <int CNT, bool NORM>
 __device__ __forceinline__ void p_apply(const PCtx& c, int k, const int* lf, bool& alive, float& score, unsigned& my_carts) {
-  ThNormF p[CNT];
+  ThNorm<float> p[CNT];
   float lsv[CNT];
 #pragma unroll
-  for (int u = 0; u < CNT; u++) { p[u] = *(const ThNormF*)&c.t_par[k + u]; lsv[u] = c.t_leaf[(k + u) * c.leaf_n + lf[u]]; }
+  for (int u = 0; u < CNT; u++) { p[u] = *(const ThNorm<float>*)&c.t_par[k + u]; lsv[u] = c.t_leaf[(k + u) * c.leaf_n + lf[u]]; }
   float s = score;
   bool dead = false;
   int kd = k;
@@ -211,7 +192,7 @@ __device__ __forceinline__ void p_pair(const PCtx& c, uint8_t* lf, int lg, int c
       // registers, strictly in cart order (c/jda.c:395-399)
       for (; k + 16 <= r1; k += 16) {
         if (__ballot(alive) == 0ull) break;
-        const ThNormF pm = *(const ThNormF*)&c.t_par[k + (lane & 15)];      // lane u (mod 16): cart k+u
+        const ThNorm<float> pm = *(const ThNorm<float>*)&c.t_par[k + (lane & 15)];      // lane u (mod 16): cart k+u
         if (__ballot(pm.norm != 0.f) != 0ull) break;                        // rare: the generic loop below takes over
         float thv[16];
 #pragma unroll
@@ -428,20 +409,10 @@ void k_scan_p(const DevPlan* __restrict__ plan, DevModelT<float> m, const S0Node
       const int tw_s = RAGGED ? g2.z : lv.tw;
       const int wy = widx / tw_s, wx = widx - wy * tw_s;
       const int frame = g.z, wx0 = g.w & 0xffff, wy0 = (int)((unsigned)g.w >> 16);
-      const unsigned slot = gbase + (unsigned)rank;
-      if (slot < (cfg.to_mid ? w.cap_m : w.cap_q)) {
-        JDA_BC(Bc(0, cfg.to_mid ? w.cap_m : w.cap_q), slot, 1, kBcQueue);
-        const uint32_t gid = RAGGED ? (uint32_t)(g2.x + (wy0 + wy) * g2.y + wx0 + wx)
-                                    : (uint32_t)(frame * plan->windows + lv.base + (wy0 + wy) * lv.nx + wx0 + wx);
-        const uint32_t xy = (uint32_t)((wx0 + wx) * lv.step) | ((uint32_t)((wy0 + wy) * lv.step) << 16);
-        const uint32_t wf = (uint32_t)lv.win | ((uint32_t)frame << 16);
-        if (cfg.to_mid) {                  // stage 0 passed: k_finish(survivors) takes it from the mid queue, as k_filter0 leaves it
-          w.m_gid[slot] = gid; w.m_score[slot] = score; w.m_xy[slot] = xy; w.m_wf[slot] = wf;
-          w.m_k0[slot] = (uint32_t)K;      // (no stage-0 leaves come with it: k_finish walks them all)
-        } else {
-          w.q_gid[slot] = gid; w.q_score[slot] = score; w.q_kstart[slot] = (uint32_t)K; w.q_xy[slot] = xy; w.q_wf[slot] = wf;
-        }
-      }
+      const uint32_t gid = RAGGED ? (uint32_t)(g2.x + (wy0 + wy) * g2.y + wx0 + wx)
+                                  : (uint32_t)(frame * plan->windows + lv.base + (wy0 + wy) * lv.nx + wx0 + wx);
+      // (to_mid: stage 0 passed -- k_finish(survivors) takes it from the mid queue, as k_filter0 leaves it)
+      handoff_write(w, gbase + (unsigned)rank, cfg.to_mid != 0, gid, score, K, wx0 + wx, wy0 + wy, lv.step, lv.win, frame);
       handed += K;
       if (cfg.to_mid) mids += 1;
     }
@@ -587,17 +558,14 @@ void k_scan_p(const DevPlan* __restrict__ plan, DevModelT<float> m, const S0Node
             } else {
               img = w.frames + (size_t)frame * w.frame_stride;
             }
-            const int ty = trel / tiles_x, tx = trel - ty * tiles_x;
-            const int wx0 = tx * tw_s, wy0 = ty * th_s;
-            const int twe = min(tw_s, nx_s - wx0), the = min(th_s, ny_s - wy0);
-            const int x0 = wx0 * lv.step, y0 = wy0 * lv.step;
-            const int pw = lv.win + (twe - 1) * lv.step, ph = lv.win + (the - 1) * lv.step;
+            const TileGeo tg = tile_geo(trel, tiles_x, tw_s, th_s, nx_s, ny_s, lv.step, lv.win);
+            const int wx0 = tg.wx0, wy0 = tg.wy0, twe = tg.twe, the = tg.the;
 #ifdef JDA_BOUNDS_CHECK
             const Bc bc_fr((long long)(uintptr_t)w.bc_lo, (long long)(uintptr_t)w.bc_hi);
 #else
             const Bc bc_fr;
 #endif
-            const int xshift = load_tile<64>(lds + L.slots + s * cfg.slot_bytes, w.frames, w.frame_stride, img, W, x0, y0, pw, ph,
+            const int xshift = load_tile<64>(lds + L.slots + s * cfg.slot_bytes, w.frames, w.frame_stride, img, W, tg.x0, tg.y0, tg.pw, tg.ph,
                                              lv.pitch, lane, bc_fr, Bc(0, cfg.slot_bytes));
             const int nbatch = (tw_s * the + 63) >> 6;
             if (lane == 0) {

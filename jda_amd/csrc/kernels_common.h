@@ -270,24 +270,38 @@ __device__ __forceinline__ int load_tile(unsigned char* lds_pix, const uint8_t* 
   return 0;
 }
 
-// global -> LDS by LDS-DMA (16 bytes per lane, no VGPR round trip); falls back to stage_to_lds
-// for sources that are not 16-byte aligned and for the tail.  The caller waits vmcnt(0) + barrier.
-template <int BLOCK>
-__device__ __forceinline__ void dma_to_lds(unsigned char* lds_dst, const void* __restrict__ src, int nbytes, int tid) {
+// The 16-byte chunks of a global -> LDS copy by LDS-DMA (16 bytes per lane, no VGPR round trip), by a workgroup of
+// `nthreads`; returns the bytes covered (0: the source is not 16-byte aligned).  The caller copies the rest.
+__device__ __forceinline__ int dma_chunks_to_lds(unsigned char* lds_dst, const unsigned char* __restrict__ g, int nbytes, int tid, int nthreads) {
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-  const unsigned char* g = (const unsigned char*)src;
   int done = 0;
   if ((((uintptr_t)g) & 15) == 0) {
     const int chunks = nbytes >> 4;
     const int lane = tid & 63, wv = tid >> 6;
-    for (int base = wv * 64; base < chunks; base += BLOCK) {
+    for (int base = wv * 64; base < chunks; base += nthreads) {
       if (base + lane < chunks)
         __builtin_amdgcn_global_load_lds((gbl_ptr_t)(g + ((size_t)(base + lane) << 4)), (lds_ptr_t)(lds_dst + (base << 4)), 16, 0, 0);
     }
     done = chunks << 4;
   }
+  return done;
+}
+
+// global -> LDS by LDS-DMA; falls back to stage_to_lds for sources that are not 16-byte aligned and for the tail.
+// The caller waits vmcnt(0) + barrier.
+template <int BLOCK>
+__device__ __forceinline__ void dma_to_lds(unsigned char* lds_dst, const void* __restrict__ src, int nbytes, int tid) {
+  const unsigned char* g = (const unsigned char*)src;
+  const int done = dma_chunks_to_lds(lds_dst, g, nbytes, tid, BLOCK);
   stage_to_lds<unsigned char, BLOCK, 4>(lds_dst + done, g + done, nbytes - done, tid);
+}
+
+// The same with a run-time workgroup size (k_scan_p); the tail and unaligned sources go through registers byte by byte.
+__device__ __forceinline__ void dma_to_lds_rt(unsigned char* lds_dst, const void* __restrict__ src, int nbytes, int tid, int nthreads) {
+  const unsigned char* g = (const unsigned char*)src;
+  const int done = dma_chunks_to_lds(lds_dst, g, nbytes, tid, nthreads);
+  for (int i = done + tid; i < nbytes; i += nthreads) lds_dst[i] = g[i];
 }
 
 // lane-masked move: r = (bit `lane` of m) ? s : mine, one v_cndmask per dword with the mask in an SGPR pair (no compare,

@@ -1,4 +1,8 @@
-// Stage-0 tree walks over resolved nodes (S0Node): shared by k_scan.hip and k_scan_p.hip.
+// Stage 0 over resolved nodes (S0Node), what k_scan (k_scan_impl.h, closed tiles) and k_scan_p (k_scan_p.hip,
+// persistent) share and must agree on bit for bit: the tree walks (s0_left, scan_tree, scan_trees), the record the
+// score step reads (ThNorm), a tile's geometry (tile_geo) and the hand-off record (handoff_write).
+// The score recurrence, the batch replay, the survivor compaction and the fetch of a ragged block are still spelled out
+// in both kernels; what was measured of sharing them is in profiles/scan_shared_isa.txt.
 // Reference loop being replaced: c/jda.c:357-402 (stage 0: every window still holds the mean shape, so the
 // feature offsets are resolved per (node, level) by k_prep_stage0).
 #pragma once
@@ -93,6 +97,42 @@ __device__ __forceinline__ void scan_trees(const S0Node* __restrict__ t_nodes, i
   }
 #pragma unroll
   for (int u = 0; u < N; u++) lf[u] = node[u] - node_n;
+}
+
+// First half of CartPar: all a cart's score step needs where the cart does not normalise (the common case)
+template <typename Real>
+struct ThNorm { Real th, norm; };
+
+// Tile `trel` of a grid of nx x ny windows cut into tiles of tw x th: its first window, its windows (edge tiles are
+// smaller), its origin and its extent in pixels.
+struct TileGeo { int wx0, wy0, twe, the, x0, y0, pw, ph; };
+__device__ __forceinline__ TileGeo tile_geo(int trel, int tiles_x, int tw, int th, int nx, int ny, int step, int win) {
+  TileGeo g;
+  const int ty = trel / tiles_x, tx = trel - ty * tiles_x;
+  g.wx0 = tx * tw; g.wy0 = ty * th;
+  g.twe = min(tw, nx - g.wx0); g.the = min(th, ny - g.wy0);
+  g.x0 = g.wx0 * step; g.y0 = g.wy0 * step;
+  g.pw = win + (g.twe - 1) * step; g.ph = win + (g.the - 1) * step;
+  return g;
+}
+
+// One window that is alive after cart K - 1 of stage 0 -> entry `slot` of the hand-off queue (k_filter0 / k_finish
+// continue at cart K) or, to_mid (K = all of stage 0), of the mid queue as k_filter0 leaves it -- without stage-0
+// leaves (m_k0 = K: k_finish(survivors) walks them all).  (wx, wy): the window in its level's grid.  false: the queue
+// is full (the counters keep counting: Pass::recover_overflow).
+template <typename Real>
+__device__ __forceinline__ bool handoff_write(const WorkT<Real>& w, unsigned slot, bool to_mid, uint32_t gid, Real score, int K,
+                                              int wx, int wy, int step, int win, int frame) {
+  if (slot >= (to_mid ? w.cap_m : w.cap_q)) return false;
+  JDA_BC(Bc(0, to_mid ? w.cap_m : w.cap_q), slot, 1, kBcQueue);
+  const uint32_t xy = (uint32_t)(wx * step) | ((uint32_t)(wy * step) << 16);
+  const uint32_t wf = (uint32_t)win | ((uint32_t)frame << 16);
+  if (to_mid) {
+    w.m_gid[slot] = gid; w.m_score[slot] = score; w.m_xy[slot] = xy; w.m_wf[slot] = wf; w.m_k0[slot] = (uint32_t)K;
+  } else {
+    w.q_gid[slot] = gid; w.q_score[slot] = score; w.q_kstart[slot] = (uint32_t)K; w.q_xy[slot] = xy; w.q_wf[slot] = wf;
+  }
+  return true;
 }
 
 }  // namespace
