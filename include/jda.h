@@ -185,6 +185,31 @@ enum {
  * Returns 0, or -1 for a null argument. */
 JDA_API int jdaFinishForms(void *cascador, long long counts[JDA_FINISH_FORM_N]);
 
+/* Which stage-0 scan the passes of a cascador launched.  A scan launch is one instantiation of
+ * k_scan or k_scan_p; which one depends on the model, the scan plan's tiles, the options and the size of the job, and
+ * never changes a result.  Every launch counts once under the full key of what it instantiates:
+ *   kernel   JDA_SCAN_K_SCAN (closed tiles) or JDA_SCAN_K_SCAN_P (the persistent form)
+ *   dialect  JDA_DIALECT_C (fp32) or JDA_DIALECT_CPP (fp64)
+ *   depth    JDA_SCAN_DEPTH_4, JDA_SCAN_DEPTH_6 or JDA_SCAN_DEPTH_GENERIC (any other tree depth)
+ *   pix      JDA_SCAN_T16_256 / JDA_SCAN_T16_512: LDS pixel tile, 16-bit node offsets, workgroups of 256 / 512 threads
+ *            (k_scan_p: of fewer than 512 / of 512 or more threads, its size being the scan_p_block option);
+ *            JDA_SCAN_T21: LDS tile, 21-bit offsets; JDA_SCAN_GLB: no tile, pixels through the caches
+ *   ragged   1: a launch over the block map of a ragged job
+ *   lean     1: the form without the per-cart normalisation test (no cart of the scanned range normalises)
+ *   trace    1: the pass records carts, score and leaf hash per window
+ *   merged   1: one launch over several levels (a ragged launch: over blocks of several levels), 0: a single level
+ * at counts[JDA_SCAN_FORM(kernel, dialect, depth, pix, ragged, lean, trace, merged)]. */
+enum { JDA_SCAN_K_SCAN = 0, JDA_SCAN_K_SCAN_P = 1 };
+enum { JDA_SCAN_DEPTH_4 = 0, JDA_SCAN_DEPTH_6 = 1, JDA_SCAN_DEPTH_GENERIC = 2 };
+enum { JDA_SCAN_T16_256 = 0, JDA_SCAN_T16_512 = 1, JDA_SCAN_T21 = 2, JDA_SCAN_GLB = 3 };
+#define JDA_SCAN_FORM(kernel, dialect, depth, pix, ragged, lean, trace, merged) \
+  ((((((((kernel) * 2 + (dialect)) * 3 + (depth)) * 4 + (pix)) * 2 + (ragged)) * 2 + (lean)) * 2 + (trace)) * 2 + (merged))
+#define JDA_SCAN_FORM_N 768
+/* counts[i]: how often the passes of this cascador have launched form i since it was created.  Cumulative, added
+ * atomically on the host where the launches are issued; take the difference around a call, as with jdaFinishForms.  A
+ * pass that is issued again (jdaStats ws_regrows / scan_fallbacks) counts its launches again.  Returns 0, or -1 for a null argument. */
+JDA_API int jdaScanForms(void *cascador, long long counts[JDA_SCAN_FORM_N]);
+
 /* Window enumeration of reference c/jda.c:320-339 without running anything:
  * number of candidate windows and pyramid levels for one frame. */
 JDA_API int jdaCountWindows(int width, int height, float scale, int min_size, int max_size,

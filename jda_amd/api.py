@@ -9,6 +9,7 @@ trace entry points of include/jda.h.
 There is no fallback: if libjda.so is missing this module raises at import
 time, and if no HIP device is usable every detect call raises JdaError.
 """
+import collections
 import ctypes as C
 import os
 
@@ -21,6 +22,30 @@ JDA_DIALECT_C = 0
 JDA_DIALECT_CPP = 1
 # include/jda.h: JDA_FINISH_*, the finishing forms a pass can take, in the order of jdaFinishForms' counts
 FINISH_FORMS = ("WIDE_CONC", "WIDE_SEQ", "MERGED", "FILTER0", "MID_DIRECT", "TWO_LAUNCH", "DENSE")
+# include/jda.h: the fields of a scan form's key in the order of JDA_SCAN_FORM, each with its values in index order
+SCAN_FORM_FIELDS = (("kernel", ("k_scan", "k_scan_p")), ("dialect", ("C", "CPP")), ("depth", (4, 6, 0)),
+                    ("pix", ("T16_256", "T16_512", "T21", "GLB")), ("ragged", (False, True)), ("lean", (False, True)),
+                    ("trace", (False, True)), ("merged", (False, True)))
+SCAN_FORM_N = 768
+
+
+class ScanForm(collections.namedtuple("ScanForm", [f for f, _ in SCAN_FORM_FIELDS])):
+    """The key of one scan instantiation (include/jda.h: JDA_SCAN_FORM); depth 0 = the generic walk."""
+    __slots__ = ()
+
+    def index(self):
+        i = 0
+        for (_, values), v in zip(SCAN_FORM_FIELDS, self):
+            i = i * len(values) + values.index(v)
+        return i
+
+    @classmethod
+    def of_index(cls, i):
+        out = []
+        for _, values in reversed(SCAN_FORM_FIELDS):
+            out.append(values[i % len(values)])
+            i //= len(values)
+        return cls(*reversed(out))
 
 
 class JdaError(RuntimeError):
@@ -210,6 +235,7 @@ def _load():
     lib.jdaGetOption.restype = C.c_longlong
     lib.jdaGetOption.argtypes = [C.c_void_p, C.c_char_p]
     lib.jdaFinishForms.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+    lib.jdaScanForms.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.jdaCountWindows.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                     C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     lib.jdaDetectOptionsInit.restype = None
@@ -1204,6 +1230,15 @@ class Cascador:
         if lib.jdaFinishForms(self.h, counts) != 0:
             raise JdaError(last_error())
         return dict(zip(FINISH_FORMS, (int(x) for x in counts)))
+
+    def scan_forms(self):
+        """jdaScanForms: how often this cascador's passes have launched each stage-0 scan instantiation since it was
+        created -> {ScanForm(kernel, dialect, depth, pix, ragged, lean, trace, merged): count}, zeros left out.  The
+        counts only grow; take the difference around a call."""
+        counts = (C.c_longlong * SCAN_FORM_N)()
+        if lib.jdaScanForms(self.h, counts) != 0:
+            raise JdaError(last_error())
+        return {ScanForm.of_index(i): int(x) for i, x in enumerate(counts) if x}
 
     def serialize(self, path):
         lib.jdaCascadorSerializeTo(self.h, os.fsencode(path))

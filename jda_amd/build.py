@@ -110,7 +110,9 @@ def build_watchdog(force=False):
     os.makedirs(objdir, exist_ok=True)
     obj = os.path.join(objdir, "k_scan_p_hip.o")
     main_objs = [os.path.join(OBJDIR, s.replace(".", "_") + ".o") for s in SOURCES]
-    newest = max([os.path.getmtime(o) for o in main_objs] + [os.path.getmtime(src), _deps_mtime()])
+    # (a tree that carries its libraries but not its object files -- a packaged copy -- keeps a library that is newer
+    # than every source)
+    newest = max([os.path.getmtime(o) for o in main_objs if os.path.exists(o)] + [os.path.getmtime(src), _deps_mtime()])
     if not force and os.path.exists(WD_LIB) and os.path.getmtime(WD_LIB) >= newest:
         return WD_LIB
     subprocess.check_call([hipcc()] + CFLAGS + ["-DJDA_SCAN_P_IDLE_MAX=0", "-c", src, "-o", obj])

@@ -214,6 +214,13 @@ int jdaFinishForms(void* cascador, long long counts[JDA_FINISH_FORM_N]) try {
   return 0;
 } JDA_ABI_CATCH(-1)
 
+int jdaScanForms(void* cascador, long long counts[JDA_SCAN_FORM_N]) try {
+  Cascador* c = (Cascador*)cascador;
+  if (!c || !counts) { fail("jdaScanForms: null cascador or counts"); return -1; }
+  for (int f = 0; f < JDA_SCAN_FORM_N; f++) counts[f] = c->scan_forms[f].load(std::memory_order_relaxed);
+  return 0;
+} JDA_ABI_CATCH(-1)
+
 int jdaCountWindows(int width, int height, float scale, int min_size, int max_size,
                     long long* n_windows, int* n_levels) try {
   ScanPlan sp; std::string err;

@@ -512,6 +512,8 @@ struct Cascador {
   bool last_dense = false;
   // finishing forms the passes of this cascador have issued (jdaFinishForms): counted where the launches are issued
   std::atomic<long long> finish_forms[JDA_FINISH_FORM_N] = {};
+  // scan launches the passes of this cascador have issued, by what they instantiate (jdaScanForms, JDA_SCAN_FORM)
+  std::atomic<long long> scan_forms[JDA_SCAN_FORM_N] = {};
   int similarity = 0;          // dialect CPP: Config::with_similarity_transform (reference common.cpp:214)
   int device = -1;
   int n_cus = 256;             // compute units of the device

@@ -608,16 +608,17 @@ hipError_t launch_scan_mode(const DevPlan* d_plan, const DevPlan& h_plan, const 
                        pix_bytes, handoff, chunk, cp_max, opts, ranged ? (lv_lo | (lv_hi << 8)) : 0);
   };
   // (opts bit 1: no cart of [0, handoff) normalises -- the lean instantiation, passes without trace only)
+  const int depth = scan_depth_class(m.D);
   if constexpr (!TRACE) {
-    if (opts & 2) {
-      if (m.D == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK, false, false>);
-      else if (m.D == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK, false, false>);
+    if (scan_lean_form(opts, TRACE)) {
+      if (depth == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK, false, false>);
+      else if (depth == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK, false, false>);
       else go(k_scan<Real, 0, TRACE, MODE, BLOCK, false, false>);
       return hipGetLastError();
     }
   }
-  if (m.D == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK>);
-  else if (m.D == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK>);
+  if (depth == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK>);
+  else if (depth == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK>);
   else go(k_scan<Real, 0, TRACE, MODE, BLOCK>);
   return hipGetLastError();
 }
@@ -628,13 +629,10 @@ template <typename Real>
 hipError_t launch_scan(int mode, int level, bool trace, int handoff, int cp_max, int opts, const DevPlan* d_plan,
                        const DevPlan& h_plan, const DevModelT<Real>& m, const S0Node* table,
                        const WorkT<Real>& w, hipStream_t stream, int lv_lo, int lv_hi) {
-  if (w.n_frames == 0) return hipSuccess;
-  if (level >= 0 && h_plan.lv[level].tiled != mode) return hipSuccess;
+  if (!scan_covers_tiles(h_plan, w.n_frames, mode, level, lv_lo, lv_hi)) return hipSuccess;     // (kernels.h: no frame, or no tile of the mode)
   // 512-thread workgroups where a level's tiles hold more than 256 windows (one window per lane in
   // phase 0, twice the waves per LDS byte); a merged launch when any of its levels does
-  bool big = false;
-  for (int i = 0; i < h_plan.n_levels && mode == 1; i++)
-    if (h_plan.lv[i].tiled == 1 && (level < 0 ? (i >= lv_lo && i < lv_hi) : i == level)) big = big || h_plan.lv[i].tw * h_plan.lv[i].th > 256;
+  const bool big = scan_block_big(h_plan, mode, level, lv_lo, lv_hi);     // (kernels.h: the record of the form asks there too)
   auto pick = [&](auto trace_tag) {
     constexpr bool TR = decltype(trace_tag)::value;
     switch (mode) {
@@ -664,16 +662,17 @@ hipError_t launch_scan_ragged_mode(const DevPlan* d_plan, const DevModelT<Real>&
     hipLaunchKernelGGL(kern, dim3((unsigned)blk_n), dim3(BLOCK), L.total, stream, d_plan, m, table, w, -1, 0,
                        pix_bytes, handoff, chunk, cp_max, opts, blk_base);
   };
+  const int depth = scan_depth_class(m.D);
   if constexpr (!TRACE) {
-    if (opts & 2) {
-      if (m.D == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK, true, false>);
-      else if (m.D == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK, true, false>);
+    if (scan_lean_form(opts, TRACE)) {
+      if (depth == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK, true, false>);
+      else if (depth == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK, true, false>);
       else go(k_scan<Real, 0, TRACE, MODE, BLOCK, true, false>);
       return hipGetLastError();
     }
   }
-  if (m.D == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK, true>);
-  else if (m.D == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK, true>);
+  if (depth == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK, true>);
+  else if (depth == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK, true>);
   else go(k_scan<Real, 0, TRACE, MODE, BLOCK, true>);
   return hipGetLastError();
 }

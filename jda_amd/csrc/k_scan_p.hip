@@ -711,13 +711,14 @@ hipError_t launch_scan_persistent(int level, const PScanCfg& cfg, int block, int
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)block), L.total, stream, d_plan, m, table, w, level, cfg,
                        total_blocks, ragged ? rag_blk_base : 0);
   };
+  const int depth = scan_depth_class(m.D);
   if (ragged) {
-    if (m.D == 4) go(k_scan_p<4, true>);
-    else if (m.D == 6) go(k_scan_p<6, true>);
+    if (depth == 4) go(k_scan_p<4, true>);
+    else if (depth == 6) go(k_scan_p<6, true>);
     else go(k_scan_p<0, true>);
   } else {
-    if (m.D == 4) go(k_scan_p<4, false>);
-    else if (m.D == 6) go(k_scan_p<6, false>);
+    if (depth == 4) go(k_scan_p<4, false>);
+    else if (depth == 6) go(k_scan_p<6, false>);
     else go(k_scan_p<0, false>);
   }
   return hipGetLastError();

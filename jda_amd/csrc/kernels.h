@@ -284,6 +284,33 @@ hipError_t launch_scan(int mode, int level, bool trace, int handoff, int cp_max,
                        const WorkT<Real>& w, hipStream_t stream, int lv_lo = 0, int lv_hi = kMaxLevels);
 // (level < 0: ONE launch for every level of pixel mode `mode` among levels [lv_lo, lv_hi))
 
+// What a scan launch instantiates, decided here once: the launchers (k_scan_impl.h, k_scan_p.hip) and the record of
+// the form that ran (Pass::count_scan, jdaScanForms) both ask these.
+// DEPTH: the tree depths with a kernel of their own, 0 = the generic walk.
+inline int scan_depth_class(int D) { return D == 4 ? 4 : (D == 6 ? 6 : 0); }
+// 512-thread workgroups where a level's tiles hold more than 256 windows (one window per lane in phase 0, twice the
+// waves per LDS byte); a merged launch when any of its levels does.  Pixel mode 1 only.
+inline bool scan_block_big(const DevPlan& h_plan, int mode, int level, int lv_lo, int lv_hi) {
+  bool big = false;
+  for (int i = 0; i < h_plan.n_levels && mode == 1; i++)
+    if (h_plan.lv[i].tiled == 1 && (level < 0 ? (i >= lv_lo && i < lv_hi) : i == level)) big = big || h_plan.lv[i].tw * h_plan.lv[i].th > 256;
+  return big;
+}
+// Does launch_scan with these arguments launch a kernel -- are there frames, and does any level of the mode in the
+// range have a tile?  launch_scan returns at once where not, and the record of the form counts nothing: both ask here.
+inline bool scan_covers_tiles(const DevPlan& h_plan, int n_frames, int mode, int level, int lv_lo, int lv_hi) {
+  if (n_frames == 0) return false;
+  for (int i = 0; i < h_plan.n_levels; i++)
+    if (h_plan.lv[i].tiled == mode && (level < 0 ? (i >= lv_lo && i < lv_hi) : i == level) && h_plan.lv[i].tiles_x * h_plan.lv[i].tiles_y > 0) return true;
+  return false;
+}
+// NORM = false, the lean instantiation: opts bit 1 (no cart of [0, handoff) normalises), passes without trace only.
+inline bool scan_lean_form(int opts, bool trace) { return !trace && (opts & 2) != 0; }
+// Threads per workgroup of a persistent launch (the scan_p_block option, whole waves within 64..1,024).
+inline int scan_p_block_of(long long knob) { return (int)std::max<long long>(64, std::min<long long>(1024, knob)) & ~63; }
+// The JDA_SCAN_T* value (include/jda.h) of a pixel mode (DevLevel::tiled) and workgroup size.
+inline int scan_pix_form(int mode, int block) { return mode == 2 ? 3 : (mode == 3 ? 2 : (block >= 512 ? 1 : 0)); }
+
 // The same for a ragged batch: one launch over blocks [blk_base, blk_base + blk_n) of WorkT::blk, all of pixel mode
 // `mode` with workgroups of `block` threads and pixel tiles of at most pix_bytes.
 template <typename Real>

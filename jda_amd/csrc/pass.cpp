@@ -24,7 +24,7 @@ int scan_p_base_cfg(const Cascador* c, PScanCfg* cfg, int* block, int* wgs) {
   cfg->bound[cfg->nb] = K;
   cfg->bound_last = K;
   cfg->any_norm = stage0_any_norm(c->hm, K, true) ? 1 : 0;
-  *block = (int)std::max<long long>(64, std::min<long long>(1024, kn.scan_p_block)) & ~63;
+  *block = scan_p_block_of(kn.scan_p_block);
   *wgs = (int)std::max<long long>(1, std::min<long long>(8, kn.scan_p_wgs));
   cfg->ring_cap[0] = (int)std::max<long long>(64, std::min<long long>(4096, kn.scan_p_ring));
   scan_p_ring_caps(cfg, *block / 64);
@@ -218,6 +218,7 @@ template <typename Real> bool Pass<Real>::scan_persistent(int level, hipStream_t
                             : launch_scan_persistent(level, cfg, block, grid, pe->dp, pe->hp, m, pe->table, w, s);
     if (e == hipErrorInvalidValue) { (void)hipGetLastError(); return false; }
     if (e != hipSuccess) { fail(std::string("launch_scan_persistent failed: ") + hipGetErrorString(e)); return false; }
+    count_scan(JDA_SCAN_K_SCAN_P, 1, block, rl != nullptr, !cfg.any_norm, false);
     if (cfg.to_mid) at.mid_direct = true;
     at.p_launches++;
     return true;
@@ -279,6 +280,7 @@ template <typename Real> bool Pass<Real>::issue_scan() {
     auto scan = [&](int mode, int level, hipStream_t s) -> bool {
       if (mode == 1 && level >= 0 && scan_persistent(level, s)) { rs->scan_launches++; at.my_scan_launches++; return true; }
       JDA_HIP(launch_scan<Real>(mode, level, want_trace(), sa.handoff, sa.cp_max, sa.opts, pe->dp, pe->hp, m, pe->table, w, s));
+      count_k_scan(mode, level);
       rs->scan_launches++; at.my_scan_launches++;
       return true;
     };
@@ -347,6 +349,7 @@ template <typename Real> bool Pass<Real>::issue_scan() {
           const int lead = rev ? run_last[l] : run_first[l];
           if (l == lead) {
             JDA_HIP(launch_scan<Real>(1, -1, false, sa.handoff, sa.cp_max, sa.opts, pe->dp, pe->hp, m, pe->table, w, st, run_first[l], run_last[l] + 1));
+            count_k_scan(1, -1, run_first[l], run_last[l] + 1);
             rs->scan_launches++; at.my_scan_launches++;
             if (fork_in > 0 && --fork_in == 0) { if (!fork_glb()) return false; fork_in = -1; }
           }
@@ -432,6 +435,7 @@ template <typename Real> bool Pass<Real>::issue_scan_ragged() {
     if (try_persistent && l.mode == 1 && l.level >= 0 && scan_persistent(l.level, s, &l)) { rs->scan_launches++; at.my_scan_launches++; return true; }
     JDA_HIP(launch_scan_ragged<Real>(l.mode, l.block, false, sa.handoff, sa.cp_max, sa.opts, pe->dp, m, pe->table, w, l.pix_bytes,
                                      l.blk_base, l.blk_n, s));
+    if (l.blk_n > 0) count_scan(JDA_SCAN_K_SCAN, l.mode, l.block, true, scan_lean_form(sa.opts, false), l.level < 0);   // (blk_n <= 0: the launcher launches nothing)
     rs->scan_launches++; at.my_scan_launches++;
     return true;
   };

@@ -119,6 +119,22 @@ struct Pass {
   long long windows() const { return rag ? rag->windows : (long long)nf * pe->sp.windows; }
   // the finishing form this pass is about to issue, for jdaFinishForms (a pass that is issued again counts again)
   void count_form(int form) { c->finish_forms[form].fetch_add(1, std::memory_order_relaxed); }
+  // the scan launch this pass is about to issue, for jdaScanForms, under the key of what the launcher instantiates: the
+  // same functions (kernels.h) and the same arguments the launchers take.  mode, block: DevLevel::tiled and the
+  // workgroup size; lean: NORM = false (k_scan) / PScanCfg::any_norm == 0 (k_scan_p); merged: the launch spans levels.
+  void count_scan(int kernel, int mode, int block, bool ragged, bool lean, bool merged) {
+    const int depth = scan_depth_class(model().D);
+    const int form = JDA_SCAN_FORM(kernel, sizeof(Real) == 4 ? JDA_DIALECT_C : JDA_DIALECT_CPP,
+                                   depth == 4 ? JDA_SCAN_DEPTH_4 : (depth == 6 ? JDA_SCAN_DEPTH_6 : JDA_SCAN_DEPTH_GENERIC),
+                                   scan_pix_form(mode, block), ragged ? 1 : 0, lean ? 1 : 0, want_trace() ? 1 : 0, merged ? 1 : 0);
+    c->scan_forms[form].fetch_add(1, std::memory_order_relaxed);
+  }
+  // ... a k_scan launch of a uniform pass (launch_scan's arguments)
+  void count_k_scan(int mode, int level, int lv_lo = 0, int lv_hi = kMaxLevels) {
+    if (!scan_covers_tiles(pe->hp, w.n_frames, mode, level, lv_lo, lv_hi)) return;     // (launch_scan launches nothing then)
+    count_scan(JDA_SCAN_K_SCAN, mode, scan_block_big(pe->hp, mode, level, lv_lo, lv_hi) ? 512 : 256, false,
+               scan_lean_form(sa.opts, want_trace()), level < 0);
+  }
 
   bool dense_ok(int* pix_cap, int* lds_max) const;
   bool run_dense();

@@ -44,6 +44,28 @@ def test_finish_forms_entry_and_its_python_mirror(built, model_file):
     c.close()
 
 
+def test_scan_forms_entry_and_its_python_mirror(built, model_file):
+    """jdaScanForms (include/jda.h): exported, JDA_SCAN_FORM_N counts indexed by JDA_SCAN_FORM, which the Python mirror
+    (api.ScanForm.index) restates field for field; all zero on a cascador that has run nothing; null arguments refused."""
+    from jda_amd import api
+    assert "jdaScanForms" in declared_symbols()
+    src = open(HEADER).read()
+    assert int(re.search(r"#define JDA_SCAN_FORM_N (\d+)", src).group(1)) == api.SCAN_FORM_N
+    args = re.search(r"#define JDA_SCAN_FORM\(([^)]*)\)", src).group(1).replace(" ", "").split(",")
+    assert tuple(args) == tuple(f for f, _ in api.SCAN_FORM_FIELDS) == api.ScanForm._fields
+    for field, values, enum in (("kernel", ("k_scan", "k_scan_p"), ("JDA_SCAN_K_SCAN", "JDA_SCAN_K_SCAN_P")),
+                                ("depth", (4, 6, 0), ("JDA_SCAN_DEPTH_4", "JDA_SCAN_DEPTH_6", "JDA_SCAN_DEPTH_GENERIC")),
+                                ("pix", ("T16_256", "T16_512", "T21", "GLB"), ("JDA_SCAN_T16_256", "JDA_SCAN_T16_512", "JDA_SCAN_T21", "JDA_SCAN_GLB"))):
+        assert dict(api.SCAN_FORM_FIELDS)[field] == values
+        for i, e in enumerate(enum):
+            assert int(re.search(r"\b%s = (\d+)" % e, src).group(1)) == i, e
+    p, _ = model_file((2, 8, 5, 3), 8, seed=1)
+    c = api.Cascador(p)
+    assert c.scan_forms() == {}
+    assert api.lib.jdaScanForms(c.h, None) == -1 and api.lib.jdaScanForms(None, (C.c_longlong * api.SCAN_FORM_N)()) == -1
+    c.close()
+
+
 def test_header_is_plain_c_and_links(built, tmp_path):
     """What a maintainer of the reference would do: compile a C caller against
     include/jda.h and link libjda.so (no torch, no C++)."""

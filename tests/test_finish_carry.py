@@ -179,11 +179,14 @@ def test_entries_from_the_persistent_scan_mix_with_carried_ones(built, gpu, mode
     c1 = _cascador(p, env=env)
     assert c1.get_option("scan_p_mid") == 1 and c1.get_option("fin_carry") == 1
     for rep in range(2):                                   # (the second pass sizes its launches from the first)
-        before = c1.finish_forms()
+        before, scans_before = c1.finish_forms(), c1.scan_forms()
         got, st1 = c1.detect_batch_device(d, stats=True)
         forms = {k: v - before[k] for k, v in c1.finish_forms().items() if v != before[k]}
-        print("pass", rep, "forms:", forms)
+        scans = {k: v - scans_before.get(k, 0) for k, v in c1.scan_forms().items() if v != scans_before.get(k, 0)}
+        print("pass", rep, "forms:", forms, scans)
         assert forms and set(forms) == {"MID_DIRECT"}, forms       # k_filter0 + k_finish(survivors) fed from k_scan_p's mid queue
+        # ... and the scan that filled it was k_scan_p (jdaScanForms), next to k_scan's global-pixel launch
+        assert any(k.kernel == "k_scan_p" and k.depth == 4 and not k.ragged for k in scans) and any(k.pix == "GLB" for k in scans), scans
         _same_dets(want, got)
         for k in ("cart_total_n", "face_patch_n", "stage_done_n", "patch_n"):
             assert st0[k] == st1[k], (rep, k)

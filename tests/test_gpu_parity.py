@@ -730,6 +730,12 @@ def test_very_wide_frame_stage0_offsets_beyond_21_bits(built, gpu, model_file):
     _compare_trace(c, o, wide, scale=1.1, min_size=80)
     d = c.detect_batch(wide, scale=1.1, min_size=80, th=0.0)[0]
     _compare_detect(d, o.detect(wide[0], scale=1.1, min_size=80, th=0.0))
+    # jdaScanForms: the scan launches were the LDS-tiled ones the plan names, traced and not, and no global-pixel one
+    assert not any(lv["mode"] == 2 for lv in levels), levels
+    want_pix = {"T21" if lv["mode"] == 3 else "T16" for lv in levels if lv["mode"] in (1, 3)}
+    forms = c.scan_forms()
+    assert forms and all(k.kernel == "k_scan" and k.pix != "GLB" for k in forms), forms
+    assert {k.pix[:3] for k in forms} == want_pix and {k.trace for k in forms} == {False, True}, (forms, levels)
 
 
 def test_batch_larger_than_workspace_is_processed_in_passes(built, gpu, model_file, monkeypatch):

@@ -176,7 +176,9 @@ def test_ragged_chunks_through_the_persistent_scan(built, gpu, model_file, monke
     block map, the level's tile re-cut per image, the image's own window grid travelling with the slot): same results,
     bit for bit, as with the closed-tile k_scan and as jdaDetect image by image -- 300 images of mixed sizes (some with
     fewer levels than others, one too small for any window) in several chunks, scan_p = 2 so that every level it fits
-    takes the persistent form."""
+    takes the persistent form, and merge_blocks = 0: chunks this small otherwise share ONE merged launch for all their
+    LDS-tiled levels, which the persistent kernel never takes (jdaScanForms showed that this test launched no k_scan_p
+    before it set that option).  The counts of both cascadors say what was launched."""
     from jda_amd import api, synth
     p, _ = model_file(dims, 8, seed=3, cart_th=th, norm_every=5)
     rng = np.random.default_rng(9)
@@ -186,7 +188,7 @@ def test_ragged_chunks_through_the_persistent_scan(built, gpu, model_file, monke
         w, h = int(rng.integers(60, 361)), int(rng.integers(50, 301))
         imgs.append(np.ascontiguousarray(base[i % 8][:h, :w]))
     imgs[17] = np.ascontiguousarray(base[0][:20, :30])
-    monkeypatch.setenv("JDA_SCAN_P", "2")
+    monkeypatch.setenv("JDA_SCAN_P", "2"); monkeypatch.setenv("JDA_MERGE_BLOCKS", "0")
     monkeypatch.setenv("JDA_RAGGED_CHUNK_WINDOWS", "700000"); monkeypatch.setenv("JDA_RAGGED_CHUNK_MIN_WINDOWS", "100000")
     on = api.Cascador(p)
     monkeypatch.setenv("JDA_SCAN_P_RAGGED", "0")
@@ -194,6 +196,13 @@ def test_ragged_chunks_through_the_persistent_scan(built, gpu, model_file, monke
     assert on.get_option("scan_p_ragged") == 1 and off.get_option("scan_p_ragged") == 0
     (a, sa), (b, sb) = on.detect_ragged(imgs, stats=True), off.detect_ragged(imgs, stats=True)
     assert len(a) == len(b) == 300
+    fa, fb = on.scan_forms(), off.scan_forms()
+    print("scan forms with the ragged persistent scan:", fa, "without:", fb)
+    depth = dims[3] if dims[3] in (4, 6) else 0
+    persistent = {k: v for k, v in fa.items() if k.kernel == "k_scan_p"}
+    assert persistent and all(k.ragged and k.dialect == "C" and k.depth == depth and not k.merged and not k.trace for k in persistent), fa
+    assert fb and all(k.kernel == "k_scan" for k in fb), fb
+    assert sa["scan_fallbacks"] == 0
     for i in range(300):
         _eq(a[i], b[i], i)
     for k in ("patch_n", "face_patch_n", "cart_gothrough_n", "cart_total_n", "handoff_n", "scan_cart_n", "scan_patch_n"):

@@ -56,8 +56,21 @@ def _run(path, frames_dev, env, th):
         os.environ.clear(); os.environ.update(old)
     out1, st1 = c.detect_batch_device(frames_dev, th=th, stats=True)
     out2, st2 = c.detect_batch_device(frames_dev, th=th, stats=True)      # second pass: finishing launches sized by prediction
+    st2["scan_forms"] = c.scan_forms()          # (jdaScanForms: what the two passes launched)
     c.close()
     return out1, st1, out2, st2
+
+
+def _persistent(st):
+    """-> the k_scan_p launches among a cascador's scan forms; all of them must be what a uniform pass can launch."""
+    p = {k: v for k, v in st["scan_forms"].items() if k.kernel == "k_scan_p"}
+    assert all(k.dialect == "C" and not k.ragged and not k.trace and not k.merged for k in p), p
+    return p
+
+
+def api_form(*a):
+    from jda_amd import api
+    return api.ScanForm(*a)
 
 
 def _same_dets(a, b):
@@ -68,7 +81,8 @@ def _check(path, frames, th, variants, oracle_frames=0):
     import torch
     dev = torch.from_numpy(frames).cuda()
     base = {"JDA_MERGE_BLOCKS": "0"}          # a launch per level, so that k_scan_p gets every LDS-tiled level it fits
-    ref, st, _, _ = _run(path, dev, dict(base, JDA_SCAN_P="0"), th)
+    ref, st, _, st_ = _run(path, dev, dict(base, JDA_SCAN_P="0"), th)
+    assert not _persistent(st_) and st_["scan_forms"]
     if oracle_frames:
         from oracle.pyoracle import Oracle
         o = Oracle(path)
@@ -83,6 +97,10 @@ def _check(path, frames, th, variants, oracle_frames=0):
                 continue
             assert st[k] == s1[k] == s2[k], (v, k, st[k], s1[k], s2[k])
         assert s1["scan_launches"] > 0
+        # k_scan_p ran, in the workgroup size the variant asks for (768 threads by default: T16_512)
+        p = _persistent(s2)
+        block = int(v.get("JDA_SCAN_P_BLOCK", "768"))
+        assert p and {k.pix for k in p} == {"T16_512" if block >= 512 else "T16_256"}, (v, s2["scan_forms"])
 
 
 @pytest.mark.parametrize("dims,cart_th,size,n", [
@@ -116,9 +134,10 @@ def test_persistent_scan_is_what_a_large_batch_runs_by_default(built, gpu, model
     calib = synth.make_frames(8, 640, 480, seed=0, first=10_000_000)
     mp = bench.model_path(S_DIMS, "cascade", 1, calib)
     dev = torch.from_numpy(synth.make_frames(64, 640, 480, seed=0)).cuda()
-    ref, st, _, _ = _run(mp, dev, {"JDA_SCAN_P": "0"}, 0.0)
+    ref, st, _, st_ = _run(mp, dev, {"JDA_SCAN_P": "0"}, 0.0)
     got, s1, got2, s2 = _run(mp, dev, {}, 0.0)
     assert _same_dets(ref, got) and _same_dets(ref, got2)
+    assert not _persistent(st_) and set(_persistent(s2)) == {api_form("k_scan_p", "C", 4, "T16_512", False, True, False, False)}, s2["scan_forms"]
     for k in STAT_KEYS:
         assert st[k] == s1[k] == s2[k], (k, st[k], s1[k], s2[k])
 
