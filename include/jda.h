@@ -210,6 +210,35 @@ enum { JDA_SCAN_T16_256 = 0, JDA_SCAN_T16_512 = 1, JDA_SCAN_T21 = 2, JDA_SCAN_GL
  * pass that is issued again (jdaStats ws_regrows / scan_fallbacks) counts its launches again.  Returns 0, or -1 for a null argument. */
 JDA_API int jdaScanForms(void *cascador, long long counts[JDA_SCAN_FORM_N]);
 
+/* Which k_finish and k_filter0 launches the passes of a cascador issued.  The forms MERGED,
+ * FILTER0, MID_DIRECT and TWO_LAUNCH above are made of launches of these two kernels; every launch counts once under
+ * the full key of what it instantiates and how it was set up:
+ *   kernel     JDA_FINISH_K_FINISH or JDA_FINISH_K_FILTER0
+ *   dialect    JDA_DIALECT_C (fp32) or JDA_DIALECT_CPP (fp64)
+ *   trace      1: the pass records carts, score, leaf hash and shape per window
+ *   groups     k_finish: the 64-cart groups a round walks, 1..4 (from K, or 1 for stage 0 of TWO_LAUNCH); k_filter0: 0
+ *   multi      1: a multi-scale model, the nodes read the half and quarter images (no window tile)
+ *   st         1: dialect CPP under the similarity transform
+ *   stream     1: the weight rows are read with non-temporal loads (w_stream_mb; the form without trace, multi and st only)
+ *   survivors  1: k_finish on the mid queue as k_filter0 (or the persistent scan) left it
+ *   carry      1: the launch writes (k_filter0) or reads (k_finish on survivors) the stage-0 leaves carried in the mid queue
+ *   tile       1: windows up to jdaFinishTileWin pixels walk from an LDS copy of their pixels
+ * at counts[JDA_FINISH_LAUNCH(kernel, dialect, trace, groups, multi, st, stream, survivors, carry, tile)].  The fields that
+ * do not apply to k_filter0 are 0 in its keys. */
+enum { JDA_FINISH_K_FINISH = 0, JDA_FINISH_K_FILTER0 = 1 };
+#define JDA_FINISH_LAUNCH(kernel, dialect, trace, groups, multi, st, stream, survivors, carry, tile) \
+  ((((((((((kernel) * 2 + (dialect)) * 2 + (trace)) * 5 + (groups)) * 2 + (multi)) * 2 + (st)) * 2 + (stream)) * 2 + (survivors)) * 2 + (carry)) * 2 + (tile))
+#define JDA_FINISH_LAUNCH_N 2560
+/* counts[i]: how often the passes of this cascador have issued launch i since it was created: one count per launch
+ * (TWO_LAUNCH adds two k_finish, FILTER0 and MID_DIRECT one k_filter0 and one k_finish).  Cumulative, added atomically on
+ * the host where the launches are issued; take the difference around a call, as with jdaFinishForms.  A pass that is issued
+ * again (jdaStats ws_regrows / scan_fallbacks) counts its launches again.  Returns 0, or -1 for a null argument. */
+JDA_API int jdaFinishLaunches(void *cascador, long long counts[JDA_FINISH_LAUNCH_N]);
+/* The largest window side, in pixels, that k_finish copies to LDS with this cascador's model in `dialect` (as the
+ * similarity transform stands): windows up to it walk from the copy, larger ones read the frame.  0: no window does (the
+ * model's state leaves no room, or it is multi-scale).  -1: a null cascador or an unknown dialect. */
+JDA_API int jdaFinishTileWin(void *cascador, int dialect);
+
 /* Window enumeration of reference c/jda.c:320-339 without running anything:
  * number of candidate windows and pyramid levels for one frame. */
 JDA_API int jdaCountWindows(int width, int height, float scale, int min_size, int max_size,

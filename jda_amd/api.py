@@ -48,6 +48,32 @@ class ScanForm(collections.namedtuple("ScanForm", [f for f, _ in SCAN_FORM_FIELD
         return cls(*reversed(out))
 
 
+# include/jda.h: the fields of a finishing launch's key in the order of JDA_FINISH_LAUNCH, each with its values in index order
+FINISH_LAUNCH_FIELDS = (("kernel", ("k_finish", "k_filter0")), ("dialect", ("C", "CPP")), ("trace", (False, True)),
+                        ("groups", (0, 1, 2, 3, 4)), ("multi", (False, True)), ("st", (False, True)), ("stream", (False, True)),
+                        ("survivors", (False, True)), ("carry", (False, True)), ("tile", (False, True)))
+FINISH_LAUNCH_N = 2560
+
+
+class FinishLaunch(collections.namedtuple("FinishLaunch", [f for f, _ in FINISH_LAUNCH_FIELDS])):
+    """The key of one k_finish / k_filter0 launch (include/jda.h: JDA_FINISH_LAUNCH); groups 0 = k_filter0."""
+    __slots__ = ()
+
+    def index(self):
+        i = 0
+        for (_, values), v in zip(FINISH_LAUNCH_FIELDS, self):
+            i = i * len(values) + values.index(v)
+        return i
+
+    @classmethod
+    def of_index(cls, i):
+        out = []
+        for _, values in reversed(FINISH_LAUNCH_FIELDS):
+            out.append(values[i % len(values)])
+            i //= len(values)
+        return cls(*reversed(out))
+
+
 class JdaError(RuntimeError):
     pass
 
@@ -236,6 +262,8 @@ def _load():
     lib.jdaGetOption.argtypes = [C.c_void_p, C.c_char_p]
     lib.jdaFinishForms.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.jdaScanForms.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+    lib.jdaFinishLaunches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+    lib.jdaFinishTileWin.argtypes = [C.c_void_p, C.c_int]
     lib.jdaCountWindows.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                     C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     lib.jdaDetectOptionsInit.restype = None
@@ -1239,6 +1267,23 @@ class Cascador:
         if lib.jdaScanForms(self.h, counts) != 0:
             raise JdaError(last_error())
         return {ScanForm.of_index(i): int(x) for i, x in enumerate(counts) if x}
+
+    def finish_launches(self):
+        """jdaFinishLaunches: how often this cascador's passes have launched each k_finish / k_filter0 instantiation since it
+        was created -> {FinishLaunch(kernel, dialect, trace, groups, multi, st, stream, survivors, carry, tile): count},
+        zeros left out.  One count per launch; the counts only grow; take the difference around a call."""
+        counts = (C.c_longlong * FINISH_LAUNCH_N)()
+        if lib.jdaFinishLaunches(self.h, counts) != 0:
+            raise JdaError(last_error())
+        return {FinishLaunch.of_index(i): int(x) for i, x in enumerate(counts) if x}
+
+    def finish_tile_win(self, dialect):
+        """jdaFinishTileWin: the largest window side k_finish copies to LDS with this model in `dialect` ("C" / "CPP", or
+        JDA_DIALECT_*); 0: none."""
+        r = int(lib.jdaFinishTileWin(self.h, {"C": JDA_DIALECT_C, "CPP": JDA_DIALECT_CPP}.get(dialect, dialect)))
+        if r < 0:
+            raise JdaError(last_error())
+        return r
 
     def serialize(self, path):
         lib.jdaCascadorSerializeTo(self.h, os.fsencode(path))

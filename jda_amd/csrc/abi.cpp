@@ -221,6 +221,23 @@ int jdaScanForms(void* cascador, long long counts[JDA_SCAN_FORM_N]) try {
   return 0;
 } JDA_ABI_CATCH(-1)
 
+int jdaFinishLaunches(void* cascador, long long counts[JDA_FINISH_LAUNCH_N]) try {
+  Cascador* c = (Cascador*)cascador;
+  if (!c || !counts) { fail("jdaFinishLaunches: null cascador or counts"); return -1; }
+  for (int f = 0; f < JDA_FINISH_LAUNCH_N; f++) counts[f] = c->finish_launches[f].load(std::memory_order_relaxed);
+  return 0;
+} JDA_ABI_CATCH(-1)
+
+int jdaFinishTileWin(void* cascador, int dialect) try {
+  Cascador* c = (Cascador*)cascador;
+  if (!c || (dialect != JDA_DIALECT_C && dialect != JDA_DIALECT_CPP)) { fail("jdaFinishTileWin: null cascador or unknown dialect"); return -1; }
+  std::lock_guard<std::mutex> lk(c->mu);             // (multi_scale() caches its answer in the model on first use)
+  const int real_bytes = dialect == JDA_DIALECT_C ? 4 : 8;
+  // (what launch_finish decides with fin_tile = -1: the same function on the same model -- dialect CPP's DevModelT::similarity
+  // is nonzero exactly where the cascador's is)
+  return finish_tile_win(c->hm.dim(), c->hm.K, real_bytes, finish_st(real_bytes, c->similarity), c->hm.multi_scale(), -1);
+} JDA_ABI_CATCH(-1)
+
 int jdaCountWindows(int width, int height, float scale, int min_size, int max_size,
                     long long* n_windows, int* n_levels) try {
   ScanPlan sp; std::string err;

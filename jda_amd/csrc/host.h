@@ -514,6 +514,8 @@ struct Cascador {
   std::atomic<long long> finish_forms[JDA_FINISH_FORM_N] = {};
   // scan launches the passes of this cascador have issued, by what they instantiate (jdaScanForms, JDA_SCAN_FORM)
   std::atomic<long long> scan_forms[JDA_SCAN_FORM_N] = {};
+  // k_finish / k_filter0 launches the passes of this cascador have issued, by what they instantiate (jdaFinishLaunches, JDA_FINISH_LAUNCH)
+  std::atomic<long long> finish_launches[JDA_FINISH_LAUNCH_N] = {};
   int similarity = 0;          // dialect CPP: Config::with_similarity_transform (reference common.cpp:214)
   int device = -1;
   int n_cus = 256;             // compute units of the device

@@ -467,31 +467,15 @@ hipError_t launch_finish_impl(bool trace, int t_begin, int t_end, bool apply_th,
                               const WorkT<typename DL::Real>& w, int groups, long long n_hint, const S0Node* s0_table,
                               int tile_win, bool survivors, hipStream_t stream) {
   using Real = typename DL::Real;
-  const int dim_pad = (m.dim + 1) & ~1;
-  const bool st = sizeof(Real) == 8 && m.similarity != 0;
+  // (every decision of this launch is a function of kernels.h, which the record of the launch asks too: Pass::count_finish)
+  const bool st = finish_st((int)sizeof(Real), m.similarity);
   const int multi = (w.half != nullptr) ? 1 : 0;
-  if (multi) tile_win = 0;
-  const size_t base = (size_t)dim_pad * sizeof(Real) + (size_t)((m.K + 3) & ~3) * 4 + kMaxStages * sizeof(int) +
-                      (st ? (2 * (size_t)dim_pad + 8) * sizeof(Real) : 0);
-  // tile_win < 0: the largest window tile that keeps 16 workgroups on a CU.  Measured on MI355X with one-wave
-  // workgroups (profiles/r02_finish_experiments.txt): up to 7,680 bytes of LDS per workgroup the launch time does
-  // not depend on the LDS size, 7,712 bytes cost +17 %, 7,856 +23 % (16 x 7.5 KB = 120 KB) -- the launch is bound
-  // by the texture addresser but still needs its 16 windows per CU.
-  if (tile_win < 0) {
-    tile_win = 0;
-    for (int tw = 16; tw <= 255; tw++)
-      if (base + (size_t)tw * ((tw + 3) & ~3) + 16 <= kFinishLdsPerGroup) tile_win = tw;
-  }
-  const size_t tile_bytes = tile_win > 0 ? (size_t)tile_win * ((tile_win + 3) & ~3) + 16 : 0;
-  const size_t lds = base + tile_bytes;
+  tile_win = finish_tile_win(m.dim, m.K, (int)sizeof(Real), st, multi != 0, tile_win);
+  const size_t lds = finish_lds_base(m.dim, m.K, (int)sizeof(Real), st) + finish_tile_bytes(tile_win);
   const float r = 1.f / sqrtf(2.f);
-  // n_hint >= 0: the queue length is known on the host -> one window per workgroup (up to
-  // 1M workgroups, grid-stride beyond), so the hardware dispatcher balances the very
-  // uneven per-window cost; n_hint < 0: fixed grid, windows dealt round-robin.
-  unsigned blocks = t_begin == 0 && !survivors ? w.cap_q : w.cap_m;
-  if (blocks > 256u * 64u) blocks = 256u * 64u;
-  if (n_hint >= 0) blocks = (unsigned)std::min<long long>(n_hint, 1 << 20);
+  const unsigned blocks = finish_grid(n_hint, t_begin == 0 && !survivors ? w.cap_q : w.cap_m);
   if (blocks == 0) return hipSuccess;
+  groups = finish_groups(groups);
   auto go = [&](auto kern) {
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, d_plan, m, w, multi, r, t_begin, t_end,
@@ -504,17 +488,17 @@ hipError_t launch_finish_impl(bool trace, int t_begin, int t_end, bool apply_th,
     constexpr bool STT = decltype(st_tag)::value && sizeof(Real) == 8;
     if constexpr (!TR && !MU && !STT) {
       // a stage's weight rows far larger than L2 (DevModelT::w_stream): the form that reads them with non-temporal loads
-      if (m.w_stream) {
-        if (groups >= 4) go(k_finish<DL, false, 4, false, false, true>);
+      if (finish_stream(TR, MU, STT, m.w_stream)) {
+        if (groups == 4) go(k_finish<DL, false, 4, false, false, true>);
         else if (groups == 3) go(k_finish<DL, false, 3, false, false, true>);
-        else if (groups >= 2) go(k_finish<DL, false, 2, false, false, true>);
+        else if (groups == 2) go(k_finish<DL, false, 2, false, false, true>);
         else go(k_finish<DL, false, 1, false, false, true>);
         return;
       }
     }
-    if (groups >= 4) go(k_finish<DL, TR, 4, MU, STT>);
+    if (groups == 4) go(k_finish<DL, TR, 4, MU, STT>);
     else if (groups == 3) go(k_finish<DL, TR, 3, MU, STT>);
-    else if (groups >= 2) go(k_finish<DL, TR, 2, MU, STT>);
+    else if (groups == 2) go(k_finish<DL, TR, 2, MU, STT>);
     else go(k_finish<DL, TR, 1, MU, STT>);
   };
   auto pick_m = [&](auto trace_tag, auto st_tag) {

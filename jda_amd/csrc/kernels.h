@@ -216,6 +216,12 @@ static_assert(round_trip(2, 64) && round_trip(4, 64) && round_trip(8, 64), "K = 
 static_assert(round_trip(2, 540) && round_trip(4, 540) && round_trip(8, 540), "K = 540: 27 bits with depth-4 trees");
 static_assert(round_trip(2, 682) && round_trip(4, 682) && !carry_fits(8, 682), "K = 682: 11 rounds, depth 4 needs 33 bits -- no carry");
 static_assert(!carry_fits(32, 2000) && carry_fits(2, 2048) && !carry_fits(2, 2049), "depth 6 with K = 2000 walks as before; 32 rounds of one bit fit");
+// the word's edge: bits * rounds == 32 puts the last round's leaf in the top bits (bit 31 included); one cart more does not fit
+static_assert(round_trip(4, 1024) && !carry_fits(4, 1025), "depth 3: 2 bits x 16 rounds = 32");
+static_assert(round_trip(16, 512) && !carry_fits(16, 513), "depth 5: 4 bits x 8 rounds = 32");
+static_assert(round_trip(256, 256) && !carry_fits(256, 257), "depth 9: 8 bits x 4 rounds = 32");
+static_assert(round_trip(8, 640) && !carry_fits(8, 641), "depth 4: 3 bits x 10 rounds = 30, an eleventh round would need 33");
+static_assert(carry_unpack(carry_pack(0u, 3, 2, 15), 2, 15) == 3 && carry_pack(0u, 3, 2, 15) == 0xc0000000u, "the top round of a full word keeps bit 31");
 }  // namespace carry_check
 
 // Work counters live in kCntShards copies, one 256-byte line apart, so that the
@@ -369,6 +375,43 @@ hipError_t launch_filter0(bool trace, const DevPlan* d_plan, const DevModelT<Rea
 // tile_win: windows up to this side copy their pixels to LDS first (0: every pixel is read from the frame,
 // < 0: the largest side that leaves the workgroup within kFinishLdsPerGroup)
 constexpr size_t kFinishLdsPerGroup = 7680;
+
+// What a k_finish launch instantiates and how much LDS it takes, decided here once: the launcher (k_finish.hip:
+// launch_finish_impl) and the record of the launch (Pass::count_finish, jdaFinishLaunches, jdaFinishTileWin) both ask these.
+// ST: the similarity transform exists in dialect CPP only.
+constexpr bool finish_st(int real_bytes, int similarity) { return real_bytes == 8 && similarity != 0; }
+// kG, the 64-cart groups a round walks: an instantiation each for 1..4.
+constexpr int finish_groups(int groups) { return groups >= 4 ? 4 : (groups == 3 ? 3 : (groups >= 2 ? 2 : 1)); }
+// STREAM (DevModelT::w_stream): only the form without trace, pyramid images and similarity transform has one.
+constexpr bool finish_stream(bool trace, bool multi, bool st, int w_stream) { return !trace && !multi && !st && w_stream != 0; }
+// LDS in front of the window tile: shape, the carts' weight rows, stage counters, the transform's scratch (ST).
+constexpr size_t finish_lds_base(int dim, int K, int real_bytes, bool st) {
+  const size_t dim_pad = (size_t)((dim + 1) & ~1);
+  return dim_pad * (size_t)real_bytes + (size_t)((K + 3) & ~3) * 4 + kMaxStages * sizeof(int) + (st ? (2 * dim_pad + 8) * (size_t)real_bytes : 0);
+}
+constexpr size_t finish_tile_bytes(int tile_win) { return tile_win > 0 ? (size_t)tile_win * (size_t)((tile_win + 3) & ~3) + 16 : 0; }
+// The window tile of a launch asked for `tile_win` (0: none, n: windows up to n pixels, < 0: the largest that keeps the
+// workgroup within kFinishLdsPerGroup -- 16 workgroups on a CU; measured on MI355X with one-wave workgroups,
+// profiles/r02_finish_experiments.txt: up to 7,680 bytes the launch time does not depend on the LDS size, 7,712 bytes
+// cost +17 %, 7,856 +23 %).  A multi-scale model has none: its nodes read the half and quarter images too.
+constexpr int finish_tile_win(int dim, int K, int real_bytes, bool st, bool multi, int tile_win) {
+  if (multi) return 0;
+  if (tile_win >= 0) return tile_win;
+  const size_t base = finish_lds_base(dim, K, real_bytes, st);
+  int best = 0;
+  for (int tw = 16; tw <= 255; tw++)
+    if (base + finish_tile_bytes(tw) <= kFinishLdsPerGroup) best = tw;
+  return best;
+}
+// Workgroups of a launch over a queue of capacity `cap` -- n_hint >= 0: the queue length is known on the host, one window
+// per workgroup (up to 1M workgroups, grid-stride beyond), so that the hardware dispatcher balances the very uneven
+// per-window cost; n_hint < 0: a fixed grid, windows dealt round-robin.  0: nothing is launched.
+inline unsigned finish_grid(long long n_hint, unsigned cap) {
+  if (n_hint >= 0) return (unsigned)(n_hint < (1 << 20) ? n_hint : (1 << 20));
+  return cap > 256u * 64u ? 256u * 64u : cap;
+}
+static_assert(finish_tile_win(54, 540, 4, false, false, -1) == 72 && finish_tile_win(54, 540, 4, false, true, -1) == 0, "the shipped model's tile (DESIGN.md section 4)");
+static_assert(finish_tile_win(10, 1808, 4, false, false, -1) == 16 && finish_tile_win(10, 1828, 4, false, false, -1) == 0, "the search starts at 16 pixels");
 
 // The finishing path of small jobs: one WORKGROUP per queued window (k_wide.hip), every remaining cart, stage and the
 // final cut; reads the hand-off queue.  finish_wide_ok: the model fits (single-scale nodes, no similarity transform,

@@ -470,8 +470,8 @@ template <typename Real> bool Pass<Real>::launch_finishers(long long n_grid) {
     const long long nmid = pred_mid >= 0 ? (long long)(pred_mid * (double)windows() * 1.25) + 64 : 0;
     const long long wg2 = std::min<long long>((long long)cap_m, std::max<long long>(std::max<long long>(2048, n_grid / std::max<long long>(1, kn().fin_grid_div)), nmid));
     count_form(JDA_FINISH_MID_DIRECT);
-    JDA_HIP(launch_filter0<Real>(want_trace(), pe->dp, model(), wc, n_grid, s0_tbl(), st));
-    JDA_HIP(launch_finish<Real>(want_trace(), 0, T, apply_th, th, pe->dp, model(), wc, g2, wg2, s0_tbl(), (int)kn().fin_tile, st, true));
+    JDA_HIP(filter0(wc, n_grid));
+    JDA_HIP(finish(wc, 0, T, g2, wg2, s0_tbl(), (int)kn().fin_tile, true));
     at.finished = true;
     return true;
   }
@@ -492,7 +492,7 @@ template <typename Real> bool Pass<Real>::launch_finishers(long long n_grid) {
     // few windows left: one launch walks them through every remaining stage (no balance problem,
     // one launch less)
     count_form(JDA_FINISH_MERGED);
-    JDA_HIP(launch_finish<Real>(want_trace(), 0, T, apply_th, th, pe->dp, model(), w, gm, n_grid, s0_tbl(), (int)kn().fin_tile, st));
+    JDA_HIP(finish(w, 0, T, gm, n_grid, s0_tbl(), (int)kn().fin_tile));
     at.finished = true;
     return true;
   }
@@ -501,8 +501,8 @@ template <typename Real> bool Pass<Real>::launch_finishers(long long n_grid) {
     // the dying majority is filtered by a lean kernel (four windows per workgroup, stage 0 only); the survivors --
     // a few per cent -- go through k_finish for the regression of stage 0 and every later stage
     count_form(JDA_FINISH_FILTER0);
-    JDA_HIP(launch_filter0<Real>(want_trace(), pe->dp, model(), wc, n_grid, s0_tbl(), st));
-    JDA_HIP(launch_finish<Real>(want_trace(), 0, T, apply_th, th, pe->dp, model(), wc, g2, wg2, s0_tbl(), (int)kn().fin_tile, st, true));
+    JDA_HIP(filter0(wc, n_grid));
+    JDA_HIP(finish(wc, 0, T, g2, wg2, s0_tbl(), (int)kn().fin_tile, true));
     at.finished = true;
     return true;
   }
@@ -512,8 +512,8 @@ template <typename Real> bool Pass<Real>::launch_finishers(long long n_grid) {
   // -- one workgroup per window as long as fewer than 25 % pass stage 0 (6.7 % in the cascade regime), a grid-stride
   // loop beyond that; the surplus workgroups exit at once (an empty workgroup costs ~1.3 ns of dispatcher time).
   count_form(JDA_FINISH_TWO_LAUNCH);
-  JDA_HIP(launch_finish<Real>(want_trace(), 0, 1, apply_th, th, pe->dp, model(), w, (int)kn().fin_g1, n_grid, s0_tbl(), (int)kn().fin_tile1, st));
-  JDA_HIP(launch_finish<Real>(want_trace(), 1, T, apply_th, th, pe->dp, model(), w, g2, wg2, nullptr, (int)kn().fin_tile, st));
+  JDA_HIP(finish(w, 0, 1, (int)kn().fin_g1, n_grid, s0_tbl(), (int)kn().fin_tile1));
+  JDA_HIP(finish(w, 1, T, g2, wg2, nullptr, (int)kn().fin_tile));
   at.finished = true;
   return true;
 }

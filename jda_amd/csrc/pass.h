@@ -119,6 +119,26 @@ struct Pass {
   long long windows() const { return rag ? rag->windows : (long long)nf * pe->sp.windows; }
   // the finishing form this pass is about to issue, for jdaFinishForms (a pass that is issued again counts again)
   void count_form(int form) { c->finish_forms[form].fetch_add(1, std::memory_order_relaxed); }
+  // A k_finish / k_filter0 launch of this pass, counted for jdaFinishLaunches under the key of what the launcher
+  // instantiates: the same functions (kernels.h) on the same arguments.  wk: the workspace as the launch sees it (w, or
+  // launch_finishers' copy without leaf words where the carry does not apply).
+  hipError_t finish(const WorkT<Real>& wk, int t_begin, int t_end, int groups, long long n_hint, const S0Node* s0, int tile_win,
+                    bool survivors = false) {
+    const DevModelT<Real>& m = model();
+    const bool stt = finish_st((int)sizeof(Real), m.similarity), mu = wk.half != nullptr;
+    if (finish_grid(n_hint, t_begin == 0 && !survivors ? wk.cap_q : wk.cap_m) != 0)        // (0: the launcher launches nothing)
+      c->finish_launches[JDA_FINISH_LAUNCH(JDA_FINISH_K_FINISH, Sel<Real>::dialect, want_trace() ? 1 : 0, finish_groups(groups), mu ? 1 : 0,
+                                           stt ? 1 : 0, finish_stream(want_trace(), mu, stt, m.w_stream) ? 1 : 0, survivors ? 1 : 0,
+                                           survivors && wk.m_leaf != nullptr ? 1 : 0,
+                                           finish_tile_win(m.dim, m.K, (int)sizeof(Real), stt, mu, tile_win) > 0 ? 1 : 0)]
+          .fetch_add(1, std::memory_order_relaxed);
+    return launch_finish<Real>(want_trace(), t_begin, t_end, apply_th, th, pe->dp, m, wk, groups, n_hint, s0, tile_win, st, survivors);
+  }
+  hipError_t filter0(const WorkT<Real>& wk, long long n_hint) {
+    c->finish_launches[JDA_FINISH_LAUNCH(JDA_FINISH_K_FILTER0, Sel<Real>::dialect, want_trace() ? 1 : 0, 0, 0, 0, 0, 0, wk.m_leaf != nullptr ? 1 : 0, 0)]
+        .fetch_add(1, std::memory_order_relaxed);
+    return launch_filter0<Real>(want_trace(), pe->dp, model(), wk, n_hint, s0_tbl(), st);
+  }
   // the scan launch this pass is about to issue, for jdaScanForms, under the key of what the launcher instantiates: the
   // same functions (kernels.h) and the same arguments the launchers take.  mode, block: DevLevel::tiled and the
   // workgroup size; lean: NORM = false (k_scan) / PScanCfg::any_norm == 0 (k_scan_p); merged: the launch spans levels.

@@ -36,6 +36,24 @@ int main() {
           if (carry_unpack(word[k & 63], bits, k >> 6) != leaf[k]) bad++;
       }
     }
+  // the word's edge (tests/test_finish_launches.py, carry_*): bits * rounds == 32 puts the last round's leaf in the top bits,
+  // bit 31 included; 3 x 10 = 30 leaves two bits unused; one cart more and the model does not carry.  The LARGEST leaf in
+  // every round: every bit of the word set, every round read back.
+  const int edge[][3] = {{4, 1024, 1}, {4, 1025, 0}, {16, 512, 1}, {16, 513, 0}, {256, 256, 1}, {256, 257, 0}, {8, 640, 1}, {8, 641, 0}};
+  for (const auto& e : edge) {
+    const int leaf_n = e[0], K = e[1], bits = carry_bits(leaf_n), rounds = carry_rounds(K);
+    std::printf("edge leaf_n %d K %d bits %d fits %d\n", leaf_n, K, bits * rounds, carry_fits(leaf_n, K) ? 1 : 0);
+    if (carry_fits(leaf_n, K) != (e[2] != 0)) bad++;
+    if (!e[2]) continue;
+    uint32_t word = 0;
+    for (int r = 0; r < rounds; r++) word = carry_pack(word, leaf_n - 1, bits, r);
+    if (bits * rounds == 32 && word != 0xffffffffu) bad++;
+    if (bits * rounds == 30 && word != 0x3fffffffu) bad++;
+    for (int r = 0; r < rounds; r++) if (carry_unpack(word, bits, r) != leaf_n - 1) bad++;
+    // ... and a lone top-round leaf with its top bit set comes back from a word that is otherwise zero
+    const uint32_t top = carry_pack(0u, leaf_n / 2, bits, rounds - 1);
+    if (carry_unpack(top, bits, rounds - 1) != leaf_n / 2 || (bits * rounds == 32 && top != 0x80000000u)) bad++;
+  }
   if (bad) { std::printf("carry FAILED: %d\n", bad); return 1; }
   std::printf("carry ok\n");
   return 0;

@@ -66,6 +66,41 @@ def test_scan_forms_entry_and_its_python_mirror(built, model_file):
     c.close()
 
 
+def test_finish_launches_entries_and_their_python_mirror(built, model_file):
+    """jdaFinishLaunches and jdaFinishTileWin (include/jda.h): exported; JDA_FINISH_LAUNCH_N counts indexed by
+    JDA_FINISH_LAUNCH, which the Python mirror (api.FinishLaunch.index) restates field for field -- checked against the
+    macro itself, evaluated from the header's text; all zero on a cascador that has run nothing; null arguments and an unknown
+    dialect refused.  No GPU needed: counts and model live in the host object."""
+    from jda_amd import api
+    assert {"jdaFinishLaunches", "jdaFinishTileWin"} <= set(declared_symbols())
+    src = open(HEADER).read()
+    assert int(re.search(r"#define JDA_FINISH_LAUNCH_N (\d+)", src).group(1)) == api.FINISH_LAUNCH_N == 2 * 2 * 2 * 5 * 2 ** 6
+    mac = re.search(r"#define JDA_FINISH_LAUNCH\(([^)]*)\)\s*\\\n(.*)\n", src)
+    args = mac.group(1).replace(" ", "").split(",")
+    assert tuple(args) == tuple(f for f, _ in api.FINISH_LAUNCH_FIELDS) == api.FinishLaunch._fields
+    for i, e in enumerate(("JDA_FINISH_K_FINISH", "JDA_FINISH_K_FILTER0")):
+        assert int(re.search(r"\b%s = (\d+)" % e, src).group(1)) == i, e
+    assert dict(api.FINISH_LAUNCH_FIELDS)["kernel"] == ("k_finish", "k_filter0") and dict(api.FINISH_LAUNCH_FIELDS)["groups"] == (0, 1, 2, 3, 4)
+    body = re.sub(r"\b(%s)\b" % "|".join(args), lambda m_: "a[%r]" % m_.group(1), mac.group(2))      # the macro's body is integer arithmetic
+    seen = set()
+    for i in range(api.FINISH_LAUNCH_N):
+        f = api.FinishLaunch.of_index(i)
+        a = {n: dict(api.FINISH_LAUNCH_FIELDS)[n].index(v) for n, v in zip(api.FinishLaunch._fields, f)}
+        assert f.index() == i == eval(body, {"a": a}), f
+        seen.add(f)
+    assert len(seen) == api.FINISH_LAUNCH_N
+    p, _ = model_file((2, 8, 5, 3), 8, seed=1)
+    c = api.Cascador(p)
+    assert c.finish_launches() == {}
+    assert api.lib.jdaFinishLaunches(c.h, None) == -1 and api.lib.jdaFinishLaunches(None, (C.c_longlong * api.FINISH_LAUNCH_N)()) == -1
+    # dim 10, K 8: (10 * real + 8 * 4 + 64) bytes in front of the tile, the largest tw with tw * ((tw + 3) & ~3) + 16 <= 7,680 - that
+    want = {rb: max(tw for tw in range(16, 256) if 10 * rb + 8 * 4 + 64 + tw * ((tw + 3) & ~3) + 16 <= 7680) for rb in (4, 8)}
+    assert want == {4: 85, 8: 85}          # (85 x 88 + 16 = 7,496 fits either; 86 x 88 + 16 = 7,584 neither)
+    assert c.finish_tile_win("C") == want[4] and c.finish_tile_win("CPP") == want[8]
+    assert api.lib.jdaFinishTileWin(None, 0) == -1 and api.lib.jdaFinishTileWin(c.h, 2) == -1
+    c.close()
+
+
 def test_header_is_plain_c_and_links(built, tmp_path):
     """What a maintainer of the reference would do: compile a C caller against
     include/jda.h and link libjda.so (no torch, no C++)."""

@@ -70,6 +70,23 @@ def _trace_vs_oracle(c, o, frames):
     return g
 
 
+def _launches(c, fn, *a, **kw):
+    """-> (what the call returned, {FinishLaunch: count} and {form: count} of its passes: jdaFinishLaunches / jdaFinishForms
+    after minus before, zeros left out)."""
+    b_l, b_f = c.finish_launches(), c.finish_forms()
+    r = fn(*a, **kw)
+    a_l, a_f = c.finish_launches(), c.finish_forms()
+    return r, {k: v - b_l.get(k, 0) for k, v in a_l.items() if v != b_l.get(k, 0)}, {k: a_f[k] - b_f[k] for k in a_f if a_f[k] != b_f[k]}
+
+
+def _pair(dialect, trace, carry, groups=3, n=1):
+    """The launches of n passes that take k_filter0 + k_finish(survivors) with the shipped dimensions: three cart groups a round
+    (K = 540), windows up to the tile in LDS, both kernels with the carry or both without."""
+    from jda_amd import api
+    return {api.FinishLaunch("k_filter0", dialect, trace, 0, False, False, False, False, carry, False): n,
+            api.FinishLaunch("k_finish", dialect, trace, groups, False, False, False, True, carry, True): n}
+
+
 def _same_dets(a, b, keys=("bboxes", "scores", "shapes")):
     assert len(a) == len(b)
     for i, (x, y) in enumerate(zip(a, b)):
@@ -117,10 +134,15 @@ def test_carry_vs_oracle_and_reference_and_with_the_carry_off(built, gpu, model_
     assert small > 0 and large > 0
     assert int((g["carts_n"] == T * K).sum()) > 0
     d = torch.from_numpy(frames).to(gpu)
-    before = c.finish_forms()
+    before, l_before = c.finish_forms(), c.finish_launches()
     dets, st = c.detect_batch_device(d, stats=True)
     forms = {k: v - before[k] for k, v in c.finish_forms().items() if v != before[k]}
-    print("forms:", forms)
+    launches = {k: v - l_before.get(k, 0) for k, v in c.finish_launches().items() if v != l_before.get(k, 0)}
+    print("forms:", forms, sorted(launches.items()))
+    # every launch of the call is k_filter0 or k_finish(survivors), both with the carry, k_finish with three cart groups (K = 540)
+    assert launches and {k.kernel for k in launches} == {"k_filter0", "k_finish"}, launches
+    assert all(k.carry and not k.trace and k.dialect == "C" for k in launches), launches
+    assert all(k.survivors and k.groups == 3 and k.tile for k in launches if k.kernel == "k_finish"), launches
     assert forms and set(forms) <= {"FILTER0", "MID_DIRECT"}, forms      # k_filter0 + k_finish(survivors): the carry's path
     assert st["handoff_n"] > FINISH_MERGE and st["dense_passes"] == 0
     ref = pyoracle.Reference(p, S_DIMS, 8) if pyoracle.reference_lib_path(*S_DIMS) else None
@@ -179,12 +201,13 @@ def test_entries_from_the_persistent_scan_mix_with_carried_ones(built, gpu, mode
     c1 = _cascador(p, env=env)
     assert c1.get_option("scan_p_mid") == 1 and c1.get_option("fin_carry") == 1
     for rep in range(2):                                   # (the second pass sizes its launches from the first)
-        before, scans_before = c1.finish_forms(), c1.scan_forms()
-        got, st1 = c1.detect_batch_device(d, stats=True)
-        forms = {k: v - before[k] for k, v in c1.finish_forms().items() if v != before[k]}
+        scans_before = c1.scan_forms()
+        (got, st1), launches, forms = _launches(c1, c1.detect_batch_device, d, stats=True)
         scans = {k: v - scans_before.get(k, 0) for k, v in c1.scan_forms().items() if v != scans_before.get(k, 0)}
-        print("pass", rep, "forms:", forms, scans)
+        print("pass", rep, "forms:", forms, scans, sorted(launches.items()))
         assert forms and set(forms) == {"MID_DIRECT"}, forms       # k_filter0 + k_finish(survivors) fed from k_scan_p's mid queue
+        # ... a k_filter0 and a k_finish(survivors) launch a pass, both with the carry (jdaFinishLaunches)
+        assert launches == _pair("C", False, True, n=forms["MID_DIRECT"]), launches
         # ... and the scan that filled it was k_scan_p (jdaScanForms), next to k_scan's global-pixel launch
         assert any(k.kernel == "k_scan_p" and k.depth == 4 and not k.ragged for k in scans) and any(k.pix == "GLB" for k in scans), scans
         _same_dets(want, got)
@@ -193,7 +216,9 @@ def test_entries_from_the_persistent_scan_mix_with_carried_ones(built, gpu, mode
         # the persistent scan did run past the common hand-off (its carts count as scan carts): its survivors are in the mid queue
         assert st1["scan_cart_n"] > st0["scan_cart_n"] and st1["scan_fallbacks"] == 0 and st1["dense_passes"] == 0
     c1o = _cascador(p, env=env, fin_carry=0)
-    got, _ = c1o.detect_batch_device(d, stats=True)
+    (got, _), launches, forms = _launches(c1o, c1o.detect_batch_device, d, stats=True)
+    print("fin_carry = 0:", forms, sorted(launches.items()))
+    assert set(forms) == {"MID_DIRECT"} and launches == _pair("C", False, False, n=forms["MID_DIRECT"]), (forms, launches)
     _same_dets(want, got)
     for c in (c0, c1, c1o):
         c.close()
@@ -213,6 +238,11 @@ def test_a_model_too_deep_for_the_word_walks_as_before(built, gpu, model_file):
     c, o = _cascador(p), Oracle(p)
     assert c.get_option("fin_carry") == 1
     g = _trace_vs_oracle(c, o, frames)
+    # k_filter0 and k_finish(survivors) ran, neither with the carry (jdaFinishLaunches); K = 448 walks four cart groups a round
+    launches = c.finish_launches()
+    print("launches:", sorted(launches.items()))
+    assert {k.kernel for k in launches} == {"k_filter0", "k_finish"} and not any(k.carry for k in launches), launches
+    assert all(k.survivors and k.groups == 4 and k.trace for k in launches if k.kernel == "k_finish"), launches
     assert int((g["carts_n"] > HANDOFF).sum()) > FINISH_MERGE and int((g["carts_n"] > dims[1]).sum()) > 0
     dets = c.detect_batch_device(torch.from_numpy(frames).to(gpu))
     for i in range(len(frames)):
@@ -236,8 +266,11 @@ def test_ragged_job_and_dialect_cpp(built, gpu, model_file):
     base = synth.make_frames(6, 400, 300, seed=15)
     imgs = [np.ascontiguousarray(base[i % 6][:int(rng.integers(150, 301)), :int(rng.integers(200, 401))]) for i in range(24)]
     c = _cascador(p)
-    got, st = c.detect_ragged(imgs, stats=True)
+    (got, st), launches, forms = _launches(c, c.detect_ragged, imgs, stats=True)
+    print("ragged:", forms, sorted(launches.items()))
     assert st["handoff_n"] > FINISH_MERGE and st["dense_passes"] == 0
+    # the job's passes took k_filter0 + k_finish(survivors), every launch with the carry
+    assert forms and set(forms) <= {"FILTER0", "MID_DIRECT"} and launches == _pair("C", False, True, n=sum(forms.values())), (forms, launches)
     n_pass0 = 0
     for i in (0, 5, 11, 23):
         want = o.detect(imgs[i])
@@ -246,12 +279,16 @@ def test_ragged_job_and_dialect_cpp(built, gpu, model_file):
         n_pass0 += int((o.trace(imgs[i], want_shapes=False)["carts_n"] > K).sum())
     assert n_pass0 > 0 and sum(len(x["scores"]) for x in got) > 0
     c0 = _cascador(p, fin_carry=0)
-    _same_dets(got, c0.detect_ragged(imgs))
+    got0, launches, forms = _launches(c0, c0.detect_ragged, imgs)
+    assert forms and set(forms) <= {"FILTER0", "MID_DIRECT"} and launches == _pair("C", False, False, n=sum(forms.values())), (forms, launches)
+    _same_dets(got, got0)
     c0.close()
     # dialect CPP: the fp64 instantiation of the same two kernels
     frames = synth.make_frames(2, 400, 300, seed=16)
     kw = dict(minimum_size=20, step=5, factor=1.2)
-    gt = c.trace_cpp(frames, **kw)
+    gt, launches, forms = _launches(c, c.trace_cpp, frames, **kw)
+    print("trace_cpp:", forms, sorted(launches.items()))
+    assert forms == {"FILTER0": 1} and launches == _pair("CPP", True, True), (forms, launches)
     off = 0
     for i in range(len(frames)):
         r = o.trace_cpp(frames[i], **kw)
@@ -261,7 +298,9 @@ def test_ragged_job_and_dialect_cpp(built, gpu, model_file):
         off += n
     assert off == len(gt["carts_n"])
     assert int((gt["carts_n"] > HANDOFF).sum()) > FINISH_MERGE and int((gt["carts_n"] > K).sum()) > 0
-    dets, stc = c.detect_batch_cpp_device(torch.from_numpy(frames).to(gpu), overlap=0.3, nms=True, stats=True, **kw)
+    (dets, stc), launches, forms = _launches(c, c.detect_batch_cpp_device, torch.from_numpy(frames).to(gpu), overlap=0.3, nms=True, stats=True, **kw)
+    print("detect_cpp:", forms, sorted(launches.items()))
+    assert forms == {"FILTER0": 1} and launches == _pair("CPP", False, True), (forms, launches)
     assert stc["handoff_n"] > FINISH_MERGE and stc["dense_passes"] == 0
     for i in range(len(frames)):
         want = o.detect_cpp(frames[i], overlap=0.3, nms=True, **kw)
@@ -294,17 +333,24 @@ def test_mid_queue_overflow_regrows_the_leaf_words_too(built, gpu, tmp_path):
     # preconditions (host.h: queue_caps without a prediction): the hand-off queue holds, the mid queue does not
     assert FINISH_MERGE < tail < n // 8 and mid > n // 32 + 64
     c = _cascador(p, ws_min_entries=1, ws_factor_pct=100)
-    got, st = c.detect_batch_device(d, th=-1.0e30, stats=True)
+    (got, st), launches, forms = _launches(c, c.detect_batch_device, d, th=-1.0e30, stats=True)
+    print("first call:", forms, sorted(launches.items()), "ws_regrows", st["ws_regrows"])
     assert st["ws_regrows"] >= 1 and api.last_error() == ""
+    # the pass that overflowed and every rerun launched the pair again: whole multiples, one more pass than regrows at least
+    n = sum(forms.values())
+    assert set(forms) == {"FILTER0"} and n >= 2 and launches == _pair("C", False, True, n=n), (forms, launches)
     assert st["handoff_n"] == tail and st["stage_done_n"][0] == mid
-    got2, st2 = c.detect_batch_device(d, th=-1.0e30, stats=True)          # (the rerun taught the plan its fractions)
+    (got2, st2), launches, forms = _launches(c, c.detect_batch_device, d, th=-1.0e30, stats=True)          # (the rerun taught the plan its fractions)
     assert st2["ws_regrows"] == 0
+    assert set(forms) == {"FILTER0"} and launches == _pair("C", False, True, n=sum(forms.values())), (forms, launches)
     _same_dets(got, got2)
     for i in range(len(frames)):
         want = o.detect(frames[i], th=-1.0e30)
         for k in ("bboxes", "scores", "shapes"):
             assert same(got[i][k], want[k]), (i, k)
     c0 = _cascador(p, ws_bound=0, fin_carry=0)
-    _same_dets(got, c0.detect_batch_device(d, th=-1.0e30))
+    got0, launches, forms = _launches(c0, c0.detect_batch_device, d, th=-1.0e30)
+    assert set(forms) == {"FILTER0"} and launches == _pair("C", False, False, n=sum(forms.values())), (forms, launches)
+    _same_dets(got, got0)
     assert sum(len(x["scores"]) for x in got) > 0
     c.close(); c0.close()

@@ -461,14 +461,26 @@ def test_k_finish_forms_vs_oracle(built, gpu, form, opts):
     c.set_option("dense", 0); c.set_option("wide_max", 0)
     for k, v in opts.items():
         c.set_option(k, v)
+    # the launches behind the form (jdaFinishLaunches; tests/test_finish_launches.py): K = 20 walks two 64-cart groups a round,
+    # stage 0 of TWO_LAUNCH one and without the window tile; the leaves of four-leaf trees fit the carry
+    FL = api.FinishLaunch
+    launches = lambda tr: {"MERGED": {FL("k_finish", "C", tr, 2, False, False, False, False, False, True): 1},
+                           "FILTER0": {FL("k_filter0", "C", tr, 0, False, False, False, False, True, False): 1,
+                                       FL("k_finish", "C", tr, 2, False, False, False, True, True, True): 1},
+                           "TWO_LAUNCH": {FL("k_finish", "C", tr, 1, False, False, False, False, False, False): 1,
+                                          FL("k_finish", "C", tr, 2, False, False, False, False, False, True): 1}}[form]
     try:
         for rep in range(2):
+            before = c.finish_launches()
             got, f = _forms(c, c.trace, frames)
-            print(form, "pass", rep, f)
-            assert f == {form: 1}, (rep, f)
+            fl = {k: v - before.get(k, 0) for k, v in c.finish_launches().items() if v != before.get(k, 0)}
+            print(form, "pass", rep, f, sorted(fl.items()))
+            assert f == {form: 1} and fl == launches(True), (rep, f, fl)
             _same_trace(want, got, form)
+        before = c.finish_launches()
         (d, st), f = _forms(c, c.detect_batch, frames, stats=True)
-        assert f == {form: 1}, f
+        fl = {k: v - before.get(k, 0) for k, v in c.finish_launches().items() if v != before.get(k, 0)}
+        assert f == {form: 1} and fl == launches(False), (f, fl)
         assert form == "MERGED" or st["handoff_n"] == handoff
     finally:
         c.close()

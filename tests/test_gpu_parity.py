@@ -1161,9 +1161,14 @@ def test_finish_table_layouts_do_not_change_results(built, gpu, model_file, monk
     loads where a stage's rows exceed w_stream_mb, and the last levels of trees with five or more node levels from
     records grouped per path (lm_deep; jda_amd/csrc/kernels.h: lm_deep_index).  None of it may change a bit: per-window
     trace and detections under every combination equal the plain layouts' and the oracle's (c/jda.c:357-426), in both
-    dialects (the options are read when a cascador is created)."""
+    dialects (the options are read when a cascador is created).  w_stream_mb is 0 (never) and 1: the first model's rows
+    exceed a megabyte per stage, padded or not, and its detect call must launch the STREAM instantiation (jdaFinishLaunches);
+    the other two models' rows stay under it (327,680 and 143,360 bytes padded) and must not; a traced pass never does."""
     from jda_amd import api, synth
     from oracle.pyoracle import Oracle
+    T, K, L, D = dims
+    row_bytes = lambda pad: K * (1 << (D - 1)) * (-(-2 * L // 32) * 32 if pad else 2 * L) * 4       # model_dev.cpp: fp32 rows on 128-byte lines
+    assert (row_bytes(1) > 1 << 20) == (row_bytes(0) > 1 << 20) == (dims == (2, 64, 68, 6))
     p, _ = model_file(dims, 8, seed=93, **kw)
     frames = synth.make_frames(2, 260, 190, seed=94)
     monkeypatch.setenv("JDA_W_PAD", "0"); monkeypatch.setenv("JDA_LM_DEEP", "0"); monkeypatch.setenv("JDA_W_STREAM_MB", "0")
@@ -1172,12 +1177,19 @@ def test_finish_table_layouts_do_not_change_results(built, gpu, model_file, monk
     _compare_trace(plain, Oracle(p), frames[:1])
     (want_t, want_d, want_c), f0 = _forms(plain, lambda: (plain.trace(frames), plain.detect_batch(frames), plain.trace_cpp(frames, 20, 5, 1.2)))
     forms = [f0]
-    for pad, deep in ((1, 1), (1, 0), (0, 1)):
-        monkeypatch.setenv("JDA_W_PAD", str(pad)); monkeypatch.setenv("JDA_LM_DEEP", str(deep))
+    assert not any(k.stream for k in plain.finish_launches()), plain.finish_launches()          # w_stream_mb = 0: never
+    for pad, deep, mb in ((1, 1, 0), (1, 0, 0), (0, 1, 0), (1, 1, 1), (1, 0, 1), (0, 1, 1), (0, 0, 1)):
+        monkeypatch.setenv("JDA_W_PAD", str(pad)); monkeypatch.setenv("JDA_LM_DEEP", str(deep)); monkeypatch.setenv("JDA_W_STREAM_MB", str(mb))
         c = api.Cascador(p)
         c.set_option("wide_max", 0)
         (t, d, tc), f = _forms(c, lambda: (c.trace(frames), c.detect_batch(frames), c.trace_cpp(frames, 20, 5, 1.2)))
         forms.append(f)
+        fl = c.finish_launches()
+        print("launches:", (pad, deep, mb), sorted(fl.items()))
+        want_stream = mb == 1 and row_bytes(pad) > 1 << 20
+        untraced = [k for k in fl if k.kernel == "k_finish" and not k.trace]
+        assert untraced and all(k.dialect == "C" and k.stream == want_stream for k in untraced), (pad, deep, mb, fl)
+        assert not any(k.stream for k in fl if k.trace or k.kernel == "k_filter0"), (pad, deep, mb, fl)
         for k in want_t:
             assert same(want_t[k], t[k]), (pad, deep, k)
         for a, b in zip(want_d, d):
@@ -1204,8 +1216,10 @@ def test_streamed_weight_rows_give_the_same_detections(built, gpu, model_file, m
     c.set_option("wide_max", 0)
     o = Oracle(p)
     got, f = _forms(c, c.detect_batch, frames)
-    print("forms:", f)
+    print("forms:", f, sorted(c.finish_launches().items()))
     assert f == {"MERGED": 1}, f                # (k_finish, not k_finish_wide or k_stage)
+    # ... and its STREAM instantiation: one launch, three cart groups a round (K = 300), windows up to the tile in LDS
+    assert c.finish_launches() == {api.FinishLaunch("k_finish", "C", False, 3, False, False, True, False, False, True): 1}, c.finish_launches()
     for i in range(len(frames)):
         _compare_detect(o.detect(frames[i]), got[i])
     assert sum(len(g["scores"]) for g in got) > 0
