@@ -1,5 +1,6 @@
 // Device helpers of the finishing kernels (k_finish.hip: wave = window; k_wide.hip: workgroup = window): window
-// views, split-node features, tree walks of a stage's carts, similarity transform (dialect CPP).
+// views, split-node features, tree walks of a stage's carts, similarity transform (dialect CPP).  One level up -- a
+// stage's tables, the choice of walk, the regression, the end of a window: stage_body.h.
 #pragma once
 #include "kernels_common.h"
 
@@ -182,6 +183,13 @@ __device__ __forceinline__ int node_feature(typename DL::Node nd, const typename
   return a - b;
 }
 
+// Dialect C's half / quarter views of the window (x, y, wn) (c/jda.c:345-354): origins by float multiply / integer halving,
+// every patch side = the window's.
+__device__ __forceinline__ void views_c(int x, int y, int wn, float inv_sqrt2, View* v1, View* v2) {
+  v1->ox = (int)((float)x * inv_sqrt2); v1->oy = (int)((float)y * inv_sqrt2); v1->pw = wn;
+  v2->ox = x / 2; v2->oy = y / 2; v2->pw = wn;
+}
+
 // Views of a queued window from its packed (x, y, win, frame) -- the producers of the queues
 // know these, so no division or level search is needed here.
 template <typename Real>
@@ -207,9 +215,7 @@ __device__ __forceinline__ void decode_window(const DevPlan* plan, const WorkT<R
     v1->img = w.half + (size_t)frame * w.half_stride; v1->w = w.hw; v1->h = w.hh;
     v2->img = w.quarter + (size_t)frame * w.quarter_stride; v2->w = w.qw; v2->h = w.qh;
     if (sizeof(Real) == 4) {
-      // dialect C, c/jda.c:345-354: origins by float multiply / integer halving, full-size patches
-      v1->ox = (int)((float)x * inv_sqrt2); v1->oy = (int)((float)y * inv_sqrt2); v1->pw = wn;
-      v2->ox = x / 2; v2->oy = y / 2; v2->pw = wn;
+      views_c(x, y, wn, inv_sqrt2, v1, v2);
     } else {
       // dialect CPP, cascador.cpp:340-343: Rect(int(x/r), int(y/r), int(win/r), ..), r = sqrt(2.) in double
       const double r = sqrt(2.0);

@@ -4,7 +4,7 @@
 // btcart.cpp:407-424), final cut (c/jda.c:414) and emit.
 // Survivors of k_filter0 bring their stage-0 leaves along (the carry: WorkT::m_leaf / m_k0, kernels.h: carry_pack), so
 // their stage 0 is the walk of the carts the scan scored, the unpacking of the rest, and the regression.
-#include "finish_common.h"
+#include "stage_body.h"
 
 #ifndef FIN_ROW_BATCH
 #define FIN_ROW_BATCH 0        // (experiment builds: -DFIN_ROW_BATCH=n forces the regression's row batch)
@@ -25,14 +25,14 @@ namespace jda {
 // windows), not by the number of windows in flight.)
 template <typename DL, bool TRACE, int kG, bool MULTI, bool ST, bool STREAM = false>
 __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan, DevModelT<typename DL::Real> m,
-                                               WorkT<typename DL::Real> w, int multi_i, float inv_sqrt2,
+                                               WorkT<typename DL::Real> w, float inv_sqrt2,
                                                int t_begin, int t_end, int apply_th, typename DL::Real final_th,
                                                const S0Node* __restrict__ s0_table, int tile_win, int survivors) {
   using Real = typename DL::Real;
   constexpr bool kCpp = sizeof(Real) == 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int lane = threadIdx.x;
-  const int T = m.T, K = m.K, node_n = m.node_n, leaf_n = m.leaf_n, dim = m.dim, w_pitch = m.w_pitch;
+  const int T = m.T, K = m.K, leaf_n = m.leaf_n, dim = m.dim, w_pitch = m.w_pitch;
   const int dim_pad = (dim + 1) & ~1;
   Real* sh = (Real*)lds;                                     // current shape        [dim_pad] (the regression updates it
                                                              // in place: coordinate d is read and written by one lane only)
@@ -44,7 +44,6 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
   // the window's pixels (windows up to tile_win pixels, single-scale models), behind the scratch, 16-byte aligned
   uint8_t* tile = lds + (((size_t)((unsigned char*)(st_tmp + (ST ? 2 * dim_pad + 8 : 0)) - lds) + 15) & ~(size_t)15);
   constexpr bool multi = MULTI;   // split nodes read the half/quarter images too
-  (void)multi_i;
   if (lane < kMaxStages) stage_cnt[lane] = 0;
   // the input queue: the hand-off queue of k_scan (t_begin == 0), the mid queue of an earlier k_finish launch
   // (t_begin > 0), or -- survivors -- the mid queue as k_filter0 leaves it: windows that passed every cart of stage 0,
@@ -79,22 +78,13 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
     decode_window<Real>(plan, w, xy, wf, inv_sqrt2, &win, &v0, &v1, &v2, multi);
     // stage 0 of a window whose level has resolved tables (every level k_scan covers): walk from them
     const S0Node* s0_tbl = nullptr;
-    if (!MULTI && s0_table != nullptr && t_begin == 0) {
-      const bool hit = lane < plan->n_levels && plan->lv[lane].win == win;
-      const unsigned long long mh = __ballot(hit);
-      if (mh) {
-        const DevLevel lv = plan->lv[__ffsll((long long)mh) - 1];
-        if (lv.tiled) s0_tbl = s0_table + lv.s0_table;
-      }
-    }
-    const uint8_t* wbase = v0.img + (size_t)v0.oy * v0.w + v0.ox;
+    if (!MULTI && s0_table != nullptr && t_begin == 0) s0_tbl = s0_table_for(plan, s0_table, win, lane, true);
 #ifdef JDA_SCAN_TIMING
     dbg_win = win;
 #endif
-    const bool use_tile = !MULTI && win <= tile_win;
-    const int tpitch = (win + 3) & ~3;
+    const WinPix px = win_pix(v0, win, !MULTI && win <= tile_win, tile);
     __syncthreads();                       // previous window's readers are done with sh (and the tile)
-    if (!MULTI && use_tile) load_window_tile(wbase, v0.w, win, tile, tpitch, lane, 64, v0.bc);
+    if (!MULTI && px.use_tile) load_window_tile(px.wbase, px.pitch, win, px.tile, px.tpitch, lane, 64, px.bc);
     {
       const Real* src = t_begin == 0 ? m.mean_shape : w.m_shape + (size_t)i * dim;
       for (int d = lane; d < dim; d += 64) sh[d] = src[d];
@@ -105,15 +95,7 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
     bool alive = true;
     int carts_n = 0;
     for (int t = t_begin; t < t_end; t++) {
-      const NodeOff<Real>* n_off = (const NodeOff<Real>*)m.lm_off + (size_t)t * K * node_n;
-      const uint2* n_meta = m.lm_meta + (size_t)t * K * node_n;
-      const int n_split = m.lm_split;
-      const typename DL::Node* n_deep = (const typename DL::Node*)m.lm_deep + (size_t)t * K * (node_n - ((1 << min(n_split, m.D - 1)) - 1));
-      const Real* leaf_tab = m.leaf + (size_t)t * K * leaf_n;
-      const Real* cth = m.cth + (size_t)t * K;
-      const Real* cmean = m.cmean + (size_t)t * K;
-      const Real* cstd = m.cstd + (size_t)t * K;
-      const uint8_t* cnorm = m.cnorm + (size_t)t * K;
+      const StageTables<DL> s = stage_tables<DL>(m, t);
       const int kbeg = t == 0 ? min(kstart, K) : 0;   // first cart whose score is still to be applied
       const bool carried = t == 0 && kc < K;          // (survivors: no score is left to apply in stage 0, only leaves to find)
       const int k_first = carried ? kc : kbeg & ~63;
@@ -147,20 +129,17 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
         Real ls[kG], thk[kG], mk[kG], sk[kG];
 #pragma unroll
         for (int g = 0; g < kG; g++) kk[g] = min(k0 + g * 64 + lane, K - 1);   // clamped lanes repeat cart K-1
-        if (t == 0 && s0_tbl && use_tile) walk_carts_s0<kG, true>(s0_tbl, K, kk, m.D, node_n, tile, tpitch, lf, Bc(0, (long long)tpitch * win));
-        else if (t == 0 && s0_tbl) walk_carts_s0<kG, false>(s0_tbl, K, kk, m.D, node_n, wbase, v0.w, lf, v0.bc);
-        else if (!MULTI && use_tile) walk_carts<DL, kG, MULTI, ST, true>(n_off, n_meta, K, kk, m.D, node_n, sh, win, v0, v1, v2, stp, apply_st, lf, tile, tpitch, n_deep, n_split);
-        else walk_carts<DL, kG, MULTI, ST>(n_off, n_meta, K, kk, m.D, node_n, sh, win, v0, v1, v2, stp, apply_st, lf, nullptr, 0, n_deep, n_split);
+        walk_stage<DL, kG, MULTI, ST>(s, t == 0 ? s0_tbl : nullptr, px, m, kk, sh, win, v0, v1, v2, stp, apply_st, lf);
 #pragma unroll
         for (int g = 0; g < kG; g++) {
           const int k = k0 + g * 64 + lane;
           ls[g] = 0; thk[g] = 0; mk[g] = 0; sk[g] = 1; nrm[g] = 0;
           if (k < K) {
             lbf[k] = (uint32_t)(k * leaf_n + lf[g]) * (uint32_t)w_pitch;
-            ls[g] = leaf_tab[(unsigned)(k * leaf_n + lf[g])];
-            thk[g] = cth[k];
-            nrm[g] = cnorm[k];
-            if (nrm[g]) { mk[g] = cmean[k]; sk[g] = cstd[k]; }
+            ls[g] = s.leaf[(unsigned)(k * leaf_n + lf[g])];
+            thk[g] = s.cth[k];
+            nrm[g] = s.cnorm[k];
+            if (nrm[g]) { mk[g] = s.cmean[k]; sk[g] = s.cstd[k]; }
           }
         }
 #pragma unroll
@@ -188,10 +167,7 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
       for (int k0 = 0; k0 < k_first; k0 += 128) {
         int kk[2], lf[2];
         kk[0] = min(k0 + lane, k_first - 1); kk[1] = min(k0 + 64 + lane, k_first - 1);
-        if (t == 0 && s0_tbl && use_tile) walk_carts_s0<2, true>(s0_tbl, K, kk, m.D, node_n, tile, tpitch, lf, Bc(0, (long long)tpitch * win));
-        else if (t == 0 && s0_tbl) walk_carts_s0<2, false>(s0_tbl, K, kk, m.D, node_n, wbase, v0.w, lf, v0.bc);
-        else if (!MULTI && use_tile) walk_carts<DL, 2, MULTI, ST, true>(n_off, n_meta, K, kk, m.D, node_n, sh, win, v0, v1, v2, stp, apply_st, lf, tile, tpitch, n_deep, n_split);
-        else walk_carts<DL, 2, MULTI, ST>(n_off, n_meta, K, kk, m.D, node_n, sh, win, v0, v1, v2, stp, apply_st, lf, nullptr, 0, n_deep, n_split);
+        walk_stage<DL, 2, MULTI, ST>(s, t == 0 ? s0_tbl : nullptr, px, m, kk, sh, win, v0, v1, v2, stp, apply_st, lf);
         if (k0 + lane < k_first) lbf[k0 + lane] = (uint32_t)((k0 + lane) * leaf_n + lf[0]) * (uint32_t)w_pitch;
         if (k0 + 64 + lane < k_first) lbf[k0 + 64 + lane] = (uint32_t)((k0 + 64 + lane) * leaf_n + lf[1]) * (uint32_t)w_pitch;
       }
@@ -200,36 +176,16 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
       // ---- stage regression: K weight rows added strictly in cart order
       //      (c/jda.c:404-411); dialect CPP sums the delta from zero and adds it
       //      once (btcart.cpp:407-424) ----
-      const Real* wt = m.w_rows + (size_t)t * K * leaf_n * w_pitch;
       for (int d = lane; d < dim; d += 64) {
         Real acc = kCpp ? (Real)0 : sh[d];
-        const Real* col = wt + d;
-        int k = 0;
-#ifdef JDA_EXP_NOREG
-        k = K;      // (experiment build, never the product: how long do the walks alone take?)
-#endif
-        // RB row loads in flight, then RB ordered adds.  A window's stage is a chain of K / RB such round trips to L2 --
-        // the longest part of its latency when few windows are in flight (a rank's shard, a single frame).  fp32: 64 (the
-        // registers are there: 16 one-wave workgroups per CU is the LDS limit, 4 waves per SIMD); fp64, whose rows are two
-        // registers per element: 32.
+        // A window's stage is a chain of K / RB round trips to L2 -- the longest part of its latency when few windows are in
+        // flight (a rank's shard, a single frame).  fp32: 64 rows in flight (the registers are there: 16 one-wave workgroups
+        // per CU is the LDS limit, 4 waves per SIMD); fp64, whose rows are two registers per element: 32.
         constexpr int RB = FIN_ROW_BATCH > 0 ? FIN_ROW_BATCH : (kCpp ? 32 : 64);
-        for (; k + RB <= K; k += RB) {
-          Real r[RB];
-          // (STREAM is a template parameter: as a run-time branch the optimiser merges the two forms of the load and
-          // drops the non-temporal hint)
-#pragma unroll
-          for (int u = 0; u < RB; u++) { JDA_BC(Bc(0, (long long)K * leaf_n * w_pitch), (long long)lbf[k + u] + d, 1, kBcWRow); r[u] = STREAM ? __builtin_nontemporal_load(col + lbf[k + u]) : col[lbf[k + u]]; }
-#pragma unroll
-          for (int u = 0; u < RB; u++) acc = acc + r[u];
-        }
-        for (; k < K; k++) { JDA_BC(Bc(0, (long long)K * leaf_n * w_pitch), (long long)lbf[k] + d, 1, kBcWRow); acc = acc + col[lbf[k]]; }
-        if (kCpp) {
-          // stp_mc.Apply(delta, delta) (btcart.cpp:422, data.hpp:42-45) on the (dx,dy) pair held by
-          // lanes d, d^1; with the identity parameter this is the literal 1*(1*x+0*y) / 1*(0*x+1*y)
-          const Real other = __shfl_xor(acc, 1);
-          acc = (d & 1) ? stp.scale * (stp.r10 * other + stp.r11 * acc) : stp.scale * (stp.r00 * acc + stp.r01 * other);
-          acc = sh[d] + acc;
-        }
+#ifndef JDA_EXP_NOREG   // (experiment build, never the product: how long do the walks alone take?)
+        acc = add_rows<Real, RB, STREAM>(s.w_rows + d, lbf, K, acc, Bc(0, (long long)K * leaf_n * w_pitch), d);
+#endif
+        if (kCpp) acc = sh[d] + stp_delta(stp, acc, d);
         sh[d] = acc;
       }
       __syncthreads();
@@ -241,24 +197,11 @@ __global__ __launch_bounds__(64) void k_finish(const DevPlan* __restrict__ plan,
       // the window's walk is over: account for it (reference counting: Validate's n)
       if (alive) carts_n = T * K;
       carts_acc += (unsigned long long)carts_n;
-      if (TRACE) {
-        if (lane == 0) { w.tr_carts[gid] = carts_n; w.tr_score[gid] = score; w.tr_hash[gid] = hash; }
-        for (int d = lane; d < dim; d += 64) w.tr_shape[(size_t)gid * dim + d] = sh[d];
-      }
-      if (alive && !(apply_th && score < final_th)) {            // c/jda.c:414
-        unsigned o = 0;
-        if (lane == 0) o = (unsigned)atomicAdd(&w.counters[kCntOut], 1ull);
-        o = (unsigned)__shfl((int)o, 0);
-        if (o < w.cap_m) {
-          if (lane == 0) { w.out_gid[o] = gid; w.out_score[o] = score; }
-          for (int d = lane; d < dim; d += 64) w.out_shape[(size_t)o * dim + d] = sh[d];
-        }
-      }
+      finish_window<TRACE>(w, gid, alive, carts_n, score, hash, apply_th && score < final_th, sh, dim, lane, 64,
+                           [&] { return wave_slot(&w.counters[kCntOut], lane); });
     } else {
       // alive with stages left: park it in the mid queue for the next launch
-      unsigned o = 0;
-      if (lane == 0) o = (unsigned)atomicAdd(&w.counters[kCntMid], 1ull);
-      o = (unsigned)__shfl((int)o, 0);
+      const unsigned o = wave_slot(&w.counters[kCntMid], lane);
       if (o < w.cap_m) {
         if (lane == 0) { w.m_gid[o] = gid; w.m_score[o] = score; w.m_xy[o] = xy; w.m_wf[o] = wf; if (TRACE) w.m_hash[o] = hash; }
         for (int d = lane; d < dim; d += 64) w.m_shape[(size_t)o * dim + d] = sh[d];
@@ -372,10 +315,8 @@ __global__ __launch_bounds__(256) void k_filter0(const DevPlan* __restrict__ pla
       const int win = (int)(wf[u] & 0xffffu), frame = (int)(wf[u] >> 16);
       const uint8_t* img = w.img_off != nullptr ? w.frames + w.img_off[frame] : w.frames + (size_t)frame * w.frame_stride;
       wbase[u] = img + (size_t)(xy[u] >> 16) * W + (xy[u] & 0xffffu);
-      tbl[u] = s0_table;
-      const bool hit = lane < plan->n_levels && plan->lv[lane].win == win;
-      const unsigned long long mh = __ballot(hit);
-      if (mh) tbl[u] = s0_table + plan->lv[__ffsll((long long)mh) - 1].s0_table;   // (the host only runs this kernel when every level has a table)
+      tbl[u] = s0_table_for(plan, s0_table, win, lane, false);   // (the host only runs this kernel when every level has a table)
+      if (!tbl[u]) tbl[u] = s0_table;
     }
     // rounds of 64 carts, both windows in step while both are alive (a window's own cart range starts at its kbeg)
     int k0[NW];
@@ -429,9 +370,7 @@ __global__ __launch_bounds__(256) void k_filter0(const DevPlan* __restrict__ pla
         carts_acc += (unsigned long long)(rej[u] + 1);
         if (TRACE && lane == 0) { w.tr_carts[gid[u]] = rej[u] + 1; w.tr_score[gid[u]] = score[u]; w.tr_hash[gid[u]] = hash[u]; }
       } else {
-        unsigned o = 0;
-        if (lane == 0) o = (unsigned)atomicAdd(&w.counters[kCntMid], 1ull);
-        o = (unsigned)__shfl((int)o, 0);
+        const unsigned o = wave_slot(&w.counters[kCntMid], lane);
         if (o < w.cap_m && lane == 0) {
           w.m_gid[o] = gid[u]; w.m_score[o] = score[u]; w.m_xy[o] = xy[u]; w.m_wf[o] = wf[u];
           if (TRACE) w.m_hash[o] = hash[u];
@@ -467,7 +406,7 @@ hipError_t launch_finish_impl(bool trace, int t_begin, int t_end, bool apply_th,
                               const WorkT<typename DL::Real>& w, int groups, long long n_hint, const S0Node* s0_table,
                               int tile_win, bool survivors, hipStream_t stream) {
   using Real = typename DL::Real;
-  // (every decision of this launch is a function of kernels.h, which the record of the launch asks too: Pass::count_finish)
+  // (every decision of this launch is a function of kernels.h, which the record of the launch asks too: Pass::finish)
   const bool st = finish_st((int)sizeof(Real), m.similarity);
   const int multi = (w.half != nullptr) ? 1 : 0;
   tile_win = finish_tile_win(m.dim, m.K, (int)sizeof(Real), st, multi != 0, tile_win);
@@ -478,7 +417,7 @@ hipError_t launch_finish_impl(bool trace, int t_begin, int t_end, bool apply_th,
   groups = finish_groups(groups);
   auto go = [&](auto kern) {
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, d_plan, m, w, multi, r, t_begin, t_end,
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, d_plan, m, w, r, t_begin, t_end,
                        apply_th ? 1 : 0, th, s0_table, tile_win, survivors ? 1 : 0);
   };
   // groups = 64-cart groups walked speculatively per round: 1 where most windows are

@@ -48,7 +48,6 @@ __global__ __launch_bounds__(BLOCK) void k_finish_wide(const DevPlan* __restrict
                                                        int lds_budget, int conc) {
   using Real = typename DL::Real;
   constexpr bool kCpp = sizeof(Real) == 8;
-  constexpr int NW = BLOCK / 64;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int T = m.T, K = m.K, node_n = m.node_n, leaf_n = m.leaf_n, dim = m.dim;
@@ -379,7 +378,6 @@ __global__ __launch_bounds__(BLOCK) void k_finish_wide(const DevPlan* __restrict
   __syncthreads();
   if (tid < T && stage_cnt[tid]) atomicAdd(shard_counter(w.counters, kCntStage0 + tid), (unsigned long long)stage_cnt[tid]);
   if (tid == 0 && carts_acc) atomicAdd(shard_counter(w.counters, kCntCarts), carts_acc);
-  (void)NW;
 }
 
 namespace {
@@ -392,10 +390,10 @@ hipError_t launch_finish_wide_impl(bool trace, bool apply_th, typename DL::Real 
   // window tile: as large as leaves room for at least 64 weight rows
   int tile_win = 0;
   for (int tw = 16; tw <= 255; tw++) {
-    const WideLds L(m.dim, m.K, (int)sizeof(Real), tw * ((tw + 3) & ~3) + 16, budget);
-    if (L.row_cap >= std::min(m.K, 64) && tw * ((tw + 3) & ~3) + 16 <= 40 * 1024) tile_win = tw;
+    const WideLds L(m.dim, m.K, (int)sizeof(Real), (int)finish_tile_bytes(tw), budget);
+    if (L.row_cap >= std::min(m.K, 64) && finish_tile_bytes(tw) <= 40 * 1024) tile_win = tw;
   }
-  const int tile_bytes = tile_win > 0 ? tile_win * ((tile_win + 3) & ~3) + 16 : 0;
+  const int tile_bytes = (int)finish_tile_bytes(tile_win);
   const WideLds L(m.dim, m.K, (int)sizeof(Real), tile_bytes, budget);
   if (L.row_cap < 1 || L.total > budget) return hipErrorInvalidValue;
   const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>(n_hint, 1 << 16));

@@ -1,11 +1,11 @@
 // HIP kernel of dialect C's window body on CALLER-GIVEN windows for gfx950 (reference c/jda.c:340-414 and 471-472;
 // jdaValidateWindows / jdaValidateWindowsDevice, windows.cpp): the work list is the caller's (frame, x, y, size) list, not a
 // scan plan's -- no grid, no minimum size, no NMS.
-//   k_windows  wave = window (one-wave workgroups, grid-stride over the list), the form k_finish established and k_reval
-//              restated.  The shape (2L floats) and the stage's K chosen weight rows live in the workgroup's LDS, and -- windows
+//   k_windows  wave = window (one-wave workgroups, grid-stride over the list), k_finish's form on k_finish's stage body
+//              (stage_body.h).  The shape (2L floats) and the stage's K chosen weight rows live in the workgroup's LDS, and -- windows
 //              up to WinArgs::tile_win pixels of a single-scale model -- the window's own pixels (load_window_tile); larger
 //              windows and multi-scale models read their pixels from the frame and the half / quarter images.  Per stage:
-//              walk     lane = cart, 64 carts a round: walk_carts (finish_common.h) on the level-major node tables, from cart 0
+//              walk     lane = cart, 64 carts a round: walk_stage (stage_body.h) on the level-major node tables, from cart 0
 //                       of stage 0 -- no queue, no hand-off, no stage-0 hoist table
 //              replay   the score chain of those carts IN CART ORDER (c/jda.c:396-397): one fp32 add per cart and, where the
 //                       cart normalises, one subtract and one IEEE division ((s - 0) / 1 is s, bit for bit, so the carts with
@@ -14,10 +14,10 @@
 //              reject   `score < th` per lane, one ballot: the first set bit is the first failing cart (c/jda.c:399) -- it fixes
 //                       carts_n, the score where the walk stopped, the hash and the shape as it stood
 //              regress  a window that passed the stage: lane = shape coordinate, the K rows added in cart order
-//                       (c/jda.c:404-411)
+//                       (c/jda.c:404-411; add_rows)
 //              Results go out by window index -- the caller's order, no atomics, nothing between waves.
 // No inline assembly, no scratch (the row batch of the regression is a fixed-size register array).
-#include "finish_common.h"
+#include "stage_body.h"
 
 namespace jda {
 
@@ -43,10 +43,9 @@ __global__ __launch_bounds__(64) void k_windows(DevModelT<float> m, WinArgs a, f
   uint32_t* lbf = (uint32_t*)(sh + dim_pad);                 // weight row (in elements) chosen by every cart of the stage [K]
   uint8_t* tile = win_lds + windows_lds_base(dim, K);        // the window's pixels (tile_win > 0)
   const Stp<float> stp{1.f, 1.f, 0.f, 0.f, 1.f};             // (dialect C has no similarity transform: never applied)
-  const int levels_deep = node_n - ((1 << min(m.lm_split, m.D - 1)) - 1);       // records per cart in lm_deep
   [[maybe_unused]] const Bc bc_frames((long long)(uintptr_t)a.frames,
                                       (long long)(uintptr_t)(a.frames + (size_t)(a.n_frames - 1) * a.frame_stride + (size_t)a.width * a.height));
-  [[maybe_unused]] const Bc bc_lm(0, (long long)K * node_n), bc_deep(0, (long long)K * levels_deep);
+  [[maybe_unused]] const Bc bc_lm(0, (long long)K * node_n), bc_deep(0, (long long)K * lm_deep_per_cart(m));
   [[maybe_unused]] const Bc bc_carts(0, (long long)T * K), bc_leaves(0, (long long)T * K * leaf_n);
 
   for (long long i = blockIdx.x; i < a.n; i += gridDim.x) {
@@ -57,11 +56,9 @@ __global__ __launch_bounds__(64) void k_windows(DevModelT<float> m, WinArgs a, f
     View v0{}, v1{}, v2{};
     v0.img = a.frames + (size_t)frame * a.frame_stride; v0.w = a.width; v0.h = a.height; v0.ox = x; v0.oy = y; v0.pw = win;
     if (MULTI) {
-      // c/jda.c:345-354: origins by float multiply / integer halving, every patch side = the window's
       v1.img = a.half + (size_t)frame * a.half_stride; v1.w = a.hw; v1.h = a.hh;
-      v1.ox = (int)((float)x * inv_sqrt2); v1.oy = (int)((float)y * inv_sqrt2); v1.pw = win;
       v2.img = a.quarter + (size_t)frame * a.quarter_stride; v2.w = a.qw; v2.h = a.qh;
-      v2.ox = x / 2; v2.oy = y / 2; v2.pw = win;
+      views_c(x, y, win, inv_sqrt2, &v1, &v2);
     }
 #ifdef JDA_BOUNDS_CHECK
     v0.bc = bc_frames;
@@ -70,11 +67,9 @@ __global__ __launch_bounds__(64) void k_windows(DevModelT<float> m, WinArgs a, f
       v2.bc = Bc((long long)(uintptr_t)a.quarter, (long long)(uintptr_t)(a.quarter + (size_t)(a.n_frames - 1) * a.quarter_stride + (size_t)a.qw * a.qh));
     }
 #endif
-    const uint8_t* wbase = v0.img + (size_t)y * a.width + x;
-    const bool use_tile = !MULTI && win <= a.tile_win;
-    const int tpitch = (win + 3) & ~3;
+    const WinPix px = win_pix(v0, win, !MULTI && win <= a.tile_win, tile);
     __syncthreads();                                         // the previous window's readers are done with sh, lbf and the tile
-    if (!MULTI && use_tile) load_window_tile(wbase, a.width, win, tile, tpitch, lane, 64, bc_frames);
+    if (!MULTI && px.use_tile) load_window_tile(px.wbase, px.pitch, win, px.tile, px.tpitch, lane, 64, px.bc);
     for (int d = lane; d < dim; d += 64) sh[d] = m.mean_shape[d];          // c/jda.c:361
     __syncthreads();
 
@@ -83,18 +78,13 @@ __global__ __launch_bounds__(64) void k_windows(DevModelT<float> m, WinArgs a, f
     bool alive = true;
     int carts_n = 0;
     for (int t = 0; t < T && alive; t++) {
-      const NodeOff<float>* n_off = (const NodeOff<float>*)m.lm_off + (size_t)t * K * node_n;
-      const uint2* n_meta = m.lm_meta + (size_t)t * K * node_n;
-      const NodeF* n_deep = (const NodeF*)m.lm_deep + (size_t)t * K * levels_deep;
-      const size_t c0 = (size_t)t * K;
+      const StageTables<DL> s = stage_tables<DL>(m, t);
+      const size_t c0 = (size_t)t * K;                       // the stage's cart records, read from the model's base (stage_body.h says why)
       for (int k0 = 0; k0 < K && alive; k0 += 64) {
         // ---- walk: lane = cart (lanes past cart K - 1 repeat it and are not used)
         int kk[1], lf[1];
         kk[0] = min(k0 + lane, K - 1);
-        if (!MULTI && use_tile)
-          walk_carts<DL, 1, MULTI, false, true>(n_off, n_meta, K, kk, m.D, node_n, sh, win, v0, v1, v2, stp, false, lf, tile, tpitch, n_deep, m.lm_split, bc_lm, bc_deep);
-        else
-          walk_carts<DL, 1, MULTI, false>(n_off, n_meta, K, kk, m.D, node_n, sh, win, v0, v1, v2, stp, false, lf, nullptr, 0, n_deep, m.lm_split, bc_lm, bc_deep);
+        walk_stage<DL, 1, MULTI, false>(s, nullptr, px, m, kk, sh, win, v0, v1, v2, stp, false, lf, bc_lm, bc_deep);
         const int k = k0 + lane;
         const bool active = k < K;
         float ls = 0.f, thk = 0.f, mk = 0.f, sk = 1.f;
@@ -132,22 +122,8 @@ __global__ __launch_bounds__(64) void k_windows(DevModelT<float> m, WinArgs a, f
       if (!alive) break;
       __syncthreads();                                       // the stage's rows, written by their carts' lanes
       // ---- regression (c/jda.c:404-411): lane = coordinate, rows in cart order
-      const float* wt = m.w_rows + (size_t)t * K * leaf_n * w_pitch;
-      [[maybe_unused]] const Bc bc_rows(0, (long long)K * leaf_n * w_pitch);
-      for (int d = lane; d < dim; d += 64) {
-        float acc = sh[d];
-        const float* col = wt + d;
-        int k = 0;
-        for (; k + kWinRowBatch <= K; k += kWinRowBatch) {
-          float r[kWinRowBatch];
-#pragma unroll
-          for (int u = 0; u < kWinRowBatch; u++) { JDA_BC(bc_rows, (long long)lbf[k + u] + d, 1, kBcWRow); r[u] = col[lbf[k + u]]; }
-#pragma unroll
-          for (int u = 0; u < kWinRowBatch; u++) acc = acc + r[u];
-        }
-        for (; k < K; k++) { JDA_BC(bc_rows, (long long)lbf[k] + d, 1, kBcWRow); acc = acc + col[lbf[k]]; }
-        sh[d] = acc;                                         // (coordinate d is read and written by this lane alone)
-      }
+      for (int d = lane; d < dim; d += 64)                   // (coordinate d is read and written by this lane alone)
+        sh[d] = add_rows<float, kWinRowBatch>(s.w_rows + d, lbf, K, sh[d], Bc(0, (long long)K * leaf_n * w_pitch), d);
       __syncthreads();                                       // the next stage's walk reads every coordinate
     }
     if (alive) carts_n = T * K;
@@ -177,7 +153,7 @@ int windows_tile_limit(int dim, int K) {
   const size_t base = windows_lds_base(dim, K);
   int tile_win = 0;
   for (int tw = 1; tw <= 255; tw++)
-    if (base + (size_t)tw * ((tw + 3) & ~3) + 16 <= kFinishLdsPerGroup) tile_win = tw;
+    if (base + finish_tile_bytes(tw) <= kFinishLdsPerGroup) tile_win = tw;
   return tile_win;
 }
 
@@ -188,7 +164,7 @@ hipError_t launch_windows(const DevModelT<float>& m, const WinArgs& a, hipStream
   const int tile_win = multi ? 0 : std::max(0, std::min(a.tile_win, windows_tile_limit(m.dim, m.K)));
   WinArgs b = a;
   b.tile_win = tile_win;
-  const size_t lds = windows_lds_base(m.dim, m.K) + (tile_win > 0 ? (size_t)tile_win * ((tile_win + 3) & ~3) + 16 : 0);
+  const size_t lds = windows_lds_base(m.dim, m.K) + finish_tile_bytes(tile_win);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   const float r = 1.f / sqrtf(2.f);                          // c/jda.c:341
   // one window per workgroup while the list is short enough (the dispatcher balances the very uneven walks), grid-stride beyond

@@ -377,7 +377,7 @@ hipError_t launch_filter0(bool trace, const DevPlan* d_plan, const DevModelT<Rea
 constexpr size_t kFinishLdsPerGroup = 7680;
 
 // What a k_finish launch instantiates and how much LDS it takes, decided here once: the launcher (k_finish.hip:
-// launch_finish_impl) and the record of the launch (Pass::count_finish, jdaFinishLaunches, jdaFinishTileWin) both ask these.
+// launch_finish_impl) and the record of the launch (Pass::finish, jdaFinishLaunches, jdaFinishTileWin) both ask these.
 // ST: the similarity transform exists in dialect CPP only.
 constexpr bool finish_st(int real_bytes, int similarity) { return real_bytes == 8 && similarity != 0; }
 // kG, the 64-cart groups a round walks: an instantiation each for 1..4.
