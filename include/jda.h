@@ -239,6 +239,34 @@ JDA_API int jdaFinishLaunches(void *cascador, long long counts[JDA_FINISH_LAUNCH
  * model's state leaves no room, or it is multi-scale).  -1: a null cascador or an unknown dialect. */
 JDA_API int jdaFinishTileWin(void *cascador, int dialect);
 
+/* Which k_stage launches the passes of a cascador issued.  The form DENSE above is made of one
+ * k_stage launch per stage and level; every launch counts once under the full key of what it instantiates and how it
+ * was set up:
+ *   dialect  JDA_DIALECT_C (fp32) or JDA_DIALECT_CPP (fp64)
+ *   trace    1: the pass records carts, score, leaf hash and shape per window
+ *   glb      1: the pixels of a 16 x 16 tile of the level's windows exceed the LDS pixel cap and are read through the
+ *            caches, 0: they are copied to LDS first
+ *   acc      the register width of the regression sums, the smallest class that holds the 2 * landmarks shape
+ *            coordinates: JDA_STAGE_ACC_12, _32, _64, _160
+ *   chunk    the carts whose tables and weight rows are staged in LDS at a time: JDA_STAGE_CHUNK_4, _8, _16, _32, _64
+ * at counts[JDA_STAGE_LAUNCH(dialect, trace, glb, acc, chunk)]. */
+enum { JDA_STAGE_ACC_12 = 0, JDA_STAGE_ACC_32 = 1, JDA_STAGE_ACC_64 = 2, JDA_STAGE_ACC_160 = 3 };
+enum { JDA_STAGE_CHUNK_4 = 0, JDA_STAGE_CHUNK_8 = 1, JDA_STAGE_CHUNK_16 = 2, JDA_STAGE_CHUNK_32 = 3, JDA_STAGE_CHUNK_64 = 4 };
+#define JDA_STAGE_LAUNCH(dialect, trace, glb, acc, chunk) \
+  ((((((dialect) * 2 + (trace)) * 2 + (glb)) * 4 + (acc)) * 5) + (chunk))
+#define JDA_STAGE_LAUNCH_N 160
+/* counts[i]: how often the passes of this cascador have issued launch i since it was created: one count per launch, so
+ * stages x levels per dense pass.  Cumulative, added atomically on the host where Pass::run_dense issues the launches;
+ * take the difference around a call, as with jdaFinishForms.  A pass that is issued again counts its launches again.
+ * Returns 0, or -1 for a null argument. */
+JDA_API int jdaStageLaunches(void *cascador, long long counts[JDA_STAGE_LAUNCH_N]);
+/* Runs nothing: the index in those counts that a level of `win`-pixel windows, `step` pixels apart, would launch with
+ * this cascador's model in `dialect`, traced or not; *lds_bytes (may be null) receives that launch's dynamic LDS size.
+ * -1: dense mode declines the model (more than 160 shape coordinates or 256 leaves a tree, or a tile's shapes and four
+ * carts' tables beyond 160 KB of LDS) or the dialect (dialect CPP under the similarity transform, a multi-scale
+ * model), or a null cascador, an unknown dialect, win < 1 or step < 1.  Needs no device. */
+JDA_API int jdaStageLaunchFor(void *cascador, int dialect, int trace, int win, int step, int *lds_bytes);
+
 /* Window enumeration of reference c/jda.c:320-339 without running anything:
  * number of candidate windows and pyramid levels for one frame. */
 JDA_API int jdaCountWindows(int width, int height, float scale, int min_size, int max_size,

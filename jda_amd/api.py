@@ -74,6 +74,31 @@ class FinishLaunch(collections.namedtuple("FinishLaunch", [f for f, _ in FINISH_
         return cls(*reversed(out))
 
 
+# include/jda.h: the fields of a k_stage launch's key in the order of JDA_STAGE_LAUNCH, each with its values in index order
+STAGE_LAUNCH_FIELDS = (("dialect", ("C", "CPP")), ("trace", (False, True)), ("glb", (False, True)), ("acc", (12, 32, 64, 160)),
+                       ("chunk", (4, 8, 16, 32, 64)))
+STAGE_LAUNCH_N = 160
+
+
+class StageLaunch(collections.namedtuple("StageLaunch", [f for f, _ in STAGE_LAUNCH_FIELDS])):
+    """The key of one k_stage launch (include/jda.h: JDA_STAGE_LAUNCH)."""
+    __slots__ = ()
+
+    def index(self):
+        i = 0
+        for (_, values), v in zip(STAGE_LAUNCH_FIELDS, self):
+            i = i * len(values) + values.index(v)
+        return i
+
+    @classmethod
+    def of_index(cls, i):
+        out = []
+        for _, values in reversed(STAGE_LAUNCH_FIELDS):
+            out.append(values[i % len(values)])
+            i //= len(values)
+        return cls(*reversed(out))
+
+
 class JdaError(RuntimeError):
     pass
 
@@ -264,6 +289,8 @@ def _load():
     lib.jdaScanForms.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.jdaFinishLaunches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.jdaFinishTileWin.argtypes = [C.c_void_p, C.c_int]
+    lib.jdaStageLaunches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
+    lib.jdaStageLaunchFor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     lib.jdaCountWindows.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                     C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     lib.jdaDetectOptionsInit.restype = None
@@ -1284,6 +1311,27 @@ class Cascador:
         if r < 0:
             raise JdaError(last_error())
         return r
+
+    def stage_launches(self):
+        """jdaStageLaunches: how often this cascador's dense passes have launched each k_stage instantiation and cart chunk
+        since it was created -> {StageLaunch(dialect, trace, glb, acc, chunk): count}, zeros left out.  One count per launch
+        (stages x levels a pass); the counts only grow; take the difference around a call."""
+        counts = (C.c_longlong * STAGE_LAUNCH_N)()
+        if lib.jdaStageLaunches(self.h, counts) != 0:
+            raise JdaError(last_error())
+        return {StageLaunch.of_index(i): int(x) for i, x in enumerate(counts) if x}
+
+    def stage_launch_for(self, dialect, trace, win, step):
+        """jdaStageLaunchFor: (the StageLaunch key, the dynamic LDS bytes) of the k_stage launch a level of `win`-pixel
+        windows `step` pixels apart would take with this model in `dialect` ("C" / "CPP", or JDA_DIALECT_*); None where
+        dense mode declines the model or the dialect; an unknown dialect, or a window or step below 1, raises JdaError.
+        Runs nothing, needs no device."""
+        lds = C.c_int(0)
+        d = {"C": JDA_DIALECT_C, "CPP": JDA_DIALECT_CPP}.get(dialect, dialect)
+        r = int(lib.jdaStageLaunchFor(self.h, d, 1 if trace else 0, int(win), int(step), C.byref(lds)))
+        if r < 0 and (d not in (JDA_DIALECT_C, JDA_DIALECT_CPP) or int(win) < 1 or int(step) < 1):
+            raise JdaError(last_error())
+        return None if r < 0 else (StageLaunch.of_index(r), int(lds.value))
 
     def serialize(self, path):
         lib.jdaCascadorSerializeTo(self.h, os.fsencode(path))

@@ -238,6 +238,30 @@ int jdaFinishTileWin(void* cascador, int dialect) try {
   return finish_tile_win(c->hm.dim(), c->hm.K, real_bytes, finish_st(real_bytes, c->similarity), c->hm.multi_scale(), -1);
 } JDA_ABI_CATCH(-1)
 
+int jdaStageLaunches(void* cascador, long long counts[JDA_STAGE_LAUNCH_N]) try {
+  Cascador* c = (Cascador*)cascador;
+  if (!c || !counts) { fail("jdaStageLaunches: null cascador or counts"); return -1; }
+  for (int f = 0; f < JDA_STAGE_LAUNCH_N; f++) counts[f] = c->stage_launches[f].load(std::memory_order_relaxed);
+  return 0;
+} JDA_ABI_CATCH(-1)
+
+int jdaStageLaunchFor(void* cascador, int dialect, int trace, int win, int step, int* lds_bytes) try {
+  Cascador* c = (Cascador*)cascador;
+  if (!c || (dialect != JDA_DIALECT_C && dialect != JDA_DIALECT_CPP) || win < 1 || step < 1) {
+    fail("jdaStageLaunchFor: null cascador, unknown dialect, or a window or step below 1"); return -1;
+  }
+  std::lock_guard<std::mutex> lk(c->mu);             // (multi_scale() caches its answer in the model on first use)
+  // (what Pass::dense_ok and launch_stage decide: the same functions on the same model and the same constants)
+  const int real_bytes = dialect == JDA_DIALECT_C ? 4 : 8, lds_max = (int)Knobs::dense_lds_max;
+  int pix_cap = 0;
+  if (c->hm.multi_scale() || (dialect == JDA_DIALECT_CPP && c->similarity) ||
+      !stage_model_ok(c->hm.dim(), c->hm.node_n(), c->hm.leaf_n(), real_bytes, (int)Knobs::dense_pix, lds_max, &pix_cap)) return -1;
+  const StageChoice sc = stage_choice(win, step, c->hm.dim(), c->hm.node_n(), c->hm.leaf_n(), c->hm.K, real_bytes, pix_cap, lds_max);
+  if (sc.chunk == 0) return -1;
+  if (lds_bytes) *lds_bytes = sc.lds_bytes;
+  return stage_launch_key(dialect, trace != 0, sc);
+} JDA_ABI_CATCH(-1)
+
 int jdaCountWindows(int width, int height, float scale, int min_size, int max_size,
                     long long* n_windows, int* n_levels) try {
   ScanPlan sp; std::string err;

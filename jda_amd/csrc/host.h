@@ -500,6 +500,13 @@ struct Lane {
   }
 };
 
+// A k_stage launch's index in jdaStageLaunches' counts, from what stage_choice (kernels.h) decided for it.
+inline int stage_launch_key(int dialect, bool trace, const StageChoice& s) {
+  const int acc = s.acc == 12 ? JDA_STAGE_ACC_12 : (s.acc == 32 ? JDA_STAGE_ACC_32 : (s.acc == 64 ? JDA_STAGE_ACC_64 : JDA_STAGE_ACC_160));
+  const int chunk = s.chunk == 4 ? JDA_STAGE_CHUNK_4 : (s.chunk == 8 ? JDA_STAGE_CHUNK_8 : (s.chunk == 16 ? JDA_STAGE_CHUNK_16 : (s.chunk == 32 ? JDA_STAGE_CHUNK_32 : JDA_STAGE_CHUNK_64)));
+  return JDA_STAGE_LAUNCH(dialect, trace ? 1 : 0, s.glb ? 1 : 0, acc, chunk);
+}
+
 struct Cascador {
   HostModel hm;
   Knobs kn;
@@ -516,6 +523,8 @@ struct Cascador {
   std::atomic<long long> scan_forms[JDA_SCAN_FORM_N] = {};
   // k_finish / k_filter0 launches the passes of this cascador have issued, by what they instantiate (jdaFinishLaunches, JDA_FINISH_LAUNCH)
   std::atomic<long long> finish_launches[JDA_FINISH_LAUNCH_N] = {};
+  // k_stage launches the dense passes of this cascador have issued, by what they instantiate (jdaStageLaunches, JDA_STAGE_LAUNCH)
+  std::atomic<long long> stage_launches[JDA_STAGE_LAUNCH_N] = {};
   int similarity = 0;          // dialect CPP: Config::with_similarity_transform (reference common.cpp:214)
   int device = -1;
   int n_cus = 256;             // compute units of the device

@@ -269,43 +269,49 @@ int dense_chunk(int pix_bytes, int dim, int node_n, int leaf_n, int K, int lds_m
   return 0;
 }
 
+template <typename Real, typename Node>
+StageChoice stage_choice_impl(int win, int step, int dim, int node_n, int leaf_n, int K, int pix_cap, int lds_max) {
+  const int pw = win + (kDenseTw - 1) * step, ph = win + (kDenseTh - 1) * step;
+  StageChoice s{};
+  s.pitch = (pw + 15) & ~15;
+  if ((s.pitch & 127) == 0) s.pitch += 16;
+  const long long need = (long long)s.pitch * ph;
+  s.glb = need > pix_cap;
+  s.pix_bytes = s.glb ? 0 : (int)need;
+  s.acc = dense_acc(dim);
+  s.chunk = dense_chunk<Real, Node>(s.pix_bytes, dim, node_n, leaf_n, K, lds_max);
+  s.lds_bytes = s.chunk ? DenseLds<Real, Node>(s.pix_bytes, dim, node_n, leaf_n, s.chunk, s.acc).total : 0;
+  return s;
+}
+
 template <typename DL>
 hipError_t launch_stage_impl(bool trace, int level, int t, bool apply_th, typename DL::Real th, const DevPlan* d_plan,
                              const DevPlan& h_plan, const DevModelT<typename DL::Real>& m,
                              const WorkT<typename DL::Real>& w, int pix_cap, int lds_max, hipStream_t stream) {
   using Real = typename DL::Real;
-  using Node = typename DL::Node;
   const DevLevel& lv = h_plan.lv[level];
-  const int pw = lv.win + (kDenseTw - 1) * lv.step, ph = lv.win + (kDenseTh - 1) * lv.step;
-  int pitch = (pw + 15) & ~15;
-  if ((pitch & 127) == 0) pitch += 16;
-  const long long need = (long long)pitch * ph;
-  const bool glb = need > pix_cap;
-  const int pix_bytes = glb ? 0 : (int)need;
-  const int acc = dense_acc(m.dim);
-  const int chunk = dense_chunk<Real, Node>(pix_bytes, m.dim, m.node_n, m.leaf_n, m.K, lds_max);
-  if (chunk == 0) return hipErrorInvalidValue;
-  const DenseLds<Real, Node> L(pix_bytes, m.dim, m.node_n, m.leaf_n, chunk, acc);
+  const StageChoice sc = stage_choice(lv.win, lv.step, m.dim, m.node_n, m.leaf_n, m.K, (int)sizeof(Real), pix_cap, lds_max);
+  if (sc.chunk == 0) return hipErrorInvalidValue;
   const int tiles = ((lv.nx + kDenseTw - 1) / kDenseTw) * ((lv.ny + kDenseTh - 1) / kDenseTh);
   const int groups = (w.n_frames + 7) / 8;
   dim3 grid((unsigned)(groups * 8 * tiles)), block(kDenseM);
   auto go = [&](auto kern) {
-    if (L.total > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
-    hipLaunchKernelGGL(kern, grid, block, L.total, stream, d_plan, m, w, level, t, pix_bytes, pitch, chunk,
+    if (sc.lds_bytes > 48 * 1024)
+      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, sc.lds_bytes);
+    hipLaunchKernelGGL(kern, grid, block, sc.lds_bytes, stream, d_plan, m, w, level, t, sc.pix_bytes, sc.pitch, sc.chunk,
                        apply_th ? 1 : 0, th);
   };
   auto pick = [&](auto trace_tag, auto glb_tag) {
     constexpr bool TR = decltype(trace_tag)::value, GL = decltype(glb_tag)::value;
-    switch (acc) {
+    switch (sc.acc) {
       case 12: go(k_stage<DL, TR, GL, 12>); break;
       case 32: go(k_stage<DL, TR, GL, 32>); break;
       case 64: go(k_stage<DL, TR, GL, 64>); break;
       default: go(k_stage<DL, TR, GL, 160>); break;
     }
   };
-  if (trace) { if (glb) pick(std::true_type{}, std::true_type{}); else pick(std::true_type{}, std::false_type{}); }
-  else { if (glb) pick(std::false_type{}, std::true_type{}); else pick(std::false_type{}, std::false_type{}); }
+  if (trace) { if (sc.glb) pick(std::true_type{}, std::true_type{}); else pick(std::true_type{}, std::false_type{}); }
+  else { if (sc.glb) pick(std::false_type{}, std::true_type{}); else pick(std::false_type{}, std::false_type{}); }
   return hipGetLastError();
 }
 }  // namespace
@@ -321,6 +327,17 @@ hipError_t launch_stage<double>(bool trace, int level, int t, bool apply_final_t
                                 const DevPlan& h_plan, const DevModelT<double>& m, const WorkT<double>& w, int pix_cap,
                                 int lds_max, hipStream_t stream) {
   return launch_stage_impl<DialectCPP>(trace, level, t, apply_final_th, final_th, d_plan, h_plan, m, w, pix_cap, lds_max, stream);
+}
+
+StageChoice stage_choice(int win, int step, int dim, int node_n, int leaf_n, int K, int real_bytes, int pix_cap, int lds_max) {
+  return real_bytes == 4 ? stage_choice_impl<float, NodeF>(win, step, dim, node_n, leaf_n, K, pix_cap, lds_max)
+                         : stage_choice_impl<double, NodeD>(win, step, dim, node_n, leaf_n, K, pix_cap, lds_max);
+}
+
+bool stage_model_ok(int dim, int node_n, int leaf_n, int real_bytes, int pix_max, int lds_max, int* pix_cap) {
+  const int fixed = (int)stage_lds_bytes(dim, node_n, leaf_n, real_bytes);
+  *pix_cap = std::max(0, std::min(pix_max, lds_max - fixed));
+  return dim <= 160 && leaf_n <= 256 && fixed <= lds_max;
 }
 
 // LDS bytes of k_stage with no pixel tile and the smallest chunk: the floor the host checks a model against

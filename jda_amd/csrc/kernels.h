@@ -436,6 +436,18 @@ hipError_t launch_stage(bool trace, int level, int t, bool apply_final_th, Real 
                         const DevPlan& h_plan, const DevModelT<Real>& m, const WorkT<Real>& w, int pix_cap,
                         int lds_max, hipStream_t stream);
 size_t stage_lds_bytes(int dim, int node_n, int leaf_n, int real_bytes);
+// What a k_stage launch over a level of `win`-pixel windows at `step` instantiates and how it is set up, decided here
+// once (k_stage.hip): the launcher (launch_stage_impl) and the record of the launch (Pass::run_dense, jdaStageLaunches,
+// jdaStageLaunchFor) both ask this.  acc: the register width of the regression sums, the smallest of 12 / 32 / 64 / 160
+// that holds dim; glb: the padded pixel tile of 16 x 16 windows exceeds pix_cap, pixels come through the caches
+// (pix_bytes = 0); pitch: the tile's row pitch, a multiple of 16 and never of 128; chunk: carts staged in LDS at a
+// time, 4..64 (0: not even four fit under lds_max, nothing is launched); lds_bytes: the launch's dynamic LDS.
+struct StageChoice { int acc, chunk, pitch, pix_bytes, lds_bytes; bool glb; };
+StageChoice stage_choice(int win, int step, int dim, int node_n, int leaf_n, int K, int real_bytes, int pix_cap, int lds_max);
+// Dense mode takes the model at all (Pass::dense_ok's part that depends on the model alone): at most 160 shape
+// coordinates and 256 leaves, and the LDS floor -- a 4-cart chunk without a pixel tile -- within lds_max.  *pix_cap:
+// min(pix_max, what the floor leaves of lds_max), the largest pixel tile a launch may put in LDS.
+bool stage_model_ok(int dim, int node_n, int leaf_n, int real_bytes, int pix_max, int lds_max, int* pix_cap);
 
 // Device -> mapped pinned host memory by a kernel on `stream` (instead of the copy engine): up to 4 segments, 16-byte
 // aligned.

@@ -122,19 +122,21 @@ template <typename Real> bool Pass<Real>::dense_ok(int* pix_cap, int* lds_max) c
   constexpr int dialect = Sel<Real>::dialect;
   const long long dense_env = kn().dense;                       // 0 off, 1 auto, 2 always
   *lds_max = (int)kn().dense_lds_max;
-  const int dim = hm().dim();
-  const int fixed = (int)stage_lds_bytes(dim, hm().node_n(), hm().leaf_n(), (int)sizeof(Real));
-  *pix_cap = std::max(0, std::min<int>((int)kn().dense_pix, *lds_max - fixed));
-  return dense_env != 0 && !multi && !(dialect == JDA_DIALECT_CPP && c->similarity) &&
-         dim <= 160 && hm().leaf_n() <= 256 && fixed <= *lds_max;
+  const bool model_ok = stage_model_ok(hm().dim(), hm().node_n(), hm().leaf_n(), (int)sizeof(Real), (int)kn().dense_pix, *lds_max, pix_cap);
+  return dense_env != 0 && !multi && !(dialect == JDA_DIALECT_CPP && c->similarity) && model_ok;
 }
 template <typename Real> bool Pass<Real>::run_dense() {
   int pix_cap, lds_max;
   (void)dense_ok(&pix_cap, &lds_max);
   count_form(JDA_FINISH_DENSE);
   for (int t = 0; t < hm().T; t++)
-    for (int l = 0; l < pe->hp.n_levels; l++)
+    for (int l = 0; l < pe->hp.n_levels; l++) {
+      // counted for jdaStageLaunches under the key of what the launcher instantiates: the same function on the same arguments
+      const DevLevel& lv = pe->hp.lv[l];
+      const StageChoice sc = stage_choice(lv.win, lv.step, model().dim, model().node_n, model().leaf_n, model().K, (int)sizeof(Real), pix_cap, lds_max);
+      if (sc.chunk != 0) c->stage_launches[stage_launch_key(Sel<Real>::dialect, want_trace(), sc)].fetch_add(1, std::memory_order_relaxed);
       JDA_HIP(launch_stage<Real>(want_trace(), l, t, apply_th, th, pe->dp, pe->hp, model(), w, pix_cap, lds_max, st));
+    }
   return true;
 }
 template <typename Real> bool Pass<Real>::clear_counters() {

@@ -101,6 +101,59 @@ def test_finish_launches_entries_and_their_python_mirror(built, model_file):
     c.close()
 
 
+def test_stage_launches_entries_and_their_python_mirror(built, model_file):
+    """jdaStageLaunches and jdaStageLaunchFor (include/jda.h): exported; JDA_STAGE_LAUNCH_N counts indexed by JDA_STAGE_LAUNCH,
+    which the Python mirror (api.StageLaunch.index) restates field for field -- checked against the macro itself, evaluated
+    from the header's text; nothing counted on a cascador that has run nothing; null arguments, an unknown dialect, a window
+    or step below 1, a declined model and a declined dialect refused.  No GPU needed."""
+    from jda_amd import api, synth
+    assert {"jdaStageLaunches", "jdaStageLaunchFor"} <= set(declared_symbols())
+    src = open(HEADER).read()
+    assert int(re.search(r"#define JDA_STAGE_LAUNCH_N (\d+)", src).group(1)) == api.STAGE_LAUNCH_N == 2 * 2 * 2 * 4 * 5
+    mac = re.search(r"#define JDA_STAGE_LAUNCH\(([^)]*)\)\s*\\\n(.*)\n", src)
+    args = mac.group(1).replace(" ", "").split(",")
+    assert tuple(args) == tuple(f for f, _ in api.STAGE_LAUNCH_FIELDS) == api.StageLaunch._fields
+    for field, values, fmt in (("acc", (12, 32, 64, 160), "JDA_STAGE_ACC_%d"), ("chunk", (4, 8, 16, 32, 64), "JDA_STAGE_CHUNK_%d")):
+        assert dict(api.STAGE_LAUNCH_FIELDS)[field] == values
+        for i, v in enumerate(values):
+            assert int(re.search(r"\b%s = (\d+)" % (fmt % v), src).group(1)) == i, (field, v)
+    body = re.sub(r"\b(%s)\b" % "|".join(args), lambda m_: "a[%r]" % m_.group(1), mac.group(2))      # the macro's body is integer arithmetic
+    seen = set()
+    for i in range(api.STAGE_LAUNCH_N):
+        f = api.StageLaunch.of_index(i)
+        a = {n: dict(api.STAGE_LAUNCH_FIELDS)[n].index(v) for n, v in zip(api.StageLaunch._fields, f)}
+        assert f.index() == i == eval(body, {"a": a}), f
+        seen.add(f)
+    assert len(seen) == api.STAGE_LAUNCH_N
+    p, _ = model_file((2, 8, 5, 3), 8, seed=1)
+    c = api.Cascador(p)
+    assert c.stage_launches() == {}
+    assert api.lib.jdaStageLaunches(c.h, None) == -1 and api.lib.jdaStageLaunches(None, (C.c_longlong * api.STAGE_LAUNCH_N)()) == -1
+    lds = C.c_int(-7)
+    # dim 10, 3 nodes and 4 leaves a tree, 24-pixel windows 2 apart: a 64 x 54 byte tile; the smallest tier (32 KB) holds
+    # 64-cart chunks in fp32 (32,176 bytes) and 16-cart chunks in fp64 (32,480; 32 carts: 40,928)
+    lds_of = lambda rb, nb, ch: 3456 + 10 * 256 * rb + ch * 3 * nb + ch * 4 * rb + ch * 4 * rb + (((ch * 4 * 10 + 12) * rb + 15) & ~15)
+    assert (lds_of(4, 32, 64), lds_of(8, 48, 16), lds_of(8, 48, 32)) == (32176, 32480, 40928) and 32480 <= 32768 < 40928
+    for dial, rb, nb, ch in (("C", 4, 32, 64), ("CPP", 8, 48, 16)):
+        for trace in (False, True):
+            assert c.stage_launch_for(dial, trace, 24, 2) == (api.StageLaunch(dial, trace, False, 12, ch), lds_of(rb, nb, ch)), (dial, trace)
+    assert c.stage_launch_for("C", False, 150, 15)[0] == api.StageLaunch("C", False, True, 12, 64)
+    assert api.lib.jdaStageLaunchFor(c.h, 0, 0, 24, 2, None) == api.StageLaunch("C", False, False, 12, 64).index()     # (lds_bytes may be null)
+    for bad in ((None, 0, 0, 24, 2), (c.h, 2, 0, 24, 2), (c.h, -1, 0, 24, 2), (c.h, 0, 0, 0, 2), (c.h, 0, 0, 24, 0)):
+        assert api.lib.jdaStageLaunchFor(*bad, C.byref(lds)) == -1 and lds.value == -7, bad
+    for bad in (("C", False, 0, 2), ("C", False, 24, 0), (2, False, 24, 2)):      # the Python mirror: bad arguments raise, a declined model is None
+        with pytest.raises(api.JdaError):
+            c.stage_launch_for(*bad)
+    c.set_similarity_transform(True)                       # declines dialect CPP alone
+    assert c.stage_launch_for("CPP", False, 24, 2) is None and c.stage_launch_for("C", False, 24, 2) is not None
+    c.close()
+    for dims, kw in (((2, 3, 78, 2), {}), ((2, 3, 2, 10), {}), ((2, 3, 5, 3), dict(multi_scale=True))):      # LDS floor, 512 leaves, multi-scale
+        p, _ = model_file(dims, 8, seed=1, **kw)
+        c = api.Cascador(p)
+        assert c.stage_launch_for("C", False, 24, 2) is None and c.stage_launch_for("CPP", True, 24, 2) is None, dims
+        c.close()
+
+
 def test_header_is_plain_c_and_links(built, tmp_path):
     """What a maintainer of the reference would do: compile a C caller against
     include/jda.h and link libjda.so (no torch, no C++)."""

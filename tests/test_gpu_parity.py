@@ -527,6 +527,11 @@ def test_dialects_agree_where_they_must(built, gpu, tmp_path, kernel, dims, win,
     a, fa = _forms(c, c.trace, frames, scale=np.float32(scale), min_size=win, max_size=win)
     b, fb = _forms(c, c.trace_cpp, frames, minimum_size=win, step=step, factor=100.0)
     print(kernel, "forms:", fa, fb)
+    if kernel == "k_stage":
+        # one level, a traced pass in each dialect: T launches under the level's key each
+        assert c.stage_launches() == {c.stage_launch_for(dl, True, win, step)[0]: dims[0] for dl in ("C", "CPP")}, c.stage_launches()
+    else:
+        assert c.stage_launches() == {}
     want = DIFF_FORMS[kernel]
     assert fa and fb and set(fa) <= want and set(fb) <= want, (kernel, fa, fb)
     n = n_frames * ((w - win) // step + 1) * ((h - win) // step + 1)
@@ -809,6 +814,16 @@ def test_plan_cache_is_bounded(built, gpu, model_file, monkeypatch):
 
 # ---------------------------------------------------------------- dense mode (k_stage)
 
+def _stage_keys(c, dialect, L, traces, T):
+    """What the dense passes of cascador c launched (jdaStageLaunches): k_stage ran, in `dialect`
+    alone, with the ACC class of 2 * L shape coordinates, traced and not as `traces` says, T launches a level."""
+    sl = c.stage_launches()
+    print("k_stage launches:", sorted(sl.items()))
+    assert sl and all(k.dialect == dialect and k.acc == min(a for a in (12, 32, 64, 160) if a >= 2 * L) for k in sl), sl
+    assert (traces is None or {k.trace for k in sl} == set(traces)) and all(v % T == 0 for v in sl.values()), sl
+    return sl
+
+
 @pytest.mark.parametrize("dims,cart_th", [((3, 70, 9, 5), None), ((3, 70, 9, 5), -0.4), ((2, 130, 27, 4), -0.2),
                                           ((4, 12, 40, 3), None)])
 def test_dense_mode_is_a_third_implementation_of_the_walk(built, gpu, model_file, monkeypatch, dims, cart_th):
@@ -843,6 +858,20 @@ def test_dense_mode_is_a_third_implementation_of_the_walk(built, gpu, model_file
         if mode == "2" or cart_th is None:
             assert s["dense_passes"] >= 1, "dense mode did not run"
             assert f.get("DENSE", 0) >= 1 and (mode == "1" or set(f) == {"DENSE"}), f
+            sl = _stage_keys(c, "C", dims[2], (False, True) if mode == "2" else None, dims[0])
+            if mode == "2":
+                # every call of this cascador ran dense: two traces and a detect call, T launches a level each, tile and global
+                lv = synth.levels_c(333, 250)[0]
+                want = {}
+                for trace, n in ((True, 2), (False, 1)):
+                    for l in lv:
+                        k = c.stage_launch_for("C", trace, l["win"], l["step"])[0]
+                        want[k] = want.get(k, 0) + n * dims[0]
+                assert sl == want and {k.glb for k in sl} == {False, True}, (sl, want)
+                # the chunk classes these models reach: tile / global
+                assert {(k.glb, k.chunk) for k in sl} == {(3, 70, 9, 5): {(False, 4), (True, 16)}, (2, 130, 27, 4): {(False, 4), (True, 8)},
+                                                          (4, 12, 40, 3): {(False, 32), (True, 32)}}[dims], sl
+    assert c0.stage_launches() == {}
 
 
 def test_dense_mode_dialect_cpp(built, gpu, model_file, monkeypatch):
@@ -854,6 +883,11 @@ def test_dense_mode_dialect_cpp(built, gpu, model_file, monkeypatch):
     c, o = api.Cascador(p), Oracle(p)
     g, f = _forms(c, c.trace_cpp, frames, 20, 5, 1.2)
     assert f == {"DENSE": 1}, f
+    want = {}
+    for l in synth.levels_cpp(200, 150, 20, 5, 1.2)[0]:
+        k = c.stage_launch_for("CPP", True, l["win"], l["step"])[0]
+        want[k] = want.get(k, 0) + 3
+    assert _stage_keys(c, "CPP", 5, (True,), 3) == want, want
     off = 0
     for i in range(len(frames)):
         r = o.trace_cpp(frames[i], 20, 5, 1.2)
@@ -947,6 +981,16 @@ def test_two_lanes_dialect_cpp_and_dense_mode(built, gpu, model_file, monkeypatc
         tr2 = c2.trace_cpp(frames, 20, 5, 1.2)
         for k in tr1:
             assert same(tr1[k], tr2[k]), (env, k)
+        if env.get("JDA_DENSE") == "2":
+            # two lanes, a pass each, in the detect call and in the trace: 2 x T launches a level
+            want_sl = {}
+            for trace in (False, True):
+                for l in synth.levels_cpp(220, 170, 20, 5, 1.2)[0]:
+                    key = c2.stage_launch_for("CPP", trace, l["win"], l["step"])[0]
+                    want_sl[key] = want_sl.get(key, 0) + 2 * 3
+            assert _stage_keys(c2, "CPP", 9, (False, True), 3) == want_sl, want_sl
+        else:
+            assert c2.stage_launches() == {}
         for k in env:
             monkeypatch.delenv(k)
         monkeypatch.setenv("JDA_SIDE_STREAM", "0")
@@ -1289,6 +1333,9 @@ def test_submit_wait_all_pass_model_takes_the_dense_path(built, gpu, model_file)
     for a, b in zip(got, want):
         _compare_detect(a, b)
     assert sg["cart_total_n"] == sw["cart_total_n"] and sg["dense_passes"] >= 1
+    sl = _stage_keys(c, "C", 5, (False,), 2)
+    assert set(sl) == {c.stage_launch_for("C", False, l["win"], l["step"])[0] for l in synth.levels_c(200, 150)[0]}, sl
+    assert set(sl) == {api.StageLaunch("C", False, False, 12, 16), api.StageLaunch("C", False, True, 12, 32)}, sl
 
 
 def test_submit_host_frames_pageable_and_pinned(built, gpu, model_file):

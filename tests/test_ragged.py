@@ -131,6 +131,10 @@ def test_ragged_models_outside_the_fast_scan_run_image_by_image(built, gpu, mode
         for a, b in zip(got, want):
             _eq(a, b)
     assert dense[0] == 0 and dense[1] > 0, dense
+    sl = c3.stage_launches()                     # (jdaStageLaunches: the per-image dense passes ran k_stage, 3 launches a level)
+    assert sl and all(k.dialect == "C" and k.acc == 12 and not k.trace and v % 3 == 0 for k, v in sl.items()), sl
+    assert set(sl) == {api.StageLaunch("C", False, False, 12, 16), api.StageLaunch("C", False, True, 12, 32)}, sl
+    assert c.stage_launches() == {}              # (dense mode declines a multi-scale model)
 
 
 def test_ragged_fddb_sized_job_shipped_dims(built, gpu, tmp_path):

@@ -313,6 +313,9 @@ def test_bounded_queues_overflow_is_noticed_and_the_pass_rerun(built, model_file
     ga, sa = ca.detect_batch_device(d, th=0.0, stats=True)
     wa = c0.detect_batch_device(d, th=0.0)
     assert sa["dense_passes"] >= 1
+    sl = ca.stage_launches()                     # (jdaStageLaunches: k_stage ran, dialect C, 10 shape coordinates, no trace)
+    assert sl and all(k.dialect == "C" and k.acc == 12 and not k.trace for k in sl) and c0.stage_launches().keys() <= sl.keys(), sl
+    assert set(sl) == {api.StageLaunch("C", False, False, 12, 32), api.StageLaunch("C", False, True, 12, 64)}, sl
     for a, b in zip(ga, wa):
         for k in ("bboxes", "scores", "shapes"):
             assert same(a[k], b[k]), k
@@ -387,6 +390,9 @@ def test_reruns_in_a_row_on_one_cascador_overflow_then_sized_then_dense(built, m
         got, st = call(c)
         check(got, st, mode + " 3")
         assert st["dense_passes"] >= 1, (mode, st)
+        sl = c.stage_launches()                  # (only call 3 went dense: what it launched is all there is)
+        assert sl and all(k.dialect == "C" and not k.trace and v % 3 == 0 for k, v in sl.items()), (mode, sl)
+        assert set(sl) == {api.StageLaunch("C", False, False, 12, 16), api.StageLaunch("C", False, True, 12, 32)}, (mode, sl)
         assert (st["ws_regrows"] >= 1) == predicted, (mode, st)
         c.close()
 
