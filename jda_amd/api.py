@@ -22,81 +22,47 @@ JDA_DIALECT_C = 0
 JDA_DIALECT_CPP = 1
 # include/jda.h: JDA_FINISH_*, the finishing forms a pass can take, in the order of jdaFinishForms' counts
 FINISH_FORMS = ("WIDE_CONC", "WIDE_SEQ", "MERGED", "FILTER0", "MID_DIRECT", "TWO_LAUNCH", "DENSE")
+
+
+def _launch_key(name, fields, doc):
+    """The namedtuple of one launch report's key: `fields` are (name, values in index order) in the order of the header's
+    index macro, whose mixed-radix index the class computes (index) and takes apart (of_index)."""
+    def index(self):
+        i = 0
+        for (_, values), v in zip(fields, self):
+            i = i * len(values) + values.index(v)
+        return i
+
+    def of_index(cls, i):
+        out = []
+        for _, values in reversed(fields):
+            out.append(values[i % len(values)])
+            i //= len(values)
+        return cls(*reversed(out))
+
+    base = collections.namedtuple(name, [f for f, _ in fields])
+    return type(name, (base,), dict(__slots__=(), __doc__=doc, index=index, of_index=classmethod(of_index)))
+
+
 # include/jda.h: the fields of a scan form's key in the order of JDA_SCAN_FORM, each with its values in index order
 SCAN_FORM_FIELDS = (("kernel", ("k_scan", "k_scan_p")), ("dialect", ("C", "CPP")), ("depth", (4, 6, 0)),
                     ("pix", ("T16_256", "T16_512", "T21", "GLB")), ("ragged", (False, True)), ("lean", (False, True)),
                     ("trace", (False, True)), ("merged", (False, True)))
 SCAN_FORM_N = 768
-
-
-class ScanForm(collections.namedtuple("ScanForm", [f for f, _ in SCAN_FORM_FIELDS])):
-    """The key of one scan instantiation (include/jda.h: JDA_SCAN_FORM); depth 0 = the generic walk."""
-    __slots__ = ()
-
-    def index(self):
-        i = 0
-        for (_, values), v in zip(SCAN_FORM_FIELDS, self):
-            i = i * len(values) + values.index(v)
-        return i
-
-    @classmethod
-    def of_index(cls, i):
-        out = []
-        for _, values in reversed(SCAN_FORM_FIELDS):
-            out.append(values[i % len(values)])
-            i //= len(values)
-        return cls(*reversed(out))
-
-
+ScanForm = _launch_key("ScanForm", SCAN_FORM_FIELDS,
+                       "The key of one scan instantiation (include/jda.h: JDA_SCAN_FORM); depth 0 = the generic walk.")
 # include/jda.h: the fields of a finishing launch's key in the order of JDA_FINISH_LAUNCH, each with its values in index order
 FINISH_LAUNCH_FIELDS = (("kernel", ("k_finish", "k_filter0")), ("dialect", ("C", "CPP")), ("trace", (False, True)),
                         ("groups", (0, 1, 2, 3, 4)), ("multi", (False, True)), ("st", (False, True)), ("stream", (False, True)),
                         ("survivors", (False, True)), ("carry", (False, True)), ("tile", (False, True)))
 FINISH_LAUNCH_N = 2560
-
-
-class FinishLaunch(collections.namedtuple("FinishLaunch", [f for f, _ in FINISH_LAUNCH_FIELDS])):
-    """The key of one k_finish / k_filter0 launch (include/jda.h: JDA_FINISH_LAUNCH); groups 0 = k_filter0."""
-    __slots__ = ()
-
-    def index(self):
-        i = 0
-        for (_, values), v in zip(FINISH_LAUNCH_FIELDS, self):
-            i = i * len(values) + values.index(v)
-        return i
-
-    @classmethod
-    def of_index(cls, i):
-        out = []
-        for _, values in reversed(FINISH_LAUNCH_FIELDS):
-            out.append(values[i % len(values)])
-            i //= len(values)
-        return cls(*reversed(out))
-
-
+FinishLaunch = _launch_key("FinishLaunch", FINISH_LAUNCH_FIELDS,
+                           "The key of one k_finish / k_filter0 launch (include/jda.h: JDA_FINISH_LAUNCH); groups 0 = k_filter0.")
 # include/jda.h: the fields of a k_stage launch's key in the order of JDA_STAGE_LAUNCH, each with its values in index order
 STAGE_LAUNCH_FIELDS = (("dialect", ("C", "CPP")), ("trace", (False, True)), ("glb", (False, True)), ("acc", (12, 32, 64, 160)),
                        ("chunk", (4, 8, 16, 32, 64)))
 STAGE_LAUNCH_N = 160
-
-
-class StageLaunch(collections.namedtuple("StageLaunch", [f for f, _ in STAGE_LAUNCH_FIELDS])):
-    """The key of one k_stage launch (include/jda.h: JDA_STAGE_LAUNCH)."""
-    __slots__ = ()
-
-    def index(self):
-        i = 0
-        for (_, values), v in zip(STAGE_LAUNCH_FIELDS, self):
-            i = i * len(values) + values.index(v)
-        return i
-
-    @classmethod
-    def of_index(cls, i):
-        out = []
-        for _, values in reversed(STAGE_LAUNCH_FIELDS):
-            out.append(values[i % len(values)])
-            i //= len(values)
-        return cls(*reversed(out))
+StageLaunch = _launch_key("StageLaunch", STAGE_LAUNCH_FIELDS, "The key of one k_stage launch (include/jda.h: JDA_STAGE_LAUNCH).")
 
 
 class JdaError(RuntimeError):

@@ -24,6 +24,14 @@ int rows_out(Cascador* c, int rc, RowsOut<typename D::Real>& v, typename D::Real
   if (!*rows) { *n_rows = 0; fail("out of memory for the detection rows"); return -1; }
   return 0;
 }
+// One launch report (host.h: LaunchLog) -> the caller's array.
+template <int N>
+int launch_report(const char* who, void* cascador, std::atomic<long long> (LaunchLog::*report)[N], long long* counts) {
+  Cascador* c = (Cascador*)cascador;
+  if (!c || !counts) { fail(std::string(who) + ": null cascador or counts"); return -1; }
+  LaunchLog::copy_out(c->log.*report, counts);
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -208,24 +216,15 @@ long long jdaGetOption(void* cascador, const char* key) try {
 } JDA_ABI_CATCH(-1)
 
 int jdaFinishForms(void* cascador, long long counts[JDA_FINISH_FORM_N]) try {
-  Cascador* c = (Cascador*)cascador;
-  if (!c || !counts) { fail("jdaFinishForms: null cascador or counts"); return -1; }
-  for (int f = 0; f < JDA_FINISH_FORM_N; f++) counts[f] = c->finish_forms[f].load(std::memory_order_relaxed);
-  return 0;
+  return launch_report("jdaFinishForms", cascador, &LaunchLog::finish_forms, counts);
 } JDA_ABI_CATCH(-1)
 
 int jdaScanForms(void* cascador, long long counts[JDA_SCAN_FORM_N]) try {
-  Cascador* c = (Cascador*)cascador;
-  if (!c || !counts) { fail("jdaScanForms: null cascador or counts"); return -1; }
-  for (int f = 0; f < JDA_SCAN_FORM_N; f++) counts[f] = c->scan_forms[f].load(std::memory_order_relaxed);
-  return 0;
+  return launch_report("jdaScanForms", cascador, &LaunchLog::scan_forms, counts);
 } JDA_ABI_CATCH(-1)
 
 int jdaFinishLaunches(void* cascador, long long counts[JDA_FINISH_LAUNCH_N]) try {
-  Cascador* c = (Cascador*)cascador;
-  if (!c || !counts) { fail("jdaFinishLaunches: null cascador or counts"); return -1; }
-  for (int f = 0; f < JDA_FINISH_LAUNCH_N; f++) counts[f] = c->finish_launches[f].load(std::memory_order_relaxed);
-  return 0;
+  return launch_report("jdaFinishLaunches", cascador, &LaunchLog::finish_launches, counts);
 } JDA_ABI_CATCH(-1)
 
 int jdaFinishTileWin(void* cascador, int dialect) try {
@@ -239,10 +238,7 @@ int jdaFinishTileWin(void* cascador, int dialect) try {
 } JDA_ABI_CATCH(-1)
 
 int jdaStageLaunches(void* cascador, long long counts[JDA_STAGE_LAUNCH_N]) try {
-  Cascador* c = (Cascador*)cascador;
-  if (!c || !counts) { fail("jdaStageLaunches: null cascador or counts"); return -1; }
-  for (int f = 0; f < JDA_STAGE_LAUNCH_N; f++) counts[f] = c->stage_launches[f].load(std::memory_order_relaxed);
-  return 0;
+  return launch_report("jdaStageLaunches", cascador, &LaunchLog::stage_launches, counts);
 } JDA_ABI_CATCH(-1)
 
 int jdaStageLaunchFor(void* cascador, int dialect, int trace, int win, int step, int* lds_bytes) try {
@@ -251,7 +247,7 @@ int jdaStageLaunchFor(void* cascador, int dialect, int trace, int win, int step,
     fail("jdaStageLaunchFor: null cascador, unknown dialect, or a window or step below 1"); return -1;
   }
   std::lock_guard<std::mutex> lk(c->mu);             // (multi_scale() caches its answer in the model on first use)
-  // (what Pass::dense_ok and launch_stage decide: the same functions on the same model and the same constants)
+  // (what Pass::dense_ok and launch_stage would decide: their functions, on the same model and the same constants, without a device)
   const int real_bytes = dialect == JDA_DIALECT_C ? 4 : 8, lds_max = (int)Knobs::dense_lds_max;
   int pix_cap = 0;
   if (c->hm.multi_scale() || (dialect == JDA_DIALECT_CPP && c->similarity) ||

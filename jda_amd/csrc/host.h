@@ -500,12 +500,96 @@ struct Lane {
   }
 };
 
-// A k_stage launch's index in jdaStageLaunches' counts, from what stage_choice (kernels.h) decided for it.
-inline int stage_launch_key(int dialect, bool trace, const StageChoice& s) {
+// ---- the launch reports (include/jda.h: jdaFinishForms, jdaScanForms, jdaFinishLaunches, jdaStageLaunches) ----
+// A launcher says what it launched in a record (kernels.h: ScanLaunch, FinishLaunch, WideLaunch, StageChoice); here, and
+// nowhere else, a record becomes the public index of its report and is counted.
+
+// A scan launch's index in jdaScanForms' counts.
+constexpr int scan_form_key(int dialect, const ScanLaunch& s) {
+  const int depth = s.depth == 4 ? JDA_SCAN_DEPTH_4 : (s.depth == 6 ? JDA_SCAN_DEPTH_6 : JDA_SCAN_DEPTH_GENERIC);
+  const int pix = s.mode == 2 ? JDA_SCAN_GLB : (s.mode == 3 ? JDA_SCAN_T21 : (s.block >= 512 ? JDA_SCAN_T16_512 : JDA_SCAN_T16_256));
+  return JDA_SCAN_FORM(s.persistent ? JDA_SCAN_K_SCAN_P : JDA_SCAN_K_SCAN, dialect, depth, pix, s.ragged ? 1 : 0, s.lean ? 1 : 0,
+                       s.trace ? 1 : 0, s.merged ? 1 : 0);
+}
+// A k_finish / k_filter0 launch's index in jdaFinishLaunches' counts.
+constexpr int finish_launch_key(int dialect, const FinishLaunch& f) {
+  return JDA_FINISH_LAUNCH(f.filter0 ? JDA_FINISH_K_FILTER0 : JDA_FINISH_K_FINISH, dialect, f.trace ? 1 : 0, f.groups, f.multi ? 1 : 0,
+                           f.st ? 1 : 0, f.stream ? 1 : 0, f.survivors ? 1 : 0, f.carry ? 1 : 0, f.tile ? 1 : 0);
+}
+// A k_stage launch's index in jdaStageLaunches' counts (jdaStageLaunchFor: of the choice a launch would make).
+constexpr int stage_launch_key(int dialect, bool trace, const StageChoice& s) {
   const int acc = s.acc == 12 ? JDA_STAGE_ACC_12 : (s.acc == 32 ? JDA_STAGE_ACC_32 : (s.acc == 64 ? JDA_STAGE_ACC_64 : JDA_STAGE_ACC_160));
   const int chunk = s.chunk == 4 ? JDA_STAGE_CHUNK_4 : (s.chunk == 8 ? JDA_STAGE_CHUNK_8 : (s.chunk == 16 ? JDA_STAGE_CHUNK_16 : (s.chunk == 32 ? JDA_STAGE_CHUNK_32 : JDA_STAGE_CHUNK_64)));
   return JDA_STAGE_LAUNCH(dialect, trace ? 1 : 0, s.glb ? 1 : 0, acc, chunk);
 }
+namespace launch_key_check {
+// every field at its first and at its last value, alone and together; the last index of a report is its size - 1
+constexpr ScanLaunch scan(bool persistent, int depth, int mode, int block, bool ragged, bool lean, bool trace, bool merged) {
+  return ScanLaunch{true, persistent, depth, mode, block, ragged, lean, trace, merged};
+}
+static_assert(scan_form_key(JDA_DIALECT_C, scan(false, 4, 1, 256, false, false, false, false)) == 0, "every field at its first value");
+static_assert(scan_form_key(JDA_DIALECT_CPP, scan(true, 0, 2, 256, true, true, true, true)) == JDA_SCAN_FORM_N - 1, "every field at its last value");
+static_assert(scan_form_key(JDA_DIALECT_C, scan(false, 4, 1, 256, false, false, false, true)) == 1 &&
+              scan_form_key(JDA_DIALECT_C, scan(false, 4, 1, 256, false, false, true, false)) == 2 &&
+              scan_form_key(JDA_DIALECT_C, scan(false, 4, 1, 256, false, true, false, false)) == 4 &&
+              scan_form_key(JDA_DIALECT_C, scan(false, 4, 1, 256, true, false, false, false)) == 8, "merged, trace, lean, ragged");
+static_assert(scan_form_key(JDA_DIALECT_C, scan(false, 4, 1, 512, false, false, false, false)) == 16 * JDA_SCAN_T16_512 &&
+              scan_form_key(JDA_DIALECT_C, scan(false, 4, 3, 256, false, false, false, false)) == 16 * JDA_SCAN_T21 &&
+              scan_form_key(JDA_DIALECT_C, scan(false, 4, 3, 512, false, false, false, false)) == 16 * JDA_SCAN_T21 &&
+              scan_form_key(JDA_DIALECT_C, scan(false, 4, 2, 256, false, false, false, false)) == 16 * JDA_SCAN_GLB &&
+              scan_form_key(JDA_DIALECT_C, scan(false, 4, 2, 512, false, false, false, false)) == 16 * JDA_SCAN_GLB,
+              "pix: the workgroup size tells the two 16-bit tile forms apart, modes 2 and 3 have one form each");
+static_assert(scan_form_key(JDA_DIALECT_C, scan(true, 4, 1, 448, false, false, false, false)) == 384 &&
+              scan_form_key(JDA_DIALECT_C, scan(true, 4, 1, 1024, false, false, false, false)) == 384 + 16,
+              "k_scan_p: fewer than 512 threads / 512 or more");
+static_assert(scan_form_key(JDA_DIALECT_C, scan(false, 6, 1, 256, false, false, false, false)) == 64 * JDA_SCAN_DEPTH_6 &&
+              scan_form_key(JDA_DIALECT_C, scan(false, 0, 1, 256, false, false, false, false)) == 64 * JDA_SCAN_DEPTH_GENERIC &&
+              scan_form_key(JDA_DIALECT_CPP, scan(false, 4, 1, 256, false, false, false, false)) == 192, "depth 6, the generic walk, dialect");
+constexpr FinishLaunch fin(bool filter0, bool trace, int groups, bool multi, bool st, bool stream, bool survivors, bool carry, bool tile) {
+  return FinishLaunch{true, filter0, trace, groups, multi, st, stream, survivors, carry, tile};
+}
+static_assert(finish_launch_key(JDA_DIALECT_C, fin(false, false, 0, false, false, false, false, false, false)) == 0, "every field at its first value");
+static_assert(finish_launch_key(JDA_DIALECT_CPP, fin(true, true, 4, true, true, true, true, true, true)) == JDA_FINISH_LAUNCH_N - 1, "every field at its last value");
+static_assert(finish_launch_key(JDA_DIALECT_C, fin(false, false, 0, false, false, false, false, false, true)) == 1 &&
+              finish_launch_key(JDA_DIALECT_C, fin(false, false, 0, false, false, false, false, true, false)) == 2 &&
+              finish_launch_key(JDA_DIALECT_C, fin(false, false, 0, false, false, false, true, false, false)) == 4 &&
+              finish_launch_key(JDA_DIALECT_C, fin(false, false, 0, false, false, true, false, false, false)) == 8 &&
+              finish_launch_key(JDA_DIALECT_C, fin(false, false, 0, false, true, false, false, false, false)) == 16 &&
+              finish_launch_key(JDA_DIALECT_C, fin(false, false, 0, true, false, false, false, false, false)) == 32, "tile, carry, survivors, stream, st, multi");
+static_assert(finish_launch_key(JDA_DIALECT_C, fin(false, false, 1, false, false, false, false, false, false)) == 64 &&
+              finish_launch_key(JDA_DIALECT_C, fin(false, false, 4, false, false, false, false, false, false)) == 256 &&
+              finish_launch_key(JDA_DIALECT_C, fin(false, true, 0, false, false, false, false, false, false)) == 320 &&
+              finish_launch_key(JDA_DIALECT_CPP, fin(false, false, 0, false, false, false, false, false, false)) == 640 &&
+              finish_launch_key(JDA_DIALECT_C, fin(true, false, 0, false, false, false, false, false, false)) == 1280, "groups 1 and 4, trace, dialect, k_filter0");
+constexpr StageChoice stage(int acc, int chunk, bool glb) { return StageChoice{acc, chunk, 0, 0, 0, glb}; }
+static_assert(stage_launch_key(JDA_DIALECT_C, false, stage(12, 4, false)) == 0, "every field at its first value");
+static_assert(stage_launch_key(JDA_DIALECT_CPP, true, stage(160, 64, true)) == JDA_STAGE_LAUNCH_N - 1, "every field at its last value");
+static_assert(stage_launch_key(JDA_DIALECT_C, false, stage(12, 8, false)) == 1 && stage_launch_key(JDA_DIALECT_C, false, stage(12, 64, false)) == 4 &&
+              stage_launch_key(JDA_DIALECT_C, false, stage(32, 4, false)) == 5 && stage_launch_key(JDA_DIALECT_C, false, stage(160, 4, false)) == 15 &&
+              stage_launch_key(JDA_DIALECT_C, false, stage(12, 4, true)) == 20 && stage_launch_key(JDA_DIALECT_C, true, stage(12, 4, false)) == 40 &&
+              stage_launch_key(JDA_DIALECT_CPP, false, stage(12, 4, false)) == 80, "chunk 8 and 64, acc 32 and 160, glb, trace, dialect");
+}  // namespace launch_key_check
+
+// The four reports of a cascador: cumulative counts, added atomically where a pass has issued a launch (or, the five
+// path forms, is about to issue its launches).  count() holds the only additions.
+struct LaunchLog {
+  std::atomic<long long> finish_forms[JDA_FINISH_FORM_N] = {};        // jdaFinishForms
+  std::atomic<long long> scan_forms[JDA_SCAN_FORM_N] = {};            // jdaScanForms
+  std::atomic<long long> finish_launches[JDA_FINISH_LAUNCH_N] = {};   // jdaFinishLaunches
+  std::atomic<long long> stage_launches[JDA_STAGE_LAUNCH_N] = {};     // jdaStageLaunches
+  // a finishing form that is a decision of the pass, not of a launcher: MERGED, FILTER0, MID_DIRECT, TWO_LAUNCH, DENSE
+  void count_form(int form) { add(finish_forms, form); }
+  // a launcher's record; one that launched nothing counts nothing
+  void count(int dialect, const ScanLaunch& s) { if (s.launched) add(scan_forms, scan_form_key(dialect, s)); }
+  void count(int dialect, const FinishLaunch& f) { if (f.launched) add(finish_launches, finish_launch_key(dialect, f)); }
+  void count(int, const WideLaunch& w) { if (w.launched) add(finish_forms, w.conc ? JDA_FINISH_WIDE_CONC : JDA_FINISH_WIDE_SEQ); }
+  void count(int dialect, bool trace, const StageChoice& s) { add(stage_launches, stage_launch_key(dialect, trace, s)); }
+  template <int N> static void copy_out(const std::atomic<long long> (&a)[N], long long* counts) {
+    for (int i = 0; i < N; i++) counts[i] = a[i].load(std::memory_order_relaxed);
+  }
+ private:
+  static void add(std::atomic<long long>* a, int i) { a[i].fetch_add(1, std::memory_order_relaxed); }
+};
 
 struct Cascador {
   HostModel hm;
@@ -517,14 +601,7 @@ struct Cascador {
   // them, see PlanEntry::pred_tail
   double pred_tail = -1, pred_out = -1;
   bool last_dense = false;
-  // finishing forms the passes of this cascador have issued (jdaFinishForms): counted where the launches are issued
-  std::atomic<long long> finish_forms[JDA_FINISH_FORM_N] = {};
-  // scan launches the passes of this cascador have issued, by what they instantiate (jdaScanForms, JDA_SCAN_FORM)
-  std::atomic<long long> scan_forms[JDA_SCAN_FORM_N] = {};
-  // k_finish / k_filter0 launches the passes of this cascador have issued, by what they instantiate (jdaFinishLaunches, JDA_FINISH_LAUNCH)
-  std::atomic<long long> finish_launches[JDA_FINISH_LAUNCH_N] = {};
-  // k_stage launches the dense passes of this cascador have issued, by what they instantiate (jdaStageLaunches, JDA_STAGE_LAUNCH)
-  std::atomic<long long> stage_launches[JDA_STAGE_LAUNCH_N] = {};
+  LaunchLog log;               // what the passes of this cascador have launched (the four launch reports)
   int similarity = 0;          // dialect CPP: Config::with_similarity_transform (reference common.cpp:214)
   int device = -1;
   int n_cus = 256;             // compute units of the device

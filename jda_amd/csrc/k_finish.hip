@@ -389,24 +389,41 @@ __global__ __launch_bounds__(256) void k_filter0(const DevPlan* __restrict__ pla
 
 template <typename Real>
 hipError_t launch_filter0(bool trace, const DevPlan* d_plan, const DevModelT<Real>& m, const WorkT<Real>& w, long long n_hint,
-                          const S0Node* s0_table, hipStream_t stream) {
+                          const S0Node* s0_table, FinishLaunch* how, hipStream_t stream) {
   using DL = typename std::conditional<sizeof(Real) == 4, DialectC, DialectCPP>::type;
   const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>((n_hint + 7) / 8, 1 << 20));   // 4 waves x 2 windows
-  if (trace) hipLaunchKernelGGL((k_filter0<DL, true>), dim3(blocks), dim3(256), 0, stream, d_plan, m, w, s0_table);
-  else hipLaunchKernelGGL((k_filter0<DL, false>), dim3(blocks), dim3(256), 0, stream, d_plan, m, w, s0_table);
+  auto go = [&](auto trace_tag) {
+    constexpr bool TR = decltype(trace_tag)::value;
+    hipLaunchKernelGGL((k_filter0<DL, TR>), dim3(blocks), dim3(256), 0, stream, d_plan, m, w, s0_table);
+    *how = FinishLaunch{};
+    how->launched = how->filter0 = true; how->trace = TR; how->carry = w.m_leaf != nullptr;   // (carry: as the kernel reads it from w)
+  };
+  if (trace) go(std::true_type{}); else go(std::false_type{});
   return hipGetLastError();
 }
-template hipError_t launch_filter0<float>(bool, const DevPlan*, const DevModelT<float>&, const WorkT<float>&, long long, const S0Node*, hipStream_t);
-template hipError_t launch_filter0<double>(bool, const DevPlan*, const DevModelT<double>&, const WorkT<double>&, long long, const S0Node*, hipStream_t);
+template hipError_t launch_filter0<float>(bool, const DevPlan*, const DevModelT<float>&, const WorkT<float>&, long long, const S0Node*, FinishLaunch*, hipStream_t);
+template hipError_t launch_filter0<double>(bool, const DevPlan*, const DevModelT<double>&, const WorkT<double>&, long long, const S0Node*, FinishLaunch*, hipStream_t);
 
 namespace {
+// kG, the 64-cart groups a round walks: an instantiation each for 1..4.
+constexpr int finish_groups(int groups) { return groups >= 4 ? 4 : (groups == 3 ? 3 : (groups >= 2 ? 2 : 1)); }
+// STREAM (DevModelT::w_stream): only the form without trace, pyramid images and similarity transform has one.
+constexpr bool finish_stream(bool trace, bool multi, bool st, int w_stream) { return !trace && !multi && !st && w_stream != 0; }
+// Workgroups of a launch over a queue of capacity `cap` -- n_hint >= 0: the queue length is known on the host, one window
+// per workgroup (up to 1M workgroups, grid-stride beyond), so that the hardware dispatcher balances the very uneven
+// per-window cost; n_hint < 0: a fixed grid, windows dealt round-robin.  0: nothing is launched.
+inline unsigned finish_grid(long long n_hint, unsigned cap) {
+  if (n_hint >= 0) return (unsigned)(n_hint < (1 << 20) ? n_hint : (1 << 20));
+  return cap > 256u * 64u ? 256u * 64u : cap;
+}
+
 template <typename DL>
 hipError_t launch_finish_impl(bool trace, int t_begin, int t_end, bool apply_th, typename DL::Real th,
                               const DevPlan* d_plan, const DevModelT<typename DL::Real>& m,
                               const WorkT<typename DL::Real>& w, int groups, long long n_hint, const S0Node* s0_table,
-                              int tile_win, bool survivors, hipStream_t stream) {
+                              int tile_win, bool survivors, FinishLaunch* how, hipStream_t stream) {
   using Real = typename DL::Real;
-  // (every decision of this launch is a function of kernels.h, which the record of the launch asks too: Pass::finish)
+  *how = FinishLaunch{};                 // (nothing launched, until go says otherwise)
   const bool st = finish_st((int)sizeof(Real), m.similarity);
   const int multi = (w.half != nullptr) ? 1 : 0;
   tile_win = finish_tile_win(m.dim, m.K, (int)sizeof(Real), st, multi != 0, tile_win);
@@ -415,30 +432,34 @@ hipError_t launch_finish_impl(bool trace, int t_begin, int t_end, bool apply_th,
   const unsigned blocks = finish_grid(n_hint, t_begin == 0 && !survivors ? w.cap_q : w.cap_m);
   if (blocks == 0) return hipSuccess;
   groups = finish_groups(groups);
-  auto go = [&](auto kern) {
+  // (the record names the instantiation from the constants that select it, and the launch from what the kernel is handed:
+  // survivors, the leaf words of w, the tile)
+  auto go = [&](auto trace_tag, auto groups_tag, auto multi_tag, auto st_tag, auto stream_tag) {
+    constexpr bool TR = decltype(trace_tag)::value, MU = decltype(multi_tag)::value, STT = decltype(st_tag)::value;
+    constexpr bool STREAM = decltype(stream_tag)::value;
+    constexpr int G = decltype(groups_tag)::value;
+    auto kern = k_finish<DL, TR, G, MU, STT, STREAM>;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, d_plan, m, w, r, t_begin, t_end,
                        apply_th ? 1 : 0, th, s0_table, tile_win, survivors ? 1 : 0);
+    *how = FinishLaunch{true, false, TR, G, MU, STT, STREAM, survivors, survivors && w.m_leaf != nullptr, tile_win > 0};
   };
   // groups = 64-cart groups walked speculatively per round: 1 where most windows are
   // rejected within a few carts (throughput), 4 where most pass (latency)
+  auto pick_g = [&](auto trace_tag, auto multi_tag, auto st_tag, auto stream_tag) {
+    if (groups == 4) go(trace_tag, std::integral_constant<int, 4>{}, multi_tag, st_tag, stream_tag);
+    else if (groups == 3) go(trace_tag, std::integral_constant<int, 3>{}, multi_tag, st_tag, stream_tag);
+    else if (groups == 2) go(trace_tag, std::integral_constant<int, 2>{}, multi_tag, st_tag, stream_tag);
+    else go(trace_tag, std::integral_constant<int, 1>{}, multi_tag, st_tag, stream_tag);
+  };
   auto pick = [&](auto trace_tag, auto multi_tag, auto st_tag) {
     constexpr bool TR = decltype(trace_tag)::value, MU = decltype(multi_tag)::value;
     constexpr bool STT = decltype(st_tag)::value && sizeof(Real) == 8;
     if constexpr (!TR && !MU && !STT) {
       // a stage's weight rows far larger than L2 (DevModelT::w_stream): the form that reads them with non-temporal loads
-      if (finish_stream(TR, MU, STT, m.w_stream)) {
-        if (groups == 4) go(k_finish<DL, false, 4, false, false, true>);
-        else if (groups == 3) go(k_finish<DL, false, 3, false, false, true>);
-        else if (groups == 2) go(k_finish<DL, false, 2, false, false, true>);
-        else go(k_finish<DL, false, 1, false, false, true>);
-        return;
-      }
+      if (finish_stream(TR, MU, STT, m.w_stream)) { pick_g(trace_tag, multi_tag, std::false_type{}, std::true_type{}); return; }
     }
-    if (groups == 4) go(k_finish<DL, TR, 4, MU, STT>);
-    else if (groups == 3) go(k_finish<DL, TR, 3, MU, STT>);
-    else if (groups == 2) go(k_finish<DL, TR, 2, MU, STT>);
-    else go(k_finish<DL, TR, 1, MU, STT>);
+    pick_g(trace_tag, multi_tag, std::integral_constant<bool, STT>{}, std::false_type{});
   };
   auto pick_m = [&](auto trace_tag, auto st_tag) {
     if (multi) pick(trace_tag, std::true_type{}, st_tag); else pick(trace_tag, std::false_type{}, st_tag);
@@ -452,16 +473,16 @@ hipError_t launch_finish_impl(bool trace, int t_begin, int t_end, bool apply_th,
 template <>
 hipError_t launch_finish<float>(bool trace, int t_begin, int t_end, bool apply_final_th, float final_th,
                                 const DevPlan* d_plan, const DevModelT<float>& m, const WorkT<float>& w,
-                                int groups, long long n_hint, const S0Node* s0_table, int tile_win, hipStream_t stream,
-                                bool survivors) {
-  return launch_finish_impl<DialectC>(trace, t_begin, t_end, apply_final_th, final_th, d_plan, m, w, groups, n_hint, s0_table, tile_win, survivors, stream);
+                                int groups, long long n_hint, const S0Node* s0_table, int tile_win, FinishLaunch* how,
+                                hipStream_t stream, bool survivors) {
+  return launch_finish_impl<DialectC>(trace, t_begin, t_end, apply_final_th, final_th, d_plan, m, w, groups, n_hint, s0_table, tile_win, survivors, how, stream);
 }
 template <>
 hipError_t launch_finish<double>(bool trace, int t_begin, int t_end, bool apply_final_th, double final_th,
                                  const DevPlan* d_plan, const DevModelT<double>& m, const WorkT<double>& w,
-                                 int groups, long long n_hint, const S0Node* s0_table, int tile_win, hipStream_t stream,
-                                 bool survivors) {
-  return launch_finish_impl<DialectCPP>(trace, t_begin, t_end, apply_final_th, final_th, d_plan, m, w, groups, n_hint, s0_table, tile_win, survivors, stream);
+                                 int groups, long long n_hint, const S0Node* s0_table, int tile_win, FinishLaunch* how,
+                                 hipStream_t stream, bool survivors) {
+  return launch_finish_impl<DialectCPP>(trace, t_begin, t_end, apply_final_th, final_th, d_plan, m, w, groups, n_hint, s0_table, tile_win, survivors, how, stream);
 }
 
 

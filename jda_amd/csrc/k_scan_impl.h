@@ -579,10 +579,13 @@ void k_scan(const DevPlan* __restrict__ plan, DevModelT<Real> m,
 
 namespace {
 
+// NORM = false, the lean instantiation: opts bit 1 (no cart of [0, handoff) normalises), passes without trace only.
+inline bool scan_lean_form(int opts, bool trace) { return !trace && (opts & 2) != 0; }
+
 template <typename Real, bool TRACE, int MODE, int BLOCK>
 hipError_t launch_scan_mode(const DevPlan* d_plan, const DevPlan& h_plan, const DevModelT<Real>& m,
                             const S0Node* table, const WorkT<Real>& w, int level, int handoff, int cp_max, int opts,
-                            hipStream_t stream, int lv_lo, int lv_hi) {
+                            ScanLaunch* how, hipStream_t stream, int lv_lo, int lv_hi) {
   lv_lo = std::max(0, lv_lo); lv_hi = std::min(lv_hi, h_plan.n_levels);
   // level >= 0: that level; level < 0: every level of pixel mode MODE in one launch, sized for the
   // largest tile (small batches, where one launch per level would only add launch latency)
@@ -600,26 +603,29 @@ hipError_t launch_scan_mode(const DevPlan* d_plan, const DevPlan& h_plan, const 
   const int groups = (w.n_frames + 7) / 8;
   dim3 grid((unsigned)(groups * 8 * tiles)), block(BLOCK);
   const int lds_req = L.total;
-  auto go = [&](auto kern) {
+  // (the record names the instantiation from the constants that select it)
+  auto go = [&](auto depth_tag, auto norm_tag) {
+    constexpr int DEPTH = decltype(depth_tag)::value;
+    constexpr bool NORM = decltype(norm_tag)::value;
+    auto kern = k_scan<Real, DEPTH, TRACE, MODE, BLOCK, false, NORM>;
     if (lds_req > 48 * 1024)
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_req);
     const bool ranged = level < 0 && (lv_lo > 0 || lv_hi < h_plan.n_levels);
     hipLaunchKernelGGL(kern, grid, block, lds_req, stream, d_plan, m, table, w, level < 0 ? -1 : level, tiles,
                        pix_bytes, handoff, chunk, cp_max, opts, ranged ? (lv_lo | (lv_hi << 8)) : 0);
+    *how = ScanLaunch{true, false, DEPTH, MODE, BLOCK, false, !NORM, TRACE, level < 0};
+  };
+  auto pick = [&](auto norm_tag) {
+    const int depth = scan_depth_class(m.D);
+    if (depth == 4) go(std::integral_constant<int, 4>{}, norm_tag);
+    else if (depth == 6) go(std::integral_constant<int, 6>{}, norm_tag);
+    else go(std::integral_constant<int, 0>{}, norm_tag);
   };
   // (opts bit 1: no cart of [0, handoff) normalises -- the lean instantiation, passes without trace only)
-  const int depth = scan_depth_class(m.D);
   if constexpr (!TRACE) {
-    if (scan_lean_form(opts, TRACE)) {
-      if (depth == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK, false, false>);
-      else if (depth == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK, false, false>);
-      else go(k_scan<Real, 0, TRACE, MODE, BLOCK, false, false>);
-      return hipGetLastError();
-    }
+    if (scan_lean_form(opts, TRACE)) { pick(std::false_type{}); return hipGetLastError(); }
   }
-  if (depth == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK>);
-  else if (depth == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK>);
-  else go(k_scan<Real, 0, TRACE, MODE, BLOCK>);
+  pick(std::true_type{});
   return hipGetLastError();
 }
 
@@ -628,19 +634,22 @@ hipError_t launch_scan_mode(const DevPlan* d_plan, const DevPlan& h_plan, const 
 template <typename Real>
 hipError_t launch_scan(int mode, int level, bool trace, int handoff, int cp_max, int opts, const DevPlan* d_plan,
                        const DevPlan& h_plan, const DevModelT<Real>& m, const S0Node* table,
-                       const WorkT<Real>& w, hipStream_t stream, int lv_lo, int lv_hi) {
-  if (!scan_covers_tiles(h_plan, w.n_frames, mode, level, lv_lo, lv_hi)) return hipSuccess;     // (kernels.h: no frame, or no tile of the mode)
+                       const WorkT<Real>& w, ScanLaunch* how, hipStream_t stream, int lv_lo, int lv_hi) {
+  *how = ScanLaunch{};                  // (nothing launched, until launch_scan_mode says otherwise)
+  if (w.n_frames == 0) return hipSuccess;
   // 512-thread workgroups where a level's tiles hold more than 256 windows (one window per lane in
   // phase 0, twice the waves per LDS byte); a merged launch when any of its levels does
-  const bool big = scan_block_big(h_plan, mode, level, lv_lo, lv_hi);     // (kernels.h: the record of the form asks there too)
+  bool big = false;
+  for (int i = 0; i < h_plan.n_levels && mode == 1; i++)
+    if (h_plan.lv[i].tiled == 1 && (level < 0 ? (i >= lv_lo && i < lv_hi) : i == level)) big = big || h_plan.lv[i].tw * h_plan.lv[i].th > 256;
   auto pick = [&](auto trace_tag) {
     constexpr bool TR = decltype(trace_tag)::value;
     switch (mode) {
       case 1:
-        return big ? launch_scan_mode<Real, TR, 1, 512>(d_plan, h_plan, m, table, w, level, handoff, cp_max, opts, stream, lv_lo, lv_hi)
-                   : launch_scan_mode<Real, TR, 1, 256>(d_plan, h_plan, m, table, w, level, handoff, cp_max, opts, stream, lv_lo, lv_hi);
-      case 2: return launch_scan_mode<Real, TR, 2, 256>(d_plan, h_plan, m, table, w, level, handoff, cp_max, opts, stream, lv_lo, lv_hi);
-      case 3: return launch_scan_mode<Real, TR, 3, 256>(d_plan, h_plan, m, table, w, level, handoff, cp_max, opts, stream, lv_lo, lv_hi);
+        return big ? launch_scan_mode<Real, TR, 1, 512>(d_plan, h_plan, m, table, w, level, handoff, cp_max, opts, how, stream, lv_lo, lv_hi)
+                   : launch_scan_mode<Real, TR, 1, 256>(d_plan, h_plan, m, table, w, level, handoff, cp_max, opts, how, stream, lv_lo, lv_hi);
+      case 2: return launch_scan_mode<Real, TR, 2, 256>(d_plan, h_plan, m, table, w, level, handoff, cp_max, opts, how, stream, lv_lo, lv_hi);
+      case 3: return launch_scan_mode<Real, TR, 3, 256>(d_plan, h_plan, m, table, w, level, handoff, cp_max, opts, how, stream, lv_lo, lv_hi);
       default: return hipErrorInvalidValue;
     }
   };
@@ -651,29 +660,31 @@ namespace {
 template <typename Real, bool TRACE, int MODE, int BLOCK>
 hipError_t launch_scan_ragged_mode(const DevPlan* d_plan, const DevModelT<Real>& m, const S0Node* table, const WorkT<Real>& w,
                                    int pix_bytes, int blk_base, int blk_n, int handoff, int cp_max, int opts,
-                                   hipStream_t stream) {
+                                   bool merged, ScanLaunch* how, hipStream_t stream) {
   if (MODE == 2) pix_bytes = 0;
   const int chunk = std::min(std::min(m.K, handoff), scan_handoff_cap(m.node_n, m.leaf_n, (int)sizeof(Real)));
   const ScanLds<Real, TRACE> L(pix_bytes, chunk, m.node_n, m.leaf_n, kScanMaxWindows, BLOCK * 8);
   if (L.total > 160 * 1024) return hipErrorInvalidValue;
-  auto go = [&](auto kern) {
+  auto go = [&](auto depth_tag, auto norm_tag) {
+    constexpr int DEPTH = decltype(depth_tag)::value;
+    constexpr bool NORM = decltype(norm_tag)::value;
+    auto kern = k_scan<Real, DEPTH, TRACE, MODE, BLOCK, true, NORM>;
     if (L.total > 48 * 1024)
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
     hipLaunchKernelGGL(kern, dim3((unsigned)blk_n), dim3(BLOCK), L.total, stream, d_plan, m, table, w, -1, 0,
                        pix_bytes, handoff, chunk, cp_max, opts, blk_base);
+    *how = ScanLaunch{true, false, DEPTH, MODE, BLOCK, true, !NORM, TRACE, merged};
   };
-  const int depth = scan_depth_class(m.D);
+  auto pick = [&](auto norm_tag) {
+    const int depth = scan_depth_class(m.D);
+    if (depth == 4) go(std::integral_constant<int, 4>{}, norm_tag);
+    else if (depth == 6) go(std::integral_constant<int, 6>{}, norm_tag);
+    else go(std::integral_constant<int, 0>{}, norm_tag);
+  };
   if constexpr (!TRACE) {
-    if (scan_lean_form(opts, TRACE)) {
-      if (depth == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK, true, false>);
-      else if (depth == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK, true, false>);
-      else go(k_scan<Real, 0, TRACE, MODE, BLOCK, true, false>);
-      return hipGetLastError();
-    }
+    if (scan_lean_form(opts, TRACE)) { pick(std::false_type{}); return hipGetLastError(); }
   }
-  if (depth == 4) go(k_scan<Real, 4, TRACE, MODE, BLOCK, true>);
-  else if (depth == 6) go(k_scan<Real, 6, TRACE, MODE, BLOCK, true>);
-  else go(k_scan<Real, 0, TRACE, MODE, BLOCK, true>);
+  pick(std::true_type{});
   return hipGetLastError();
 }
 }  // namespace
@@ -688,27 +699,28 @@ hipError_t launch_scan_ragged_mode(const DevPlan* d_plan, const DevModelT<Real>&
 template <>
 hipError_t launch_scan_ragged<JDA_RAGGED_REAL>(int mode, int block, bool trace, int handoff, int cp_max, int opts, const DevPlan* d_plan,
                                      const DevModelT<JDA_RAGGED_REAL>& m, const S0Node* table, const WorkT<JDA_RAGGED_REAL>& w, int pix_bytes,
-                                     int blk_base, int blk_n, hipStream_t stream) {
+                                     int blk_base, int blk_n, int level, ScanLaunch* how, hipStream_t stream) {
   using Real = JDA_RAGGED_REAL;
+  *how = ScanLaunch{};                  // (nothing launched, until launch_scan_ragged_mode says otherwise)
   if (blk_n <= 0) return hipSuccess;
   if (!w.segs || !w.blk || trace) return hipErrorInvalidValue;
   switch (mode) {
     case 1:
-      return block == 512 ? launch_scan_ragged_mode<Real, false, 1, 512>(d_plan, m, table, w, pix_bytes, blk_base, blk_n, handoff, cp_max, opts, stream)
-                          : launch_scan_ragged_mode<Real, false, 1, 256>(d_plan, m, table, w, pix_bytes, blk_base, blk_n, handoff, cp_max, opts, stream);
-    case 2: return launch_scan_ragged_mode<Real, false, 2, 256>(d_plan, m, table, w, pix_bytes, blk_base, blk_n, handoff, cp_max, opts, stream);
-    case 3: return launch_scan_ragged_mode<Real, false, 3, 256>(d_plan, m, table, w, pix_bytes, blk_base, blk_n, handoff, cp_max, opts, stream);
+      return block == 512 ? launch_scan_ragged_mode<Real, false, 1, 512>(d_plan, m, table, w, pix_bytes, blk_base, blk_n, handoff, cp_max, opts, level < 0, how, stream)
+                          : launch_scan_ragged_mode<Real, false, 1, 256>(d_plan, m, table, w, pix_bytes, blk_base, blk_n, handoff, cp_max, opts, level < 0, how, stream);
+    case 2: return launch_scan_ragged_mode<Real, false, 2, 256>(d_plan, m, table, w, pix_bytes, blk_base, blk_n, handoff, cp_max, opts, level < 0, how, stream);
+    case 3: return launch_scan_ragged_mode<Real, false, 3, 256>(d_plan, m, table, w, pix_bytes, blk_base, blk_n, handoff, cp_max, opts, level < 0, how, stream);
     default: return hipErrorInvalidValue;
   }
 }
 #endif
 #ifdef JDA_SCAN_TU_DOUBLE
 template hipError_t launch_scan<double>(int, int, bool, int, int, int, const DevPlan*, const DevPlan&, const DevModelT<double>&,
-                                        const S0Node*, const WorkT<double>&, hipStream_t, int, int);
+                                        const S0Node*, const WorkT<double>&, ScanLaunch*, hipStream_t, int, int);
 #endif
 #ifdef JDA_SCAN_TU_MAIN
 template hipError_t launch_scan<float>(int, int, bool, int, int, int, const DevPlan*, const DevPlan&, const DevModelT<float>&,
-                                       const S0Node*, const WorkT<float>&, hipStream_t, int, int);
+                                       const S0Node*, const WorkT<float>&, ScanLaunch*, hipStream_t, int, int);
 #endif
 
 #ifdef JDA_SCAN_TU_MAIN

@@ -687,8 +687,9 @@ void k_scan_p(const DevPlan* __restrict__ plan, DevModelT<float> m, const S0Node
 
 hipError_t launch_scan_persistent(int level, const PScanCfg& cfg, int block, int grid_max, const DevPlan* d_plan,
                                   const DevPlan& h_plan, const DevModelT<float>& m, const S0Node* table,
-                                  const WorkT<float>& w, hipStream_t stream, int rag_blk_base, int rag_blk_n) {
+                                  const WorkT<float>& w, ScanLaunch* how, hipStream_t stream, int rag_blk_base, int rag_blk_n) {
   const bool ragged = rag_blk_n >= 0;
+  *how = ScanLaunch{};                   // (nothing launched, until go says otherwise)
   if (!ragged && w.n_frames == 0) return hipSuccess;
   if (ragged && rag_blk_n == 0) return hipSuccess;
   const DevLevel& lv = h_plan.lv[level];
@@ -705,22 +706,25 @@ hipError_t launch_scan_persistent(int level, const PScanCfg& cfg, int block, int
   const int total_blocks = ragged ? rag_blk_n : groups * 8 * lv.tiles_x * cfg.tiles_y;
   int grid = std::min(total_blocks, grid_max);
   if (grid >= 8) grid &= ~7;             // block b runs on XCD b % 8: a workgroup's tiles b + j * grid stay on its XCD's frames
-  auto go = [&](auto kern) {
+  // (the record names the instantiation from the constants that select it, and the launch from what the kernel is handed:
+  // the workgroup size, and cfg.any_norm, which the kernel tests at run time -- it has no NORM instantiation)
+  auto go = [&](auto depth_tag, auto ragged_tag) {
+    constexpr int DEPTH = decltype(depth_tag)::value;
+    constexpr bool RAGGED = decltype(ragged_tag)::value;
+    auto kern = k_scan_p<DEPTH, RAGGED>;
     if (L.total > 48 * 1024)
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)block), L.total, stream, d_plan, m, table, w, level, cfg,
                        total_blocks, ragged ? rag_blk_base : 0);
+    *how = ScanLaunch{true, true, DEPTH, 1, block, RAGGED, cfg.any_norm == 0, false, false};
   };
-  const int depth = scan_depth_class(m.D);
-  if (ragged) {
-    if (depth == 4) go(k_scan_p<4, true>);
-    else if (depth == 6) go(k_scan_p<6, true>);
-    else go(k_scan_p<0, true>);
-  } else {
-    if (depth == 4) go(k_scan_p<4, false>);
-    else if (depth == 6) go(k_scan_p<6, false>);
-    else go(k_scan_p<0, false>);
-  }
+  auto pick = [&](auto ragged_tag) {
+    const int depth = scan_depth_class(m.D);
+    if (depth == 4) go(std::integral_constant<int, 4>{}, ragged_tag);
+    else if (depth == 6) go(std::integral_constant<int, 6>{}, ragged_tag);
+    else go(std::integral_constant<int, 0>{}, ragged_tag);
+  };
+  if (ragged) pick(std::true_type{}); else pick(std::false_type{});
   return hipGetLastError();
 }
 

@@ -287,7 +287,7 @@ StageChoice stage_choice_impl(int win, int step, int dim, int node_n, int leaf_n
 template <typename DL>
 hipError_t launch_stage_impl(bool trace, int level, int t, bool apply_th, typename DL::Real th, const DevPlan* d_plan,
                              const DevPlan& h_plan, const DevModelT<typename DL::Real>& m,
-                             const WorkT<typename DL::Real>& w, int pix_cap, int lds_max, hipStream_t stream) {
+                             const WorkT<typename DL::Real>& w, int pix_cap, int lds_max, StageChoice* how, hipStream_t stream) {
   using Real = typename DL::Real;
   const DevLevel& lv = h_plan.lv[level];
   const StageChoice sc = stage_choice(lv.win, lv.step, m.dim, m.node_n, m.leaf_n, m.K, (int)sizeof(Real), pix_cap, lds_max);
@@ -295,19 +295,23 @@ hipError_t launch_stage_impl(bool trace, int level, int t, bool apply_th, typena
   const int tiles = ((lv.nx + kDenseTw - 1) / kDenseTw) * ((lv.ny + kDenseTh - 1) / kDenseTh);
   const int groups = (w.n_frames + 7) / 8;
   dim3 grid((unsigned)(groups * 8 * tiles)), block(kDenseM);
-  auto go = [&](auto kern) {
+  // (the record is the choice as launched: acc and glb from the constants that select the instantiation)
+  auto go = [&](auto trace_tag, auto glb_tag, auto acc_tag) {
+    constexpr bool TR = decltype(trace_tag)::value, GL = decltype(glb_tag)::value;
+    constexpr int ACC = decltype(acc_tag)::value;
+    auto kern = k_stage<DL, TR, GL, ACC>;
     if (sc.lds_bytes > 48 * 1024)
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, sc.lds_bytes);
     hipLaunchKernelGGL(kern, grid, block, sc.lds_bytes, stream, d_plan, m, w, level, t, sc.pix_bytes, sc.pitch, sc.chunk,
                        apply_th ? 1 : 0, th);
+    *how = sc; how->acc = ACC; how->glb = GL;
   };
   auto pick = [&](auto trace_tag, auto glb_tag) {
-    constexpr bool TR = decltype(trace_tag)::value, GL = decltype(glb_tag)::value;
     switch (sc.acc) {
-      case 12: go(k_stage<DL, TR, GL, 12>); break;
-      case 32: go(k_stage<DL, TR, GL, 32>); break;
-      case 64: go(k_stage<DL, TR, GL, 64>); break;
-      default: go(k_stage<DL, TR, GL, 160>); break;
+      case 12: go(trace_tag, glb_tag, std::integral_constant<int, 12>{}); break;
+      case 32: go(trace_tag, glb_tag, std::integral_constant<int, 32>{}); break;
+      case 64: go(trace_tag, glb_tag, std::integral_constant<int, 64>{}); break;
+      default: go(trace_tag, glb_tag, std::integral_constant<int, 160>{}); break;
     }
   };
   if (trace) { if (sc.glb) pick(std::true_type{}, std::true_type{}); else pick(std::true_type{}, std::false_type{}); }
@@ -319,14 +323,14 @@ hipError_t launch_stage_impl(bool trace, int level, int t, bool apply_th, typena
 template <>
 hipError_t launch_stage<float>(bool trace, int level, int t, bool apply_final_th, float final_th, const DevPlan* d_plan,
                                const DevPlan& h_plan, const DevModelT<float>& m, const WorkT<float>& w, int pix_cap,
-                               int lds_max, hipStream_t stream) {
-  return launch_stage_impl<DialectC>(trace, level, t, apply_final_th, final_th, d_plan, h_plan, m, w, pix_cap, lds_max, stream);
+                               int lds_max, StageChoice* how, hipStream_t stream) {
+  return launch_stage_impl<DialectC>(trace, level, t, apply_final_th, final_th, d_plan, h_plan, m, w, pix_cap, lds_max, how, stream);
 }
 template <>
 hipError_t launch_stage<double>(bool trace, int level, int t, bool apply_final_th, double final_th, const DevPlan* d_plan,
                                 const DevPlan& h_plan, const DevModelT<double>& m, const WorkT<double>& w, int pix_cap,
-                                int lds_max, hipStream_t stream) {
-  return launch_stage_impl<DialectCPP>(trace, level, t, apply_final_th, final_th, d_plan, h_plan, m, w, pix_cap, lds_max, stream);
+                                int lds_max, StageChoice* how, hipStream_t stream) {
+  return launch_stage_impl<DialectCPP>(trace, level, t, apply_final_th, final_th, d_plan, h_plan, m, w, pix_cap, lds_max, how, stream);
 }
 
 StageChoice stage_choice(int win, int step, int dim, int node_n, int leaf_n, int K, int real_bytes, int pix_cap, int lds_max) {

@@ -381,10 +381,16 @@ __global__ __launch_bounds__(BLOCK) void k_finish_wide(const DevPlan* __restrict
 }
 
 namespace {
+// The workgroup: a thread per cart of a stage, up to 1,024 (more carts take further rounds).
+inline int finish_wide_block(int K) { return K > 512 ? 1024 : (K > 256 ? 512 : 256); }
+// Replay and regression side by side (the concurrent form) need a wave for the replay and one per 64 shape coordinates
+// in that workgroup; a model that does not fit them takes the sequential form whatever `conc` asks for.
+inline bool finish_wide_conc_ok(int dim, int K) { return 1 + (dim + 63) / 64 <= finish_wide_block(K) / 64; }
+
 template <typename DL>
 hipError_t launch_finish_wide_impl(bool trace, bool apply_th, typename DL::Real th, const DevPlan* d_plan,
                                    const DevModelT<typename DL::Real>& m, const WorkT<typename DL::Real>& w,
-                                   long long n_hint, const S0Node* s0_table, hipStream_t stream, bool conc) {
+                                   long long n_hint, const S0Node* s0_table, WideLaunch* how, hipStream_t stream, bool conc) {
   using Real = typename DL::Real;
   const int budget = 160 * 1024;
   // window tile: as large as leaves room for at least 64 weight rows
@@ -398,12 +404,13 @@ hipError_t launch_finish_wide_impl(bool trace, bool apply_th, typename DL::Real 
   if (L.row_cap < 1 || L.total > budget) return hipErrorInvalidValue;
   const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>(n_hint, 1 << 16));
   const int block = finish_wide_block(m.K);
-  // replay and regression side by side: a wave for the replay + one per 64 shape coordinates (kernels.h)
+  // replay and regression side by side: a wave for the replay + one per 64 shape coordinates
   const bool conc_ok = conc && finish_wide_conc_ok(m.dim, m.K);
   auto go = [&](auto kern) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(block), L.total, stream, d_plan, m, w, apply_th ? 1 : 0, th, s0_table,
                        tile_win, tile_bytes, budget, conc_ok ? 1 : 0);
+    *how = WideLaunch{true, conc_ok};     // (the form the kernel was handed)
   };
   auto pick = [&](auto trace_tag) {
     constexpr bool TR = decltype(trace_tag)::value;
@@ -425,14 +432,14 @@ bool finish_wide_ok(int dim, int K, int leaf_n, int real_bytes, bool multi, bool
 template <>
 hipError_t launch_finish_wide<float>(bool trace, bool apply_final_th, float final_th, const DevPlan* d_plan,
                                      const DevModelT<float>& m, const WorkT<float>& w, long long n_hint,
-                                     const S0Node* s0_table, hipStream_t stream, bool conc) {
-  return launch_finish_wide_impl<DialectC>(trace, apply_final_th, final_th, d_plan, m, w, n_hint, s0_table, stream, conc);
+                                     const S0Node* s0_table, WideLaunch* how, hipStream_t stream, bool conc) {
+  return launch_finish_wide_impl<DialectC>(trace, apply_final_th, final_th, d_plan, m, w, n_hint, s0_table, how, stream, conc);
 }
 template <>
 hipError_t launch_finish_wide<double>(bool trace, bool apply_final_th, double final_th, const DevPlan* d_plan,
                                       const DevModelT<double>& m, const WorkT<double>& w, long long n_hint,
-                                      const S0Node* s0_table, hipStream_t stream, bool conc) {
-  return launch_finish_wide_impl<DialectCPP>(trace, apply_final_th, final_th, d_plan, m, w, n_hint, s0_table, stream, conc);
+                                      const S0Node* s0_table, WideLaunch* how, hipStream_t stream, bool conc) {
+  return launch_finish_wide_impl<DialectCPP>(trace, apply_final_th, final_th, d_plan, m, w, n_hint, s0_table, how, stream, conc);
 }
 
 JDA_BC_READER(k_wide)

@@ -251,6 +251,25 @@ static_assert(kCntTotal <= kCntStride, "counter shard too small");
 
 // ---- launchers (k_misc.hip, k_scan.hip, k_finish.hip, k_stage.hip) ------------------------------------------------
 
+// What a launcher of the detect path launched.  Each takes `how` (never null), as launch_lbf / launch_reval / plan_fit do,
+// and fills it where it chooses the kernel's template arguments, from the constants that name the instantiation handed to
+// hipLaunchKernelGGL -- not from its own arguments: the record cannot name another kernel than the one that ran.
+// launched = false: the launcher found nothing to launch and returned hipSuccess.  After an error `how` is unspecified.
+// The host turns a record into its public key and counts it in one place (host.h: LaunchLog).
+struct ScanLaunch {                    // launch_scan, launch_scan_ragged, launch_scan_persistent
+  bool launched, persistent;           // persistent: k_scan_p, else k_scan
+  int depth, mode, block;              // DEPTH (scan_depth_class), pixel mode (DevLevel::tiled), threads per workgroup
+  bool ragged, lean, trace, merged;    // lean: NORM = false (k_scan) / PScanCfg::any_norm == 0 (k_scan_p); merged: the launch spans levels
+};
+struct FinishLaunch {                  // launch_finish, launch_filter0
+  bool launched, filter0, trace;       // filter0: k_filter0, else k_finish
+  int groups;                          // kG, 1..4 (k_filter0: 0, like every field below but carry)
+  bool multi, st, stream, survivors;   // MULTI, ST, STREAM; the launch reads the mid queue as k_filter0 left it
+  bool carry, tile;                    // the launch sees leaf words (WorkT::m_leaf; k_finish: and reads survivors); a window tile in LDS
+};
+struct WideLaunch { bool launched, conc; };   // launch_finish_wide; conc: the conc_ok it handed to the kernel
+// (launch_stage reports the StageChoice it used: below, with the launcher)
+
 // Pyramid images of reference c/jda.c:450-457 for n frames.
 hipError_t launch_resize(const uint8_t* src, size_t src_stride, int n, int sw, int sh,
                          uint8_t* dst, size_t dst_stride, int dw, int dh, float rx, float ry,
@@ -287,42 +306,21 @@ hipError_t launch_enqueue(const DevPlan* d_plan, const DevPlan& h_plan, bool all
 template <typename Real>
 hipError_t launch_scan(int mode, int level, bool trace, int handoff, int cp_max, int opts, const DevPlan* d_plan,
                        const DevPlan& h_plan, const DevModelT<Real>& m, const S0Node* table,
-                       const WorkT<Real>& w, hipStream_t stream, int lv_lo = 0, int lv_hi = kMaxLevels);
+                       const WorkT<Real>& w, ScanLaunch* how, hipStream_t stream, int lv_lo = 0, int lv_hi = kMaxLevels);
 // (level < 0: ONE launch for every level of pixel mode `mode` among levels [lv_lo, lv_hi))
 
-// What a scan launch instantiates, decided here once: the launchers (k_scan_impl.h, k_scan_p.hip) and the record of
-// the form that ran (Pass::count_scan, jdaScanForms) both ask these.
-// DEPTH: the tree depths with a kernel of their own, 0 = the generic walk.
+// DEPTH of a scan kernel (k_scan_impl.h, k_scan_p.hip): the tree depths with a kernel of their own, 0 = the generic walk.
 inline int scan_depth_class(int D) { return D == 4 ? 4 : (D == 6 ? 6 : 0); }
-// 512-thread workgroups where a level's tiles hold more than 256 windows (one window per lane in phase 0, twice the
-// waves per LDS byte); a merged launch when any of its levels does.  Pixel mode 1 only.
-inline bool scan_block_big(const DevPlan& h_plan, int mode, int level, int lv_lo, int lv_hi) {
-  bool big = false;
-  for (int i = 0; i < h_plan.n_levels && mode == 1; i++)
-    if (h_plan.lv[i].tiled == 1 && (level < 0 ? (i >= lv_lo && i < lv_hi) : i == level)) big = big || h_plan.lv[i].tw * h_plan.lv[i].th > 256;
-  return big;
-}
-// Does launch_scan with these arguments launch a kernel -- are there frames, and does any level of the mode in the
-// range have a tile?  launch_scan returns at once where not, and the record of the form counts nothing: both ask here.
-inline bool scan_covers_tiles(const DevPlan& h_plan, int n_frames, int mode, int level, int lv_lo, int lv_hi) {
-  if (n_frames == 0) return false;
-  for (int i = 0; i < h_plan.n_levels; i++)
-    if (h_plan.lv[i].tiled == mode && (level < 0 ? (i >= lv_lo && i < lv_hi) : i == level) && h_plan.lv[i].tiles_x * h_plan.lv[i].tiles_y > 0) return true;
-  return false;
-}
-// NORM = false, the lean instantiation: opts bit 1 (no cart of [0, handoff) normalises), passes without trace only.
-inline bool scan_lean_form(int opts, bool trace) { return !trace && (opts & 2) != 0; }
 // Threads per workgroup of a persistent launch (the scan_p_block option, whole waves within 64..1,024).
 inline int scan_p_block_of(long long knob) { return (int)std::max<long long>(64, std::min<long long>(1024, knob)) & ~63; }
-// The JDA_SCAN_T* value (include/jda.h) of a pixel mode (DevLevel::tiled) and workgroup size.
-inline int scan_pix_form(int mode, int block) { return mode == 2 ? 3 : (mode == 3 ? 2 : (block >= 512 ? 1 : 0)); }
 
 // The same for a ragged batch: one launch over blocks [blk_base, blk_base + blk_n) of WorkT::blk, all of pixel mode
-// `mode` with workgroups of `block` threads and pixel tiles of at most pix_bytes.
+// `mode` with workgroups of `block` threads and pixel tiles of at most pix_bytes.  level: the level every block belongs
+// to, < 0: blocks of several levels (the kernel finds each block's level itself; the record says merged).
 template <typename Real>
 hipError_t launch_scan_ragged(int mode, int block, bool trace, int handoff, int cp_max, int opts, const DevPlan* d_plan,
                               const DevModelT<Real>& m, const S0Node* table, const WorkT<Real>& w, int pix_bytes,
-                              int blk_base, int blk_n, hipStream_t stream);
+                              int blk_base, int blk_n, int level, ScanLaunch* how, hipStream_t stream);
 
 // The persistent form of the LDS-tiled scan (k_scan_p.hip; dialect C, pixel mode 1, uniform batches): one workgroup per
 // CU walks its share of the level's tiles through `slots` pixel-tile slots; items that have completed bound[b] carts
@@ -349,7 +347,7 @@ size_t scan_p_lds_bytes(const PScanCfg& cfg, int carts, int node_n, int leaf_n, 
 // `level` (cfg.slot_bytes = the largest tile any image of the chunk cut from it; cfg.th / tiles_y / tw_magic unused).
 hipError_t launch_scan_persistent(int level, const PScanCfg& cfg, int block, int grid_max, const DevPlan* d_plan,
                                   const DevPlan& h_plan, const DevModelT<float>& m, const S0Node* table,
-                                  const WorkT<float>& w, hipStream_t stream, int rag_blk_base = 0, int rag_blk_n = -1);
+                                  const WorkT<float>& w, ScanLaunch* how, hipStream_t stream, int rag_blk_base = 0, int rag_blk_n = -1);
 
 // Tight images (row stride = width) at raw + src_off -> rows of `pitch` bytes at dst + dst_off, n images of at most
 // max_h rows.
@@ -360,8 +358,8 @@ hipError_t launch_repack(const uint8_t* raw, uint8_t* dst, const RagImg* imgs, i
 template <typename Real>
 hipError_t launch_finish(bool trace, int t_begin, int t_end, bool apply_final_th, Real final_th,
                          const DevPlan* d_plan, const DevModelT<Real>& m, const WorkT<Real>& w,
-                         int groups, long long n_hint, const S0Node* s0_table, int tile_win, hipStream_t stream,
-                         bool survivors = false);
+                         int groups, long long n_hint, const S0Node* s0_table, int tile_win, FinishLaunch* how,
+                         hipStream_t stream, bool survivors = false);
 // survivors: the input is the mid queue as launch_filter0 leaves it (windows that passed every cart of stage 0, still
 // holding the mean shape); t_begin must be 0.
 
@@ -370,20 +368,16 @@ hipError_t launch_finish(bool trace, int t_begin, int t_end, bool apply_final_th
 // table of every level.
 template <typename Real>
 hipError_t launch_filter0(bool trace, const DevPlan* d_plan, const DevModelT<Real>& m, const WorkT<Real>& w, long long n_hint,
-                          const S0Node* s0_table, hipStream_t stream);
+                          const S0Node* s0_table, FinishLaunch* how, hipStream_t stream);
 // s0_table: the plan's resolved stage-0 tables (or null): stage 0 of windows from levels that have one walks from it
 // tile_win: windows up to this side copy their pixels to LDS first (0: every pixel is read from the frame,
 // < 0: the largest side that leaves the workgroup within kFinishLdsPerGroup)
 constexpr size_t kFinishLdsPerGroup = 7680;
 
-// What a k_finish launch instantiates and how much LDS it takes, decided here once: the launcher (k_finish.hip:
-// launch_finish_impl) and the record of the launch (Pass::finish, jdaFinishLaunches, jdaFinishTileWin) both ask these.
+// The window tile of a k_finish launch and the LDS in front of it: the launcher (k_finish.hip: launch_finish_impl) asks
+// these, and so does jdaFinishTileWin, which answers without a device.
 // ST: the similarity transform exists in dialect CPP only.
 constexpr bool finish_st(int real_bytes, int similarity) { return real_bytes == 8 && similarity != 0; }
-// kG, the 64-cart groups a round walks: an instantiation each for 1..4.
-constexpr int finish_groups(int groups) { return groups >= 4 ? 4 : (groups == 3 ? 3 : (groups >= 2 ? 2 : 1)); }
-// STREAM (DevModelT::w_stream): only the form without trace, pyramid images and similarity transform has one.
-constexpr bool finish_stream(bool trace, bool multi, bool st, int w_stream) { return !trace && !multi && !st && w_stream != 0; }
 // LDS in front of the window tile: shape, the carts' weight rows, stage counters, the transform's scratch (ST).
 constexpr size_t finish_lds_base(int dim, int K, int real_bytes, bool st) {
   const size_t dim_pad = (size_t)((dim + 1) & ~1);
@@ -403,13 +397,6 @@ constexpr int finish_tile_win(int dim, int K, int real_bytes, bool st, bool mult
     if (base + finish_tile_bytes(tw) <= kFinishLdsPerGroup) best = tw;
   return best;
 }
-// Workgroups of a launch over a queue of capacity `cap` -- n_hint >= 0: the queue length is known on the host, one window
-// per workgroup (up to 1M workgroups, grid-stride beyond), so that the hardware dispatcher balances the very uneven
-// per-window cost; n_hint < 0: a fixed grid, windows dealt round-robin.  0: nothing is launched.
-inline unsigned finish_grid(long long n_hint, unsigned cap) {
-  if (n_hint >= 0) return (unsigned)(n_hint < (1 << 20) ? n_hint : (1 << 20));
-  return cap > 256u * 64u ? 256u * 64u : cap;
-}
 static_assert(finish_tile_win(54, 540, 4, false, false, -1) == 72 && finish_tile_win(54, 540, 4, false, true, -1) == 0, "the shipped model's tile (DESIGN.md section 4)");
 static_assert(finish_tile_win(10, 1808, 4, false, false, -1) == 16 && finish_tile_win(10, 1828, 4, false, false, -1) == 0, "the search starts at 16 pixels");
 
@@ -417,32 +404,28 @@ static_assert(finish_tile_win(10, 1808, 4, false, false, -1) == 16 && finish_til
 // final cut; reads the hand-off queue.  finish_wide_ok: the model fits (single-scale nodes, no similarity transform,
 // a weight row within the LDS row buffer).
 bool finish_wide_ok(int dim, int K, int leaf_n, int real_bytes, bool multi, bool similarity);
-// Its workgroup: a thread per cart of a stage, up to 1,024 (more carts take further rounds).
-inline int finish_wide_block(int K) { return K > 512 ? 1024 : (K > 256 ? 512 : 256); }
-// Replay and regression side by side (the concurrent form) need a wave for the replay and one per 64 shape coordinates
-// in that workgroup; a model that does not fit them takes the sequential form whatever `conc` asks for.  The launcher
-// and the record of the form that ran (Pass::launch_finishers, jdaFinishForms) both ask here.
-inline bool finish_wide_conc_ok(int dim, int K) { return 1 + (dim + 63) / 64 <= finish_wide_block(K) / 64; }
 template <typename Real>
 hipError_t launch_finish_wide(bool trace, bool apply_final_th, Real final_th, const DevPlan* d_plan,
                               const DevModelT<Real>& m, const WorkT<Real>& w, long long n_hint, const S0Node* s0_table,
-                              hipStream_t stream, bool conc = true);
-// conc: the stage's score replay (one wave) and its regression (a wave per 64 shape coordinates) run side by side
+                              WideLaunch* how, hipStream_t stream, bool conc = true);
+// conc: the stage's score replay (one wave) and its regression (a wave per 64 shape coordinates) run side by side, where
+// the model's workgroup has the waves for it (k_wide.hip: finish_wide_conc_ok) -- how->conc says whether it did
 
+// What a k_stage launch over a level of `win`-pixel windows at `step` instantiates and how it is set up (k_stage.hip:
+// stage_choice).  acc: the register width of the regression sums, the smallest of 12 / 32 / 64 / 160
+// that holds dim; glb: the padded pixel tile of 16 x 16 windows exceeds pix_cap, pixels come through the caches
+// (pix_bytes = 0); pitch: the tile's row pitch, a multiple of 16 and never of 128; chunk: carts staged in LDS at a
+// time, 4..64 (0: not even four fit under lds_max, launch_stage refuses); lds_bytes: the launch's dynamic LDS.
+struct StageChoice { int acc, chunk, pitch, pix_bytes, lds_bytes; bool glb; };
 // Dense mode: stage t for every window of one level, a 16 x 8 tile of windows per workgroup.
 // pix_cap = largest pixel tile that may live in LDS (larger windows read the frame through L1/L2).
+// how (never null): the choice the launch used, acc and glb as the instantiation it picked has them.
 template <typename Real>
 hipError_t launch_stage(bool trace, int level, int t, bool apply_final_th, Real final_th, const DevPlan* d_plan,
                         const DevPlan& h_plan, const DevModelT<Real>& m, const WorkT<Real>& w, int pix_cap,
-                        int lds_max, hipStream_t stream);
+                        int lds_max, StageChoice* how, hipStream_t stream);
 size_t stage_lds_bytes(int dim, int node_n, int leaf_n, int real_bytes);
-// What a k_stage launch over a level of `win`-pixel windows at `step` instantiates and how it is set up, decided here
-// once (k_stage.hip): the launcher (launch_stage_impl) and the record of the launch (Pass::run_dense, jdaStageLaunches,
-// jdaStageLaunchFor) both ask this.  acc: the register width of the regression sums, the smallest of 12 / 32 / 64 / 160
-// that holds dim; glb: the padded pixel tile of 16 x 16 windows exceeds pix_cap, pixels come through the caches
-// (pix_bytes = 0); pitch: the tile's row pitch, a multiple of 16 and never of 128; chunk: carts staged in LDS at a
-// time, 4..64 (0: not even four fit under lds_max, nothing is launched); lds_bytes: the launch's dynamic LDS.
-struct StageChoice { int acc, chunk, pitch, pix_bytes, lds_bytes; bool glb; };
+// The launcher asks this, and so does jdaStageLaunchFor, which answers without a device.
 StageChoice stage_choice(int win, int step, int dim, int node_n, int leaf_n, int K, int real_bytes, int pix_cap, int lds_max);
 // Dense mode takes the model at all (Pass::dense_ok's part that depends on the model alone): at most 160 shape
 // coordinates and 256 leaves, and the LDS floor -- a 4-cart chunk without a pixel tile -- within lds_max.  *pix_cap:

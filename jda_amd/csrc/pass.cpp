@@ -131,11 +131,9 @@ template <typename Real> bool Pass<Real>::run_dense() {
   count_form(JDA_FINISH_DENSE);
   for (int t = 0; t < hm().T; t++)
     for (int l = 0; l < pe->hp.n_levels; l++) {
-      // counted for jdaStageLaunches under the key of what the launcher instantiates: the same function on the same arguments
-      const DevLevel& lv = pe->hp.lv[l];
-      const StageChoice sc = stage_choice(lv.win, lv.step, model().dim, model().node_n, model().leaf_n, model().K, (int)sizeof(Real), pix_cap, lds_max);
-      if (sc.chunk != 0) c->stage_launches[stage_launch_key(Sel<Real>::dialect, want_trace(), sc)].fetch_add(1, std::memory_order_relaxed);
-      JDA_HIP(launch_stage<Real>(want_trace(), l, t, apply_th, th, pe->dp, pe->hp, model(), w, pix_cap, lds_max, st));
+      StageChoice how;                 // counted for jdaStageLaunches: the choice the launcher used
+      JDA_HIP(launch_stage<Real>(want_trace(), l, t, apply_th, th, pe->dp, pe->hp, model(), w, pix_cap, lds_max, &how, st));
+      c->log.count(Sel<Real>::dialect, want_trace(), how);
     }
   return true;
 }
@@ -216,11 +214,12 @@ template <typename Real> bool Pass<Real>::scan_persistent(int level, hipStream_t
     if (dry) return true;
     cfg.dyn_slot = (kn().scan_p_dyn && at.p_launches < kCntMidScan - kCntTotal) ? at.p_launches : -1;
     const int grid = kn().scan_p_grid > 0 ? (int)std::min<long long>(kn().scan_p_grid, 1 << 16) : c->n_cus * wgs;
-    const hipError_t e = rl ? launch_scan_persistent(level, cfg, block, grid, pe->dp, pe->hp, m, pe->table, w, s, rl->blk_base, rl->blk_n)
-                            : launch_scan_persistent(level, cfg, block, grid, pe->dp, pe->hp, m, pe->table, w, s);
+    ScanLaunch how;
+    const hipError_t e = rl ? launch_scan_persistent(level, cfg, block, grid, pe->dp, pe->hp, m, pe->table, w, &how, s, rl->blk_base, rl->blk_n)
+                            : launch_scan_persistent(level, cfg, block, grid, pe->dp, pe->hp, m, pe->table, w, &how, s);
     if (e == hipErrorInvalidValue) { (void)hipGetLastError(); return false; }
     if (e != hipSuccess) { fail(std::string("launch_scan_persistent failed: ") + hipGetErrorString(e)); return false; }
-    count_scan(JDA_SCAN_K_SCAN_P, 1, block, rl != nullptr, !cfg.any_norm, false);
+    count_scan(how);
     if (cfg.to_mid) at.mid_direct = true;
     at.p_launches++;
     return true;
@@ -280,10 +279,10 @@ template <typename Real> bool Pass<Real>::issue_scan() {
       if (pe->hp.lv[l].tiled == 1) lds_blocks += (long long)pe->hp.lv[l].tiles_x * pe->hp.lv[l].tiles_y * nf;
     }
     auto scan = [&](int mode, int level, hipStream_t s) -> bool {
-      if (mode == 1 && level >= 0 && scan_persistent(level, s)) { rs->scan_launches++; at.my_scan_launches++; return true; }
-      JDA_HIP(launch_scan<Real>(mode, level, want_trace(), sa.handoff, sa.cp_max, sa.opts, pe->dp, pe->hp, m, pe->table, w, s));
-      count_k_scan(mode, level);
-      rs->scan_launches++; at.my_scan_launches++;
+      if (mode == 1 && level >= 0 && scan_persistent(level, s)) return true;
+      ScanLaunch how;
+      JDA_HIP(launch_scan<Real>(mode, level, want_trace(), sa.handoff, sa.cp_max, sa.opts, pe->dp, pe->hp, m, pe->table, w, &how, s));
+      count_scan(how);
       return true;
     };
     // the global-pixel launch of a lone lane goes to a side stream, forked here and joined before the
@@ -350,9 +349,9 @@ template <typename Real> bool Pass<Real>::issue_scan() {
           // (the run's launch goes where its first member -- in this lane's order -- stands)
           const int lead = rev ? run_last[l] : run_first[l];
           if (l == lead) {
-            JDA_HIP(launch_scan<Real>(1, -1, false, sa.handoff, sa.cp_max, sa.opts, pe->dp, pe->hp, m, pe->table, w, st, run_first[l], run_last[l] + 1));
-            count_k_scan(1, -1, run_first[l], run_last[l] + 1);
-            rs->scan_launches++; at.my_scan_launches++;
+            ScanLaunch how;
+            JDA_HIP(launch_scan<Real>(1, -1, false, sa.handoff, sa.cp_max, sa.opts, pe->dp, pe->hp, m, pe->table, w, &how, st, run_first[l], run_last[l] + 1));
+            count_scan(how);
             if (fork_in > 0 && --fork_in == 0) { if (!fork_glb()) return false; fork_in = -1; }
           }
           continue;
@@ -434,11 +433,11 @@ template <typename Real> bool Pass<Real>::issue_scan_ragged() {
   auto issue = [&](const RaggedChunk::Launch& l, hipStream_t s, bool try_persistent) -> bool {
     // (the persistent form for the levels it suits, as in a uniform pass: one workgroup per CU walks the level's tiles
     // of every image of the chunk through its slots)
-    if (try_persistent && l.mode == 1 && l.level >= 0 && scan_persistent(l.level, s, &l)) { rs->scan_launches++; at.my_scan_launches++; return true; }
+    if (try_persistent && l.mode == 1 && l.level >= 0 && scan_persistent(l.level, s, &l)) return true;
+    ScanLaunch how;
     JDA_HIP(launch_scan_ragged<Real>(l.mode, l.block, false, sa.handoff, sa.cp_max, sa.opts, pe->dp, m, pe->table, w, l.pix_bytes,
-                                     l.blk_base, l.blk_n, s));
-    if (l.blk_n > 0) count_scan(JDA_SCAN_K_SCAN, l.mode, l.block, true, scan_lean_form(sa.opts, false), l.level < 0);   // (blk_n <= 0: the launcher launches nothing)
-    rs->scan_launches++; at.my_scan_launches++;
+                                     l.blk_base, l.blk_n, l.level, &how, s));
+    count_scan(how);
     return true;
   };
   if (fork_glb) {
@@ -449,7 +448,7 @@ template <typename Real> bool Pass<Real>::issue_scan_ragged() {
     if (l.mode == 2 && fork_glb) continue;
     if (fork_glb && kn().ragged_side == 2 && l.mode != 2) {
       // would the persistent kernel take it?  (asked by trying: a declined level costs nothing)
-      if (l.mode == 1 && l.level >= 0 && scan_persistent(l.level, st, &l)) { rs->scan_launches++; at.my_scan_launches++; continue; }
+      if (l.mode == 1 && l.level >= 0 && scan_persistent(l.level, st, &l)) continue;
       if (!issue(l, ln->side, false)) return false;
       continue;
     }
@@ -482,8 +481,8 @@ template <typename Real> bool Pass<Real>::launch_finishers(long long n_grid) {
   if (n_grid <= kn().wide_max && busy_lanes <= kn().wide_busy_max && finish_wide_ok(hm().dim(), hm().K, hm().leaf_n(), (int)sizeof(Real), multi, Sel<Real>::dialect == JDA_DIALECT_CPP && c->similarity)) {
     // a small job (a frame or a few): the call's time is the latency of one window's chain through the stages --
     // every queued window gets a whole workgroup (k_wide.hip)
-    count_form(kn().wide_conc != 0 && finish_wide_conc_ok(hm().dim(), hm().K) ? JDA_FINISH_WIDE_CONC : JDA_FINISH_WIDE_SEQ);
-    JDA_HIP(launch_finish_wide<Real>(want_trace(), apply_th, th, pe->dp, model(), w, n_grid, s0_tbl(), st, kn().wide_conc != 0));
+    WideLaunch how;                      // (counted as WIDE_CONC or WIDE_SEQ: the form the launcher handed the kernel)
+    JDA_HIP(counted(launch_finish_wide<Real>(want_trace(), apply_th, th, pe->dp, model(), w, n_grid, s0_tbl(), &how, st, kn().wide_conc != 0), how));
     at.finished = true;
     return true;
   }

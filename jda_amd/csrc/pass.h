@@ -117,44 +117,25 @@ struct Pass {
   // ... and its survivors take their stage-0 leaves along to k_finish (WorkT::m_leaf; kernels.h: carry_pack)
   bool carry_ok() const { return kn().fin_carry && filter0_ok() && carry_fits(hm().leaf_n(), hm().K); }
   long long windows() const { return rag ? rag->windows : (long long)nf * pe->sp.windows; }
-  // the finishing form this pass is about to issue, for jdaFinishForms (a pass that is issued again counts again)
-  void count_form(int form) { c->finish_forms[form].fetch_add(1, std::memory_order_relaxed); }
-  // A k_finish / k_filter0 launch of this pass, counted for jdaFinishLaunches under the key of what the launcher
-  // instantiates: the same functions (kernels.h) on the same arguments.  wk: the workspace as the launch sees it (w, or
-  // launch_finishers' copy without leaf words where the carry does not apply).
+  // ---- the launch reports (host.h: LaunchLog): a pass counts the record its launcher filled, once the launcher has
+  //      returned hipSuccess, and restates none of the launcher's decisions.  A pass that is issued again counts again. ----
+  // the finishing form this pass is about to issue, where that is the pass's own decision (launch_finishers, run_dense)
+  void count_form(int form) { c->log.count_form(form); }
+  template <typename Record> hipError_t counted(hipError_t e, const Record& how) { if (e == hipSuccess) c->log.count(Sel<Real>::dialect, how); return e; }
+  // A k_finish / k_filter0 launch of this pass.  wk: the workspace as the launch sees it (w, or launch_finishers' copy
+  // without leaf words where the carry does not apply).
   hipError_t finish(const WorkT<Real>& wk, int t_begin, int t_end, int groups, long long n_hint, const S0Node* s0, int tile_win,
                     bool survivors = false) {
-    const DevModelT<Real>& m = model();
-    const bool stt = finish_st((int)sizeof(Real), m.similarity), mu = wk.half != nullptr;
-    if (finish_grid(n_hint, t_begin == 0 && !survivors ? wk.cap_q : wk.cap_m) != 0)        // (0: the launcher launches nothing)
-      c->finish_launches[JDA_FINISH_LAUNCH(JDA_FINISH_K_FINISH, Sel<Real>::dialect, want_trace() ? 1 : 0, finish_groups(groups), mu ? 1 : 0,
-                                           stt ? 1 : 0, finish_stream(want_trace(), mu, stt, m.w_stream) ? 1 : 0, survivors ? 1 : 0,
-                                           survivors && wk.m_leaf != nullptr ? 1 : 0,
-                                           finish_tile_win(m.dim, m.K, (int)sizeof(Real), stt, mu, tile_win) > 0 ? 1 : 0)]
-          .fetch_add(1, std::memory_order_relaxed);
-    return launch_finish<Real>(want_trace(), t_begin, t_end, apply_th, th, pe->dp, m, wk, groups, n_hint, s0, tile_win, st, survivors);
+    FinishLaunch how;
+    return counted(launch_finish<Real>(want_trace(), t_begin, t_end, apply_th, th, pe->dp, model(), wk, groups, n_hint, s0, tile_win, &how, st, survivors), how);
   }
   hipError_t filter0(const WorkT<Real>& wk, long long n_hint) {
-    c->finish_launches[JDA_FINISH_LAUNCH(JDA_FINISH_K_FILTER0, Sel<Real>::dialect, want_trace() ? 1 : 0, 0, 0, 0, 0, 0, wk.m_leaf != nullptr ? 1 : 0, 0)]
-        .fetch_add(1, std::memory_order_relaxed);
-    return launch_filter0<Real>(want_trace(), pe->dp, model(), wk, n_hint, s0_tbl(), st);
+    FinishLaunch how;
+    return counted(launch_filter0<Real>(want_trace(), pe->dp, model(), wk, n_hint, s0_tbl(), &how, st), how);
   }
-  // the scan launch this pass is about to issue, for jdaScanForms, under the key of what the launcher instantiates: the
-  // same functions (kernels.h) and the same arguments the launchers take.  mode, block: DevLevel::tiled and the
-  // workgroup size; lean: NORM = false (k_scan) / PScanCfg::any_norm == 0 (k_scan_p); merged: the launch spans levels.
-  void count_scan(int kernel, int mode, int block, bool ragged, bool lean, bool merged) {
-    const int depth = scan_depth_class(model().D);
-    const int form = JDA_SCAN_FORM(kernel, sizeof(Real) == 4 ? JDA_DIALECT_C : JDA_DIALECT_CPP,
-                                   depth == 4 ? JDA_SCAN_DEPTH_4 : (depth == 6 ? JDA_SCAN_DEPTH_6 : JDA_SCAN_DEPTH_GENERIC),
-                                   scan_pix_form(mode, block), ragged ? 1 : 0, lean ? 1 : 0, want_trace() ? 1 : 0, merged ? 1 : 0);
-    c->scan_forms[form].fetch_add(1, std::memory_order_relaxed);
-  }
-  // ... a k_scan launch of a uniform pass (launch_scan's arguments)
-  void count_k_scan(int mode, int level, int lv_lo = 0, int lv_hi = kMaxLevels) {
-    if (!scan_covers_tiles(pe->hp, w.n_frames, mode, level, lv_lo, lv_hi)) return;     // (launch_scan launches nothing then)
-    count_scan(JDA_SCAN_K_SCAN, mode, scan_block_big(pe->hp, mode, level, lv_lo, lv_hi) ? 512 : 256, false,
-               scan_lean_form(sa.opts, want_trace()), level < 0);
-  }
+  // A scan launcher has returned hipSuccess: its record is counted, and so is the call -- jdaStats::scan_launches counts
+  // the calls to a scan launcher, also one that found nothing to launch (no frame, no tile of the mode, no block).
+  void count_scan(const ScanLaunch& how) { c->log.count(Sel<Real>::dialect, how); rs->scan_launches++; at.my_scan_launches++; }
 
   bool dense_ok(int* pix_cap, int* lds_max) const;
   bool run_dense();
