@@ -838,6 +838,34 @@ JDA_API int jdaSplitNodeCpp(void *cascador, const jdaSamplesCpp *pos, const jdaS
                             int half_size, int quarter_size, const jdaFeatureCpp *pool, int F, int mode, const double *u,
                             int *feature_idx, int *threshold, double *criterion, int *thresholds);
 
+/* What the device wrote for one node, before the host's sweep reads it (a test and diagnosis entry: the criterion is a lossy
+ * function of these).  Every pointer is a caller buffer or NULL (not wanted); the call zeroes the given buffers first, then
+ * fills what the node's mode makes: a buffer of the other mode, and everything after a regression node without positives
+ * (which launches nothing), stays zero.  P = positives on the node's list, N = negatives on it. */
+typedef struct {
+  short *pos_values;     /* F * P: value of pool[f] at list position j, row = feature (the device's 16-bit values)  */
+  short *neg_values;     /* F * N, mode 1                                                                          */
+  double *pos_hist_w;    /* F * 511, mode 1: bin value + 255, the weights added in list order                      */
+  double *neg_hist_w;    /* F * 511, mode 1                                                                        */
+  int *pos_hist_c;       /* F * 511, both modes: the count histogram                                               */
+  int *neg_hist_c;       /* F * 511, mode 1                                                                        */
+  double *var_sums;      /* F * 8, mode 0: left x, x*x, y, y*y, right x, x*x, y, y*y in list order over has_gt     */
+  int *var_n_left;       /* F, mode 0                                                                              */
+  int *var_n_right;      /* F, mode 0                                                                              */
+  int *var_th;           /* F, mode 0: the order statistic the device took from the counts                         */
+  int chunks;            /* OUT: feature chunks the pool was processed in ("workspace_mb")                         */
+} jdaSplitSumsCpp;
+
+/* jdaSplitNodeCpp on caller-given lists, with the device's raw outputs.  pos_list / neg_list: pos_list_n / neg_list_n sample
+ * indices, STRICTLY ASCENDING and inside [0, n) -- the form Cart::SplitNode's recursion hands a node's samples down in;
+ * anything else is refused (-1).  A NULL list means all samples of the set (its count argument is ignored).  The same launch
+ * sequence as jdaSplitNodeCpp and jdaTrainCartCpp: one function, which copies each chunk's buffers into `sums` when it is
+ * given.  feature_idx, threshold, criterion and thresholds as in jdaSplitNodeCpp. */
+JDA_API int jdaSplitNodeSumsCpp(void *cascador, const jdaSamplesCpp *pos, const jdaSamplesCpp *neg, int origin_size,
+                                int half_size, int quarter_size, const jdaFeatureCpp *pool, int F, int mode, const double *u,
+                                const int *pos_list, int pos_list_n, const int *neg_list, int neg_list_n, int *feature_idx,
+                                int *threshold, double *criterion, int *thresholds, jdaSplitSumsCpp *sums);
+
 /* One cart.  With nodes_n = 2^tree_depth: pools is (nodes_n/2 - 1) * F features, node i = 1 .. nodes_n/2 - 1 (the root is 1,
  * the children of i are 2i and 2i + 1, like Cart::features) uses pools[(i - 1) * F ..], modes[i - 1] and
  * us[(i - 1) * F ..] (us may be NULL when no node is a regression node).  Outputs (any may be NULL): out_features /

@@ -130,6 +130,14 @@ class jdaTrainStatsCpp(C.Structure):
                 ("nodes", C.POINTER(jdaTrainNodeCpp))]
 
 
+class jdaSplitSumsCpp(C.Structure):
+    _fields_ = [("pos_values", C.POINTER(C.c_short)), ("neg_values", C.POINTER(C.c_short)),
+                ("pos_hist_w", C.POINTER(C.c_double)), ("neg_hist_w", C.POINTER(C.c_double)),
+                ("pos_hist_c", C.POINTER(C.c_int)), ("neg_hist_c", C.POINTER(C.c_int)), ("var_sums", C.POINTER(C.c_double)),
+                ("var_n_left", C.POINTER(C.c_int)), ("var_n_right", C.POINTER(C.c_int)), ("var_th", C.POINTER(C.c_int)),
+                ("chunks", C.c_int)]
+
+
 class jdaStageCartsCpp(C.Structure):
     _fields_ = [("features", C.POINTER(jdaFeatureCpp)), ("thresholds", C.POINTER(C.c_int)), ("K", C.c_int)]
 
@@ -363,6 +371,9 @@ def _load():
         lib.jdaSplitNodeCpp.argtypes = [C.c_void_p, sp, sp, C.c_int, C.c_int, C.c_int, fp, C.c_int, C.c_int, dp, ip, ip, dp, ip]
         lib.jdaTrainCartCpp.argtypes = [C.c_void_p, sp, sp, C.c_int, C.c_int, C.c_int, fp, C.c_int, ip, dp, fp, ip, dp, ip, ip,
                                         C.POINTER(jdaTrainStatsCpp)]
+    if hasattr(lib, "jdaSplitNodeSumsCpp"):
+        lib.jdaSplitNodeSumsCpp.argtypes = [C.c_void_p, sp, sp, C.c_int, C.c_int, C.c_int, fp, C.c_int, C.c_int, dp, ip, C.c_int, ip,
+                                            C.c_int, ip, ip, dp, ip, C.POINTER(jdaSplitSumsCpp)]
     if hasattr(lib, "jdaStageUpdateShapesCpp"):
         sp, dp, ip, cp = C.POINTER(jdaSamplesCpp), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(jdaStageCartsCpp)
         lib.jdaGenLbfCpp.argtypes = [C.c_void_p, sp, C.c_int, C.c_int, C.c_int, cp, ip]
@@ -1899,6 +1910,46 @@ class Cascador:
         if rc != 0:
             raise JdaError(last_error())
         return dict(feature_idx=fi.value, threshold=th.value, criterion=crit, thresholds=ths)
+
+    def split_node_sums_cpp(self, pos, neg, pool, mode, u=None, pos_list=None, neg_list=None, origin_size=48, half_size=36,
+                            quarter_size=24):
+        """jdaSplitNodeSumsCpp: split_node_cpp on the lists pos_list / neg_list (strictly ascending sample indices; None: all
+        samples), with what the device wrote for the node -> split_node_cpp's dict plus pos_values [F, P] int16 and
+        pos_hist_c [F, 511] int32; mode 1: neg_values [F, N], pos_hist_w / neg_hist_w [F, 511] float64, neg_hist_c; mode 0:
+        var_sums [F, 8] float64, var_n_left / var_n_right / var_th [F] int32; chunks."""
+        pb = _patch_bytes(origin_size, half_size, quarter_size)
+        sp, kp = _samples(pos, self.dim, pb)
+        sn, kn = _samples(neg, self.dim, pb)
+        fa, fp = _features(pool)
+        F = len(fa)
+        ua = None if u is None else np.ascontiguousarray(u, np.float64).reshape(-1)
+        assert ua is None or ua.size == F
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        pl = None if pos_list is None else np.ascontiguousarray(pos_list, np.int32).reshape(-1)
+        nl = None if neg_list is None else np.ascontiguousarray(neg_list, np.int32).reshape(-1)
+        P, N = (sp.n if pl is None else pl.size), (sn.n if nl is None else nl.size)
+        out = dict(pos_values=np.zeros((F, P), np.int16), pos_hist_c=np.zeros((F, 511), np.int32))
+        if mode == 1:
+            out.update(neg_values=np.zeros((F, N), np.int16), pos_hist_w=np.zeros((F, 511), np.float64),
+                       neg_hist_w=np.zeros((F, 511), np.float64), neg_hist_c=np.zeros((F, 511), np.int32))
+        else:
+            out.update(var_sums=np.zeros((F, 8), np.float64), var_n_left=np.zeros(F, np.int32), var_n_right=np.zeros(F, np.int32),
+                       var_th=np.zeros(F, np.int32))
+        sums = jdaSplitSumsCpp()
+        for k, a in out.items():
+            setattr(sums, k, a.ctypes.data_as(dict(jdaSplitSumsCpp._fields_)[k]))
+        crit = np.zeros(F, np.float64)
+        ths = np.zeros(F, np.int32)
+        fi, th = C.c_int(), C.c_int()
+        rc = lib.jdaSplitNodeSumsCpp(self.h, C.byref(sp), C.byref(sn), origin_size, half_size, quarter_size, fp, F, int(mode),
+                                     None if ua is None else ua.ctypes.data_as(dp),
+                                     None if pl is None else pl.ctypes.data_as(ip), P, None if nl is None else nl.ctypes.data_as(ip), N,
+                                     C.byref(fi), C.byref(th), crit.ctypes.data_as(dp), ths.ctypes.data_as(ip), C.byref(sums))
+        del kp, kn
+        if rc != 0:
+            raise JdaError(last_error())
+        out.update(feature_idx=fi.value, threshold=th.value, criterion=crit, thresholds=ths, chunks=sums.chunks)
+        return out
 
     def train_cart_cpp(self, pos, neg, pools, modes, us=None, origin_size=48, half_size=36, quarter_size=24):
         """Cart::Train (reference cart.cpp:41-162) with the caller's pools [nodes_n/2 - 1, F], modes [nodes_n/2 - 1] and

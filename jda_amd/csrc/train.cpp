@@ -197,8 +197,46 @@ struct Ctx {
 
 // ---- SplitNode's choice (cart.cpp:99-115, 176-350) over the lists pl / nl (ascending sample indices) --------------------
 
+// Copies one chunk's device buffers into the caller's jdaSplitSumsCpp (jdaSplitNodeSumsCpp): features [f0, f0 + fc), after the
+// chunk's hipStreamSynchronize.  The histograms of mode 1 and the TrainVar rows are already on the host by then; the value
+// matrices (and mode 0's count histogram) are fetched here.
+bool sink_chunk(Ctx& x, jdaSplitSumsCpp* k, int mode, int f0, int fc, int pos_n, int neg_n) {
+  const size_t hb = (size_t)fc * kTrainBins, ho = (size_t)f0 * kTrainBins;
+  auto values = [&](const short* dev, size_t stride, int count, short* out) -> bool {
+    if (!out || !count) return true;
+    x.row.resize((size_t)fc * stride);
+    JDA_HIP(hipMemcpyAsync(x.row.data(), dev, (size_t)fc * stride * sizeof(short), hipMemcpyDeviceToHost, x.st));
+    JDA_HIP(hipStreamSynchronize(x.st));
+    for (int i = 0; i < fc; i++)
+      std::memcpy(out + (size_t)(f0 + i) * count, x.row.data() + (size_t)i * stride, (size_t)count * sizeof(short));
+    return true;
+  };
+  if (!values(x.d_vals_p, x.stride_p, pos_n, k->pos_values)) return false;
+  if (mode == 1) {
+    if (!values(x.d_vals_n, x.stride_n, neg_n, k->neg_values)) return false;
+    if (k->pos_hist_w) std::memcpy(k->pos_hist_w + ho, x.hw_p.data(), hb * sizeof(double));
+    if (k->neg_hist_w) std::memcpy(k->neg_hist_w + ho, x.hw_n.data(), hb * sizeof(double));
+    if (k->pos_hist_c) std::memcpy(k->pos_hist_c + ho, x.hc_p.data(), hb * sizeof(int));
+    if (k->neg_hist_c) std::memcpy(k->neg_hist_c + ho, x.hc_n.data(), hb * sizeof(int));
+  } else {
+    if (k->pos_hist_c) {
+      JDA_HIP(hipMemcpyAsync(k->pos_hist_c + ho, x.d_hc_p, hb * sizeof(int), hipMemcpyDeviceToHost, x.st));
+      JDA_HIP(hipStreamSynchronize(x.st));
+    }
+    for (int i = 0; i < fc; i++) {
+      const TrainVar& v = x.var[i];
+      if (k->var_sums) std::memcpy(k->var_sums + 8 * (size_t)(f0 + i), v.s, sizeof v.s);
+      if (k->var_n_left) k->var_n_left[f0 + i] = v.n_left;
+      if (k->var_n_right) k->var_n_right[f0 + i] = v.n_right;
+      if (k->var_th) k->var_th[f0 + i] = v.th;
+    }
+  }
+  return true;
+}
+
+// sink != nullptr: every chunk's raw device outputs are copied out as well (sink_chunk).
 bool split_node(Ctx& x, const std::vector<int>& pl, const std::vector<int>& nl, const jdaFeatureCpp* pool, int mode, const double* u,
-                int* feature_idx, int* threshold, double* best, double* criterion, int* thresholds) {
+                int* feature_idx, int* threshold, double* best, double* criterion, int* thresholds, jdaSplitSumsCpp* sink = nullptr) {
   const int F = x.F, pos_n = (int)pl.size(), neg_n = (int)nl.size();
   std::vector<double> es(F, 0.);
   std::vector<int> ths(F, -256);
@@ -263,6 +301,7 @@ bool split_node(Ctx& x, const std::vector<int>& pl, const std::vector<int>& nl, 
       }
       x.device_ms += t1 - t0; x.sweep_ms += now_ms() - t1;
     }
+    if (sink && !sink_chunk(x, sink, mode, f0, fc, pos_n, neg_n)) return false;
     x.chunks++;
   }
   double mn = std::numeric_limits<double>::max();                              // cart.cpp:243-250, 341-348
@@ -420,6 +459,48 @@ int jdaSplitNodeCpp(void* cascador, const jdaSamplesCpp* pos, const jdaSamplesCp
     std::iota(pl.begin(), pl.end(), 0); std::iota(nl.begin(), nl.end(), 0);
     double best;
     return split_node(x, pl, nl, pool, mode, u, feature_idx, threshold, &best, criterion, thresholds);
+  };
+  return body() ? 0 : -1;
+} JDA_ABI_CATCH_SYNC(-1)
+
+int jdaSplitNodeSumsCpp(void* cascador, const jdaSamplesCpp* pos, const jdaSamplesCpp* neg, int origin_size, int half_size,
+                        int quarter_size, const jdaFeatureCpp* pool, int F, int mode, const double* u, const int* pos_list,
+                        int pos_list_n, const int* neg_list, int neg_list_n, int* feature_idx, int* threshold, double* criterion,
+                        int* thresholds, jdaSplitSumsCpp* sums) try {
+  g_err.clear();
+  Cascador* c = (Cascador*)cascador;
+  if (!begin(c, origin_size, half_size, quarter_size, __func__)) return -1;
+  if (F < 1 || !pool || (mode != 0 && mode != 1) || !feature_idx || !threshold) { fail("bad arguments"); return -1; }
+  if (!check_set(pos, "pos", true) || !check_set(neg, "neg", true) || !check_pool(pool, (size_t)F, c->hm.L)) return -1;
+  std::vector<int> pl, nl;
+  auto take = [](const int* list, int count, int n, const char* name, std::vector<int>* out) -> bool {
+    if (!list) { out->resize(n); std::iota(out->begin(), out->end(), 0); return true; }
+    if (count < 0) { fail(std::string(name) + ": negative count"); return false; }
+    for (int j = 0; j < count; j++)
+      if (list[j] < 0 || list[j] >= n || (j > 0 && list[j] <= list[j - 1])) {
+        fail(std::string(name) + ": entry " + std::to_string(j) + " is outside [0, n) or not above the entry before it "
+             "(a node's list is strictly ascending)");
+        return false;
+      }
+    out->assign(list, list + count);
+    return true;
+  };
+  if (!take(pos_list, pos_list_n, pos->n, "pos_list", &pl) || !take(neg_list, neg_list_n, neg->n, "neg_list", &nl)) return -1;
+  if (sums) {
+    const size_t P = pl.size(), N = nl.size(), hb = (size_t)F * kTrainBins;
+    auto zero = [](auto* p, size_t count) { if (p && count) std::memset(p, 0, count * sizeof *p); };
+    zero(sums->pos_values, (size_t)F * P); zero(sums->neg_values, (size_t)F * N);
+    zero(sums->pos_hist_w, hb); zero(sums->neg_hist_w, hb); zero(sums->pos_hist_c, hb); zero(sums->neg_hist_c, hb);
+    zero(sums->var_sums, 8 * (size_t)F); zero(sums->var_n_left, F); zero(sums->var_n_right, F); zero(sums->var_th, F);
+    sums->chunks = 0;
+  }
+  Ctx x(c);
+  auto body = [&]() -> bool {
+    if (!x.open(pos, neg, origin_size, half_size, quarter_size, F)) return false;
+    double best;
+    if (!split_node(x, pl, nl, pool, mode, u, feature_idx, threshold, &best, criterion, thresholds, sums)) return false;
+    if (sums) sums->chunks = x.chunks;
+    return true;
   };
   return body() ? 0 : -1;
 } JDA_ABI_CATCH_SYNC(-1)

@@ -25,6 +25,7 @@ def test_every_declared_symbol_is_exported(built):
     names = declared_symbols()
     assert set(REFERENCE_SYMBOLS) <= set(names)
     assert len(names) >= 15
+    assert {"jdaSplitNodeCpp", "jdaSplitNodeSumsCpp", "jdaTrainCartCpp"} <= set(names)
     for n in names:
         assert hasattr(api.lib, n), n
 

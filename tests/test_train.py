@@ -101,6 +101,15 @@ def test_classification_split_corner_cases(built, gpu, model_file, what):
     got = _check_node(c, pd, nd, rows, 1, None)
     if what in ("no_negatives", "no_positives", "one_value"):
         assert got["threshold"] == -256 and (got["thresholds"] == -256).all()      # no gate ever opens
+    if what == "one_value":
+        # no gate opens, so the criterion never reads the histograms: compare them themselves (jdaSplitNodeSumsCpp) -- one bin,
+        # 64 rounds of k_train_hist's rank loop per batch, whose order tests/test_train_limits_host.py shows in the bits
+        pos, neg, det = train_ref.ref_set(pd), train_ref.ref_set(nd), {}
+        train_ref.split_node(pos, list(range(pos.n)), neg, list(range(neg.n)), train_ref.pool_of(rows), 1, None, detail=det)
+        sums = c.split_node_sums_cpp(pd, nd, _pool(rows), 1)
+        assert same(sums["pos_hist_w"], np.array(det["wp"], np.float64)) and same(sums["neg_hist_w"], np.array(det["wn"], np.float64))
+        assert same(sums["pos_hist_c"], np.array(det["p_n"], np.int32)) and same(sums["neg_hist_c"], np.array(det["n_n"], np.int32))
+        assert sums["pos_hist_c"][:, 255].tolist() == [260] * 24 and same(sums["criterion"], got["criterion"])
     c.close()
 
 

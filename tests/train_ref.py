@@ -127,9 +127,11 @@ def calc_feature_values(s, pool, idx):
 
 # ---- the two criteria --------------------------------------------------------------------------------------------------
 
-def split_classification(pos, pos_idx, neg, neg_idx, pf, nf, reverse=False):
+def split_classification(pos, pos_idx, neg, neg_idx, pf, nf, reverse=False, detail=None):
     """SplitNodeWithClassification (cart.cpp:176-252) -> (feature_idx, threshold, es_, ths_).  reverse=True adds every bin
-    and both totals in REVERSED sample order: the control that summation order is visible in the criterion."""
+    and both totals in REVERSED sample order: the control that summation order is visible in the criterion.  detail: a dict
+    that receives the intermediates as they stood before the sweep -- wp / wn (weighted histograms [F][511]) and p_n / n_n
+    (count histograms)."""
     feature_n, pos_n, neg_n = len(pf), len(pos_idx), len(neg_idx)
     feature_idx, threshold = 0, -256
     es_, ths_ = [0.] * feature_n, [0] * feature_n
@@ -147,6 +149,9 @@ def split_classification(pos, pos_idx, neg, neg_idx, pf, nf, reverse=False):
             wn[nf[i][j] + 255] += neg.weights[neg_idx[j]]
             wn_r += neg.weights[neg_idx[j]]
             n_n[nf[i][j] + 255] += 1
+        if detail is not None:
+            for k, v in (("wp", wp), ("wn", wn), ("p_n", p_n), ("n_n", n_n)):
+                detail.setdefault(k, []).append(v)
         current_p = current_n = 0
         w = wp_r + wn_r
         threshold_ = -256
@@ -193,9 +198,20 @@ def calc_variance(vec):
     return m2 - m1 * m1
 
 
-def split_regression(pos, pos_idx, pf, u):
+def ordered_sums(vec):
+    """calc_variance's two sums of vec, in its order -> (sum v, sum v * v)."""
+    s1 = s2 = 0.
+    for v in vec:
+        s1 += v
+        s2 += v * v
+    return s1, s2
+
+
+def split_regression(pos, pos_idx, pf, u, detail=None):
     """SplitNodeWithRegression (cart.cpp:288-350) -> (feature_idx, threshold, vs_, ths_); pos.residual[s] is
-    CalcShapeResidual(idx, landmark_id)'s row of sample s."""
+    CalcShapeResidual(idx, landmark_id)'s row of sample s.  detail: a dict that receives the intermediates -- kidx (the index
+    into the sorted values), th, counts (the values' count histogram [F][511]), sums ([F][8]: calc_variance's sums of lx, ly,
+    rx, ry as left x, x*x, y, y*y, right x, x*x, y, y*y), n_left, n_right."""
     feature_n, pos_n = len(pf), len(pos_idx)
     feature_idx, threshold = 0, -256
     if pos_n == 0:                                                   # cart.cpp:299-301 (include/jda.h: 0 / -256 reported)
@@ -216,6 +232,16 @@ def split_regression(pos, pos_idx, pf, u):
         vs_[i] = (calc_variance(lx) + calc_variance(ly)) * float(len(lx)) + \
                  (calc_variance(rx) + calc_variance(ry)) * float(len(rx))
         ths_[i] = threshold_
+        if detail is not None:
+            counts = [0] * 511
+            for v in pf[i]:
+                counts[v + 255] += 1
+            detail.setdefault("kidx", []).append(min(pos_n - 1, int(pos_n * u[i])))
+            detail.setdefault("th", []).append(threshold_)
+            detail.setdefault("counts", []).append(counts)
+            detail.setdefault("sums", []).append(list(ordered_sums(lx) + ordered_sums(ly) + ordered_sums(rx) + ordered_sums(ry)))
+            detail.setdefault("n_left", []).append(len(lx))
+            detail.setdefault("n_right", []).append(len(rx))
     variance_min = DBL_MAX                                           # cart.cpp:341-348
     for i in range(feature_n):
         if vs_[i] < variance_min:
@@ -225,14 +251,23 @@ def split_regression(pos, pos_idx, pf, u):
     return feature_idx, threshold, vs_, ths_
 
 
-def split_node(pos, pos_idx, neg, neg_idx, pool, mode, u):
+def ordered_histogram(values, idx, weights):
+    """The ordered histogram of cart.cpp:199-203 said once more, by brute force: the second opinion on split_classification's
+    wp / wn for the crafted inputs of tests/test_train_limits_host.py."""
+    bins = [0.] * 511
+    for j, s in enumerate(idx):
+        bins[values[j] + 255] += weights[s]
+    return bins
+
+
+def split_node(pos, pos_idx, neg, neg_idx, pool, mode, u, detail=None):
     """The choice of cart.cpp:93-115 -> (feature_idx, threshold, criteria, thresholds, pos_feature, neg_feature)."""
     pf = calc_feature_values(pos, pool, pos_idx)
     nf = calc_feature_values(neg, pool, neg_idx)
     if mode == 1:
-        fi, th, es, ths = split_classification(pos, pos_idx, neg, neg_idx, pf, nf)
+        fi, th, es, ths = split_classification(pos, pos_idx, neg, neg_idx, pf, nf, detail=detail)
     else:
-        fi, th, es, ths = split_regression(pos, pos_idx, pf, u)
+        fi, th, es, ths = split_regression(pos, pos_idx, pf, u, detail=detail)
     return fi, th, es, ths, pf, nf
 
 
@@ -318,3 +353,73 @@ def ref_set(d):
 # on the CPU that reversed summation order changes bits of their criteria
 CLS_CASES = [(11, 500, 400, 5, False, 48), (12, 450, 520, 27, True, 48)]
 RADIUS = 0.3
+
+
+# ---- crafted sample sets of tests/test_train_limits*.py (the host file proves each property on this restatement alone) --
+
+FEW_LEVELS, FEW_PROBS = (40, 120, 200), (0.7, 0.2, 0.1)
+
+
+def make_few_valued(seed, n, L, sizes=(48, 36, 24), outside=0.15, gt_drop=0.0):
+    """make_samples with every pixel drawn from three equally spaced gray levels (shares 0.7 / 0.2 / 0.1): a feature takes
+    at most the five values 0, +-80, +-160, about half of a list falls into bin 255, and the weights keep make_samples'
+    score spread of +-8."""
+    import numpy as np
+    d = make_samples(seed, n, L, sizes, outside=outside, gt_drop=gt_drop)
+    rng = np.random.default_rng(seed + 5000)
+    d["patches"] = np.array(FEW_LEVELS, np.uint8)[rng.choice(3, size=d["patches"].shape, p=FEW_PROBS)]
+    return d
+
+
+def make_extreme(seed, n, L, sizes=(48, 36, 24), outside=0.3, gt_drop=0.0):
+    """make_samples with every pixel 0 or 255 (so also every pixel a pool reads, and every border pixel a shape pushed
+    outside the patch is clamped to): a feature takes the values -255, 0 and 255."""
+    import numpy as np
+    d = make_samples(seed, n, L, sizes, outside=outside, gt_drop=gt_drop)
+    rng = np.random.default_rng(seed + 6000)
+    d["patches"] = (rng.integers(0, 2, d["patches"].shape, dtype=np.uint8) * 255).astype(np.uint8)
+    return d
+
+
+def deepest_rank(values, count):
+    """Over the FULL 64-entry batches of every feature's row (k_train_hist's batches of the list), the smallest and the
+    largest number of entries the most-hit bin of a batch receives -> (min, max); a bin hit m times is added to in ranks
+    0 .. m - 1.  count < 64 has no full batch: (0, 0)."""
+    lo, hi = None, 0
+    for row in values:
+        for j0 in range(0, count - 63, 64):
+            seen = {}
+            for v in row[j0:j0 + 64]:
+                seen[v] = seen.get(v, 0) + 1
+            m = max(seen.values())
+            lo = m if lo is None else min(lo, m)
+            hi = max(hi, m)
+    return (lo or 0), hi
+
+
+def pairwise_cover(factors, allowed=lambda row: True):
+    """Rows (one value per factor) in which every pair of values of two different factors occurs at least once, except pairs
+    that `allowed` (called with a dict factor index -> value, partial rows included) rules out.  Greedy and deterministic:
+    the first uncovered pair opens a row, every other factor takes the value that covers most of what is still uncovered."""
+    todo = [(i, a, j, b) for i in range(len(factors)) for j in range(i + 1, len(factors)) for a in range(len(factors[i]))
+            for b in range(len(factors[j])) if allowed({i: factors[i][a], j: factors[j][b]})]
+    left = set(todo)
+    rows = []
+    for pair in todo:
+        if pair not in left:
+            continue
+        i, a, j, b = pair
+        row = {i: a, j: b}
+        for k in range(len(factors)):
+            if k in row:
+                continue
+            def gain(v):
+                return sum(((k, v, m, row[m]) if k < m else (m, row[m], k, v)) in left for m in row)
+            ok = [v for v in range(len(factors[k])) if allowed({**{m: factors[m][row[m]] for m in row}, k: factors[k][v]})]
+            row[k] = max(ok, key=lambda v: (gain(v), -((v + len(rows)) % len(factors[k]))))
+        for m in row:
+            for q in row:
+                if m < q:
+                    left.discard((m, row[m], q, row[q]))
+        rows.append(tuple(factors[k][row[k]] for k in range(len(factors))))
+    return rows
