@@ -1458,6 +1458,61 @@ JDA_API int jdaOrientBack(const jdaPixels *images, const int *orients, int n_ima
                           const int *right, int sym_n);
 
 /* ------------------------------------------------------------------------ */
+/* Frames larger than the faces need                                        */
+/* ------------------------------------------------------------------------ */
+/* A 1080p or 4K camera frame does not need scanning at full resolution to find faces of 100 pixels and more; every consumer
+ * of a face detector halves or thirds such frames first.  These entries are jdaPackGrayOriented[Device] with ONE more step in
+ * front of the turn -- every image is reduced by an integer factor, block means -- and the way back: jdaReduceBack takes the
+ * boxes and landmarks a detect call found on the reduced, turned images into the source images the caller holds, so that
+ * jdaFaceChips can cut the faces from the full-resolution frame.
+ *
+ * Definition, to the bit, on the host and on the device.  For image i with rectangle w x h, factor f = factors[i] in 1..8
+ * and orientation t = orients[i] in 0..7 (orients == NULL: every t is 0):
+ *   1. Gray.    Every source pixel becomes gray by the Q14 formula of "frames as they arrive" (GRAY8: a copy), ROUNDED PER
+ *               PIXEL FIRST: reducing a colour image equals reducing its jdaPackGray image.
+ *   2. Reduce.  rw = w / f, rh = h / f (integer division): the w % f rightmost columns and the h % f bottom rows are
+ *               dropped.  Reduced pixel (i, j) = (S + f * f / 2) / (f * f) in integer arithmetic, S the sum of the f x f grays
+ *               at columns [i f, i f + f) and rows [j f, j f + f): the mean, to nearest, halves up.  For f = 2 that is
+ *               (S + 2) >> 2, the fast area path cv::resize takes at exactly 2x (what jdaResizeCv restates).
+ *   3. Turn.    The rw x rh image is turned by t exactly as "frames in any orientation" defines, rw and rh in place of w and
+ *               h, and written as W' x H' bytes, rows back to back, at dst + dst_offsets[i].  jdaReduceSize gives (W', H')
+ *               = swap ? (h / f, w / f) : (w / f, h / f); it refuses NULL rw / rh, a factor outside 1..8, an orientation
+ *               outside 0..7 and a negative w or h (a w or h below f gives 0).
+ *
+ * jdaPackGrayReduced / jdaPackGrayReducedDevice have the contract of jdaPackGrayOriented / jdaPackGrayOrientedDevice in every
+ * other respect -- formats, pitch, rectangle, the refusals with nothing written and nothing launched, the stream, the return
+ * on completion, re-entrancy, stats with launches == 1 for n > 0 -- where pixels and bytes_out count the rw * rh reduced
+ * pixels, bytes_in the bytes of the rectangle's pixels that take part (rw f * rh f * bytes per pixel), and the two overlap
+ * checks read the rw * rh destination bytes of an image (against the whole rectangle's bytes of every source row).
+ * Additionally refused, the message naming the image index: NULL factors with n > 0, a factor outside 1..8, w < f or h < f
+ * (the reduced image would be empty).  With every factor 1 the call forwards to jdaPackGrayOriented[Device] (which forwards
+ * to jdaPackGray[Device] when every orientation is 0): the bytes are theirs.  The host form is plain loops over the
+ * definition; the device form makes ONE kernel launch for all n images of whatever sizes, formats, factors and orientations
+ * (k_reduce.hip: 64 x 64 tiles of the turned reduced image through LDS) and never reads a byte outside the dwords that hold
+ * the rectangle's participating pixels of a source row: a source that ends with its allocation is safe.
+ *
+ * jdaReduceBack (host only, in place) has the arguments of jdaOrientBack and factors.  Boxes and landmarks are in the
+ * coordinates of image face_image[f]'s turned, reduced rectangle and on return in those of the WHOLE source image:
+ *   first    jdaOrientBack's own mapping with (rw, rh) as the rectangle's size and WITHOUT the rectangle's origin, the
+ *            sequential exchange of the (left, right) pairs for orientations 4..7 included;
+ *   then     the scale.  Boxes, integer exact: x0 = x0 * f, y0 = y0 * f, every size times f.  Landmarks, under the
+ *            pixel-index convention -- reduced pixel i covers source pixels i f .. i f + f - 1, whose centre is
+ *            i f + (f - 1) / 2 --, in the type's own precision, one operation per line, no fused multiply-add:
+ *                x = x * (real)f      then      x = x + c,   c = (real)(f - 1) / 2  (exact in binary);      y alike
+ *   then     x0 += rx, y0 += ry;  x = x + (real)rx, y = y + (real)ry.
+ * With every factor 1 the results are jdaOrientBack's, bit for bit.  Refused with nothing written: everything jdaOrientBack
+ * refuses, NULL factors with n_faces > 0, a factor outside 1..8, w < f or h < f. */
+JDA_API int jdaReduceSize(int w, int h, int factor, int orient, int *rw, int *rh);
+JDA_API int jdaPackGrayReduced(const jdaPixels *images, const int *factors, const int *orients, int n, unsigned char *dst,
+                               const size_t *dst_offsets);
+JDA_API int jdaPackGrayReducedDevice(void *cascador, const jdaPixels *images, const int *factors, const int *orients,
+                                     int n, unsigned char *d_dst, const size_t *dst_offsets, void *hip_stream,
+                                     jdaPackStats *stats);
+JDA_API int jdaReduceBack(const jdaPixels *images, const int *factors, const int *orients, int n_images,
+                          const int *face_image, int n_faces, int *boxes, int box_ints, void *landmarks,
+                          int real_bytes, int landmark_n, const int *left, const int *right, int sym_n);
+
+/* ------------------------------------------------------------------------ */
 /* Faces as they leave                                                      */
 /* ------------------------------------------------------------------------ */
 /* Every detect entry hands back boxes, scores and landmarks.  What a recogniser, an attribute net, a quality filter or a

@@ -437,6 +437,14 @@ def _load():
                                                   C.c_void_p, C.POINTER(jdaPackStats)]
         lib.jdaOrientBack.argtypes = [C.POINTER(jdaPixels), ip, C.c_int, ip, C.c_int, ip, C.c_int, C.c_void_p, C.c_int, C.c_int, ip, ip,
                                       C.c_int]
+    if hasattr(lib, "jdaPackGrayReducedDevice"):
+        ip = C.POINTER(C.c_int)
+        lib.jdaReduceSize.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]
+        lib.jdaPackGrayReduced.argtypes = [C.POINTER(jdaPixels), ip, ip, C.c_int, C.c_void_p, C.POINTER(C.c_size_t)]
+        lib.jdaPackGrayReducedDevice.argtypes = [C.c_void_p, C.POINTER(jdaPixels), ip, ip, C.c_int, C.c_void_p, C.POINTER(C.c_size_t),
+                                                 C.c_void_p, C.POINTER(jdaPackStats)]
+        lib.jdaReduceBack.argtypes = [C.POINTER(jdaPixels), ip, ip, C.c_int, ip, C.c_int, ip, C.c_int, C.c_void_p, C.c_int, C.c_int, ip,
+                                      ip, C.c_int]
     return lib
 
 
@@ -853,16 +861,20 @@ def _device_buffer(buf, tot, images):
     return buf
 
 
-def _pack_gray(who, images, formats, orients, rects):
-    """pack_gray (orients None) and pack_gray_oriented."""
+def _pack_gray(who, images, formats, orients, rects, factors=None):
+    """pack_gray (orients None), pack_gray_oriented and, with factors, pack_gray_reduced."""
     images, px, sizes = _pixels(who, images, formats, rects, False)
     n = len(images)
     o = None if orients is None else _orients(orients, n)
-    sizes = _turned_sizes(sizes, o)
+    f = None if factors is None else _factors(factors, n)
+    sizes = _turned_sizes(_reduced_sizes(sizes, f), o)
     offs, tot = _offsets(sizes)
     dst = np.empty(max(tot, 1), np.uint8)
     offp = offs.ctypes.data_as(C.POINTER(C.c_size_t))
-    if o is None:
+    if f is not None:
+        rc = lib.jdaPackGrayReduced(px, f.ctypes.data_as(C.POINTER(C.c_int)), None if o is None else o.ctypes.data_as(C.POINTER(C.c_int)), n,
+                                    dst.ctypes.data, offp)
+    elif o is None:
         rc = lib.jdaPackGray(px, n, dst.ctypes.data, offp)
     else:
         rc = lib.jdaPackGrayOriented(px, o.ctypes.data_as(C.POINTER(C.c_int)), n, dst.ctypes.data, offp)
@@ -917,8 +929,8 @@ def pack_gray_oriented(images, formats, orients, rects=None):
     return _pack_gray("pack_gray_oriented", images, formats, orients, rects)
 
 
-def orient_back(images, formats, orients, faces, boxes=None, landmarks=None, rects=None, left=(), right=()):
-    """jdaOrientBack: what a detect call found on images TURNED by orients (pack_gray_oriented[_device]) -> the coordinates of
+def orient_back(images, formats, orients, faces, boxes=None, landmarks=None, rects=None, left=(), right=(), factors=None):
+    """jdaOrientBack (with factors: jdaReduceBack, see reduce_back): what a detect call found on images TURNED by orients (pack_gray_oriented[_device]) -> the coordinates of
     the whole source images.  images / formats / rects as the pack call got them (numpy arrays or torch tensors: only their
     shapes are read).  Either faces = the image index of every face with boxes (int [n, 3] (x, y, size) or [n, 4]
     (x, y, w, h), or None) and landmarks (float32 / float64 [n, 2L], or None) -> (boxes, landmarks), new arrays; or faces = one
@@ -949,10 +961,14 @@ def orient_back(images, formats, orients, faces, boxes=None, landmarks=None, rec
     if len(le) != len(ri):
         raise ValueError("orient_back: left and right name the two landmarks of every pair")
     ip = C.POINTER(C.c_int)
-    rc = lib.jdaOrientBack(px, o.ctypes.data_as(ip), n_img, fi.ctypes.data_as(ip), n, None if b is None else b.ctypes.data_as(ip),
-                           b.shape[1] if b is not None else 0, None if lm is None else lm.ctypes.data,
-                           lm.dtype.itemsize if lm is not None else 0, lm.shape[1] // 2 if lm is not None else 0,
-                           le.ctypes.data_as(ip) if len(le) else None, ri.ctypes.data_as(ip) if len(le) else None, len(le))
+    tail = (n_img, fi.ctypes.data_as(ip), n, None if b is None else b.ctypes.data_as(ip),
+            b.shape[1] if b is not None else 0, None if lm is None else lm.ctypes.data,
+            lm.dtype.itemsize if lm is not None else 0, lm.shape[1] // 2 if lm is not None else 0,
+            le.ctypes.data_as(ip) if len(le) else None, ri.ctypes.data_as(ip) if len(le) else None, len(le))
+    if factors is None:
+        rc = lib.jdaOrientBack(px, o.ctypes.data_as(ip), *tail)
+    else:
+        rc = lib.jdaReduceBack(px, _factors(factors, n_img).ctypes.data_as(ip), o.ctypes.data_as(ip), *tail)
     if rc != 0:
         raise JdaError(last_error())
     if not results:
@@ -968,6 +984,42 @@ def orient_back(images, formats, orients, faces, boxes=None, landmarks=None, rec
         out.append(d)
         at += m
     return out
+
+
+# ---- frames larger than the faces need (include/jda.h) ------------------------------------------------------------------------
+def reduce_size(w, h, factor, orient=0):
+    """jdaReduceSize: (W', H') of a w x h rectangle reduced by factor (1..8), then turned by orient."""
+    rw, rh = C.c_int(), C.c_int()
+    if lib.jdaReduceSize(int(w), int(h), int(factor), int(orient), C.byref(rw), C.byref(rh)) != 0:
+        raise JdaError(last_error())
+    return rw.value, rh.value
+
+
+def _factors(factors, n):
+    """One factor for all images or one per image -> int32 [max(n, 1)]."""
+    f = np.full(n, int(factors), np.int32) if np.ndim(factors) == 0 else np.ascontiguousarray(factors, np.int32).reshape(-1)
+    if len(f) != n:
+        raise ValueError("factors: one factor for all images or one per image")
+    return f if n else np.ones(1, np.int32)
+
+
+def _reduced_sizes(sizes, factors):
+    """The (w, h) of rectangles reduced by their factors (None: none is; a factor the library will refuse: as it is)."""
+    return sizes if factors is None else [(w // max(int(f), 1), h // max(int(f), 1)) for (w, h), f in zip(sizes, factors)]
+
+
+def pack_gray_reduced(images, formats, factors, orients=None, rects=None):
+    """jdaPackGrayReduced: pack_gray_oriented with every image reduced by its factor first (1..8: one for all or one per image;
+    block means, include/jda.h, "frames larger than the faces need"); orients None: every image upright -> a list of uint8
+    [H', W'] gray arrays.  Host only: no cascador, no GPU."""
+    return _pack_gray("pack_gray_reduced", images, formats, orients, rects, factors)
+
+
+def reduce_back(images, formats, factors, orients, faces, boxes=None, landmarks=None, rects=None, left=(), right=()):
+    """jdaReduceBack: what a detect call found on images REDUCED by factors and turned by orients (pack_gray_reduced[_device];
+    orients None: upright) -> the coordinates of the whole source images, e.g. to cut chips from the full-resolution frames
+    (face_chips[_device] on the original images).  Both calling forms of orient_back."""
+    return orient_back(images, formats, 0 if orients is None else orients, faces, boxes, landmarks, rects, left, right, factors)
 
 
 def lib_landmarks(casc):
@@ -1445,12 +1497,13 @@ class Cascador:
         return (out, st.asdict()) if stats else out
 
     # -- frames as they arrive: colour / pitched / cropped device images -> dense gray ----------
-    def _pack_gray_device(self, who, images, formats, orients, rects, frame_stride, stats, hip_stream, out):
-        """pack_gray_device (orients None) and pack_gray_oriented_device."""
+    def _pack_gray_device(self, who, images, formats, orients, rects, frame_stride, stats, hip_stream, out, factors=None):
+        """pack_gray_device (orients None), pack_gray_oriented_device and, with factors, pack_gray_reduced_device."""
         images, px, sizes = _pixels(who, images, formats, rects, True)
         n = len(images)
         o = None if orients is None else _orients(orients, n)
-        sizes = _turned_sizes(sizes, o)
+        f = None if factors is None else _factors(factors, n)
+        sizes = _turned_sizes(_reduced_sizes(sizes, f), o)
         offs, tot = _offsets(sizes, 256, frame_stride)
         if out is not None:
             offs = np.ascontiguousarray(out[1], np.uint64)
@@ -1459,7 +1512,10 @@ class Cascador:
         st = jdaPackStats() if stats else None
         tail = (C.c_void_p(buf.data_ptr()), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
                 C.c_void_p(hip_stream) if hip_stream is not None else None, C.byref(st) if stats else None)
-        if o is None:
+        if f is not None:
+            rc = lib.jdaPackGrayReducedDevice(self.h, px, f.ctypes.data_as(C.POINTER(C.c_int)),
+                                              None if o is None else o.ctypes.data_as(C.POINTER(C.c_int)), n, *tail)
+        elif o is None:
             rc = lib.jdaPackGrayDevice(self.h, px, n, *tail)
         else:
             rc = lib.jdaPackGrayOrientedDevice(self.h, px, o.ctypes.data_as(C.POINTER(C.c_int)), n, *tail)
@@ -1485,6 +1541,14 @@ class Cascador:
         heights) of the TURNED images, like pack_gray_device's; api.orient_back takes what a detect call finds on them back
         to the source images."""
         return self._pack_gray_device("pack_gray_oriented_device", images, formats, orients, rects, frame_stride, stats, hip_stream, out)
+
+    def pack_gray_reduced_device(self, images, formats, factors, orients=None, rects=None, frame_stride=None, stats=False, hip_stream=None,
+                                 out=None):
+        """jdaPackGrayReducedDevice: pack_gray_oriented_device with every image reduced by its factor first (1..8: one for all
+        or one per image; block means; include/jda.h, "frames larger than the faces need") by ONE kernel launch; orients
+        None: every image upright.  -> (buffer, offsets, widths, heights) of the REDUCED, turned images, like
+        pack_gray_device's; api.reduce_back takes what a detect call finds on them back to the source images."""
+        return self._pack_gray_device("pack_gray_reduced_device", images, formats, orients, rects, frame_stride, stats, hip_stream, out, factors)
 
     # -- faces as they leave: upright chips cut from device images ---------------------------------
     def mean_shape(self):

@@ -83,9 +83,10 @@ struct PackOne {
   long long pitch, npix;
   int w, h, bpp, format;
   int tf;                             // kTf[orientation] (0 without orients)
+  int f;                              // the factor (1 unless reduced: then npix = (w / f) * (h / f), the bytes of dst)
 };
 bool check_pack(const std::string& who, const jdaPixels* images, const int* orients, bool turned, int n, unsigned char* dst,
-                const size_t* dst_offsets, std::vector<PackOne>* out);
+                const size_t* dst_offsets, std::vector<PackOne>* out, const int* factors = nullptr, bool reduced = false);
 // The units of `bytes` bytes at dst (kernels.h: PackImg, ChipArgs): bytes in front of dst's first 16-byte boundary, runs of 16, bytes behind
 struct DstUnits { int head; long long nq; int tail; long long total() const { return nq + head + tail; } };
 inline DstUnits dst_units(const void* dst, long long bytes) {
@@ -95,7 +96,7 @@ inline DstUnits dst_units(const void* dst, long long bytes) {
   u.tail = (int)(bytes - u.head - (u.nq << 4));
   return u;
 }
-// What PackImg and TurnImg have in common, the rest zero: the image, its first unit / tile in the launch and the Q14 weights,
+// What PackImg, TurnImg and ReduceImg have in common, the rest zero: the image, its first unit / tile in the launch and the Q14 weights,
 // split into their low and high bytes
 template <typename Img>
 void pack_img(Img* t, const PackOne& o, long long first) {
@@ -106,6 +107,32 @@ void pack_img(Img* t, const PackOne& o, long long first) {
   pack_weights(o.format, w);
   t->w_lo = (uint32_t)(w[0] & 255) | ((uint32_t)(w[1] & 255) << 8) | ((uint32_t)(w[2] & 255) << 16);
   t->w_hi = (uint32_t)(w[0] >> 8) | ((uint32_t)(w[1] >> 8) << 8) | ((uint32_t)(w[2] >> 8) << 16);
+}
+// The image table of a launch that deals 64 x 64 tiles of the turned images (Img: TurnImg, or ReduceImg, whose w x h is the
+// rectangle reduced by its factor; kernels.h) and the image of every workgroup's tile
+template <typename Img>
+bool turn_tiles(const std::string& who, const std::vector<PackOne>& v, std::vector<Img>* tab, std::vector<int>* block_img, long long* total_out) {
+  const int n = (int)v.size();
+  tab->resize((size_t)n);
+  long long total = 0, pixels = 0;
+  for (int i = 0; i < n; i++) {
+    const PackOne& o = v[(size_t)i];
+    Img& t = (*tab)[(size_t)i];
+    pack_img(&t, o, total);
+    t.tf = o.tf;
+    if constexpr (std::is_same<Img, ReduceImg>::value) { t.f = o.f; t.w = o.w / o.f; t.h = o.h / o.f; }
+    const int TW = (o.tf & kMineSwap) ? t.h : t.w, TH = (o.tf & kMineSwap) ? t.w : t.h;
+    t.off = (int)((uintptr_t)o.dst & 15);
+    t.ntu = (int)(((long long)TW + t.off + kTurnTile - 1) / kTurnTile);
+    t.ntv = (TH + kTurnTile - 1) / kTurnTile;
+    total += (long long)t.ntu * t.ntv;
+    pixels += o.npix;
+  }
+  if (total > 0x7fffffffll) { fail(who + "too many pixels for one launch (" + std::to_string(pixels) + ")"); return false; }
+  block_img->resize((size_t)total);
+  for (int i = 0; i < n; i++) std::fill_n(block_img->begin() + (*tab)[(size_t)i].first, (long long)(*tab)[(size_t)i].ntu * (*tab)[(size_t)i].ntv, i);
+  *total_out = total;
+  return true;
 }
 // jdaPackStats of a call that made its one launch
 void pack_stats(jdaPackStats* stats, const std::vector<PackOne>& v, const LaneCall& call);
@@ -123,6 +150,19 @@ struct OrientBackCall {
   void* landmarks; int real_bytes, landmark_n; const int* left; const int* right; int sym_n;
 };
 int orient_back(const OrientBackCall& call);
+// ... and what it shares with reduce.cpp: the writing half of turn_host and the launching half of turn_device (which is
+// pack_launch where every image is upright), on images check_pack has passed, in the name `who` of the entry the caller
+// called; orient_back with a factor per image (nullptr: jdaOrientBack itself)
+void turn_write(const std::vector<PackOne>& v);
+int turn_launch(LaneCall& call, const std::string& who, const std::vector<PackOne>& v, hipStream_t user_stream, jdaPackStats* stats);
+int orient_back(const std::string& who, const OrientBackCall& call, const int* factors);
+
+// reduce.cpp: frames larger than the faces need (jdaReduceSize, jdaPackGrayReduced[Device], jdaReduceBack)
+int reduce_size(int w, int h, int factor, int orient, int* rw, int* rh);
+int reduce_host(const jdaPixels* images, const int* factors, const int* orients, int n, unsigned char* dst, const size_t* dst_offsets);
+int reduce_device(Cascador* c, const jdaPixels* images, const int* factors, const int* orients, int n, unsigned char* d_dst,
+                  const size_t* dst_offsets, hipStream_t user_stream, jdaPackStats* stats);
+int reduce_back(const OrientBackCall& call, const int* factors);
 
 // chips.cpp: faces as they leave (jdaFaceChips / jdaFaceChipsDevice)
 struct ChipsCall {

@@ -18,7 +18,7 @@
 //             - the weights are split into their low and high bytes, so a pixel is two v_dot4_u32_u8 on the dword that holds
 //               it: the byte that is alpha, or the next pixel's, meets a zero weight.  GRAY8 is the same kernel without it.
 //             No LDS, no atomics, no inline assembly, no scratch.
-#include "pack_pixel.h"   // pack_row, pack_pixel, pack_unit, pack_divmod, the pack_*_t typedefs: shared with k_turn.hip and k_chips.hip
+#include "pack_pixel.h"   // pack_row, pack_pixel, pack_unit, pack_divmod, the pack_*_t typedefs: shared with k_turn.hip, k_reduce.hip and k_chips.hip
 
 namespace jda {
 

@@ -648,6 +648,23 @@ static_assert(sizeof(TurnImg) == 72, "TurnImg is uploaded as it is");
 struct TurnArgs { const TurnImg* imgs; const int* block_img; int n; long long total; };
 hipError_t launch_turn(const TurnArgs& a, hipStream_t stream);
 
+// ---- frames larger than the faces need: the same, reduced by an integer factor first (k_reduce.hip, reduce.cpp; include/jda.h) ----
+constexpr int kReduceMax = 8;            // factors 1 .. kReduceMax
+// One image of a launch: TurnImg with the REDUCED rectangle in w x h (w = rectangle width / f) -- tiles, tf, off, ntu, ntv are
+// those of the w x h image -- and the factor: reduced pixel (i, j) is the rounded mean of the f x f source pixels from column
+// i * f, row j * f of src on.  The tile kernels read both records through the same names.
+struct ReduceImg {
+  const uint8_t* src; uint8_t* dst;
+  long long pitch, first;
+  int w, h, bpp, tf, ntu, ntv, off;
+  uint32_t w_lo, w_hi;
+  int f;
+};
+static_assert(sizeof(ReduceImg) == 72, "ReduceImg is uploaded as it is");
+// One launch: imgs[0 .. n), total = the tiles of all of them; block_img[b] = the image of tile (workgroup) b.
+struct ReduceArgs { const ReduceImg* imgs; const int* block_img; int n; long long total; };
+hipError_t launch_reduce(const ReduceArgs& a, hipStream_t stream);
+
 // ---- faces as they leave: upright face chips cut from detections (k_chips.hip, chips.cpp; include/jda.h) ----
 constexpr int kChipBlock = 256;          // lanes of a workgroup: consecutive lanes take consecutive units
 // One face of a launch: M maps chip pixel centres to source pixels (sx = (m[0] * cu + m[1] * cv) + m[2], sy with m[3..5]),

@@ -2,7 +2,7 @@
 // jdaPackGrayDevice on the kernel of k_pack.hip.  Both validate everything before a byte is written or anything is launched;
 // the device form builds the image table and the item list of the launch, puts them into its lane's grow-only buffer and
 // makes one launch for all images.  No model is read.  What the entries refuse about ONE image (check_pixels) is shared with
-// chips.cpp, what they refuse about a call (check_pack) with turn.cpp.
+// chips.cpp, what they refuse about a call (check_pack) with turn.cpp and reduce.cpp.
 #include "detect.h"
 
 namespace jda {
@@ -21,14 +21,17 @@ bool touches_rows(const PackOne& s, uintptr_t d0, uintptr_t d1) {
 }  // namespace
 
 // Everything jdaPackGray / jdaPackGrayDevice refuse (include/jda.h); on success one PackOne per image.  With orients (turn.cpp)
-// an orientation outside 0..7 is refused like an unknown format; a turned image takes the same w * h bytes of dst.
+// an orientation outside 0..7 is refused like an unknown format; a turned image takes the same w * h bytes of dst.  With
+// reduced (reduce.cpp) factors are needed, a factor outside 1..kReduceMax or above w or h is refused the same way, and image
+// i takes (w / f) * (h / f) bytes of dst: npix, which every overlap check below reads.
 bool check_pack(const std::string& who, const jdaPixels* images, const int* orients, bool turned, int n, unsigned char* dst,
-                const size_t* dst_offsets, std::vector<PackOne>* out) {
+                const size_t* dst_offsets, std::vector<PackOne>* out, const int* factors, bool reduced) {
   if (n < 0) { fail(who + "negative number of images (n = " + std::to_string(n) + ")"); return false; }
   if (n == 0) return true;
   if (!images) { fail(who + "null images"); return false; }
   if (!dst) { fail(who + "null destination"); return false; }
   if (turned && !orients) { fail(who + "null orients"); return false; }
+  if (reduced && !factors) { fail(who + "null factors"); return false; }
   if (!dst_offsets) { fail(who + "null dst_offsets"); return false; }
   out->resize((size_t)n);
   for (int i = 0; i < n; i++) {
@@ -37,10 +40,19 @@ bool check_pack(const std::string& who, const jdaPixels* images, const int* orie
     PackOne& o = (*out)[(size_t)i];
     o.src = r.src;
     o.dst = dst + dst_offsets[i];
-    o.pitch = r.pitch; o.npix = (long long)r.w * r.h; o.w = r.w; o.h = r.h; o.bpp = r.bpp; o.format = r.format; o.tf = 0;
+    o.pitch = r.pitch; o.npix = (long long)r.w * r.h; o.w = r.w; o.h = r.h; o.bpp = r.bpp; o.format = r.format; o.tf = 0; o.f = 1;
     if (turned) {
       if (orients[i] < 0 || orients[i] > 7) { fail(who + "image " + std::to_string(i) + ": unknown orientation " + std::to_string(orients[i]) + " (0..7)"); return false; }
       o.tf = kTf[orients[i]];
+    }
+    if (reduced) {
+      const int f = factors[i];
+      if (f < 1 || f > kReduceMax) { fail(who + "image " + std::to_string(i) + ": factor " + std::to_string(f) + " (1.." + std::to_string(kReduceMax) + ")"); return false; }
+      if (r.w < f || r.h < f) {
+        fail(who + "image " + std::to_string(i) + ": a rectangle of " + std::to_string(r.w) + " x " + std::to_string(r.h) + " reduced by factor " + std::to_string(f) + " has no pixel");
+        return false;
+      }
+      o.f = f; o.npix = (long long)(r.w / f) * (r.h / f);
     }
   }
   // two destination images that overlap: neighbours in address order

@@ -9,20 +9,22 @@ namespace jda {
 
 namespace {
 
-bool all_upright(const int* orients, int n) {
-  if (!orients) return false;
-  for (int i = 0; i < n; i++) if (orients[i] != 0) return false;
-  return true;
-}
-
-// faces [0, n): landmarks in place, the type's own precision, one operation per line
+// faces [0, n): landmarks in place, the type's own precision, one operation per line.  w x h: the rectangle as it was turned
+// (reduced by f, if f: then a reduced pixel's centre goes to the centre of its f x f block, c = (f - 1) / 2)
 template <class Real>
-void back_landmarks(Real* lm, int L, int tf, bool mirror, const PixelsOne& r, const int* left, const int* right, int sym_n) {
+void back_landmarks(Real* lm, int L, int tf, bool mirror, const PixelsOne& r, int w, int h, int f, const int* left, const int* right, int sym_n) {
+  const Real c = (Real)(f - 1) / 2;
   for (int i = 0; i < L; i++) {
     Real x = lm[2 * i], y = lm[2 * i + 1];
     if (tf & kMineSwap) std::swap(x, y);
-    if (tf & kMineFlipX) x = (Real)(r.w - 1) - x;
-    if (tf & kMineFlipY) y = (Real)(r.h - 1) - y;
+    if (tf & kMineFlipX) x = (Real)(w - 1) - x;
+    if (tf & kMineFlipY) y = (Real)(h - 1) - y;
+    if (f) {
+      x = x * (Real)f;
+      y = y * (Real)f;
+      x = x + c;
+      y = y + c;
+    }
     x = x + (Real)r.x;
     y = y + (Real)r.y;
     lm[2 * i] = x; lm[2 * i + 1] = y;
@@ -49,6 +51,11 @@ int orient_size(int w, int h, int orient, int* tw, int* th) {
 int turn_host(const jdaPixels* images, const int* orients, int n, unsigned char* dst, const size_t* dst_offsets) {
   std::vector<PackOne> v;
   if (!check_pack("jdaPackGrayOriented: ", images, orients, true, n, dst, dst_offsets, &v)) return -1;
+  turn_write(v);
+  return 0;
+}
+
+void turn_write(const std::vector<PackOne>& v) {
   for (const PackOne& o : v) {
     const bool swap = (o.tf & kMineSwap) != 0;
     const int TW = swap ? o.h : o.w, TH = swap ? o.w : o.h;
@@ -65,7 +72,6 @@ int turn_host(const jdaPixels* images, const int* orients, int n, unsigned char*
       }
     }
   }
-  return 0;
 }
 
 int turn_device(Cascador* c, const jdaPixels* images, const int* orients, int n, unsigned char* d_dst, const size_t* dst_offsets,
@@ -76,27 +82,17 @@ int turn_device(Cascador* c, const jdaPixels* images, const int* orients, int n,
   std::vector<PackOne> v;
   if (!check_pack(who, images, orients, true, n, d_dst, dst_offsets, &v)) return -1;
   if (stats) std::memset(stats, 0, sizeof *stats);
-  if (n == 0) return 0;
-  if (all_upright(orients, n)) return pack_launch(call, who, v, user_stream, stats);   // the same bytes
+  return n == 0 ? 0 : turn_launch(call, who, v, user_stream, stats);
+}
 
-  // the image table (tiles: kernels.h) and the image of every workgroup's tile
-  std::vector<TurnImg> tab((size_t)n);
-  long long total = 0, pixels = 0;
-  for (int i = 0; i < n; i++) {
-    const PackOne& o = v[(size_t)i];
-    TurnImg& t = tab[(size_t)i];
-    pack_img(&t, o, total);
-    t.tf = o.tf;
-    const int TW = (o.tf & kMineSwap) ? o.h : o.w, TH = (o.tf & kMineSwap) ? o.w : o.h;
-    t.off = (int)((uintptr_t)o.dst & 15);
-    t.ntu = (int)(((long long)TW + t.off + kTurnTile - 1) / kTurnTile);
-    t.ntv = (TH + kTurnTile - 1) / kTurnTile;
-    total += (long long)t.ntu * t.ntv;
-    pixels += o.npix;
-  }
-  if (total > 0x7fffffffll) { fail(who + "too many pixels for one launch (" + std::to_string(pixels) + ")"); return -1; }
-  std::vector<int> block_img((size_t)total);
-  for (int i = 0; i < n; i++) std::fill_n(block_img.begin() + tab[(size_t)i].first, (long long)tab[(size_t)i].ntu * tab[(size_t)i].ntv, i);
+int turn_launch(LaneCall& call, const std::string& who, const std::vector<PackOne>& v, hipStream_t user_stream, jdaPackStats* stats) {
+  const int n = (int)v.size();
+  if (std::all_of(v.begin(), v.end(), [](const PackOne& o) { return o.tf == 0; })) return pack_launch(call, who, v, user_stream, stats);   // the same bytes
+
+  std::vector<TurnImg> tab;
+  std::vector<int> block_img;
+  long long total;
+  if (!turn_tiles(who, v, &tab, &block_img, &total)) return -1;
 
   if (!call.open(user_stream)) return -1;
   const hipStream_t st = call.st;
@@ -112,8 +108,9 @@ int turn_device(Cascador* c, const jdaPixels* images, const int* orients, int n,
   return 0;
 }
 
-int orient_back(const OrientBackCall& k) {
-  const std::string who = "jdaOrientBack: ";
+int orient_back(const OrientBackCall& k) { return orient_back("jdaOrientBack: ", k, nullptr); }
+
+int orient_back(const std::string& who, const OrientBackCall& k, const int* factors) {
   if (k.n_faces < 0) { fail(who + "negative number of faces (n_faces = " + std::to_string(k.n_faces) + ")"); return -1; }
   if (k.n_images < 0) { fail(who + "negative number of images (n_images = " + std::to_string(k.n_images) + ")"); return -1; }
   if (k.n_faces == 0) return 0;
@@ -138,6 +135,13 @@ int orient_back(const OrientBackCall& k) {
   for (int i = 0; i < k.n_images; i++) {
     if (!check_pixels(who + "image " + std::to_string(i) + ": ", k.images[i], &img[(size_t)i])) return -1;
     if (k.orients[i] < 0 || k.orients[i] > 7) { fail(who + "image " + std::to_string(i) + ": unknown orientation " + std::to_string(k.orients[i]) + " (0..7)"); return -1; }
+    if (!factors) continue;
+    const int f = factors[i];
+    if (f < 1 || f > kReduceMax) { fail(who + "image " + std::to_string(i) + ": factor " + std::to_string(f) + " (1.." + std::to_string(kReduceMax) + ")"); return -1; }
+    if (img[(size_t)i].w < f || img[(size_t)i].h < f) {
+      fail(who + "image " + std::to_string(i) + ": a rectangle of " + std::to_string(img[(size_t)i].w) + " x " + std::to_string(img[(size_t)i].h) + " reduced by factor " + std::to_string(f) + " has no pixel");
+      return -1;
+    }
   }
   for (int f = 0; f < k.n_faces; f++) {
     if (k.face_image[f] < 0 || k.face_image[f] >= k.n_images) {
@@ -148,21 +152,23 @@ int orient_back(const OrientBackCall& k) {
   for (int f = 0; f < k.n_faces; f++) {
     const int i = k.face_image[f], t = k.orients[i], tf = kTf[t];
     const PixelsOne& r = img[(size_t)i];
+    const int fc = factors ? factors[i] : 0, w = fc ? r.w / fc : r.w, h = fc ? r.h / fc : r.h;   // the rectangle as it was turned
     if (k.boxes) {
       int* b = k.boxes + (size_t)f * k.box_ints;
       const int bw0 = b[2], bh0 = k.box_ints == 4 ? b[3] : b[2];
       const bool swap = (tf & kMineSwap) != 0;
       int x0 = swap ? b[1] : b[0], y0 = swap ? b[0] : b[1];
-      const int bw = swap ? bh0 : bw0, bh = swap ? bw0 : bh0;
-      if (tf & kMineFlipX) x0 = r.w - bw - x0;
-      if (tf & kMineFlipY) y0 = r.h - bh - y0;
+      int bw = swap ? bh0 : bw0, bh = swap ? bw0 : bh0;
+      if (tf & kMineFlipX) x0 = w - bw - x0;
+      if (tf & kMineFlipY) y0 = h - bh - y0;
+      if (fc) { x0 *= fc; y0 *= fc; bw *= fc; bh *= fc; }
       b[0] = x0 + r.x; b[1] = y0 + r.y; b[2] = bw;
       if (k.box_ints == 4) b[3] = bh;
     }
     if (k.landmarks) {
       const bool mirror = t >= 4;                   // 4, 5, 6, 7: the swap / flip matrix has determinant -1
-      if (k.real_bytes == 4) back_landmarks((float*)k.landmarks + (size_t)f * 2 * k.landmark_n, k.landmark_n, tf, mirror, r, k.left, k.right, k.sym_n);
-      else back_landmarks((double*)k.landmarks + (size_t)f * 2 * k.landmark_n, k.landmark_n, tf, mirror, r, k.left, k.right, k.sym_n);
+      if (k.real_bytes == 4) back_landmarks((float*)k.landmarks + (size_t)f * 2 * k.landmark_n, k.landmark_n, tf, mirror, r, w, h, fc, k.left, k.right, k.sym_n);
+      else back_landmarks((double*)k.landmarks + (size_t)f * 2 * k.landmark_n, k.landmark_n, tf, mirror, r, w, h, fc, k.left, k.right, k.sym_n);
     }
   }
   return 0;
