@@ -1513,6 +1513,80 @@ JDA_API int jdaReduceBack(const jdaPixels *images, const int *factors, const int
                           int real_bytes, int landmark_n, const int *left, const int *right, int sym_n);
 
 /* ------------------------------------------------------------------------ */
+/* Frames whose faces are rolled                                            */
+/* ------------------------------------------------------------------------ */
+/* The cascade finds upright faces; "frames in any orientation" covers the quarter turns and mirrors, and between them there
+ * is nothing: a head rolled by 30 - 60 degrees, a tilted phone, a ceiling camera.  Every consumer of an upright-only detector
+ * runs it on a few rotated copies of the frame (typically +-30, +-60 degrees) and maps the hits back.  These entries are
+ * jdaPackGrayOriented[Device] with a rotation by ANY angle, each image by its own, in place of the orientation, and the way
+ * back: jdaRotateBack takes boxes and landmarks found on the rotated images into the source images the caller holds, where
+ * jdaFaceChips ("faces as they leave") cuts them upright.
+ *
+ * The plan (jdaRotationPlan; host only -- everything else is defined from its c, s, tw, th, and the pack entries and the way
+ * back call this very function, so libm is never consulted on the device and a restatement takes c and s from here).
+ *   if degrees is an integer multiple of 90 (fmod(degrees, 90) == 0), (c, s) comes from the exact table for
+ *   k = (degrees / 90) mod 4 in 0..3:   k = 0: (1, 0)    k = 1: (0, 1)    k = 2: (-1, 0)    k = 3: (0, -1)
+ *   otherwise c = cos(degrees * (pi / 180)) and s = sin(degrees * (pi / 180)), doubles, from the host's libm
+ *   tw = max(1, (int)ceil(((double)w * |c| + (double)h * |s|) - 1. / 1024))
+ *   th = max(1, (int)ceil(((double)w * |s| + (double)h * |c|) - 1. / 1024))
+ * and w, h are copied.  Refused with -1: NULL rot, a non-finite angle, |degrees| > 36000, w or h below 1.
+ *
+ * A turned pixel, to the bit, on the host and on the device.  fp64, one operation per step as written, no fused
+ * multiply-add.  With cu = (tw - 1) / 2, cv = (th - 1) / 2, cx = (w - 1) / 2, cy = (h - 1) / 2 (all exact), output pixel
+ * (column u, row v) of the tw x th image samples the rectangle at
+ *   du = u - cu                   dv = v - cv
+ *   sx = (c * du + s * dv) + cx   sy = (c * dv - s * du) + cy
+ * by the sampling of "faces as they leave" with n = 1, on the RECTANGLE:
+ *   the sample is 0 unless sx > -1 && sx < w && sy > -1 && sy < h; otherwise
+ *   X = floor(sx * 1024 + 0.5)   Y = floor(sy * 1024 + 0.5)   x0 = X >> 10   fx = X & 1023   y0 = Y >> 10   fy = Y & 1023
+ *   the taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), each 0 where outside [0, w) x [0, h) of the rectangle
+ *   -- nothing outside the rectangle is read: the pack family's rule --, weigh (1024 - fx) * (1024 - fy), fx * (1024 - fy),
+ *   (1024 - fx) * fy, fx * fy; tap * weight is summed in unsigned 32-bit integers
+ *   out = (sum + 2^19) >> 20
+ * Every TAP is made gray first by the Q14 formula of "frames as they arrive", rounded per tap: the rotated image of a colour
+ * source equals the rotated image of its jdaPackGray image.  Positive angles turn the picture clockwise as displayed.  At
+ * 90 / 180 / 270 the bytes are those of orientation 1 / 2 / 3 and at 0 jdaPackGray's, for any w x h: every quantity is then
+ * an integer or a half-integer, fx = fy = 0 and out is the tap.
+ *
+ * jdaPackGrayRotated / jdaPackGrayRotatedDevice have the contract of jdaPackGrayOriented / jdaPackGrayOrientedDevice in every
+ * other respect -- formats, pitch, rectangle, the refusals with nothing written and nothing launched, the stream, the return on
+ * completion, re-entrancy, stats with launches == 1 for n > 0 -- where image i is written as tw * th bytes, rows of tw bytes
+ * back to back, both overlap checks read the tw * th destination bytes of an image, pixels and bytes_out count tw * th and
+ * bytes_in the rectangle's w * h * bytes per pixel.  Additionally refused, the message naming the image index: NULL degrees
+ * with n > 0, an angle the plan refuses, tw or th above 32768.  When every angle is a multiple of 90 the call forwards to
+ * jdaPackGrayOriented[Device]: the bytes are equal either way.  The host form is plain loops over the definition; the
+ * device form makes ONE kernel launch for all n images of whatever sizes, formats and angles (k_rotate.hip: 64 x 64 tiles
+ * of the turned image, the source box of a tile through LDS, gray once per source pixel) and never reads a byte outside the
+ * rectangle's pixels of a source row's dwords: a source that ends with its allocation is safe.
+ *
+ * jdaRotateBack (host only, in place) has the arguments of jdaOrientBack without the pairs: nothing mirrors.  Boxes and
+ * landmarks are in the coordinates of image face_image[f]'s turned rectangle and on return in those of the WHOLE source
+ * image; (rx, ry) is the rectangle's origin:
+ *   landmarks   a feature at turned (x, y) lies at the map above with (x, y) for (u, v); then x = sx + (double)rx,
+ *               y = sy + (double)ry.  All in double: floats are widened first and rounded once at the end.
+ *   boxes       the centre (x + (bw - 1) / 2, y + (bh - 1) / 2), in double, goes through the same map to (mx, my);
+ *               x0 = (int)floor((mx - (bw - 1) / 2) + 0.5) + rx     y0 = (int)floor((my - (bh - 1) / 2) + 0.5) + ry
+ *               sizes unchanged: the box in the source frame is the upright box around the rolled face; the caller knows
+ *               its angle.
+ * At multiples of 90, square boxes equal jdaOrientBack's with orientation 0 / 1 / 2 / 3 bit for bit, and so do landmarks
+ * wherever jdaOrientBack's own steps are exact in the landmark's type (it rounds after every step in that type, this
+ * rounds in double and once to the type; (x - cu) + cx gives x back only up to double's rounding).  Scores are not touched.
+ * Refused with -1, nothing written: what jdaOrientBack refuses (NULL images or face_image with n_faces > 0, a negative
+ * count, box_ints other than 3 or 4, real_bytes other than 4 or 8, landmark_n < 1, a face_image outside [0, n_images),
+ * everything jdaPackGray refuses about an image), NULL degrees with n_faces > 0, an angle the plan refuses.  n_faces == 0
+ * returns 0 and touches nothing. */
+typedef struct { double c, s; int w, h, tw, th; } jdaRotation;   /* filled by jdaRotationPlan */
+
+JDA_API int jdaRotationPlan(int w, int h, double degrees, jdaRotation *rot);
+JDA_API int jdaPackGrayRotated(const jdaPixels *images, const double *degrees, int n, unsigned char *dst,
+                               const size_t *dst_offsets);
+JDA_API int jdaPackGrayRotatedDevice(void *cascador, const jdaPixels *images, const double *degrees, int n,
+                                     unsigned char *d_dst, const size_t *dst_offsets, void *hip_stream,
+                                     jdaPackStats *stats);
+JDA_API int jdaRotateBack(const jdaPixels *images, const double *degrees, int n_images, const int *face_image, int n_faces,
+                          int *boxes, int box_ints, void *landmarks, int real_bytes, int landmark_n);
+
+/* ------------------------------------------------------------------------ */
 /* Faces as they leave                                                      */
 /* ------------------------------------------------------------------------ */
 /* Every detect entry hands back boxes, scores and landmarks.  What a recogniser, an attribute net, a quality filter or a

@@ -188,6 +188,13 @@ class jdaPixels(C.Structure):
                 ("x", C.c_int), ("y", C.c_int), ("w", C.c_int), ("h", C.c_int)]
 
 
+class jdaRotation(C.Structure):
+    _fields_ = [("c", C.c_double), ("s", C.c_double), ("w", C.c_int), ("h", C.c_int), ("tw", C.c_int), ("th", C.c_int)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class jdaPackStats(C.Structure):
     _fields_ = [("pixels", C.c_longlong), ("bytes_in", C.c_longlong), ("bytes_out", C.c_longlong), ("launches", C.c_int),
                 ("device_ms", C.c_double), ("call_ms", C.c_double)]
@@ -445,6 +452,13 @@ def _load():
                                                  C.c_void_p, C.POINTER(jdaPackStats)]
         lib.jdaReduceBack.argtypes = [C.POINTER(jdaPixels), ip, ip, C.c_int, ip, C.c_int, ip, C.c_int, C.c_void_p, C.c_int, C.c_int, ip,
                                       ip, C.c_int]
+    if hasattr(lib, "jdaPackGrayRotatedDevice"):
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        lib.jdaRotationPlan.argtypes = [C.c_int, C.c_int, C.c_double, C.POINTER(jdaRotation)]
+        lib.jdaPackGrayRotated.argtypes = [C.POINTER(jdaPixels), dp, C.c_int, C.c_void_p, C.POINTER(C.c_size_t)]
+        lib.jdaPackGrayRotatedDevice.argtypes = [C.c_void_p, C.POINTER(jdaPixels), dp, C.c_int, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p,
+                                                 C.POINTER(jdaPackStats)]
+        lib.jdaRotateBack.argtypes = [C.POINTER(jdaPixels), dp, C.c_int, ip, C.c_int, ip, C.c_int, C.c_void_p, C.c_int, C.c_int]
     return lib
 
 
@@ -861,17 +875,20 @@ def _device_buffer(buf, tot, images):
     return buf
 
 
-def _pack_gray(who, images, formats, orients, rects, factors=None):
-    """pack_gray (orients None), pack_gray_oriented and, with factors, pack_gray_reduced."""
+def _pack_gray(who, images, formats, orients, rects, factors=None, degrees=None):
+    """pack_gray (orients None), pack_gray_oriented, with factors pack_gray_reduced and, with degrees, pack_gray_rotated."""
     images, px, sizes = _pixels(who, images, formats, rects, False)
     n = len(images)
     o = None if orients is None else _orients(orients, n)
     f = None if factors is None else _factors(factors, n)
-    sizes = _turned_sizes(_reduced_sizes(sizes, f), o)
+    g = None if degrees is None else _degrees(degrees, n)
+    sizes = _rotated_sizes(_turned_sizes(_reduced_sizes(sizes, f), o), g)
     offs, tot = _offsets(sizes)
     dst = np.empty(max(tot, 1), np.uint8)
     offp = offs.ctypes.data_as(C.POINTER(C.c_size_t))
-    if f is not None:
+    if g is not None:
+        rc = lib.jdaPackGrayRotated(px, g.ctypes.data_as(C.POINTER(C.c_double)), n, dst.ctypes.data, offp)
+    elif f is not None:
         rc = lib.jdaPackGrayReduced(px, f.ctypes.data_as(C.POINTER(C.c_int)), None if o is None else o.ctypes.data_as(C.POINTER(C.c_int)), n,
                                     dst.ctypes.data, offp)
     elif o is None:
@@ -929,8 +946,8 @@ def pack_gray_oriented(images, formats, orients, rects=None):
     return _pack_gray("pack_gray_oriented", images, formats, orients, rects)
 
 
-def orient_back(images, formats, orients, faces, boxes=None, landmarks=None, rects=None, left=(), right=(), factors=None):
-    """jdaOrientBack (with factors: jdaReduceBack, see reduce_back): what a detect call found on images TURNED by orients (pack_gray_oriented[_device]) -> the coordinates of
+def orient_back(images, formats, orients, faces, boxes=None, landmarks=None, rects=None, left=(), right=(), factors=None, degrees=None):
+    """jdaOrientBack (with factors: jdaReduceBack, see reduce_back; with degrees: jdaRotateBack, see rotate_back): what a detect call found on images TURNED by orients (pack_gray_oriented[_device]) -> the coordinates of
     the whole source images.  images / formats / rects as the pack call got them (numpy arrays or torch tensors: only their
     shapes are read).  Either faces = the image index of every face with boxes (int [n, 3] (x, y, size) or [n, 4]
     (x, y, w, h), or None) and landmarks (float32 / float64 [n, 2L], or None) -> (boxes, landmarks), new arrays; or faces = one
@@ -965,7 +982,9 @@ def orient_back(images, formats, orients, faces, boxes=None, landmarks=None, rec
             b.shape[1] if b is not None else 0, None if lm is None else lm.ctypes.data,
             lm.dtype.itemsize if lm is not None else 0, lm.shape[1] // 2 if lm is not None else 0,
             le.ctypes.data_as(ip) if len(le) else None, ri.ctypes.data_as(ip) if len(le) else None, len(le))
-    if factors is None:
+    if degrees is not None:
+        rc = lib.jdaRotateBack(px, _degrees(degrees, n_img).ctypes.data_as(C.POINTER(C.c_double)), *tail[:8])
+    elif factors is None:
         rc = lib.jdaOrientBack(px, o.ctypes.data_as(ip), *tail)
     else:
         rc = lib.jdaReduceBack(px, _factors(factors, n_img).ctypes.data_as(ip), o.ctypes.data_as(ip), *tail)
@@ -1020,6 +1039,48 @@ def reduce_back(images, formats, factors, orients, faces, boxes=None, landmarks=
     orients None: upright) -> the coordinates of the whole source images, e.g. to cut chips from the full-resolution frames
     (face_chips[_device] on the original images).  Both calling forms of orient_back."""
     return orient_back(images, formats, 0 if orients is None else orients, faces, boxes, landmarks, rects, left, right, factors)
+
+
+# ---- frames whose faces are rolled (include/jda.h) ----------------------------------------------------------------------------
+def rotation_plan(w, h, degrees):
+    """jdaRotationPlan: the plan of a w x h rectangle rotated by degrees (positive: clockwise as displayed) -> a dict with
+    c, s (the exact table at multiples of 90, the host's cos / sin otherwise), w, h and the rotated size tw, th."""
+    rot = jdaRotation()
+    if lib.jdaRotationPlan(int(w), int(h), float(degrees), C.byref(rot)) != 0:
+        raise JdaError(last_error())
+    return rot.asdict()
+
+
+def _degrees(degrees, n):
+    """One angle for all images or one per image -> float64 [max(n, 1)]."""
+    g = np.full(n, float(degrees), np.float64) if np.ndim(degrees) == 0 else np.ascontiguousarray(degrees, np.float64).reshape(-1)
+    if len(g) != n:
+        raise ValueError("degrees: one angle for all images or one per image")
+    return g if n else np.zeros(1, np.float64)
+
+
+def _rotated_sizes(sizes, degrees):
+    """The (tw, th) of rectangles rotated by their angles (None: none is; what the plan refuses: as it is, the call will say)."""
+    if degrees is None:
+        return sizes
+    out, rot = [], jdaRotation()
+    for (w, h), g in zip(sizes, degrees):
+        out.append((rot.tw, rot.th) if lib.jdaRotationPlan(int(w), int(h), float(g), C.byref(rot)) == 0 else (max(w, 0), max(h, 0)))
+    return out
+
+
+def pack_gray_rotated(images, formats, degrees, rects=None):
+    """jdaPackGrayRotated: pack_gray with every image written rotated by its angle in degrees (any angle, positive: clockwise
+    as displayed; one for all or one per image; include/jda.h, "frames whose faces are rolled") -> a list of uint8 [th, tw]
+    gray arrays, black where the rotated canvas leaves the rectangle.  Host only: no cascador, no GPU."""
+    return _pack_gray("pack_gray_rotated", images, formats, None, rects, None, degrees)
+
+
+def rotate_back(images, formats, degrees, faces, boxes=None, landmarks=None, rects=None):
+    """jdaRotateBack: what a detect call found on images ROTATED by degrees (pack_gray_rotated[_device]) -> the coordinates of
+    the whole source images: landmarks through the rotation, boxes as the upright box of the same size around the rolled
+    face's centre.  Both calling forms of orient_back; nothing mirrors, so there are no pairs."""
+    return orient_back(images, formats, 0, faces, boxes, landmarks, rects, degrees=degrees)
 
 
 def lib_landmarks(casc):
@@ -1497,13 +1558,15 @@ class Cascador:
         return (out, st.asdict()) if stats else out
 
     # -- frames as they arrive: colour / pitched / cropped device images -> dense gray ----------
-    def _pack_gray_device(self, who, images, formats, orients, rects, frame_stride, stats, hip_stream, out, factors=None):
-        """pack_gray_device (orients None), pack_gray_oriented_device and, with factors, pack_gray_reduced_device."""
+    def _pack_gray_device(self, who, images, formats, orients, rects, frame_stride, stats, hip_stream, out, factors=None, degrees=None):
+        """pack_gray_device (orients None), pack_gray_oriented_device, with factors pack_gray_reduced_device and, with degrees,
+        pack_gray_rotated_device."""
         images, px, sizes = _pixels(who, images, formats, rects, True)
         n = len(images)
         o = None if orients is None else _orients(orients, n)
         f = None if factors is None else _factors(factors, n)
-        sizes = _turned_sizes(_reduced_sizes(sizes, f), o)
+        g = None if degrees is None else _degrees(degrees, n)
+        sizes = _rotated_sizes(_turned_sizes(_reduced_sizes(sizes, f), o), g)
         offs, tot = _offsets(sizes, 256, frame_stride)
         if out is not None:
             offs = np.ascontiguousarray(out[1], np.uint64)
@@ -1512,7 +1575,9 @@ class Cascador:
         st = jdaPackStats() if stats else None
         tail = (C.c_void_p(buf.data_ptr()), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
                 C.c_void_p(hip_stream) if hip_stream is not None else None, C.byref(st) if stats else None)
-        if f is not None:
+        if g is not None:
+            rc = lib.jdaPackGrayRotatedDevice(self.h, px, g.ctypes.data_as(C.POINTER(C.c_double)), n, *tail)
+        elif f is not None:
             rc = lib.jdaPackGrayReducedDevice(self.h, px, f.ctypes.data_as(C.POINTER(C.c_int)),
                                               None if o is None else o.ctypes.data_as(C.POINTER(C.c_int)), n, *tail)
         elif o is None:
@@ -1549,6 +1614,13 @@ class Cascador:
         None: every image upright.  -> (buffer, offsets, widths, heights) of the REDUCED, turned images, like
         pack_gray_device's; api.reduce_back takes what a detect call finds on them back to the source images."""
         return self._pack_gray_device("pack_gray_reduced_device", images, formats, orients, rects, frame_stride, stats, hip_stream, out, factors)
+
+    def pack_gray_rotated_device(self, images, formats, degrees, rects=None, frame_stride=None, stats=False, hip_stream=None, out=None):
+        """jdaPackGrayRotatedDevice: pack_gray_device with every image written rotated by its angle in degrees (any angle,
+        positive: clockwise as displayed; one for all or one per image; include/jda.h, "frames whose faces are rolled") by ONE
+        kernel launch.  -> (buffer, offsets, widths, heights) of the ROTATED images, like pack_gray_device's;
+        api.rotate_back takes what a detect call finds on them back to the source images."""
+        return self._pack_gray_device("pack_gray_rotated_device", images, formats, None, rects, frame_stride, stats, hip_stream, out, None, degrees)
 
     # -- faces as they leave: upright chips cut from device images ---------------------------------
     def mean_shape(self):

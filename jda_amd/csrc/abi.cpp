@@ -494,6 +494,29 @@ int jdaReduceBack(const jdaPixels* images, const int* factors, const int* orient
                                     left, right, sym_n}, factors);
 } JDA_ABI_CATCH(-1)
 
+int jdaRotationPlan(int w, int h, double degrees, jdaRotation* rot) try {
+  g_err.clear();
+  return rotation_plan(w, h, degrees, rot);
+} JDA_ABI_CATCH(-1)
+
+int jdaPackGrayRotated(const jdaPixels* images, const double* degrees, int n, unsigned char* dst, const size_t* dst_offsets) try {
+  g_err.clear();
+  return rotate_host(images, degrees, n, dst, dst_offsets);
+} JDA_ABI_CATCH(-1)
+
+int jdaPackGrayRotatedDevice(void* cascador, const jdaPixels* images, const double* degrees, int n, unsigned char* d_dst,
+                             const size_t* dst_offsets, void* hip_stream, jdaPackStats* stats) try {
+  g_err.clear();
+  return rotate_device((Cascador*)cascador, images, degrees, n, d_dst, dst_offsets, (hipStream_t)hip_stream, stats);
+} JDA_ABI_CATCH_SYNC(-1)
+
+int jdaRotateBack(const jdaPixels* images, const double* degrees, int n_images, const int* face_image, int n_faces, int* boxes,
+                  int box_ints, void* landmarks, int real_bytes, int landmark_n) try {
+  g_err.clear();
+  return rotate_back(OrientBackCall{images, nullptr, n_images, face_image, n_faces, boxes, box_ints, landmarks, real_bytes, landmark_n,
+                                    nullptr, nullptr, 0}, degrees);
+} JDA_ABI_CATCH(-1)
+
 int jdaFaceChips(const jdaPixels* images, int n_images, const int* face_image, const void* landmarks, int real_bytes, int n_faces,
                  int landmark_n, const double* tmpl, const unsigned char* use, int chip_w, int chip_h, int chip_format, int supersample,
                  unsigned char* dst, double* matrices) try {
@@ -744,7 +767,7 @@ namespace jda {
 void jda_bc_read_k_scan(unsigned long long*); void jda_bc_read_k_scan_d(unsigned long long*); void jda_bc_read_k_scan_r(unsigned long long*);
 void jda_bc_read_k_scan_dr(unsigned long long*); void jda_bc_read_k_scan_p(unsigned long long*); void jda_bc_read_k_finish(unsigned long long*);
 void jda_bc_read_k_wide(unsigned long long*); void jda_bc_read_k_stage(unsigned long long*); void jda_bc_read_k_mine(unsigned long long*); void jda_bc_read_k_train(unsigned long long*); void jda_bc_read_k_lbf(unsigned long long*);
-void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*); void jda_bc_read_k_fit(unsigned long long*); void jda_bc_read_k_reval(unsigned long long*); void jda_bc_read_k_windows(unsigned long long*); void jda_bc_read_k_pack(unsigned long long*); void jda_bc_read_k_chips(unsigned long long*); void jda_bc_read_k_turn(unsigned long long*); void jda_bc_read_k_reduce(unsigned long long*);
+void jda_bc_read_k_gather(unsigned long long*); void jda_bc_read_k_faces(unsigned long long*); void jda_bc_read_k_fit(unsigned long long*); void jda_bc_read_k_reval(unsigned long long*); void jda_bc_read_k_windows(unsigned long long*); void jda_bc_read_k_pack(unsigned long long*); void jda_bc_read_k_chips(unsigned long long*); void jda_bc_read_k_turn(unsigned long long*); void jda_bc_read_k_reduce(unsigned long long*); void jda_bc_read_k_rotate(unsigned long long*);
 }
 // bounds-check build only (libjda_bounds.so): per translation unit {first violation: site << 32 | source line, violations}
 // since the last call -- out[16]; returns the total number of violations (kernels_common.h: Bc)
@@ -754,10 +777,10 @@ __attribute__((visibility("default"))) long long jdaDebugBoundsReport(unsigned l
                                         jda_bc_read_k_scan_p, jda_bc_read_k_finish, jda_bc_read_k_wide, jda_bc_read_k_stage};
   long long total = 0;
   for (int i = 0; i < 8; i++) { unsigned long long v[2] = {0, 0}; rd[i](v); if (out) { out[2 * i] = v[0]; out[2 * i + 1] = v[1]; } total += (long long)v[1]; }
-  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces', k_fit's, k_reval's, k_windows', k_pack's, k_chips', k_turn's and k_reduce's words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file, cpp_patch.h or cpp_wave.h
-  const struct { void (*rd)(unsigned long long*); const char* tu; } more[12] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
+  // k_mine's, k_train's, k_lbf's, k_gather's, k_faces', k_fit's, k_reval's, k_windows', k_pack's, k_chips', k_turn's, k_reduce's and k_rotate's words ride in k_finish's slot (out keeps its 16 words); the line is the source line of the check, in the .hip file, cpp_patch.h or cpp_wave.h
+  const struct { void (*rd)(unsigned long long*); const char* tu; } more[13] = {{jda_bc_read_k_mine, "k_mine"}, {jda_bc_read_k_train, "k_train"}, {jda_bc_read_k_lbf, "k_lbf"},
                                                                                 {jda_bc_read_k_gather, "k_gather"}, {jda_bc_read_k_faces, "k_faces"}, {jda_bc_read_k_fit, "k_fit"}, {jda_bc_read_k_reval, "k_reval"},
-                                                                                {jda_bc_read_k_windows, "k_windows"}, {jda_bc_read_k_pack, "k_pack"}, {jda_bc_read_k_chips, "k_chips"}, {jda_bc_read_k_turn, "k_turn"}, {jda_bc_read_k_reduce, "k_reduce"}};
+                                                                                {jda_bc_read_k_windows, "k_windows"}, {jda_bc_read_k_pack, "k_pack"}, {jda_bc_read_k_chips, "k_chips"}, {jda_bc_read_k_turn, "k_turn"}, {jda_bc_read_k_reduce, "k_reduce"}, {jda_bc_read_k_rotate, "k_rotate"}};
   for (const auto& t : more) {
     unsigned long long v[2] = {0, 0};
     t.rd(v);

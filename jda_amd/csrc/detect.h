@@ -84,9 +84,12 @@ struct PackOne {
   int w, h, bpp, format;
   int tf;                             // kTf[orientation] (0 without orients)
   int f;                              // the factor (1 unless reduced: then npix = (w / f) * (h / f), the bytes of dst)
+  double c, s;                        // the rotation's plan (0 unless rotated: then npix = tw * th, the bytes of dst)
+  int tw, th;
 };
 bool check_pack(const std::string& who, const jdaPixels* images, const int* orients, bool turned, int n, unsigned char* dst,
-                const size_t* dst_offsets, std::vector<PackOne>* out, const int* factors = nullptr, bool reduced = false);
+                const size_t* dst_offsets, std::vector<PackOne>* out, const int* factors = nullptr, bool reduced = false,
+                const double* degrees = nullptr, bool rotated = false);
 // The units of `bytes` bytes at dst (kernels.h: PackImg, ChipArgs): bytes in front of dst's first 16-byte boundary, runs of 16, bytes behind
 struct DstUnits { int head; long long nq; int tail; long long total() const { return nq + head + tail; } };
 inline DstUnits dst_units(const void* dst, long long bytes) {
@@ -96,7 +99,7 @@ inline DstUnits dst_units(const void* dst, long long bytes) {
   u.tail = (int)(bytes - u.head - (u.nq << 4));
   return u;
 }
-// What PackImg, TurnImg and ReduceImg have in common, the rest zero: the image, its first unit / tile in the launch and the Q14 weights,
+// What PackImg, TurnImg, ReduceImg and RotImg have in common, the rest zero: the image, its first unit / tile in the launch and the Q14 weights,
 // split into their low and high bytes
 template <typename Img>
 void pack_img(Img* t, const PackOne& o, long long first) {
@@ -109,7 +112,8 @@ void pack_img(Img* t, const PackOne& o, long long first) {
   t->w_hi = (uint32_t)(w[0] >> 8) | ((uint32_t)(w[1] >> 8) << 8) | ((uint32_t)(w[2] >> 8) << 16);
 }
 // The image table of a launch that deals 64 x 64 tiles of the turned images (Img: TurnImg, or ReduceImg, whose w x h is the
-// rectangle reduced by its factor; kernels.h) and the image of every workgroup's tile
+// rectangle reduced by its factor, or RotImg, whose turned image is the plan's tw x th; kernels.h) and the image of every
+// workgroup's tile
 template <typename Img>
 bool turn_tiles(const std::string& who, const std::vector<PackOne>& v, std::vector<Img>* tab, std::vector<int>* block_img, long long* total_out) {
   const int n = (int)v.size();
@@ -119,9 +123,14 @@ bool turn_tiles(const std::string& who, const std::vector<PackOne>& v, std::vect
     const PackOne& o = v[(size_t)i];
     Img& t = (*tab)[(size_t)i];
     pack_img(&t, o, total);
-    t.tf = o.tf;
-    if constexpr (std::is_same<Img, ReduceImg>::value) { t.f = o.f; t.w = o.w / o.f; t.h = o.h / o.f; }
-    const int TW = (o.tf & kMineSwap) ? t.h : t.w, TH = (o.tf & kMineSwap) ? t.w : t.h;
+    int TW, TH;
+    if constexpr (std::is_same<Img, RotImg>::value) {
+      t.c = o.c; t.s = o.s; t.tw = TW = o.tw; t.th = TH = o.th;
+    } else {
+      t.tf = o.tf;
+      if constexpr (std::is_same<Img, ReduceImg>::value) { t.f = o.f; t.w = o.w / o.f; t.h = o.h / o.f; }
+      TW = (o.tf & kMineSwap) ? t.h : t.w; TH = (o.tf & kMineSwap) ? t.w : t.h;
+    }
     t.off = (int)((uintptr_t)o.dst & 15);
     t.ntu = (int)(((long long)TW + t.off + kTurnTile - 1) / kTurnTile);
     t.ntv = (TH + kTurnTile - 1) / kTurnTile;
@@ -152,10 +161,11 @@ struct OrientBackCall {
 int orient_back(const OrientBackCall& call);
 // ... and what it shares with reduce.cpp: the writing half of turn_host and the launching half of turn_device (which is
 // pack_launch where every image is upright), on images check_pack has passed, in the name `who` of the entry the caller
-// called; orient_back with a factor per image (nullptr: jdaOrientBack itself)
+// called; orient_back with a factor per image (nullptr: jdaOrientBack itself) or, for rotate.cpp, an angle per image in place
+// of the orientations
 void turn_write(const std::vector<PackOne>& v);
 int turn_launch(LaneCall& call, const std::string& who, const std::vector<PackOne>& v, hipStream_t user_stream, jdaPackStats* stats);
-int orient_back(const std::string& who, const OrientBackCall& call, const int* factors);
+int orient_back(const std::string& who, const OrientBackCall& call, const int* factors, const double* degrees = nullptr);
 
 // reduce.cpp: frames larger than the faces need (jdaReduceSize, jdaPackGrayReduced[Device], jdaReduceBack)
 int reduce_size(int w, int h, int factor, int orient, int* rw, int* rh);
@@ -163,6 +173,17 @@ int reduce_host(const jdaPixels* images, const int* factors, const int* orients,
 int reduce_device(Cascador* c, const jdaPixels* images, const int* factors, const int* orients, int n, unsigned char* d_dst,
                   const size_t* dst_offsets, hipStream_t user_stream, jdaPackStats* stats);
 int reduce_back(const OrientBackCall& call, const int* factors);
+
+// rotate.cpp: frames whose faces are rolled (jdaRotationPlan, jdaPackGrayRotated[Device], jdaRotateBack)
+int rotation_plan(int w, int h, double degrees, jdaRotation* rot);
+int rotate_host(const jdaPixels* images, const double* degrees, int n, unsigned char* dst, const size_t* dst_offsets);
+int rotate_device(Cascador* c, const jdaPixels* images, const double* degrees, int n, unsigned char* d_dst, const size_t* dst_offsets,
+                  hipStream_t user_stream, jdaPackStats* stats);
+int rotate_back(const OrientBackCall& call, const double* degrees);
+// ... and what it shares with pack.cpp and turn.cpp: the plan in the name `who` of the entry the caller called (false after
+// fail()), and one face of the way back -- its box and landmarks through the plan's map into the whole source image
+bool rotation_plan(const std::string& who, int w, int h, double degrees, jdaRotation* rot);
+void rotate_back_face(const OrientBackCall& call, int face, const PixelsOne& rect, const jdaRotation& rot);
 
 // chips.cpp: faces as they leave (jdaFaceChips / jdaFaceChipsDevice)
 struct ChipsCall {

@@ -11,6 +11,7 @@
 //   pack.cpp       colour / pitched / cropped frames -> dense gray      chips.cpp    upright face chips cut from detections
 //   turn.cpp       the same, turned by one of the eight orientations; results mapped back
 //   reduce.cpp     the same, reduced by an integer factor first; results mapped back
+//   rotate.cpp     the same, rotated by any angle; results mapped back
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -444,7 +445,7 @@ struct Lane {
   DevBuf frames;                             // staging of host frames (the call's first lane holds the whole batch)
   DevBuf pyr;                                // half + quarter images (multi-scale models), method-0 levels
   DevBuf win;                                // jdaValidateWindows: a chunk's window list and its per-window outputs (windows.cpp)
-  DevBuf tab;                                // the host-made tables of a frame entry's one launch (LaneCall::upload: pack.cpp, turn.cpp, reduce.cpp, chips.cpp)
+  DevBuf tab;                                // the host-made tables of a frame entry's one launch (LaneCall::upload: pack.cpp, turn.cpp, reduce.cpp, rotate.cpp, chips.cpp)
   // ragged passes: images at the common pitch, tight images, tables (segments, block map, image records)
   DevBuf rag_frames, rag_raw, rag_tab;
   HostPinned h_tab, h_raw;
@@ -712,7 +713,7 @@ struct OneLane {
   }
 };
 
-// A frame entry (pack.cpp, turn.cpp, reduce.cpp, chips.cpp, windows.cpp): a call that runs on one lane, on the caller's stream or the
+// A frame entry (pack.cpp, turn.cpp, reduce.cpp, rotate.cpp, chips.cpp, windows.cpp): a call that runs on one lane, on the caller's stream or the
 // lane's, and reports device_ms and call_ms.  Made where the entry begins (t0), opened once everything is validated.
 struct LaneCall {
   const double t0 = now_ms();

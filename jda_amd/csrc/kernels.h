@@ -665,6 +665,25 @@ static_assert(sizeof(ReduceImg) == 72, "ReduceImg is uploaded as it is");
 struct ReduceArgs { const ReduceImg* imgs; const int* block_img; int n; long long total; };
 hipError_t launch_reduce(const ReduceArgs& a, hipStream_t stream);
 
+// ---- frames whose faces are rolled: the same pack, rotated by any angle (k_rotate.hip, rotate.cpp; include/jda.h) ----
+constexpr int kRotMaxSide = 32768;       // a rotated image is at most this wide and high
+constexpr int kRotBox = 92;             // a tile's source box is at most kRotBox x kRotBox pixels (the covering proof)
+constexpr int kRotPitch = 96;            // bytes from one row of the LDS box to the next: 24 dwords, a lane fills one
+// One image of a launch: the w x h pixels of bpp bytes from src (the rectangle's first pixel; rows `pitch` bytes apart), rotated
+// by the plan's (c, s) (jdaRotationPlan), to the tw * th bytes at dst.  Tiles, first, ntu, ntv and off as TurnImg's, of the
+// tw x th image.  w_lo / w_hi: PackImg's.
+struct RotImg {
+  const uint8_t* src; uint8_t* dst;
+  long long pitch, first;
+  double c, s;
+  int w, h, bpp, tw, th, ntu, ntv, off;
+  uint32_t w_lo, w_hi;
+};
+static_assert(sizeof(RotImg) == 88, "RotImg is uploaded as it is");
+// One launch: imgs[0 .. n), total = the tiles of all of them; block_img[b] = the image of tile (workgroup) b.
+struct RotArgs { const RotImg* imgs; const int* block_img; int n; long long total; };
+hipError_t launch_rotate(const RotArgs& a, hipStream_t stream);
+
 // ---- faces as they leave: upright face chips cut from detections (k_chips.hip, chips.cpp; include/jda.h) ----
 constexpr int kChipBlock = 256;          // lanes of a workgroup: consecutive lanes take consecutive units
 // One face of a launch: M maps chip pixel centres to source pixels (sx = (m[0] * cu + m[1] * cv) + m[2], sy with m[3..5]),

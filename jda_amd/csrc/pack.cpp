@@ -23,15 +23,17 @@ bool touches_rows(const PackOne& s, uintptr_t d0, uintptr_t d1) {
 // Everything jdaPackGray / jdaPackGrayDevice refuse (include/jda.h); on success one PackOne per image.  With orients (turn.cpp)
 // an orientation outside 0..7 is refused like an unknown format; a turned image takes the same w * h bytes of dst.  With
 // reduced (reduce.cpp) factors are needed, a factor outside 1..kReduceMax or above w or h is refused the same way, and image
-// i takes (w / f) * (h / f) bytes of dst: npix, which every overlap check below reads.
+// i takes (w / f) * (h / f) bytes of dst: npix, which every overlap check below reads.  With rotated (rotate.cpp) degrees are
+// needed, an angle the plan refuses or a turned side above kRotMaxSide is refused the same way, and image i takes tw * th bytes.
 bool check_pack(const std::string& who, const jdaPixels* images, const int* orients, bool turned, int n, unsigned char* dst,
-                const size_t* dst_offsets, std::vector<PackOne>* out, const int* factors, bool reduced) {
+                const size_t* dst_offsets, std::vector<PackOne>* out, const int* factors, bool reduced, const double* degrees, bool rotated) {
   if (n < 0) { fail(who + "negative number of images (n = " + std::to_string(n) + ")"); return false; }
   if (n == 0) return true;
   if (!images) { fail(who + "null images"); return false; }
   if (!dst) { fail(who + "null destination"); return false; }
   if (turned && !orients) { fail(who + "null orients"); return false; }
   if (reduced && !factors) { fail(who + "null factors"); return false; }
+  if (rotated && !degrees) { fail(who + "null degrees"); return false; }
   if (!dst_offsets) { fail(who + "null dst_offsets"); return false; }
   out->resize((size_t)n);
   for (int i = 0; i < n; i++) {
@@ -41,6 +43,7 @@ bool check_pack(const std::string& who, const jdaPixels* images, const int* orie
     o.src = r.src;
     o.dst = dst + dst_offsets[i];
     o.pitch = r.pitch; o.npix = (long long)r.w * r.h; o.w = r.w; o.h = r.h; o.bpp = r.bpp; o.format = r.format; o.tf = 0; o.f = 1;
+    o.c = o.s = 0; o.tw = o.th = 0;
     if (turned) {
       if (orients[i] < 0 || orients[i] > 7) { fail(who + "image " + std::to_string(i) + ": unknown orientation " + std::to_string(orients[i]) + " (0..7)"); return false; }
       o.tf = kTf[orients[i]];
@@ -53,6 +56,16 @@ bool check_pack(const std::string& who, const jdaPixels* images, const int* orie
         return false;
       }
       o.f = f; o.npix = (long long)(r.w / f) * (r.h / f);
+    }
+    if (rotated) {
+      jdaRotation rot;
+      if (!rotation_plan(who + "image " + std::to_string(i) + ": ", r.w, r.h, degrees[i], &rot)) return false;
+      if (rot.tw > kRotMaxSide || rot.th > kRotMaxSide) {
+        fail(who + "image " + std::to_string(i) + ": a rectangle of " + std::to_string(r.w) + " x " + std::to_string(r.h) + " rotated by " + std::to_string(degrees[i]) +
+             " degrees is " + std::to_string(rot.tw) + " x " + std::to_string(rot.th) + " (at most " + std::to_string(kRotMaxSide) + " a side)");
+        return false;
+      }
+      o.c = rot.c; o.s = rot.s; o.tw = rot.tw; o.th = rot.th; o.npix = (long long)rot.tw * rot.th;
     }
   }
   // two destination images that overlap: neighbours in address order

@@ -1,4 +1,4 @@
-// What k_pack.hip, k_turn.hip, k_reduce.hip and k_chips.hip share (include/jda.h, "frames as they arrive"): the address-space typedefs of the
+// What k_pack.hip, k_turn.hip, k_reduce.hip, k_rotate.hip and k_chips.hip share (include/jda.h, "frames as they arrive"): the address-space typedefs of the
 // records' pointers, the Q14 gray value of a colour pixel as two v_dot4_u32_u8, one pixel by byte loads, a run of pixels of one
 // source row by aligned vector loads (pack_row), the bounds-check of such a run, and the units a destination is dealt in.
 // Device code only; every name lives in the including translation unit.

@@ -110,12 +110,14 @@ int turn_launch(LaneCall& call, const std::string& who, const std::vector<PackOn
 
 int orient_back(const OrientBackCall& k) { return orient_back("jdaOrientBack: ", k, nullptr); }
 
-int orient_back(const std::string& who, const OrientBackCall& k, const int* factors) {
+// degrees (rotate.cpp): an angle per image in place of the orientations -- the same refusals, the plan's in place of the
+// orientation's, and every face through rotate_back_face
+int orient_back(const std::string& who, const OrientBackCall& k, const int* factors, const double* degrees) {
   if (k.n_faces < 0) { fail(who + "negative number of faces (n_faces = " + std::to_string(k.n_faces) + ")"); return -1; }
   if (k.n_images < 0) { fail(who + "negative number of images (n_images = " + std::to_string(k.n_images) + ")"); return -1; }
   if (k.n_faces == 0) return 0;
   if (!k.images) { fail(who + "null images"); return -1; }
-  if (!k.orients) { fail(who + "null orients"); return -1; }
+  if (!k.orients && !degrees) { fail(who + "null orients"); return -1; }
   if (!k.face_image) { fail(who + "null face_image"); return -1; }
   if (k.boxes && k.box_ints != 3 && k.box_ints != 4) { fail(who + "box_ints = " + std::to_string(k.box_ints) + ": 3 (x, y, size) or 4 (x, y, w, h)"); return -1; }
   if (k.landmarks) {
@@ -132,8 +134,13 @@ int orient_back(const std::string& who, const OrientBackCall& k, const int* fact
     }
   }
   std::vector<PixelsOne> img((size_t)k.n_images);
+  std::vector<jdaRotation> rot(degrees ? (size_t)k.n_images : 0);
   for (int i = 0; i < k.n_images; i++) {
     if (!check_pixels(who + "image " + std::to_string(i) + ": ", k.images[i], &img[(size_t)i])) return -1;
+    if (degrees) {
+      if (!rotation_plan(who + "image " + std::to_string(i) + ": ", img[(size_t)i].w, img[(size_t)i].h, degrees[i], &rot[(size_t)i])) return -1;
+      continue;
+    }
     if (k.orients[i] < 0 || k.orients[i] > 7) { fail(who + "image " + std::to_string(i) + ": unknown orientation " + std::to_string(k.orients[i]) + " (0..7)"); return -1; }
     if (!factors) continue;
     const int f = factors[i];
@@ -150,6 +157,7 @@ int orient_back(const std::string& who, const OrientBackCall& k, const int* fact
     }
   }
   for (int f = 0; f < k.n_faces; f++) {
+    if (degrees) { rotate_back_face(k, f, img[(size_t)k.face_image[f]], rot[(size_t)k.face_image[f]]); continue; }
     const int i = k.face_image[f], t = k.orients[i], tf = kTf[t];
     const PixelsOne& r = img[(size_t)i];
     const int fc = factors ? factors[i] : 0, w = fc ? r.w / fc : r.w, h = fc ? r.h / fc : r.h;   // the rectangle as it was turned
