@@ -100,6 +100,13 @@ def _cv_norm_l2(v):
     return math.sqrt(s)
 
 
+def _div(a, b):
+    """a / b as C divides doubles: a zero divisor gives +-inf, or NaN for 0 / 0, where Python raises."""
+    if b == 0.:
+        return math.nan if (a == 0. or a != a) else math.copysign(math.inf, a) * math.copysign(1., b)
+    return a / b
+
+
 def st_calc(shape1, shape2, L):
     """STParameter::Calc (data.cpp:64-114) with face.similarity_transform on.  Two OpenCV details decide bits here and
     neither can be run in this image: cv::norm's summation order (above) and `Mat /= double`, which mat.inl.hpp spells
@@ -115,8 +122,8 @@ def st_calc(shape1, shape2, L):
         t1[2 * i] = shape1[2 * i] - x1c; t1[2 * i + 1] = shape1[2 * i + 1] - y1c
         t2[2 * i] = shape2[2 * i] - x2c; t2[2 * i + 1] = shape2[2 * i + 1] - y2c
     scale1, scale2 = _cv_norm_l2(t1), _cv_norm_l2(t2)
-    scale = scale1 / scale2
-    a1, a2 = 1. / scale1, 1. / scale2
+    scale = _div(scale1, scale2)                # (a centred shape of norm 0 -- L = 1, coinciding landmarks -- divides by zero:
+    a1, a2 = _div(1., scale1), _div(1., scale2)  #  the reference goes on with inf and NaN, and so does this)
     t1 = [v * a1 + 0. for v in t1]
     t2 = [v * a2 + 0. for v in t2]
     num = den = 0.
@@ -124,7 +131,7 @@ def st_calc(shape1, shape2, L):
         num += t1[2 * i + 1] * t2[2 * i] - t1[2 * i] * t2[2 * i + 1]
         den += t1[2 * i] * t2[2 * i] + t1[2 * i + 1] * t2[2 * i + 1]
     norm = math.sqrt(num * num + den * den)
-    sin_t, cos_t = num / norm, den / norm
+    sin_t, cos_t = _div(num, norm), _div(den, norm)
     return (scale, cos_t, -sin_t, sin_t, cos_t)
 
 
@@ -387,6 +394,8 @@ def detect_pyramid(m, img, resize, origin_size=48, half_size=36, quarter_size=24
 #      (x: sx < 0 -> 0 with fx 0; sx >= w - 1 -> w - 1 with fx 0; y: coefficients untouched, the two row indices clipped), 11-bit coefficients saturate_cast<short>(c * 2048) with
 #      round-half-to-even, the horizontal pass in ints, the vertical pass ((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16)
 #      + 2) >> 2, and resize()'s switch to the 2x2 area average (a + b + c + d + 2) >> 2 when both scales are exactly 2.
+#      What it MEANS is checked apart from anybody's code: tests/test_exact_host.py holds it within a derived 0.886 gray level
+#      of real-valued bilinear interpolation (half-pixel centres, replicated borders) and to the rounded block mean at 2x.
 import numpy as _np
 
 
