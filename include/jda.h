@@ -694,6 +694,30 @@ JDA_API int jdaMineNegativesCppDevice(void *cascador, const unsigned char *d_bas
                                       long long start, int size, double shift_size, uint64_t seed, int *hits,
                                       double *score, double *shape, unsigned char *patches, jdaMineStats *stats);
 
+/* What the mining and Validate calls of a cascador launched ("the kernels at their limits").
+ * jdaMineNegativesCpp* and jdaValidateCpp* count the launches of the five kernels of k_mine.hip here, where the launch is
+ * made: a launcher that returns without launching (nothing to do) counts nothing.  (jdaValidateSamplesCpp's lane-per-sample
+ * form borrows k_mine_walk for resident samples; it is no mining call and counts nothing here.)
+ *   JDA_MINE_K_SCAN .. JDA_MINE_K_SUM  launches of k_mine_scan, k_mine_items, k_mine_patches, k_mine_walk, k_mine_sum
+ *   JDA_MINE_CHUNKS          chunks of the enumeration a mining call scanned (one k_mine_scan launch each)
+ *   JDA_MINE_WALK_BATCHES    batches of crops that went through k_mine_patches + k_mine_walk, of mining and of Validate
+ *   JDA_MINE_SUM_SATURATED   k_mine_sum launches whose grid stood at its largest, so that a lane read more than one
+ *                            window's status (more windows than lanes)
+ *   JDA_MINE_SCAN_REJECTS    windows k_mine_scan rejected below a chunk's cut (what k_mine_sum counted)
+ *   JDA_MINE_WALK_REJECTS    windows of a mining call that k_mine_walk rejected below a chunk's cut; the two add up to
+ *                            jdaMineStats::nega_n over the same calls
+ * Those ten are cumulative since the cascador was created, added atomically; take the difference around a call.  Two are
+ * not sums:
+ *   JDA_MINE_WALK_BATCH_MAX  the largest batch so far, in crops (never shrinks)
+ *   JDA_MINE_WALK_CAP        the most crops a batch could hold in the LAST call that sized its walk buffers: what
+ *                            "workspace_mb", the model and the patch sizes allow (at most 65,536), and for
+ *                            jdaValidateCpp* no more than the call's crops
+ * Returns 0, or -1 for a null argument.  Needs no device. */
+enum { JDA_MINE_K_SCAN = 0, JDA_MINE_K_ITEMS = 1, JDA_MINE_K_PATCHES = 2, JDA_MINE_K_WALK = 3, JDA_MINE_K_SUM = 4,
+       JDA_MINE_CHUNKS = 5, JDA_MINE_WALK_BATCHES = 6, JDA_MINE_SUM_SATURATED = 7, JDA_MINE_SCAN_REJECTS = 8,
+       JDA_MINE_WALK_REJECTS = 9, JDA_MINE_WALK_BATCH_MAX = 10, JDA_MINE_WALK_CAP = 11, JDA_MINE_LAUNCH_N = 12 };
+JDA_API int jdaMineLaunches(void *cascador, long long counts[JDA_MINE_LAUNCH_N]);
+
 /* Host-only (no GPU): the mining enumeration of ONE (already transformed) w x h image -- windows and levels; the listing
  * writes up to cap (x, y, win) triples in enumeration order and returns the number of windows (-1 on bad arguments). */
 JDA_API int jdaMineWindows(int w, int h, int origin_size, int step, double factor, long long *n, int *levels);

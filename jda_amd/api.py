@@ -63,6 +63,10 @@ STAGE_LAUNCH_FIELDS = (("dialect", ("C", "CPP")), ("trace", (False, True)), ("gl
                        ("chunk", (4, 8, 16, 32, 64)))
 STAGE_LAUNCH_N = 160
 StageLaunch = _launch_key("StageLaunch", STAGE_LAUNCH_FIELDS, "The key of one k_stage launch (include/jda.h: JDA_STAGE_LAUNCH).")
+# include/jda.h: jdaMineLaunches' counts in index order (JDA_MINE_K_SCAN .. JDA_MINE_WALK_CAP, lower case without the prefix)
+MINE_LAUNCH_FIELDS = ("k_scan", "k_items", "k_patches", "k_walk", "k_sum", "chunks", "walk_batches", "sum_saturated", "scan_rejects",
+                      "walk_rejects", "walk_batch_max", "walk_cap")
+MINE_LAUNCH_N = 12
 
 
 class JdaError(RuntimeError):
@@ -272,6 +276,8 @@ def _load():
     lib.jdaFinishTileWin.argtypes = [C.c_void_p, C.c_int]
     lib.jdaStageLaunches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.jdaStageLaunchFor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    if hasattr(lib, "jdaMineLaunches"):             # (older builds, loaded through JDA_LIB_PATH for A/B runs, lack it)
+        lib.jdaMineLaunches.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     lib.jdaCountWindows.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                     C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     lib.jdaDetectOptionsInit.restype = None
@@ -1410,6 +1416,16 @@ class Cascador:
         if lib.jdaStageLaunches(self.h, counts) != 0:
             raise JdaError(last_error())
         return {StageLaunch.of_index(i): int(x) for i, x in enumerate(counts) if x}
+
+    def mine_launches(self):
+        """jdaMineLaunches: what this cascador's mining and Validate calls have launched since it was created -> a dict with
+        every name of MINE_LAUNCH_FIELDS: launches of the five k_mine.hip kernels, chunks, walk batches, saturated
+        k_mine_sum launches, the scan's and the walk's rejects (cumulative: take the difference around a call), the largest
+        walk batch so far and the batch cap of the last call."""
+        counts = (C.c_longlong * MINE_LAUNCH_N)()
+        if lib.jdaMineLaunches(self.h, counts) != 0:
+            raise JdaError(last_error())
+        return {k: int(x) for k, x in zip(MINE_LAUNCH_FIELDS, counts)}
 
     def stage_launch_for(self, dialect, trace, win, step):
         """jdaStageLaunchFor: (the StageLaunch key, the dynamic LDS bytes) of the k_stage launch a level of `win`-pixel

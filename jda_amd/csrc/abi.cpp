@@ -241,6 +241,10 @@ int jdaStageLaunches(void* cascador, long long counts[JDA_STAGE_LAUNCH_N]) try {
   return launch_report("jdaStageLaunches", cascador, &LaunchLog::stage_launches, counts);
 } JDA_ABI_CATCH(-1)
 
+int jdaMineLaunches(void* cascador, long long counts[JDA_MINE_LAUNCH_N]) try {
+  return launch_report("jdaMineLaunches", cascador, &LaunchLog::mine_launches, counts);
+} JDA_ABI_CATCH(-1)
+
 int jdaStageLaunchFor(void* cascador, int dialect, int trace, int win, int step, int* lds_bytes) try {
   Cascador* c = (Cascador*)cascador;
   if (!c || (dialect != JDA_DIALECT_C && dialect != JDA_DIALECT_CPP) || win < 1 || step < 1) {

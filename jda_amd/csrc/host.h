@@ -502,8 +502,8 @@ struct Lane {
   }
 };
 
-// ---- the launch reports (include/jda.h: jdaFinishForms, jdaScanForms, jdaFinishLaunches, jdaStageLaunches) ----
-// A launcher says what it launched in a record (kernels.h: ScanLaunch, FinishLaunch, WideLaunch, StageChoice); here, and
+// ---- the launch reports (include/jda.h: jdaFinishForms, jdaScanForms, jdaFinishLaunches, jdaStageLaunches, jdaMineLaunches) ----
+// A launcher says what it launched in a record (kernels.h: ScanLaunch, FinishLaunch, WideLaunch, StageChoice, MineLaunch); here, and
 // nowhere else, a record becomes the public index of its report and is counted.
 
 // A scan launch's index in jdaScanForms' counts.
@@ -570,15 +570,18 @@ static_assert(stage_launch_key(JDA_DIALECT_C, false, stage(12, 8, false)) == 1 &
               stage_launch_key(JDA_DIALECT_C, false, stage(32, 4, false)) == 5 && stage_launch_key(JDA_DIALECT_C, false, stage(160, 4, false)) == 15 &&
               stage_launch_key(JDA_DIALECT_C, false, stage(12, 4, true)) == 20 && stage_launch_key(JDA_DIALECT_C, true, stage(12, 4, false)) == 40 &&
               stage_launch_key(JDA_DIALECT_CPP, false, stage(12, 4, false)) == 80, "chunk 8 and 64, acc 32 and 160, glb, trace, dialect");
+static_assert(kMineKScan == JDA_MINE_K_SCAN && kMineKItems == JDA_MINE_K_ITEMS && kMineKPatches == JDA_MINE_K_PATCHES &&
+              kMineKWalk == JDA_MINE_K_WALK && kMineKSum == JDA_MINE_K_SUM, "a MineLaunch's kernel is its index in jdaMineLaunches");
 }  // namespace launch_key_check
 
-// The four reports of a cascador: cumulative counts, added atomically where a pass has issued a launch (or, the five
-// path forms, is about to issue its launches).  count() holds the only additions.
+// The five reports of a cascador: cumulative counts, added atomically where a pass has issued a launch (or, the five
+// path forms, is about to issue its launches).  count() and the count_mine_* below it hold the only additions.
 struct LaunchLog {
   std::atomic<long long> finish_forms[JDA_FINISH_FORM_N] = {};        // jdaFinishForms
   std::atomic<long long> scan_forms[JDA_SCAN_FORM_N] = {};            // jdaScanForms
   std::atomic<long long> finish_launches[JDA_FINISH_LAUNCH_N] = {};   // jdaFinishLaunches
   std::atomic<long long> stage_launches[JDA_STAGE_LAUNCH_N] = {};     // jdaStageLaunches
+  std::atomic<long long> mine_launches[JDA_MINE_LAUNCH_N] = {};       // jdaMineLaunches
   // a finishing form that is a decision of the pass, not of a launcher: MERGED, FILTER0, MID_DIRECT, TWO_LAUNCH, DENSE
   void count_form(int form) { add(finish_forms, form); }
   // a launcher's record; one that launched nothing counts nothing
@@ -586,6 +589,24 @@ struct LaunchLog {
   void count(int dialect, const FinishLaunch& f) { if (f.launched) add(finish_launches, finish_launch_key(dialect, f)); }
   void count(int, const WideLaunch& w) { if (w.launched) add(finish_forms, w.conc ? JDA_FINISH_WIDE_CONC : JDA_FINISH_WIDE_SEQ); }
   void count(int dialect, bool trace, const StageChoice& s) { add(stage_launches, stage_launch_key(dialect, trace, s)); }
+  // a k_mine.hip launcher's record (mine.cpp); a saturated k_mine_sum launch counts under both of its indices
+  void count(const MineLaunch& l) {
+    if (!l.launched) return;
+    add(mine_launches, l.kernel);
+    if (l.kernel == kMineKSum && l.saturated) add(mine_launches, JDA_MINE_SUM_SATURATED);
+  }
+  // what mine.cpp's loops did: a chunk scanned, rejects below its cut, a walk batch of nb crops, the cap of a call's batches
+  void count_mine_chunk() { add(mine_launches, JDA_MINE_CHUNKS); }
+  void count_mine_rejects(long long scan, long long walk) {
+    mine_launches[JDA_MINE_SCAN_REJECTS].fetch_add(scan, std::memory_order_relaxed);
+    mine_launches[JDA_MINE_WALK_REJECTS].fetch_add(walk, std::memory_order_relaxed);
+  }
+  void count_mine_batch(long long nb) {
+    add(mine_launches, JDA_MINE_WALK_BATCHES);
+    std::atomic<long long>& mx = mine_launches[JDA_MINE_WALK_BATCH_MAX];
+    for (long long v = mx.load(std::memory_order_relaxed); v < nb && !mx.compare_exchange_weak(v, nb, std::memory_order_relaxed);) {}
+  }
+  void set_mine_cap(long long cap) { mine_launches[JDA_MINE_WALK_CAP].store(cap, std::memory_order_relaxed); }
   template <int N> static void copy_out(const std::atomic<long long> (&a)[N], long long* counts) {
     for (int i = 0; i < N; i++) counts[i] = a[i].load(std::memory_order_relaxed);
   }

@@ -107,11 +107,14 @@ __global__ __launch_bounds__(256) void k_mine_scan(MineModel m, MineSizes z, con
 
 hipError_t launch_mine_scan(const MineModel& m, const MineSizes& z, const uint8_t* base, const MineImg* imgs,
                             const MineSeg* segs, int n_segs, unsigned long long lo, unsigned long long hi, int carts0,
-                            int* status, unsigned long long* surv, unsigned* n_surv, hipStream_t stream) {
+                            int* status, unsigned long long* surv, unsigned* n_surv, hipStream_t stream, MineLaunch* how) {
+  if (how) *how = MineLaunch{false, kMineKScan, 0u, false};
   if (hi <= lo) return hipSuccess;
   const unsigned long long n = hi - lo;
-  hipLaunchKernelGGL(k_mine_scan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, m, z, base, imgs, segs, n_segs, lo,
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(k_mine_scan, dim3(grid), dim3(256), 0, stream, m, z, base, imgs, segs, n_segs, lo,
                      hi, carts0, status, surv, n_surv);
+  if (how) { how->launched = true; how->grid = grid; }
   return hipGetLastError();
 }
 
@@ -134,9 +137,12 @@ __global__ __launch_bounds__(256) void k_mine_items(const MineSeg* __restrict__ 
 }
 
 hipError_t launch_mine_items(const MineSeg* segs, int n_segs, const unsigned long long* ords, int n, MineItem* items,
-                             hipStream_t stream) {
+                             hipStream_t stream, MineLaunch* how) {
+  if (how) *how = MineLaunch{false, kMineKItems, 0u, false};
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_mine_items, dim3((n + 255) / 256), dim3(256), 0, stream, segs, n_segs, ords, n, items);
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(k_mine_items, dim3(grid), dim3(256), 0, stream, segs, n_segs, ords, n, items);
+  if (how) { how->launched = true; how->grid = grid; }
   return hipGetLastError();
 }
 
@@ -178,10 +184,12 @@ __global__ __launch_bounds__(256) void k_mine_patches(MineSizes z, const uint8_t
 }
 
 hipError_t launch_mine_patches(const MineSizes& z, const uint8_t* base, const MineImg* imgs, const MineItem* items, int n,
-                               uint8_t* patches, int pbytes, hipStream_t stream) {
+                               uint8_t* patches, int pbytes, hipStream_t stream, MineLaunch* how) {
+  if (how) *how = MineLaunch{false, kMineKPatches, 0u, false};
   if (n <= 0) return hipSuccess;
   if (z.os > kMinePatchMax || z.hs > kMinePatchMax || z.qs > kMinePatchMax) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_mine_patches, dim3(n), dim3(256), 0, stream, z, base, imgs, items, patches, pbytes);
+  if (how) { how->launched = true; how->grid = (unsigned)n; }
   return hipGetLastError();
 }
 
@@ -265,10 +273,13 @@ __global__ __launch_bounds__(64) void k_mine_walk(MineModel m, MineSizes z, cons
 
 hipError_t launch_mine_walk(const MineModel& m, const MineSizes& z, const MineItem* items, int n, const uint8_t* patches,
                             int pbytes, int similarity, uint8_t* face, int* carts_n, double* score, double* shape, int* lbf,
-                            double* t1, double* t2, hipStream_t stream, const double* init) {
+                            double* t1, double* t2, hipStream_t stream, const double* init, MineLaunch* how) {
+  if (how) *how = MineLaunch{false, kMineKWalk, 0u, false};
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_mine_walk, dim3((n + 63) / 64), dim3(64), 0, stream, m, z, items, n, patches, pbytes, similarity, face,
+  const unsigned grid = (unsigned)((n + 63) / 64);
+  hipLaunchKernelGGL(k_mine_walk, dim3(grid), dim3(64), 0, stream, m, z, items, n, patches, pbytes, similarity, face,
                      carts_n, score, shape, lbf, t1, t2, init);
+  if (how) { how->launched = true; how->grid = grid; }
   return hipGetLastError();
 }
 
@@ -291,10 +302,14 @@ __global__ __launch_bounds__(256) void k_mine_sum(const int* __restrict__ status
   if ((threadIdx.x & 63) == 0 && (cnt | sum)) { atomicAdd(&out[0], cnt); atomicAdd(&out[1], sum); }
 }
 
-hipError_t launch_mine_sum(const int* status, unsigned long long n, unsigned long long* out, hipStream_t stream) {
+hipError_t launch_mine_sum(const int* status, unsigned long long n, unsigned long long* out, hipStream_t stream,
+                           MineLaunch* how) {
+  if (how) *how = MineLaunch{false, kMineKSum, 0u, false};
   if (n == 0) return hipSuccess;
   const unsigned grid = (unsigned)std::min<unsigned long long>((n + 255) / 256, 2048);
   hipLaunchKernelGGL(k_mine_sum, dim3(grid), dim3(256), 0, stream, status, n, out);
+  // saturated: fewer lanes than windows, so the kernel's stride loop turns again for some lane
+  if (how) { how->launched = true; how->grid = grid; how->saturated = n > (unsigned long long)grid * 256; }
   return hipGetLastError();
 }
 

@@ -482,27 +482,33 @@ struct MineSeg { unsigned long long first; int image, win, step, nx; };
 // One crop Validate runs on: (x, y, w, h) in the transformed image, key of its initial-shape draw.
 struct MineItem { int image, x, y, w, h, pad; unsigned long long key; };
 struct MineSizes { int os, hs, qs, mode; double shift; unsigned long long seed; };
+// What a k_mine.hip launcher launched (`how` may be null), filled from the grid it handed to hipLaunchKernelGGL; launched =
+// false: nothing to launch, hipSuccess.  saturated (launch_mine_sum): the grid stood at its cap, lanes stride over the range.
+// Counted in one place (host.h: LaunchLog, jdaMineLaunches).
+enum { kMineKScan = 0, kMineKItems = 1, kMineKPatches = 2, kMineKWalk = 3, kMineKSum = 4 };   // (= JDA_MINE_K_*, host.h checks)
+struct MineLaunch { bool launched; int kernel; unsigned grid; bool saturated; };
 
 // Stage-0 prefix of every window with ordinals [lo, hi): carts [0, carts0) with the pixels computed on demand from the
 // background image (chain 0).  status[o - lo] = Validate's n of a window rejected there; survivors are appended to
 // surv (their ordinals, unordered) through *n_surv, status 0.
 hipError_t launch_mine_scan(const MineModel& m, const MineSizes& z, const uint8_t* base, const MineImg* imgs,
                             const MineSeg* segs, int n_segs, unsigned long long lo, unsigned long long hi, int carts0,
-                            int* status, unsigned long long* surv, unsigned* n_surv, hipStream_t stream);
+                            int* status, unsigned long long* surv, unsigned* n_surv, hipStream_t stream, MineLaunch* how = nullptr);
 // Ordinals -> crops (image, x, y, win, win, key = ordinal).
 hipError_t launch_mine_items(const MineSeg* segs, int n_segs, const unsigned long long* ords, int n, MineItem* items,
-                             hipStream_t stream);
+                             hipStream_t stream, MineLaunch* how = nullptr);
 // The o / h / q patches of n crops (chain z.mode) at patches + i * pbytes: os^2, then hs^2, then qs^2 bytes.
 hipError_t launch_mine_patches(const MineSizes& z, const uint8_t* base, const MineImg* imgs, const MineItem* items, int n,
-                               uint8_t* patches, int pbytes, hipStream_t stream);
+                               uint8_t* patches, int pbytes, hipStream_t stream, MineLaunch* how = nullptr);
 // Validate on the patches of n crops, a lane per crop: face[i], n[i], score[i], shape[i*dim ..] (also the walk's state);
 // lbf / t1 / t2: per-crop scratch of K ints and 2 x dim doubles.
 // init != nullptr: crop i starts from init[i*dim ..] instead of mean + its key's shift, and items is not read (reval.cpp).
 hipError_t launch_mine_walk(const MineModel& m, const MineSizes& z, const MineItem* items, int n, const uint8_t* patches,
                             int pbytes, int similarity, uint8_t* face, int* carts_n, double* score, double* shape, int* lbf,
-                            double* t1, double* t2, hipStream_t stream, const double* init = nullptr);
+                            double* t1, double* t2, hipStream_t stream, const double* init = nullptr, MineLaunch* how = nullptr);
 // Sum of status[0, n) over the rejected entries (status > 0): out[0] += count, out[1] += sum.
-hipError_t launch_mine_sum(const int* status, unsigned long long n, unsigned long long* out, hipStream_t stream);
+hipError_t launch_mine_sum(const int* status, unsigned long long n, unsigned long long* out, hipStream_t stream,
+                           MineLaunch* how = nullptr);
 
 // ---- dialect CPP: training one CART (k_train.hip, train.cpp; reference src/jda/cart.cpp:41-350, data.cpp:148-173) ----
 

@@ -147,12 +147,16 @@ struct MineArgs {
 };
 
 // The nb items in b.items through k_mine_patches and k_mine_walk; face, carts and (score_h given) score queued back to the
-// host.  The caller queues what else it wants back and waits for the stream.
+// host.  The caller queues what else it wants back and waits for the stream.  Counts the batch and its two launches.
 bool walk_batch(Cascador* c, const MineModel& m, const MineSizes& z, const uint8_t* d_base, const CallBuf& imgs, const WalkBufs& b,
                 int nb, uint8_t* face_h, int* carts_h, double* score_h, hipStream_t st) {
-  JDA_HIP(launch_mine_patches(z, d_base, (const MineImg*)imgs.p, b.items, nb, b.patches, pbytes_of(z), st));
+  MineLaunch how;
+  JDA_HIP(launch_mine_patches(z, d_base, (const MineImg*)imgs.p, b.items, nb, b.patches, pbytes_of(z), st, &how));
+  c->log.count(how);
   JDA_HIP(launch_mine_walk(m, z, b.items, nb, b.patches, pbytes_of(z), c->similarity, b.face, b.carts, b.score, b.shape, b.lbf,
-                           b.t1, b.t2, st));
+                           b.t1, b.t2, st, nullptr, &how));
+  c->log.count(how);
+  c->log.count_mine_batch(nb);
   JDA_HIP(hipMemcpyAsync(face_h, b.face, nb, hipMemcpyDeviceToHost, st));
   JDA_HIP(hipMemcpyAsync(carts_h, b.carts, nb * sizeof(int), hipMemcpyDeviceToHost, st));
   if (score_h) JDA_HIP(hipMemcpyAsync(score_h, b.score, nb * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -197,6 +201,7 @@ int validate_device(Cascador* c, const ValidateArgs& a) {
   auto body = [&]() -> bool {
     if (!upload_imgs(imgs, &ib, st)) return false;
     const size_t cap = walk_cap(c, m, z, (size_t)std::max(1, n_crops));
+    c->log.set_mine_cap((long long)cap);
     WalkBufs b;
     if (!carve_into(wb, [&](Carver& cv) { b.carve(cv, m, z, cap); })) return false;
     std::vector<uint8_t> f(cap);
@@ -285,6 +290,7 @@ int mine_device(Cascador* c, const MineArgs& a) {
           })) return false;
       JDA_HIP(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(MineSeg), hipMemcpyHostToDevice, st));
       const size_t cap = walk_cap(c, m, z, 65536);
+      c->log.set_mine_cap((long long)cap);
       WalkBufs b;
       if (!carve_into(wb, [&](Carver& cv) { b.carve(cv, m, z, cap); })) return false;
       std::vector<unsigned long long> surv;
@@ -298,8 +304,11 @@ int mine_device(Cascador* c, const MineArgs& a) {
         const unsigned long long hi = std::min(total, lo + chunk);
         JDA_HIP(hipMemsetAsync(d_nsurv, 0, 4 * sizeof(unsigned), st));
         JDA_HIP(hipMemsetAsync(d_sum, 0, 2 * sizeof(unsigned long long), st));
+        MineLaunch how;
         JDA_HIP(launch_mine_scan(m, z, im.d_base, (const MineImg*)ib.p, d_segs, (int)segs.size(), lo, hi, carts0, d_status, d_surv,
-                                 d_nsurv, st));
+                                 d_nsurv, st, &how));
+        c->log.count(how);
+        c->log.count_mine_chunk();
         unsigned ns = 0;
         JDA_HIP(hipMemcpyAsync(&ns, d_nsurv, sizeof ns, hipMemcpyDeviceToHost, st));
         JDA_HIP(hipStreamSynchronize(st));
@@ -314,7 +323,8 @@ int mine_device(Cascador* c, const MineArgs& a) {
         for (size_t at = 0; at < surv.size() && n_hits < size; at += cap) {
           const int nb = (int)std::min<size_t>(cap, surv.size() - at);
           JDA_HIP(hipMemcpyAsync(b.ords, surv.data() + at, nb * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-          JDA_HIP(launch_mine_items(d_segs, (int)segs.size(), b.ords, nb, b.items, st));
+          JDA_HIP(launch_mine_items(d_segs, (int)segs.size(), b.ords, nb, b.items, st, &how));
+          c->log.count(how);
           if (!walk_batch(c, m, z, im.d_base, ib, b, nb, f.data(), cn.data(), sc.data(), st)) return false;
           JDA_HIP(hipMemcpyAsync(it.data(), b.items, nb * sizeof(MineItem), hipMemcpyDeviceToHost, st));
           JDA_HIP(hipStreamSynchronize(st));
@@ -340,9 +350,11 @@ int mine_device(Cascador* c, const MineArgs& a) {
         }
         // reject lengths of the windows the scan rejected in [lo, cut), plus the walk's rejects (all below cut)
         unsigned long long sum[2] = {0, 0};
-        JDA_HIP(launch_mine_sum(d_status, cut - lo, d_sum, st));
+        JDA_HIP(launch_mine_sum(d_status, cut - lo, d_sum, st, &how));
+        c->log.count(how);
         JDA_HIP(hipMemcpyAsync(sum, d_sum, sizeof sum, hipMemcpyDeviceToHost, st));
         JDA_HIP(hipStreamSynchronize(st));
+        c->log.count_mine_rejects((long long)sum[0], walk_nega);
         nega += (long long)sum[0] + walk_nega;
         carts += (long long)sum[1] + walk_carts;
         lo = cut;

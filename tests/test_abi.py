@@ -102,6 +102,24 @@ def test_finish_launches_entries_and_their_python_mirror(built, model_file):
     c.close()
 
 
+def test_mine_launches_entry_and_its_python_mirror(built, model_file):
+    """jdaMineLaunches (include/jda.h): exported, JDA_MINE_LAUNCH_N counts in the header's order, which api.MINE_LAUNCH_FIELDS
+    restates name for name; all zero on a cascador that has run nothing; null arguments refused.  No GPU needed."""
+    from jda_amd import api
+    assert "jdaMineLaunches" in declared_symbols()
+    src = open(HEADER).read()
+    enum = src[src.index("enum { JDA_MINE_K_SCAN"):src.index("JDA_API int jdaMineLaunches")]
+    names = re.findall(r"\bJDA_MINE_(\w+) = (\d+)", enum)
+    assert [int(v) for _, v in names] == list(range(len(names)))
+    assert names[-1] == ("LAUNCH_N", str(api.MINE_LAUNCH_N)) and api.MINE_LAUNCH_N == 12
+    assert tuple(n.lower() for n, _ in names[:-1]) == api.MINE_LAUNCH_FIELDS
+    p, _ = model_file((2, 8, 5, 3), 8, seed=1)
+    c = api.Cascador(p)
+    assert c.mine_launches() == dict.fromkeys(api.MINE_LAUNCH_FIELDS, 0)
+    assert api.lib.jdaMineLaunches(c.h, None) == -1 and api.lib.jdaMineLaunches(None, (C.c_longlong * api.MINE_LAUNCH_N)()) == -1
+    c.close()
+
+
 def test_stage_launches_entries_and_their_python_mirror(built, model_file):
     """jdaStageLaunches and jdaStageLaunchFor (include/jda.h): exported; JDA_STAGE_LAUNCH_N counts indexed by JDA_STAGE_LAUNCH,
     which the Python mirror (api.StageLaunch.index) restates field for field -- checked against the macro itself, evaluated
