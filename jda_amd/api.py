@@ -881,26 +881,34 @@ def _device_buffer(buf, tot, images):
     return buf
 
 
+# the entries of each kind of frame call: host form, device form, way back (include/jda.h)
+FRAME_ENTRIES = {"pack": ("jdaPackGray", "jdaPackGrayDevice", None),
+                 "turn": ("jdaPackGrayOriented", "jdaPackGrayOrientedDevice", "jdaOrientBack"),
+                 "reduce": ("jdaPackGrayReduced", "jdaPackGrayReducedDevice", "jdaReduceBack"),
+                 "rotate": ("jdaPackGrayRotated", "jdaPackGrayRotatedDevice", "jdaRotateBack")}
+
+
+def _frame_call(sizes, orients, factors, degrees, n):
+    """How a frame call transforms its n images (each: one value for all images or one per image; None: not given) -> (the
+    entries of its kind, the kind's arrays as those entries take them behind the images, the (w, h) rectangles of the given
+    sizes come out as).  degrees: rotated; else factors: reduced (orients None: upright); else orients: turned; else packed."""
+    o = None if orients is None else _orients(orients, n)
+    f = None if factors is None else _factors(factors, n)
+    g = None if degrees is None else _degrees(degrees, n)
+    kind = "rotate" if g is not None else "reduce" if f is not None else "pack" if o is None else "turn"
+    arrays = {"pack": (), "turn": (o,), "reduce": (f, o), "rotate": (g,)}[kind]
+    ptrs = tuple(None if a is None else a.ctypes.data_as(C.POINTER(C.c_double if a.dtype == np.float64 else C.c_int)) for a in arrays)
+    return FRAME_ENTRIES[kind], ptrs, _rotated_sizes(_turned_sizes(_reduced_sizes(sizes, f), o), g)
+
+
 def _pack_gray(who, images, formats, orients, rects, factors=None, degrees=None):
     """pack_gray (orients None), pack_gray_oriented, with factors pack_gray_reduced and, with degrees, pack_gray_rotated."""
     images, px, sizes = _pixels(who, images, formats, rects, False)
     n = len(images)
-    o = None if orients is None else _orients(orients, n)
-    f = None if factors is None else _factors(factors, n)
-    g = None if degrees is None else _degrees(degrees, n)
-    sizes = _rotated_sizes(_turned_sizes(_reduced_sizes(sizes, f), o), g)
+    (host, _, _), arrays, sizes = _frame_call(sizes, orients, factors, degrees, n)
     offs, tot = _offsets(sizes)
     dst = np.empty(max(tot, 1), np.uint8)
-    offp = offs.ctypes.data_as(C.POINTER(C.c_size_t))
-    if g is not None:
-        rc = lib.jdaPackGrayRotated(px, g.ctypes.data_as(C.POINTER(C.c_double)), n, dst.ctypes.data, offp)
-    elif f is not None:
-        rc = lib.jdaPackGrayReduced(px, f.ctypes.data_as(C.POINTER(C.c_int)), None if o is None else o.ctypes.data_as(C.POINTER(C.c_int)), n,
-                                    dst.ctypes.data, offp)
-    elif o is None:
-        rc = lib.jdaPackGray(px, n, dst.ctypes.data, offp)
-    else:
-        rc = lib.jdaPackGrayOriented(px, o.ctypes.data_as(C.POINTER(C.c_int)), n, dst.ctypes.data, offp)
+    rc = getattr(lib, host)(px, *arrays, n, dst.ctypes.data, offs.ctypes.data_as(C.POINTER(C.c_size_t)))
     if rc != 0:
         raise JdaError(last_error())
     return [dst[int(offs[i]):int(offs[i]) + w * h].reshape(h, w) for i, (w, h) in enumerate(sizes)]
@@ -964,7 +972,9 @@ def orient_back(images, formats, orients, faces, boxes=None, landmarks=None, rec
     px, _ = _pixel_table(images, formats, rects, (lambda t: t.data_ptr()) if tensor else (lambda a: np.asarray(a).ctypes.data),
                          (lambda t: tuple(int(v) * t.element_size() for v in t.stride())) if tensor else (lambda a: np.asarray(a).strides))
     n_img = len(images)
-    o = _orients(orients, n_img)
+    if orients is None:
+        raise TypeError("orient_back: orients is needed (one orientation for all images or one per image)")
+    (_, _, back), arrays, _ = _frame_call([], orients, factors, degrees, n_img)
     results = boxes is None and landmarks is None and len(faces) == n_img and all(r is None or isinstance(r, dict) for r in faces)
     if results:
         key = ["bboxes" if r is not None and "bboxes" in r else "rects" for r in faces]
@@ -988,12 +998,7 @@ def orient_back(images, formats, orients, faces, boxes=None, landmarks=None, rec
             b.shape[1] if b is not None else 0, None if lm is None else lm.ctypes.data,
             lm.dtype.itemsize if lm is not None else 0, lm.shape[1] // 2 if lm is not None else 0,
             le.ctypes.data_as(ip) if len(le) else None, ri.ctypes.data_as(ip) if len(le) else None, len(le))
-    if degrees is not None:
-        rc = lib.jdaRotateBack(px, _degrees(degrees, n_img).ctypes.data_as(C.POINTER(C.c_double)), *tail[:8])
-    elif factors is None:
-        rc = lib.jdaOrientBack(px, o.ctypes.data_as(ip), *tail)
-    else:
-        rc = lib.jdaReduceBack(px, _factors(factors, n_img).ctypes.data_as(ip), o.ctypes.data_as(ip), *tail)
+    rc = getattr(lib, back)(px, *arrays, *(tail[:8] if degrees is not None else tail))   # (nothing mirrors a rotation: no pairs)
     if rc != 0:
         raise JdaError(last_error())
     if not results:
@@ -1579,10 +1584,7 @@ class Cascador:
         pack_gray_rotated_device."""
         images, px, sizes = _pixels(who, images, formats, rects, True)
         n = len(images)
-        o = None if orients is None else _orients(orients, n)
-        f = None if factors is None else _factors(factors, n)
-        g = None if degrees is None else _degrees(degrees, n)
-        sizes = _rotated_sizes(_turned_sizes(_reduced_sizes(sizes, f), o), g)
+        (_, device, _), arrays, sizes = _frame_call(sizes, orients, factors, degrees, n)
         offs, tot = _offsets(sizes, 256, frame_stride)
         if out is not None:
             offs = np.ascontiguousarray(out[1], np.uint64)
@@ -1591,15 +1593,7 @@ class Cascador:
         st = jdaPackStats() if stats else None
         tail = (C.c_void_p(buf.data_ptr()), offs.ctypes.data_as(C.POINTER(C.c_size_t)),
                 C.c_void_p(hip_stream) if hip_stream is not None else None, C.byref(st) if stats else None)
-        if g is not None:
-            rc = lib.jdaPackGrayRotatedDevice(self.h, px, g.ctypes.data_as(C.POINTER(C.c_double)), n, *tail)
-        elif f is not None:
-            rc = lib.jdaPackGrayReducedDevice(self.h, px, f.ctypes.data_as(C.POINTER(C.c_int)),
-                                              None if o is None else o.ctypes.data_as(C.POINTER(C.c_int)), n, *tail)
-        elif o is None:
-            rc = lib.jdaPackGrayDevice(self.h, px, n, *tail)
-        else:
-            rc = lib.jdaPackGrayOrientedDevice(self.h, px, o.ctypes.data_as(C.POINTER(C.c_int)), n, *tail)
+        rc = getattr(lib, device)(self.h, px, *arrays, n, *tail)
         if rc != 0:
             raise JdaError(last_error())
         res = (buf, offs[:n], [w for w, _ in sizes], [h for _, h in sizes])

@@ -12,8 +12,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libjda.so")
 SOURCES = ["k_misc.hip", "k_scan.hip", "k_scan_d.hip", "k_scan_r.hip", "k_scan_dr.hip", "k_scan_p.hip", "k_finish.hip", "k_wide.hip", "k_stage.hip", "k_post.hip", "k_mine.hip", "k_train.hip", "k_lbf.hip", "k_gather.hip", "k_faces.hip", "k_fit.hip", "k_reval.hip", "k_windows.hip", "k_pack.hip", "k_chips.hip", "k_turn.hip", "k_reduce.hip", "k_rotate.hip",
            "abi.cpp", "pass.cpp", "detect.cpp", "detect_cpp.cpp", "tickets.cpp", "ragged.cpp", "post_host.cpp", "lanes.cpp", "plans.cpp", "model_dev.cpp",
-           "model.cpp", "model_grow.cpp", "plan.cpp", "post.cpp", "mine.cpp", "train.cpp", "stage.cpp", "boost.cpp", "faces.cpp", "fit.cpp", "reval.cpp", "windows.cpp", "pack.cpp", "chips.cpp", "turn.cpp", "reduce.cpp", "rotate.cpp"]
-HEADERS = ["kernels.h", "kernels_common.h", "finish_common.h", "stage_body.h", "cpp_patch.h", "cpp_wave.h", "pack_pixel.h", "splitmix.h", "scan_walk.h", "k_scan_impl.h", "model.h", "plan.h", "post.h", "host.h", "pass.h", "run.h", "detect.h", "results.h", os.path.join("..", "..", "include", "jda.h")]
+           "model.cpp", "model_grow.cpp", "plan.cpp", "post.cpp", "mine.cpp", "train.cpp", "stage.cpp", "boost.cpp", "faces.cpp", "fit.cpp", "reval.cpp", "windows.cpp", "frames.cpp", "pack.cpp", "chips.cpp", "turn.cpp", "reduce.cpp", "rotate.cpp"]
+HEADERS = ["kernels.h", "kernels_common.h", "finish_common.h", "stage_body.h", "cpp_patch.h", "cpp_wave.h", "pack_pixel.h", "splitmix.h", "scan_walk.h", "k_scan_impl.h", "model.h", "plan.h", "post.h", "host.h", "pass.h", "run.h", "detect.h", "frames.h", "results.h", os.path.join("..", "..", "include", "jda.h")]
 OBJDIR = os.path.join(HERE, "build")
 
 # -ffp-contract=off: the cascade must round like the reference's scalar code

@@ -1,6 +1,7 @@
 // libjda.so: the extern "C" entry points of include/jda.h (reference interface: c/jda.h:18-68) and of the batch,
 // trace and dialect-CPP extensions, on top of detect.cpp / tickets.cpp / ragged.cpp.
 #include "detect.h"
+#include "frames.h"
 
 // =============================================================================
 // C ABI
@@ -441,13 +442,13 @@ int jdaValidateWindowsDevice(void* cascador, const unsigned char* d_frames, size
 
 int jdaPackGray(const jdaPixels* images, int n, unsigned char* dst, const size_t* dst_offsets) try {
   g_err.clear();
-  return pack_host(images, n, dst, dst_offsets);
+  return frames_host(FrameSpec::pack(), images, n, dst, dst_offsets);
 } JDA_ABI_CATCH(-1)
 
 int jdaPackGrayDevice(void* cascador, const jdaPixels* images, int n, unsigned char* d_dst, const size_t* dst_offsets,
                       void* hip_stream, jdaPackStats* stats) try {
   g_err.clear();
-  return pack_device((Cascador*)cascador, images, n, d_dst, dst_offsets, (hipStream_t)hip_stream, stats);
+  return frames_device((Cascador*)cascador, FrameSpec::pack(), images, n, d_dst, dst_offsets, (hipStream_t)hip_stream, stats);
 } JDA_ABI_CATCH_SYNC(-1)
 
 int jdaOrientSize(int w, int h, int orient, int* tw, int* th) try {
@@ -457,20 +458,20 @@ int jdaOrientSize(int w, int h, int orient, int* tw, int* th) try {
 
 int jdaPackGrayOriented(const jdaPixels* images, const int* orients, int n, unsigned char* dst, const size_t* dst_offsets) try {
   g_err.clear();
-  return turn_host(images, orients, n, dst, dst_offsets);
+  return frames_host(FrameSpec::turn(orients), images, n, dst, dst_offsets);
 } JDA_ABI_CATCH(-1)
 
 int jdaPackGrayOrientedDevice(void* cascador, const jdaPixels* images, const int* orients, int n, unsigned char* d_dst,
                               const size_t* dst_offsets, void* hip_stream, jdaPackStats* stats) try {
   g_err.clear();
-  return turn_device((Cascador*)cascador, images, orients, n, d_dst, dst_offsets, (hipStream_t)hip_stream, stats);
+  return frames_device((Cascador*)cascador, FrameSpec::turn(orients), images, n, d_dst, dst_offsets, (hipStream_t)hip_stream, stats);
 } JDA_ABI_CATCH_SYNC(-1)
 
 int jdaOrientBack(const jdaPixels* images, const int* orients, int n_images, const int* face_image, int n_faces, int* boxes,
                   int box_ints, void* landmarks, int real_bytes, int landmark_n, const int* left, const int* right, int sym_n) try {
   g_err.clear();
-  return orient_back(OrientBackCall{images, orients, n_images, face_image, n_faces, boxes, box_ints, landmarks, real_bytes, landmark_n,
-                                    left, right, sym_n});
+  return frames_back(FrameSpec::turn(orients), BackCall{images, n_images, face_image, n_faces, boxes, box_ints, landmarks, real_bytes,
+                                                       landmark_n, left, right, sym_n});
 } JDA_ABI_CATCH(-1)
 
 int jdaReduceSize(int w, int h, int factor, int orient, int* rw, int* rh) try {
@@ -481,44 +482,44 @@ int jdaReduceSize(int w, int h, int factor, int orient, int* rw, int* rh) try {
 int jdaPackGrayReduced(const jdaPixels* images, const int* factors, const int* orients, int n, unsigned char* dst,
                        const size_t* dst_offsets) try {
   g_err.clear();
-  return reduce_host(images, factors, orients, n, dst, dst_offsets);
+  return frames_host(FrameSpec::reduce(factors, orients), images, n, dst, dst_offsets);
 } JDA_ABI_CATCH(-1)
 
 int jdaPackGrayReducedDevice(void* cascador, const jdaPixels* images, const int* factors, const int* orients, int n,
                              unsigned char* d_dst, const size_t* dst_offsets, void* hip_stream, jdaPackStats* stats) try {
   g_err.clear();
-  return reduce_device((Cascador*)cascador, images, factors, orients, n, d_dst, dst_offsets, (hipStream_t)hip_stream, stats);
+  return frames_device((Cascador*)cascador, FrameSpec::reduce(factors, orients), images, n, d_dst, dst_offsets, (hipStream_t)hip_stream, stats);
 } JDA_ABI_CATCH_SYNC(-1)
 
 int jdaReduceBack(const jdaPixels* images, const int* factors, const int* orients, int n_images, const int* face_image, int n_faces,
                   int* boxes, int box_ints, void* landmarks, int real_bytes, int landmark_n, const int* left, const int* right,
                   int sym_n) try {
   g_err.clear();
-  return reduce_back(OrientBackCall{images, orients, n_images, face_image, n_faces, boxes, box_ints, landmarks, real_bytes, landmark_n,
-                                    left, right, sym_n}, factors);
+  return frames_back(FrameSpec::reduce(factors, orients), BackCall{images, n_images, face_image, n_faces, boxes, box_ints, landmarks,
+                                                                   real_bytes, landmark_n, left, right, sym_n});
 } JDA_ABI_CATCH(-1)
 
 int jdaRotationPlan(int w, int h, double degrees, jdaRotation* rot) try {
   g_err.clear();
-  return rotation_plan(w, h, degrees, rot);
+  return rotation_plan("jdaRotationPlan: ", w, h, degrees, rot) ? 0 : -1;
 } JDA_ABI_CATCH(-1)
 
 int jdaPackGrayRotated(const jdaPixels* images, const double* degrees, int n, unsigned char* dst, const size_t* dst_offsets) try {
   g_err.clear();
-  return rotate_host(images, degrees, n, dst, dst_offsets);
+  return frames_host(FrameSpec::rotate(degrees), images, n, dst, dst_offsets);
 } JDA_ABI_CATCH(-1)
 
 int jdaPackGrayRotatedDevice(void* cascador, const jdaPixels* images, const double* degrees, int n, unsigned char* d_dst,
                              const size_t* dst_offsets, void* hip_stream, jdaPackStats* stats) try {
   g_err.clear();
-  return rotate_device((Cascador*)cascador, images, degrees, n, d_dst, dst_offsets, (hipStream_t)hip_stream, stats);
+  return frames_device((Cascador*)cascador, FrameSpec::rotate(degrees), images, n, d_dst, dst_offsets, (hipStream_t)hip_stream, stats);
 } JDA_ABI_CATCH_SYNC(-1)
 
 int jdaRotateBack(const jdaPixels* images, const double* degrees, int n_images, const int* face_image, int n_faces, int* boxes,
                   int box_ints, void* landmarks, int real_bytes, int landmark_n) try {
   g_err.clear();
-  return rotate_back(OrientBackCall{images, nullptr, n_images, face_image, n_faces, boxes, box_ints, landmarks, real_bytes, landmark_n,
-                                    nullptr, nullptr, 0}, degrees);
+  return frames_back(FrameSpec::rotate(degrees), BackCall{images, n_images, face_image, n_faces, boxes, box_ints, landmarks, real_bytes,
+                                                          landmark_n, nullptr, nullptr, 0});
 } JDA_ABI_CATCH(-1)
 
 int jdaFaceChips(const jdaPixels* images, int n_images, const int* face_image, const void* landmarks, int real_bytes, int n_faces,

@@ -2,7 +2,7 @@
 // definition in plain loops over host memory, and jdaFaceChipsDevice on the kernel of k_chips.hip.  Both validate everything
 // and fit every face before a byte is written or anything is launched; the device form puts the face and image records into
 // its lane's grow-only buffer and makes one launch for all faces.  The model is read for its mean shape only.
-#include "detect.h"
+#include "frames.h"
 
 namespace jda {
 
@@ -115,7 +115,7 @@ inline void host_tap(const ChipImg& im, int cc, bool swap, long long x, long lon
   if (cc == 1) {
     int w[3];
     pack_weights(im.rgb ? JDA_PIX_RGB24 : JDA_PIX_BGR24, w);
-    acc[0] += wgt * (uint32_t)((p[0] * w[0] + p[1] * w[1] + p[2] * w[2] + 8192) >> 14);
+    acc[0] += wgt * (uint32_t)gray_of(p, im.bpp, w);
     return;
   }
   acc[0] += wgt * p[swap ? 2 : 0]; acc[1] += wgt * p[1]; acc[2] += wgt * p[swap ? 0 : 2];
@@ -198,16 +198,10 @@ int chips_device(Cascador* c, const ChipsCall& call, hipStream_t user_stream, jd
   a.n_faces = call.n_faces; a.n_images = call.n_images; a.cw = call.chip_w; a.ch = call.chip_h; a.cbpp = pl.cbpp; a.crgb = pl.crgb;
   if ((u.total() + kChipBlock - 1) / kChipBlock > 0x7fffffffll) { fail(who + "too many chip bytes for one launch (" + std::to_string(pl.bytes) + ")"); return -1; }
 
-  if (!lc.open(user_stream)) return -1;
-  const hipStream_t st = lc.st;
-  auto body = [&]() -> bool {
-    ChipFace* d_faces; ChipImg* d_imgs;
-    if (!lc.upload(pl.faces, pl.imgs, &d_faces, &d_imgs) || !lc.begin()) return false;
-    a.faces = d_faces; a.imgs = d_imgs;
-    JDA_HIP(launch_chips(a, st));
-    return lc.end() && lc.sync();
-  };
-  if (!lc.run(stats != nullptr, body)) return -1;
+  if (!lc.launch_one(user_stream, stats != nullptr, pl.faces, pl.imgs, "launch_chips(a, st)", [&](ChipFace* d_faces, ChipImg* d_imgs, hipStream_t st) {
+        a.faces = d_faces; a.imgs = d_imgs;
+        return launch_chips(a, st);
+      })) return -1;
   matrices_out(pl, call.matrices);
   if (stats) {
     stats->faces = call.n_faces; stats->chip_bytes = pl.bytes; stats->taps = pl.taps; stats->launches = 1;

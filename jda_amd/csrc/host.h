@@ -8,10 +8,11 @@
 //   ragged.cpp     images of different sizes as one job             abi.cpp      the extern "C" entry points of include/jda.h
 //   fit.cpp        a stage's global regression (dialect CPP)       model_grow.cpp  the model in training: put a cart, close a stage, the f64 file
 //   reval.cpp      Validate on a resident sample set (dialect CPP)   windows.cpp  the cascade on caller-given windows (dialect C)
+//   frames.h       what the frame entries share (declarations)       frames.cpp   their one call path: checks, device entry, way back
 //   pack.cpp       colour / pitched / cropped frames -> dense gray      chips.cpp    upright face chips cut from detections
-//   turn.cpp       the same, turned by one of the eight orientations; results mapped back
-//   reduce.cpp     the same, reduced by an integer factor first; results mapped back
-//   rotate.cpp     the same, rotated by any angle; results mapped back
+//   turn.cpp       the same, turned by one of the eight orientations; a face mapped back
+//   reduce.cpp     the same, reduced by an integer factor first
+//   rotate.cpp     the same, rotated by any angle; a face mapped back
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -445,7 +446,7 @@ struct Lane {
   DevBuf frames;                             // staging of host frames (the call's first lane holds the whole batch)
   DevBuf pyr;                                // half + quarter images (multi-scale models), method-0 levels
   DevBuf win;                                // jdaValidateWindows: a chunk's window list and its per-window outputs (windows.cpp)
-  DevBuf tab;                                // the host-made tables of a frame entry's one launch (LaneCall::upload: pack.cpp, turn.cpp, reduce.cpp, rotate.cpp, chips.cpp)
+  DevBuf tab;                                // the host-made tables of a frame entry's one launch (LaneCall::upload: frames.cpp, chips.cpp)
   // ragged passes: images at the common pitch, tight images, tables (segments, block map, image records)
   DevBuf rag_frames, rag_raw, rag_tab;
   HostPinned h_tab, h_raw;
@@ -734,7 +735,7 @@ struct OneLane {
   }
 };
 
-// A frame entry (pack.cpp, turn.cpp, reduce.cpp, rotate.cpp, chips.cpp, windows.cpp): a call that runs on one lane, on the caller's stream or the
+// A frame entry (frames.cpp, chips.cpp, windows.cpp): a call that runs on one lane, on the caller's stream or the
 // lane's, and reports device_ms and call_ms.  Made where the entry begins (t0), opened once everything is validated.
 struct LaneCall {
   const double t0 = now_ms();
@@ -770,6 +771,19 @@ struct LaneCall {
   bool begin() { return timer.begin(st); }
   bool end() { return timer.end(st); }
   bool sync() { JDA_HIP(hipStreamSynchronize(st)); return timer.add(&device_ms); }
+  // The whole device work of an entry that makes ONE launch on two host tables (frames.cpp, chips.cpp): open, upload, the
+  // launch -- launch(d_a, d_b, stream) -> hipError_t, named `what` where it fails -- between begin and end, the wait; timed if asked
+  template <typename A, typename B, typename Launch>
+  bool launch_one(hipStream_t user_stream, bool timed, const std::vector<A>& a, const std::vector<B>& b, const char* what, Launch&& launch) {
+    if (!open(user_stream)) return false;
+    return run(timed, [&]() -> bool {
+      A* d_a; B* d_b;
+      if (!upload(a, b, &d_a, &d_b) || !begin()) return false;
+      const hipError_t e = launch(d_a, d_b, st);
+      if (e != hipSuccess) { fail(std::string(what) + " failed: " + hipGetErrorString(e)); return false; }
+      return end() && sync();
+    });
+  }
   double call_ms() const { return now_ms() - t0; }
 };
 

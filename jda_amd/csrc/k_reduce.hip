@@ -103,7 +103,7 @@ __device__ __forceinline__ uint32_t reduce_group(pack_src_t row0, long long pitc
 // ---- in: source rows -> gray -> block means -> LDS.  A lane: reduced pixels [4 q, 4 q + 4) of a region row; lanes l and l + 16
 //      are 16 rows apart
 template <int F>
-__device__ __forceinline__ void reduce_in(const ReduceImg& im, const ReduceTile& t, int sx0, int sy0, uint32_t* tile4, int tid) {
+__device__ __forceinline__ void reduce_in(const TurnImg& im, const ReduceTile& t, int sx0, int sy0, uint32_t* tile4, int tid) {
   const int lane = tid & 63, wv = tid >> 6, h2 = lane >> 5;
   const int q = lane & 15, hf = (lane >> 4) & 1;
   const long long row_bytes = (long long)im.w * F * im.bpp;
@@ -125,14 +125,14 @@ __device__ __forceinline__ void reduce_in(const ReduceImg& im, const ReduceTile&
 
 }  // namespace
 
-__global__ __launch_bounds__(kTurnBlock) void k_reduce(ReduceArgs a) {
+__global__ __launch_bounds__(kTurnBlock) void k_reduce(TurnArgs a) {
   __shared__ uint32_t tile4[kReduceLds / 4];
   const uint8_t* tile = (const uint8_t*)tile4;
   const long long b = blockIdx.x;
   if (b >= a.total) return;
   const int i = a.block_img[b];
   if (i < 0 || i >= a.n) return;                                   // (the host made the list: never taken)
-  const ReduceImg im = a.imgs[i];
+  const TurnImg im = a.imgs[i];
   const long long tl = b - im.first;
   if (tl < 0 || tl >= (long long)im.ntu * im.ntv) {                // (the prefix sums cover [0, total): never taken)
 #ifdef JDA_BOUNDS_CHECK
@@ -208,13 +208,7 @@ __global__ __launch_bounds__(kTurnBlock) void k_reduce(ReduceArgs a) {
   }
 }
 
-hipError_t launch_reduce(const ReduceArgs& a, hipStream_t stream) {
-  if (a.n <= 0 || a.total <= 0) return hipSuccess;
-  if (!a.imgs || !a.block_img) return hipErrorInvalidValue;
-  if (a.total > 0x7fffffffll) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_reduce, dim3((unsigned)a.total), dim3(kTurnBlock), 0, stream, a);
-  return hipGetLastError();
-}
+hipError_t launch_reduce(const TurnArgs& a, hipStream_t stream) { return launch_tiles<k_reduce>(a, stream); }
 
 JDA_BC_READER(k_reduce)
 

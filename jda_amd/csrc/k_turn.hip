@@ -144,13 +144,7 @@ __global__ __launch_bounds__(kTurnBlock) void k_turn(TurnArgs a) {
   }
 }
 
-hipError_t launch_turn(const TurnArgs& a, hipStream_t stream) {
-  if (a.n <= 0 || a.total <= 0) return hipSuccess;
-  if (!a.imgs || !a.block_img) return hipErrorInvalidValue;
-  if (a.total > 0x7fffffffll) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_turn, dim3((unsigned)a.total), dim3(kTurnBlock), 0, stream, a);
-  return hipGetLastError();
-}
+hipError_t launch_turn(const TurnArgs& a, hipStream_t stream) { return launch_tiles<k_turn>(a, stream); }
 
 JDA_BC_READER(k_turn)
 

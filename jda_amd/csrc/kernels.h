@@ -612,8 +612,8 @@ struct GatherArgs {
 };
 hipError_t launch_gather(const GatherArgs& a, hipStream_t stream);
 
-// ---- frames as they arrive: colour / pitched / cropped images -> dense 8-bit gray (k_pack.hip, pack.cpp; include/jda.h) ----
-constexpr uint32_t kGrayB = 1868, kGrayG = 9617, kGrayR = 4899;   // the Q14 weights of gray = (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14 (pack.cpp: pack_weights; k_chips.hip)
+// ---- frames as they arrive: colour / pitched / cropped images -> dense 8-bit gray (k_pack.hip, frames.cpp, pack.cpp; include/jda.h) ----
+constexpr uint32_t kGrayB = 1868, kGrayG = 9617, kGrayR = 4899;   // the Q14 weights of gray = (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14 (frames.cpp: pack_weights; k_chips.hip)
 constexpr int kPackBlock = 256;          // lanes of a workgroup: consecutive lanes take consecutive units
 constexpr int kPackRounds = 4;           // units of a lane: a workgroup covers kPackBlock * kPackRounds consecutive units
 // One image of a launch: w x h pixels of bpp bytes from src (the rectangle's first pixel; rows `pitch` bytes apart) to the w * h
@@ -628,9 +628,12 @@ struct PackImg {
   int pad;
 };
 static_assert(sizeof(PackImg) == 72, "PackImg is uploaded as it is");
-// One launch: imgs[0 .. n), total = the units of all of them; block_img[b] = the image that holds unit
-// b * kPackBlock * kPackRounds (a lane walks on from there).
-struct PackArgs { const PackImg* imgs; const int* block_img; int n; long long total; };
+// One launch of k_pack, k_turn, k_reduce or k_rotate: imgs[0 .. n) and total, the units (k_pack) or tiles of all of them.
+// block_img[b]: k_pack -- the image that holds unit b * kPackBlock * kPackRounds (a lane walks on from there); the tile
+// kernels -- the image of tile (workgroup) b.
+template <typename Img>
+struct FrameArgs { const Img* imgs; const int* block_img; int n; long long total; };
+using PackArgs = FrameArgs<PackImg>;
 hipError_t launch_pack(const PackArgs& a, hipStream_t stream);
 
 // ---- frames in any orientation: the same, turned by one of the eight orientations (k_turn.hip, turn.cpp; include/jda.h) ----
@@ -641,35 +644,23 @@ constexpr int kTurnPitch = 68;           // bytes from one row of the LDS tile t
 // by tf (kMineSwap | kMineFlipX | kMineFlipY), to the tw * th bytes at dst (tw = swap ? h : w).  Its tiles are the launch's
 // workgroups [first, first + ntu * ntv), row by row; tile column k covers the turned columns [64 k - off, 64 k - off + 64)
 // inside [0, tw), off = dst & 15: on the turned row 0 -- and on every row where tw is a multiple of 16 -- a tile begins at a
-// 16-byte boundary of dst.  w_lo / w_hi: PackImg's.
+// 16-byte boundary of dst.  w_lo / w_hi: PackImg's.  For k_reduce w x h is the REDUCED rectangle (w = rectangle width / f) --
+// tiles, tf, off, ntu, ntv are those of the w x h image -- and f the factor: reduced pixel (i, j) is the rounded mean of the
+// f x f source pixels from column i * f, row j * f of src on.  k_turn does not read f (the host fills it: 1).
 struct TurnImg {
-  const uint8_t* src; uint8_t* dst;
-  long long pitch, first;
-  int w, h, bpp, tf, ntu, ntv, off;
-  uint32_t w_lo, w_hi;
-  int pad;
-};
-static_assert(sizeof(TurnImg) == 72, "TurnImg is uploaded as it is");
-// One launch: imgs[0 .. n), total = the tiles of all of them; block_img[b] = the image of tile (workgroup) b.
-struct TurnArgs { const TurnImg* imgs; const int* block_img; int n; long long total; };
-hipError_t launch_turn(const TurnArgs& a, hipStream_t stream);
-
-// ---- frames larger than the faces need: the same, reduced by an integer factor first (k_reduce.hip, reduce.cpp; include/jda.h) ----
-constexpr int kReduceMax = 8;            // factors 1 .. kReduceMax
-// One image of a launch: TurnImg with the REDUCED rectangle in w x h (w = rectangle width / f) -- tiles, tf, off, ntu, ntv are
-// those of the w x h image -- and the factor: reduced pixel (i, j) is the rounded mean of the f x f source pixels from column
-// i * f, row j * f of src on.  The tile kernels read both records through the same names.
-struct ReduceImg {
   const uint8_t* src; uint8_t* dst;
   long long pitch, first;
   int w, h, bpp, tf, ntu, ntv, off;
   uint32_t w_lo, w_hi;
   int f;
 };
-static_assert(sizeof(ReduceImg) == 72, "ReduceImg is uploaded as it is");
-// One launch: imgs[0 .. n), total = the tiles of all of them; block_img[b] = the image of tile (workgroup) b.
-struct ReduceArgs { const ReduceImg* imgs; const int* block_img; int n; long long total; };
-hipError_t launch_reduce(const ReduceArgs& a, hipStream_t stream);
+static_assert(sizeof(TurnImg) == 72, "TurnImg is uploaded as it is");
+using TurnArgs = FrameArgs<TurnImg>;
+hipError_t launch_turn(const TurnArgs& a, hipStream_t stream);
+
+// ---- frames larger than the faces need: the same, reduced by an integer factor first (k_reduce.hip, reduce.cpp; include/jda.h) ----
+constexpr int kReduceMax = 8;            // factors 1 .. kReduceMax
+hipError_t launch_reduce(const TurnArgs& a, hipStream_t stream);   // (k_reduce.hip: the same records, f read)
 
 // ---- frames whose faces are rolled: the same pack, rotated by any angle (k_rotate.hip, rotate.cpp; include/jda.h) ----
 constexpr int kRotMaxSide = 32768;       // a rotated image is at most this wide and high
@@ -686,8 +677,7 @@ struct RotImg {
   uint32_t w_lo, w_hi;
 };
 static_assert(sizeof(RotImg) == 88, "RotImg is uploaded as it is");
-// One launch: imgs[0 .. n), total = the tiles of all of them; block_img[b] = the image of tile (workgroup) b.
-struct RotArgs { const RotImg* imgs; const int* block_img; int n; long long total; };
+using RotArgs = FrameArgs<RotImg>;
 hipError_t launch_rotate(const RotArgs& a, hipStream_t stream);
 
 // ---- faces as they leave: upright face chips cut from detections (k_chips.hip, chips.cpp; include/jda.h) ----

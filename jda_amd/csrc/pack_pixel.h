@@ -1,7 +1,7 @@
 // What k_pack.hip, k_turn.hip, k_reduce.hip, k_rotate.hip and k_chips.hip share (include/jda.h, "frames as they arrive"): the address-space typedefs of the
 // records' pointers, the Q14 gray value of a colour pixel as two v_dot4_u32_u8, one pixel by byte loads, a run of pixels of one
-// source row by aligned vector loads (pack_row), the bounds-check of such a run, and the units a destination is dealt in.
-// Device code only; every name lives in the including translation unit.
+// source row by aligned vector loads (pack_row), the bounds-check of such a run, the units a destination is dealt in, and the
+// tile kernels' launcher (launch_tiles, the only host code).  Every name lives in the including translation unit.
 #pragma once
 #include "kernels_common.h"
 
@@ -101,6 +101,16 @@ __device__ __forceinline__ pack_qr pack_divmod(long long p, uint32_t d) {
   if (p <= 0xffffffffll) { const uint32_t q = (uint32_t)p / d; return {q, (uint32_t)p - q * d}; }
   const long long q = p / (long long)d;
   return {q, (uint32_t)(p - q * (long long)d)};
+}
+
+// Host side, the one launcher of the tile kernels (k_turn, k_reduce, k_rotate): a workgroup per tile
+template <auto Kernel, typename Img>
+hipError_t launch_tiles(const FrameArgs<Img>& a, hipStream_t stream) {
+  if (a.n <= 0 || a.total <= 0) return hipSuccess;
+  if (!a.imgs || !a.block_img) return hipErrorInvalidValue;
+  if (a.total > 0x7fffffffll) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)a.total), dim3(kTurnBlock), 0, stream, a);
+  return hipGetLastError();
 }
 
 }  // namespace

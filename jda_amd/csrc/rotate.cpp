@@ -1,11 +1,9 @@
-// libjda.so, host side: frames whose faces are rolled (include/jda.h) -- jdaRotationPlan; jdaPackGrayRotated, plain loops over
-// the definition in host memory; jdaPackGrayRotatedDevice on the kernel of k_rotate.hip; jdaRotateBack, which takes what a
-// detect call returned on rotated rectangles back into the source images.  The pack entries refuse what pack.cpp's refuse
-// (check_pack, shared, with the angles) and with every angle a multiple of 90 they ARE turn.cpp's; the way back is turn.cpp's
-// orient_back with an angle per image.  The device form builds the image table and the item list (a tile per workgroup: the
-// tiles of turn.cpp, of the rotated image), puts them into its lane's grow-only buffer and makes one launch.  The plan is
-// the only place that asks libm: host form, device form and way back take c, s, tw, th from it.
-#include "detect.h"
+// libjda.so, host side: frames whose faces are rolled (include/jda.h) -- jdaRotationPlan; the definition of jdaPackGrayRotated,
+// plain loops over host memory (the device form is k_rotate.hip); and one face of jdaRotateBack, which takes what a detect call
+// returned on rotated rectangles back into the source images.  The call path -- what is refused, the device entry, the way
+// back's checks -- is frames.cpp's.  The plan is the only place that asks libm: host form, device form and way back take
+// c, s, tw, th from it.
+#include "frames.h"
 
 #include <cmath>
 
@@ -15,18 +13,6 @@ namespace {
 
 constexpr double kRotMaxDegrees = 36000.0;
 constexpr double kRotPi180 = 3.14159265358979323846 / 180.0;
-
-bool check_rotated(const std::string& who, const jdaPixels* images, const double* degrees, int n, unsigned char* dst, const size_t* dst_offsets,
-                   std::vector<PackOne>* v) {
-  return check_pack(who, images, nullptr, false, n, dst, dst_offsets, v, nullptr, false, degrees, true);
-}
-
-// every angle a multiple of 90: the images as turn.cpp takes them (orientation 0 / 1 / 2 / 3 by the plan's exact table)
-bool all_quarter_turns(std::vector<PackOne>* v) {
-  for (const PackOne& o : *v) if (!((o.c == 0.0 && std::fabs(o.s) == 1.0) || (o.s == 0.0 && std::fabs(o.c) == 1.0))) return false;
-  for (PackOne& o : *v) o.tf = kTf[o.c == 1.0 ? 0 : o.s == 1.0 ? 1 : o.c == -1.0 ? 2 : 3];
-  return true;
-}
 
 // The plan's map: turned (u, v) -> the rectangle's (sx, sy).  One operation per step (-ffp-contract=off).
 struct RotMap {
@@ -43,7 +29,7 @@ struct RotMap {
 };
 
 template <class Real>
-void back_landmarks(Real* lm, int L, const RotMap& m, const PixelsOne& r) {
+void back_landmarks(Real* lm, int L, const RotMap& m, const FrameOne& r) {
   for (int i = 0; i < L; i++) {
     double x, y;
     m.at((double)lm[2 * i], (double)lm[2 * i + 1], &x, &y);
@@ -80,19 +66,13 @@ bool rotation_plan(const std::string& who, int w, int h, double degrees, jdaRota
   return true;
 }
 
-int rotation_plan(int w, int h, double degrees, jdaRotation* rot) { return rotation_plan("jdaRotationPlan: ", w, h, degrees, rot) ? 0 : -1; }
-
-int rotate_host(const jdaPixels* images, const double* degrees, int n, unsigned char* dst, const size_t* dst_offsets) {
-  std::vector<PackOne> v;
-  if (!check_rotated("jdaPackGrayRotated: ", images, degrees, n, dst, dst_offsets, &v)) return -1;
-  if (all_quarter_turns(&v)) { turn_write(v); return 0; }           // jdaPackGrayOriented's bytes
-  for (const PackOne& o : v) {
+void rotate_write(const std::vector<FrameOne>& v) {
+  for (const FrameOne& o : v) {
     int wt[3] = {0, 0, 0};
     if (o.bpp > 1) pack_weights(o.format, wt);
     auto tap = [&](long long x, long long y) -> uint32_t {           // gray, rounded per tap; 0 outside the rectangle, which is never read
       if (x < 0 || x >= o.w || y < 0 || y >= o.h) return 0u;
-      const uint8_t* p = o.src + y * o.pitch + x * o.bpp;
-      return o.bpp == 1 ? p[0] : (uint32_t)((p[0] * wt[0] + p[1] * wt[1] + p[2] * wt[2] + 8192) >> 14);
+      return gray_of(o.src + y * o.pitch + x * o.bpp, o.bpp, wt);
     };
     const RotMap m(o.c, o.s, o.w, o.h, o.tw, o.th);
     uint8_t* d = o.dst;
@@ -113,45 +93,10 @@ int rotate_host(const jdaPixels* images, const double* degrees, int n, unsigned 
       }
     }
   }
-  return 0;
 }
 
-int rotate_device(Cascador* c, const jdaPixels* images, const double* degrees, int n, unsigned char* d_dst, const size_t* dst_offsets,
-                  hipStream_t user_stream, jdaPackStats* stats) {
-  LaneCall call(c);
-  const std::string who = "jdaPackGrayRotatedDevice: ";
-  if (!c) { fail(who + "null cascador"); return -1; }
-  std::vector<PackOne> v;
-  if (!check_rotated(who, images, degrees, n, d_dst, dst_offsets, &v)) return -1;
-  if (stats) std::memset(stats, 0, sizeof *stats);
-  if (n == 0) return 0;
-  if (all_quarter_turns(&v)) return turn_launch(call, who, v, user_stream, stats);   // the same bytes
-
-  std::vector<RotImg> tab;
-  std::vector<int> block_img;
-  long long total;
-  if (!turn_tiles(who, v, &tab, &block_img, &total)) return -1;
-  if (!call.open(user_stream)) return -1;
-  const hipStream_t st = call.st;
-  auto body = [&]() -> bool {
-    RotImg* d_tab; int* d_blk;
-    if (!call.upload(tab, block_img, &d_tab, &d_blk) || !call.begin()) return false;
-    RotArgs a{d_tab, d_blk, n, total};
-    JDA_HIP(launch_rotate(a, st));
-    return call.end() && call.sync();
-  };
-  if (!call.run(stats != nullptr, body)) return -1;
-  if (stats) {
-    long long pixels = 0, bytes_in = 0;
-    for (const PackOne& o : v) { pixels += o.npix; bytes_in += (long long)o.w * o.h * o.bpp; }
-    stats->pixels = pixels; stats->bytes_in = bytes_in; stats->bytes_out = pixels; stats->launches = 1;
-    stats->device_ms = call.device_ms; stats->call_ms = call.call_ms();
-  }
-  return 0;
-}
-
-void rotate_back_face(const OrientBackCall& k, int f, const PixelsOne& r, const jdaRotation& rot) {
-  const RotMap m(rot.c, rot.s, rot.w, rot.h, rot.tw, rot.th);
+void rotate_back_face(const BackCall& k, int f, const FrameOne& r) {
+  const RotMap m(r.c, r.s, r.w, r.h, r.tw, r.th);
   if (k.boxes) {
     int* b = k.boxes + (size_t)f * k.box_ints;
     const int bw = b[2], bh = k.box_ints == 4 ? b[3] : b[2];
@@ -165,12 +110,6 @@ void rotate_back_face(const OrientBackCall& k, int f, const PixelsOne& r, const 
     if (k.real_bytes == 4) back_landmarks((float*)k.landmarks + (size_t)f * 2 * k.landmark_n, k.landmark_n, m, r);
     else back_landmarks((double*)k.landmarks + (size_t)f * 2 * k.landmark_n, k.landmark_n, m, r);
   }
-}
-
-int rotate_back(const OrientBackCall& k, const double* degrees) {
-  const std::string who = "jdaRotateBack: ";
-  if (k.n_faces > 0 && !degrees) { fail(who + "null degrees"); return -1; }
-  return orient_back(who, k, nullptr, k.n_faces > 0 ? degrees : nullptr);
 }
 
 }  // namespace jda
